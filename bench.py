@@ -19,14 +19,20 @@ Workload at N = 1 (default `cfg3`, BASELINE.json configs[2] = configs[1]'s DSM
 holds the points within the last fallback radius of its tile, which the
 synthetic generator hands it directly).
 
-Prints ONE JSON line on rank 0 (see the contract in the task description) with
-two extra objects: `roofline` (dominant kernel, algorithmic bytes / measured
-HIP-event time, vs 8 TB/s HBM) and `cpu_baseline` (the CPU oracle timed on a
-bounded sample of the same workload on this box's host cores).
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (one
+timed step), the per-kernel HIP-event times of the timed steps and `roofline` (dominant kernel,
+algorithmic bytes / measured HIP-event time, vs 8 TB/s HBM).  That is all a plain run does: set
+up, warm up, time --steps steps, print.  --dump-outputs DIR also writes the layers of the last
+timed step (see its help).
+
+--full adds everything else, after the timed steps: `cpu_baseline` (the CPU oracle timed on a
+bounded sample of the same workload on the host's cores) with its `parity_sample`, the other
+arithmetic mode, `launch_skips`, `rough_terrain`, the host-buffer route (`pcie_inclusive`,
+N > 1: `session_route`), `other_workloads` and, N > 1, the `preflight`.
 
 `value` is the library's DEFAULT arithmetic: the FP64 gather (the reference's doubles,
-dsm.cc:160-172).  The opt-in single-precision mode is timed in the same run and reported as
-the extra object `fast_mode`, with its own parity sample and roofline.
+dsm.cc:160-172).  With --full the opt-in single-precision mode is timed in the same run and
+reported as the extra object `fast_mode`, with its own parity sample and roofline.
 
 `value` is the call the reference's hosts make (main-dsm.cc:103-107, main-ortho-backward-grid.cc:
 128-141: ONE process() per process): every timed DSM call counts, sorts and gathers its cloud from
@@ -34,11 +40,11 @@ scratch -- no data pass is skipped because the cloud repeats (the round-4 plan r
 the library).  The N > 1 ranks run the same pipeline.  The one thing a repeated call still takes
 from its predecessor is a LAUNCH policy: kernels whose work lists were empty last time (the
 capacity-class gathers, the big-sub-partition placement) are not launched; the extra object
-`launch_skips` times the same steps with every such kernel launched (tuning key no_launch_skips:
-what a context's very first call runs) so the difference is on the line.
+`launch_skips` (--full) times the same steps with every such kernel launched (tuning key
+no_launch_skips: what a context's very first call runs) so the difference is on the line.
 
-The parity sample is the WHOLE map by default (--cpu-sample-side 10000: the CPU oracle -- the
-reference's loops restated over its own vendored nanoflann -- on all 1e8 cells, ~1 min of host time).
+The parity sample of --full is the WHOLE map by default (--cpu-sample-side 10000: the CPU oracle --
+the reference's loops restated over its own vendored nanoflann -- on all 1e8 cells, ~1 min of host time).
 --workload cfg1 = BASELINE.json configs[0] exactly (1 M points, std::mt19937_64 seed 42,
 1000 x 1000 cells @ 1.0 m, interpolation_radius 1: 4 % of the cells take the fallback ladder).
 """
@@ -53,6 +59,11 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
+
+# --dump-outputs: cells kept per layer (5 layers + their finite masks: 10 x 2^20 x 4 B = 40 MiB at
+# most) and the sample's seed
+DUMP_CELLS = 1 << 20
+DUMP_SEED = 20240607
 
 WORKLOADS = {
     # name: (cells per side, resolution, points, frames, W, H)
@@ -105,7 +116,7 @@ def parse():
                          "~1 min of host time; 4000 for a quick run)")
     ap.add_argument("--colored", action="store_true", help="8UC3 frames / colored_ortho")
     ap.add_argument("--host-path", action="store_true", default=True,
-                    help="(default at N = 1) also time ONE pass through the host-buffer (drop-in) "
+                    help="(default with --full at N = 1) also time ONE pass through the host-buffer (drop-in) "
                          "entry points, PCIe transfers included (reported as pcie_inclusive, never "
                          "as value)")
     ap.add_argument("--no-host-path", dest="host_path", action="store_false")
@@ -129,10 +140,10 @@ def parse():
                          "600 x 600-cell windows of the elevation layer (three corners and the middle) "
                          "with the CPU oracle's DSM of those windows")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="default run (cfg3, N = 1): skip the child runs of the other BASELINE configs "
+                    help="--full run (cfg3, N = 1): skip the child runs of the other BASELINE configs "
                          "(`other_workloads`)")
     ap.add_argument("--no-preflight", action="store_true",
-                    help="N > 1: skip the small verified step in front of the timed ones")
+                    help="N > 1, --full: skip the small verified step in front of the timed ones")
     ap.add_argument("--route", default="auto", choices=["auto", "ranks", "session"],
                     help="`value` is always the one-process-per-GPU route.  session: rank 0 ALSO times "
                          "(after the timed steps) one pass of the whole map through ONE host process "
@@ -140,11 +151,28 @@ def parse():
                          "AERIAL_MAPPER_HIP_DEVICES gives an unchanged C++ host (main-dsm.cc:103-107, "
                          "main-ortho-backward-grid.cc:128-141) -- reported as `session_route` (N = 1: "
                          "`pcie_inclusive`, the same thing), never as value.  auto (default): the same "
-                         "when the host has the memory for the whole map's matrices; ranks: never")
+                         "with --full, when the host has the memory for the whole map's matrices; ranks: never")
     ap.add_argument("--session-child", type=int, default=0, help=argparse.SUPPRESS)   # (internal: see session_route_all)
     ap.add_argument("--map-origin", default="0,0",
                     help="easting,northing of the map centre (default 0,0; e.g. 464980.25,5272690.5 "
                          "puts the same workload at UTM magnitudes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baseline and its parity "
+                         "sample, the other arithmetic mode, launch_skips, rough_terrain, the host-buffer "
+                         "route (pcie_inclusive / session_route), other_workloads and, for N > 1, the "
+                         "preflight.  Without it a run sets up, warms up, times the steps and prints its line "
+                         "(the --no-* options above switch single parts of --full off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the layers the last timed step produced (elevation; "
+                         "with frames also elevation_angle, num_observations, observation_index and ortho / "
+                         "colored_ortho) as DIR/<layer>.npy, float32, shaped (cols, rows) like "
+                         "AerialGridMap.get, every value finite: a cell without a finite value (NaN: a layer's reset value "
+                         "where nothing was written: elevation without points, observation_index without a "
+                         "view) is written as 0.0, and DIR/<layer>_finite.npy (same shape) holds 1.0 where "
+                         "the layer holds a finite value, 0.0 elsewhere.  A layer of more than %d cells is "
+                         "written as a fixed 1-D sample of %d of its cells (flat indices into that array "
+                         "drawn by numpy PCG64 seed %d, sorted), so that all files stay within 40 MiB.  "
+                         "N > 1: DIR/rank<r>_<layer>.npy per rank window" % (DUMP_CELLS, DUMP_CELLS, DUMP_SEED))
     a = ap.parse_args()
     if a.knn:   # (the CPU baseline / parity sample are the REFERENCE's algorithm: not this mode)
         a.no_cpu_baseline = True
@@ -494,6 +522,32 @@ def window_parity(map_, pts_dev, side, res, L, origin, exact, s=600):
     return out
 
 
+def dump_outputs(out_dir, m, F, colored, rank, world):
+    """--dump-outputs: the layers of the map as the last timed step left them, downloaded (not
+    handed out as device pointers: that would change how the map refills them afterwards)."""
+    import numpy as np
+    names = ["elevation"]
+    if F:
+        names += ["elevation_angle", "num_observations", "observation_index",
+                  "colored_ortho" if colored else "ortho"]
+    os.makedirs(out_dir, exist_ok=True)
+    buf = np.empty((m.cols, m.rows), np.float32)
+    n = buf.size
+    idx = None
+    if n > DUMP_CELLS:
+        rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+        idx = np.sort(rng.choice(n, DUMP_CELLS, replace=False))
+    prefix = "rank%d_" % rank if world > 1 else ""
+    for name in names:
+        m.get(name, out=buf)
+        a = buf if idx is None else buf.reshape(-1)[idx]
+        # (every file finite: NaN cells -- the reset value of elevation / observation_index /
+        # colored_ortho where nothing was written -- become 0.0, and the mask says which they were)
+        finite = np.isfinite(a)
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.where(finite, a, np.float32(0.0)))
+        np.save(os.path.join(out_dir, prefix + name + "_finite.npy"), finite.astype(np.float32))
+
+
 def other_workloads(args):
     """The other BASELINE configs on this GPU, each a CHILD `python bench.py --workload ...` of a few
     steps (its own process: its own contexts and memory, and nothing it does can cost the parent's
@@ -728,7 +782,10 @@ def main():
                "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        # a CHILD process, never exec: this process has already initialised the GPU (device_count),
+        # and replacing the program of such a process is not safe on every driver
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -914,7 +971,7 @@ def main():
         ranks_info = {"backend": dist.get_backend(), "world_size_reported": dist.get_world_size(),
                       "ranks": gathered,
                       "distinct_devices": len(set((g["host"], g["device_index"], g["uuid"]) for g in gathered))}
-        if not args.no_preflight:
+        if args.full and not args.no_preflight:
             preflight = preflight_verify(args, A, tiling, synth, dist, one_gpu, dev, local_rank, rank,
                                          world, stream, layout.tiles_i, layout.tiles_j)
             if rank == 0 and not preflight["pass"]:
@@ -941,6 +998,9 @@ def main():
     m.enable_timing(False)
     if tiled is not None:
         tiled.check_overflow()
+    if args.dump_outputs:
+        # (before anything else runs: the layers still hold the result of the last timed step)
+        dump_outputs(args.dump_outputs, m, F, args.colored, rank, world)
     verify = None
     if args.verify and world > 1:
         verify = verify_windows(args, A, tiling, dist, one_gpu, dev, st, layout, rank, world, m, pts,
@@ -1120,7 +1180,7 @@ def main():
         if valu is not None:
             out["roofline"].update(valu_roofline(valu, dom, dom_ms, args.dsm_mode))
         parity_done = False
-        if world == 1 and not args.no_cpu_baseline and not fixed:
+        if world == 1 and args.full and not args.no_cpu_baseline and not fixed:
             # (before anything else runs: the layers still hold the result of the TIMED steps)
             refs = None
             try:
@@ -1175,7 +1235,7 @@ def main():
         # The launch policy a repeated call takes from its predecessor: kernels whose work
         # lists were empty last time are not launched.  The same steps with every one launched = what
         # a context's very first call runs.
-        if world == 1 and not batch and not args.knn and tiled is None:
+        if world == 1 and args.full and not batch and not args.knn and tiled is None:
             try:
                 from aerial_mapper_amd import hip_lib as _hl
                 k3 = max(3, min(args.steps, 10))
@@ -1194,7 +1254,7 @@ def main():
                 timed_loop(1, 0)
             except Exception as e:
                 out["launch_skips"] = {"error": repr(e)}
-        if world == 1 and not fixed and not args.no_rough_terrain and not args.knn and not batch \
+        if world == 1 and args.full and not fixed and not args.no_rough_terrain and not args.knn and not batch \
                 and not wl.get("mt19937_seed"):
             try:
                 out["rough_terrain"] = rough_terrain(args, A, m, pts, dsm, side, res, tile_center, L)
@@ -1205,14 +1265,16 @@ def main():
                 out["window_parity"] = window_parity(m, pts, side, res, L, (ox, oy), args.dsm_mode == "exact")
             except Exception as e:
                 out["window_parity"] = {"error": repr(e)}
-        if world == 1 and args.host_path and not fixed and args.route != "ranks":
+        # (the host-buffer route: with --full, or when --route session asks for it by name)
+        host_route = args.route == "session" or (args.full and args.route == "auto")
+        if world == 1 and args.host_path and not fixed and host_route:
             h_pts = pts.cpu().numpy()
             h_frames = [f for f in frames.cpu().numpy()] if F else None
             out["pcie_inclusive"] = session_route(args, A, st, (1, 1), [local_rank], dsm.settings, ncam,
                                                   mosaic.settings if F else None, h_pts, poses, h_frames,
                                                   cells, res, (ox, oy))
             out["pcie_inclusive"]["route"] = "session (--route session at N = 1 is this object)"
-        if world == 1 and args.workload == "cfg3" and not args.no_other_workloads and not args.knn \
+        if world == 1 and args.full and args.workload == "cfg3" and not args.no_other_workloads and not args.knn \
                 and not args.colored and not args.no_cpu_baseline:
             # (after everything of this process: the children need the GPU's memory -- cfg4 / cfg5 hold
             # a 40000^2 map -- so this process's buffers go first)
@@ -1223,7 +1285,7 @@ def main():
             except Exception:
                 pass
             out["other_workloads"] = other_workloads(args)
-        if world > 1 and args.route != "ranks" and not batch:
+        if world > 1 and host_route and not batch:
             # In a CHILD process with a time limit: one host process driving all N devices has never
             # run next to N live ranks on real hardware -- whatever it does (fail, hang), this
             # line's own numbers are already measured and must be printed.  The ranks wait on the

@@ -43,14 +43,14 @@ def test_cfg1_whole_map(cfg1, mode, device_cloud):
 
 
 def test_cfg1_bench_line(tmp_path):
-    """`python bench.py --workload cfg1` prints the contract's line with whole-map parity"""
+    """`python bench.py --workload cfg1 --full` prints the contract's line with whole-map parity"""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg1", "--steps", "5",
-                        "--warmup", "2", "--no-host-path"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        "--warmup", "2", "--no-host-path", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        universal_newlines=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -19,7 +19,7 @@ O=/tmp/amhip_prof_$$
 OUT=$R/gpurun_out/profiles_out
 mkdir -p "$O" "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python "$R/bench.py" --steps 10 --warmup 3 > "$OUT/${RND}_bench_cfg3_n1.json" 2> "$O/bench.err"
+timeout 900 python "$R/bench.py" --steps 10 --warmup 3 --full > "$OUT/${RND}_bench_cfg3_n1.json" 2> "$O/bench.err"
 for MODE in $MODES; do
   B="python $R/bench.py --steps 5 --warmup 2 --dsm-mode $MODE --no-cpu-baseline --no-host-path --no-second-mode --no-rough-terrain"
   P="${RND}_${MODE}"
