@@ -948,7 +948,7 @@ void amhip_ctx_destroy(amhip_ctx* h) {
   for (int l = 0; l < AMHIP_NUM_LAYERS; ++l)
     if (c->layers[l]) (void)hipFree(c->layers[l]);
   void* bufs[] = {c->dev_bbox, c->ortho_list, c->zpart, c->dev_zrange, c->tile_list, c->tile_occ, c->fill_mask, c->stage_values, c->dev_err, c->sorted,       c->rank,        c->bin_start, c->bin_z, c->rec_a, c->rec_b, c->rec16, c->sidx, c->zref, c->zall, c->tmp_points, c->stripe_ws,
-                  c->scan_partials, c->stage_points, c->frame_poses, c->stage_frames};
+                  c->scan_partials, c->stage_points, c->frame_poses, c->stage_frames, c->sgbm_ws};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->host_err) (void)hipHostFree(c->host_err);
@@ -1710,6 +1710,8 @@ const char* amhip_kernel_name(int kernel) {
       return "memset/fill";
     case AMHIP_K_HALO_SELECT:
       return "k_halo_select";
+    case AMHIP_K_STEREO:
+      return "k_stereo";          // every kernel of amhip_sgbm_disparity_dev
     default:
       return "?";
   }

@@ -317,6 +317,11 @@ struct Ctx {
   unsigned long long sort_stats_sig = 0, tile_stats_sig = 0;  // the geometry the pinned counters describe
   unsigned* host_tile_stats = nullptr;  // pinned mirror of the last call's tile-list counters
 
+  // semi-global block matching (amhip_stereo.hip): C, S, the left / right maps, the median and
+  // the speckle labels of one call, carved out of one block that grows on demand
+  uint8_t* sgbm_ws = nullptr;
+  size_t sgbm_ws_cap = 0;
+
   // timing
   bool timing = false;
   std::vector<TimedRegion> regions;

@@ -1,0 +1,562 @@
+// amhip_stereo.hip -- semi-global block matching (OpenCV's StereoSGBM, MODE_SGBM, 8UC1) on MI355X.
+//
+// Replaces stereo::BlockMatchingSGBM::computeDisparityMap
+//   aerial_mapper_dense_pcl/src/block-matching-sgbm.cpp (cv::StereoSGBM::compute, then / 16 and the
+//   rectification mask), the step between amhip_rectify_stereo_pair_dev and amhip_densify_dev.
+// The rules are those of tests/sgbm_reference.py (a NumPy restatement of OpenCV's stereosgbm.cpp);
+// this file reproduces it bit for bit (tests/test_gpu_sgbm.py).  Every step is integer arithmetic.
+//
+//   k_sgbm_hsum     per (row, 64-column tile): the two prefiltered channels of both images in LDS,
+//                   the Birchfield-Tomasi pixel cost (8 bits) of the tile + halo in LDS, its
+//                   horizontal box sum (columns replicated) -> hsum (uint16, in the S buffer)
+//   k_sgbm_vsum     per (column, disparity) and 32-row chunk: the vertical running sum -> C (uint16)
+//   k_sgbm_path     one wave walks one chain of one direction (row, column or diagonal), the
+//                   disparities across the lanes (d = 64 j + lane), d +- 1 by lane shuffles, minLr
+//                   by a wave reduction; the first direction writes S, the next three add to it, the
+//                   last (right -> left) adds its Lr and picks the winner: uniqueness, subpixel,
+//                   disp1 and the right-image map disp2 (64-bit atomicMin on (minS, 0xFFFF - x))
+//   k_sgbm_lrcheck  the left-right check against disp2
+//   k_sgbm_median   3x3 median, borders replicated
+//   k_sgbm_uf_*     filterSpeckles: union-find over the 4-connected relation (halving only while
+//                   uniting), then each pixel's root read without writes, region sizes by atomics
+//   k_sgbm_final    small regions -> invalid, CV_16S out, float / 16 with the mask
+// C + S + hsum live in the context's scratch (amhip::Ctx::sgbm_ws), grown on demand.
+#include <algorithm>
+#include <cstring>
+
+#include "amhip_common.h"
+
+namespace amhip {
+
+constexpr int kSgbmTX = 64;        // output columns per k_sgbm_hsum workgroup
+constexpr int kSgbmMaxSW2 = 5;     // block_size <= 11
+constexpr int kSgbmMaxD = 256;
+constexpr int kSgbmVRows = 32;     // rows per k_sgbm_vsum chunk
+constexpr int kSgbmInf = 1 << 28;  // Lr at d = -1 / d >= D ("MAX_COST")
+
+struct SgbmDims {
+  int W, H, minD, maxD, D, minX1, maxX1, w1, SW2, SH2;
+  int ftzero, P1, P2, uniq, disp12, invalid, speckle_win, speckle_diff;
+};
+
+// calcPixelCostBT's channel c (0: x-Sobel through clipTab, 1: raw) of column r of row y, packed
+// with the min / max over it and its half-pixel neighbours: v | v0 << 8 | v1 << 16
+__device__ __forceinline__ int sgbm_chan(const uint8_t* __restrict__ img, size_t step, int W, int H,
+                                         int y, int r, int c, int ftz) {
+  if (r <= 0 || r >= W - 1) return ftz;
+  const uint8_t* row = img + (size_t)y * step;
+  if (c == 1) return row[r];
+  const uint8_t* up = img + (size_t)(y > 0 ? y - 1 : y) * step;
+  const uint8_t* dn = img + (size_t)(y < H - 1 ? y + 1 : y) * step;
+  const int s = ((int)row[r + 1] - (int)row[r - 1]) * 2 + ((int)up[r + 1] - (int)up[r - 1]) +
+                ((int)dn[r + 1] - (int)dn[r - 1]);
+  return min(max(s, -ftz), ftz) + ftz;
+}
+
+__device__ __forceinline__ unsigned sgbm_packed(const uint8_t* __restrict__ img, size_t step, int W,
+                                                int H, int y, int r, int c, int ftz) {
+  const int v = sgbm_chan(img, step, W, H, y, r, c, ftz);
+  const int vl = r > 0 ? (v + sgbm_chan(img, step, W, H, y, r - 1, c, ftz)) / 2 : v;
+  const int vr = r < W - 1 ? (v + sgbm_chan(img, step, W, H, y, r + 1, c, ftz)) / 2 : v;
+  const int v0 = min(min(vl, vr), v), v1 = max(max(vl, vr), v);
+  return (unsigned)v | ((unsigned)v0 << 8) | ((unsigned)v1 << 16);
+}
+
+__device__ __forceinline__ int sgbm_bt(unsigned a, unsigned b) {
+  const int u = a & 255, u0 = (a >> 8) & 255, u1 = (a >> 16) & 255;
+  const int v = b & 255, v0 = (b >> 8) & 255, v1 = (b >> 16) & 255;
+  const int c0 = max(max(0, u - v1), v0 - u);
+  const int c1 = max(max(0, v - u1), u0 - v);
+  return min(c0, c1);
+}
+
+__global__ void __launch_bounds__(256)
+k_sgbm_hsum(SgbmDims p, const uint8_t* __restrict__ left, size_t lstep,
+            const uint8_t* __restrict__ right, size_t rstep, uint16_t* __restrict__ hsum) {
+  constexpr int kNL = kSgbmTX + 2 * kSgbmMaxSW2;
+  __shared__ unsigned sl[2][kNL];
+  __shared__ unsigned sr[2][kNL + kSgbmMaxD];
+  __shared__ uint8_t pc[kNL * kSgbmMaxD];
+  const int y = blockIdx.y;
+  const int x0 = blockIdx.x * kSgbmTX;
+  const int xa = max(x0 - p.SW2, 0), xb = min(x0 + kSgbmTX + p.SW2, p.w1);
+  const int NL = xb - xa, NR = NL + p.D - 1;
+  const int rbase = xa + p.minX1 - p.maxD + 1;  // right column of (left xa, d = D - 1)
+  for (int i = threadIdx.x; i < 2 * NL; i += blockDim.x) {
+    const int c = i / NL, k = i - c * NL;
+    sl[c][k] = sgbm_packed(left, lstep, p.W, p.H, y, xa + p.minX1 + k, c, p.ftzero);
+  }
+  for (int i = threadIdx.x; i < 2 * NR; i += blockDim.x) {
+    const int c = i / NR, k = i - c * NR;
+    sr[c][k] = sgbm_packed(right, rstep, p.W, p.H, y, rbase + k, c, p.ftzero);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < NL * p.D; i += blockDim.x) {
+    const int k = i / p.D, d = i - k * p.D;
+    const int kr = k + p.D - 1 - d;  // right column X - (d + minD)
+    pc[i] = (uint8_t)(sgbm_bt(sl[0][k], sr[0][kr]) + (sgbm_bt(sl[1][k], sr[1][kr]) >> 2));
+  }
+  __syncthreads();
+  const int nout = min(kSgbmTX, p.w1 - x0);
+  for (int i = threadIdx.x; i < nout * p.D; i += blockDim.x) {
+    const int xo = i / p.D, d = i - xo * p.D;
+    const int x1 = x0 + xo;
+    int s = 0;
+    for (int dx = -p.SW2; dx <= p.SW2; ++dx) {
+      const int xx = min(max(x1 + dx, 0), p.w1 - 1);
+      s += pc[(xx - xa) * p.D + d];
+    }
+    hsum[((size_t)y * p.w1 + x1) * p.D + d] = (uint16_t)s;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+k_sgbm_vsum(SgbmDims p, const uint16_t* __restrict__ hsum, uint16_t* __restrict__ C) {
+  const size_t plane = (size_t)p.w1 * p.D;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= plane) return;
+  const int y0 = blockIdx.y * kSgbmVRows, y1 = min(y0 + kSgbmVRows, p.H);
+  const int hold = max(p.H - 1 - p.SH2, 0);  // the last row whose block cost is updated
+  auto ye = [&](int y) { return y == 0 ? 0 : min(y, hold); };
+  int r = ye(y0), c = 0;
+  for (int k = -p.SH2; k <= p.SH2; ++k) c += hsum[(size_t)min(max(r + k, 0), p.H - 1) * plane + i];
+  C[(size_t)y0 * plane + i] = (uint16_t)c;
+  for (int y = y0 + 1; y < y1; ++y) {
+    const int rn = ye(y);
+    if (rn != r) {
+      c += (int)hsum[(size_t)min(rn + p.SH2, p.H - 1) * plane + i] -
+           (int)hsum[(size_t)max(rn - p.SH2 - 1, 0) * plane + i];
+      r = rn;
+    }
+    C[(size_t)y * plane + i] = (uint16_t)c;
+  }
+}
+
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// directions: 0 left->right, 1 top, 2 top-left, 3 top-right, 4 right->left
+// MODE 0: S = Lr; 1: S += Lr; 2: Lr + S -> winner (disp1, disp2 keys)
+template <int NJ, int MODE>
+__global__ void __launch_bounds__(256)
+k_sgbm_path(SgbmDims p, int dir, const uint16_t* __restrict__ C, int32_t* __restrict__ S,
+            int16_t* __restrict__ disp1, unsigned long long* __restrict__ key2) {
+  const int lane = threadIdx.x & 63;
+  const int chain = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int w1 = p.w1, H = p.H, D = p.D;
+  int x, y, sx, sy, len;
+  if (dir == 0 || dir == 4) {
+    if (chain >= H) return;
+    y = chain, sy = 0, len = w1;
+    x = dir == 0 ? 0 : w1 - 1, sx = dir == 0 ? 1 : -1;
+  } else if (dir == 1) {
+    if (chain >= w1) return;
+    x = chain, y = 0, sx = 0, sy = 1, len = H;
+  } else {
+    if (chain >= H + w1 - 1) return;
+    sy = 1;
+    sx = dir == 2 ? 1 : -1;
+    if (chain < H) {
+      y = chain, x = dir == 2 ? 0 : w1 - 1;
+    } else {
+      y = 0, x = dir == 2 ? chain - H + 1 : chain - H;  // (top-right: columns 0 .. w1-2)
+    }
+    len = min(dir == 2 ? w1 - x : x + 1, H - y);
+  }
+  int Lp[NJ];
+  bool val[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    val[j] = j * 64 + lane < D;
+    Lp[j] = val[j] ? 0 : kSgbmInf;
+  }
+  int mL = 0;
+  const int P1 = p.P1, P2 = p.P2;
+  int cn[NJ], sn[NJ];
+  auto load = [&](int xx, int yy, int* cv, int* sv) {
+    const size_t o = ((size_t)yy * w1 + xx) * D;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      cv[j] = val[j] ? (int)C[o + j * 64 + lane] : 0;
+      if (MODE != 0) sv[j] = val[j] ? S[o + j * 64 + lane] : 0;
+    }
+  };
+  load(x, y, cn, sn);
+  for (int t = 0; t < len; ++t) {
+    int cc[NJ], sc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) cc[j] = cn[j], sc[j] = sn[j];
+    if (t + 1 < len) load(x + sx, y + sy, cn, sn);  // (independent of the chain: in flight meanwhile)
+    // d - 1 and d + 1 of the previous Lr: rotate by one lane, carry across the 64-blocks
+    int up[NJ], dn[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      up[j] = __shfl(Lp[j], (lane + 63) & 63, 64);
+      dn[j] = __shfl(Lp[j], (lane + 1) & 63, 64);
+    }
+    int L[NJ];
+    int m = kSgbmInf;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int lm = lane == 0 ? (j == 0 ? kSgbmInf : up[j - 1]) : up[j];
+      const int lq = lane == 63 ? (j == NJ - 1 ? kSgbmInf : dn[j + 1]) : dn[j];
+      // OpenCV: (C + P2) + min(Lr_p[d], Lr_p[d-1] + P1, Lr_p[d+1] + P1, minLr_p + P2) - (minLr_p + P2)
+      const int best = min(min(Lp[j], lm + P1), min(lq + P1, mL + P2));
+      L[j] = val[j] ? cc[j] + best - mL : kSgbmInf;
+      m = min(m, L[j]);
+    }
+    m = wave_min(m);
+    const size_t o = ((size_t)y * w1 + x) * D;
+    if (MODE == 0) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        if (val[j]) S[o + j * 64 + lane] = L[j];
+    } else if (MODE == 1) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        if (val[j]) S[o + j * 64 + lane] = sc[j] + L[j];
+    } else {
+      int s[NJ];
+      int key = 0x7fffffff;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        s[j] = min(sc[j] + L[j], 32767);  // OpenCV's int16 S: saturate_cast, every Lr >= 0
+        if (val[j]) key = min(key, s[j] * 256 + j * 64 + lane);  // lowest d of the minimum
+      }
+      key = wave_min(key);
+      const int minS = key >> 8, bd = key & 255;
+      bool bad = false;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int d = j * 64 + lane;
+        bad = bad || (val[j] && s[j] * (100 - p.uniq) < minS * 100 && abs(bd - d) > 1);
+      }
+      // (every S saturated: OpenCV's bestDisp stays -1 and the pixel ends invalid, no disp2 write)
+      bad = __any(bad) || minS >= 32767;
+      auto at = [&](int d) {  // S[d] of this pixel, d wave-uniform
+        int v = s[0];
+#pragma unroll
+        for (int j = 1; j < NJ; ++j)
+          if ((d >> 6) == j) v = s[j];
+        return __shfl(v, d & 63, 64);
+      };
+      int d16 = bd * 16;
+      if (bd > 0 && bd < D - 1) {
+        const int sm = at(bd - 1), sp = at(bd + 1), s0 = minS;
+        const int den = max(sm + sp - 2 * s0, 1);
+        d16 = bd * 16 + ((sm - sp) * 16 + den) / (den * 2);  // C division: truncates
+      }
+      if (lane == 0) {
+        const int X = x + p.minX1;
+        const size_t row = (size_t)y * p.W;
+        if (bad) {
+          disp1[row + X] = (int16_t)p.invalid;
+        } else {
+          disp1[row + X] = (int16_t)(d16 + p.minD * 16);
+          const int x2 = X - bd - p.minD;
+          atomicMin(&key2[row + x2], ((unsigned long long)minS << 16) | (unsigned long long)(0xFFFF - X));
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) Lp[j] = L[j];
+    mL = m;
+    x += sx;
+    y += sy;
+  }
+}
+
+__device__ __forceinline__ int sgbm_disp2(const unsigned long long* __restrict__ key2, size_t row,
+                                          int xx, int invalid) {
+  const unsigned long long k = key2[row + xx];
+  return k == ~0ull ? invalid : (0xFFFF - (int)(k & 0xFFFF)) - xx;
+}
+
+__global__ void __launch_bounds__(256)
+k_sgbm_lrcheck(SgbmDims p, const int16_t* __restrict__ disp1,
+               const unsigned long long* __restrict__ key2, int16_t* __restrict__ out) {
+  const int X = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (X >= p.W) return;
+  const size_t row = (size_t)y * p.W;
+  int d1 = (X >= p.minX1 && X < p.maxX1) ? (int)disp1[row + X] : p.invalid;
+  if (d1 != p.invalid) {
+    const int lo = d1 >> 4, hi = (d1 + 15) >> 4;
+    const int xl = X - lo, xh = X - hi;
+    bool fl = false, fh = false;
+    if (xl >= 0 && xl < p.W) {
+      const int v = sgbm_disp2(key2, row, xl, p.invalid);
+      fl = v >= p.minD && abs(v - lo) > p.disp12;
+    }
+    if (xh >= 0 && xh < p.W) {
+      const int v = sgbm_disp2(key2, row, xh, p.invalid);
+      fh = v >= p.minD && abs(v - hi) > p.disp12;
+    }
+    if (fl && fh) d1 = p.invalid;
+  }
+  out[row + X] = (int16_t)d1;
+}
+
+__global__ void __launch_bounds__(256)
+k_sgbm_median(int W, int H, const int16_t* __restrict__ in, int16_t* __restrict__ out) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= W) return;
+  int v[9];
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int yy = min(max(y + dy, 0), H - 1), xx = min(max(x + dx, 0), W - 1);
+      v[(dy + 1) * 3 + dx + 1] = in[(size_t)yy * W + xx];
+    }
+#pragma unroll
+  for (int i = 1; i < 9; ++i)
+#pragma unroll
+    for (int j = i; j > 0; --j) {
+      const int a = v[j - 1], b = v[j];
+      v[j - 1] = min(a, b);
+      v[j] = max(a, b);
+    }
+  out[(size_t)y * W + x] = (int16_t)v[4];
+}
+
+// ---- filterSpeckles: union-find (parents only ever point to smaller indices) ----------------
+__device__ __forceinline__ int uf_load(int* a) {
+  return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ int uf_find(int* par, int x) {
+  int p = uf_load(&par[x]);
+  while (p != x) {
+    const int g = uf_load(&par[p]);
+    if (g != p) __hip_atomic_store(&par[x], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // halving
+    x = p;
+    p = g;
+  }
+  return x;
+}
+
+// the root without writes: once the unions are done, par no longer changes under it (a halving
+// store here could put back a stale, non-root ancestor over a label another thread has written)
+__device__ __forceinline__ int uf_root(const int* __restrict__ par, int x) {
+  int p = par[x];
+  while (p != x) {
+    x = p;
+    p = par[x];
+  }
+  return x;
+}
+
+__device__ __forceinline__ void uf_unite(int* par, int a, int b) {
+  while (true) {
+    a = uf_find(par, a);
+    b = uf_find(par, b);
+    if (a == b) return;
+    if (a < b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    if (atomicCAS(&par[a], a, b) == a) return;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+k_sgbm_uf_init(int n, int* __restrict__ par, int* __restrict__ cnt) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  par[i] = i;
+  cnt[i] = 0;
+}
+
+__global__ void __launch_bounds__(256)
+k_sgbm_uf_union(SgbmDims p, const int16_t* __restrict__ a, int* par) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= p.W) return;
+  const int i = y * p.W + x;
+  const int v = a[i];
+  if (v == p.invalid) return;
+  if (x + 1 < p.W) {
+    const int w = a[i + 1];
+    if (w != p.invalid && abs(v - w) <= p.speckle_diff) uf_unite(par, i, i + 1);
+  }
+  if (y + 1 < p.H) {
+    const int w = a[i + p.W];
+    if (w != p.invalid && abs(v - w) <= p.speckle_diff) uf_unite(par, i, i + p.W);
+  }
+}
+
+__global__ void __launch_bounds__(256)
+k_sgbm_uf_count(SgbmDims p, const int16_t* __restrict__ a, const int* __restrict__ par,
+                int* __restrict__ lab, int* __restrict__ cnt) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.W * p.H || a[i] == p.invalid) return;
+  const int r = uf_root(par, i);
+  lab[i] = r;
+  atomicAdd(&cnt[r], 1);
+}
+
+__global__ void __launch_bounds__(256)
+k_sgbm_final(SgbmDims p, const int16_t* __restrict__ med, const int* __restrict__ lab,
+             const int* __restrict__ cnt, const uint8_t* __restrict__ mask, size_t mask_step,
+             float* __restrict__ disp, size_t disp_step, int16_t* __restrict__ raw, size_t raw_step) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= p.W) return;
+  const int i = y * p.W + x;
+  int v = med[i];
+  if (lab && v != p.invalid && cnt[lab[i]] <= p.speckle_win) v = p.invalid;
+  if (raw) reinterpret_cast<int16_t*>(reinterpret_cast<uint8_t*>(raw) + (size_t)y * raw_step)[x] = (int16_t)v;
+  float f = (float)v / 16.0f;
+  if (mask && mask[(size_t)y * mask_step + x] == 0) f = 1.0f;  // kMaxInvalidDisparity
+  reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(disp) + (size_t)y * disp_step)[x] = f;
+}
+
+template <int NJ>
+static void launch_paths(Ctx* c, const SgbmDims& p, const uint16_t* C, int32_t* S, int16_t* disp1,
+                         unsigned long long* key2) {
+  const unsigned rows = (unsigned)((p.H + 3) / 4), cols = (unsigned)((p.w1 + 3) / 4),
+                 diag = (unsigned)((p.H + p.w1 - 1 + 3) / 4);
+  hipLaunchKernelGGL((k_sgbm_path<NJ, 0>), dim3(rows), dim3(256), 0, c->stream, p, 0, C, S, disp1, key2);
+  hipLaunchKernelGGL((k_sgbm_path<NJ, 1>), dim3(cols), dim3(256), 0, c->stream, p, 1, C, S, disp1, key2);
+  hipLaunchKernelGGL((k_sgbm_path<NJ, 1>), dim3(diag), dim3(256), 0, c->stream, p, 2, C, S, disp1, key2);
+  hipLaunchKernelGGL((k_sgbm_path<NJ, 1>), dim3(diag), dim3(256), 0, c->stream, p, 3, C, S, disp1, key2);
+  hipLaunchKernelGGL((k_sgbm_path<NJ, 2>), dim3(rows), dim3(256), 0, c->stream, p, 4, C, S, disp1, key2);
+}
+
+static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+}  // namespace amhip
+
+using namespace amhip;
+
+extern "C" {
+
+void amhip_sgbm_default_params(amhip_sgbm_params* out) {
+  if (!out) return;
+  // BlockMatchingParameters::SGBM (aerial_mapper_dense_pcl common.h)
+  out->min_disparity = 1;
+  out->num_disparities = 80;
+  out->pre_filter_cap = 35;
+  out->uniqueness_ratio = 10;
+  out->speckle_window_size = 100;
+  out->speckle_range = 20;
+  out->disp_12_max_diff = 0;
+  out->p1 = 120;
+  out->p2 = 250;
+  out->block_size = 9;
+}
+
+int amhip_sgbm_disparity_dev(amhip_ctx* h, const amhip_sgbm_params* q, int width, int height,
+                             const uint8_t* dev_left, size_t left_step, const uint8_t* dev_right,
+                             size_t right_step, const uint8_t* dev_mask, size_t mask_step,
+                             float* dev_disparity, size_t disp_step, int16_t* dev_raw,
+                             size_t raw_step) {
+  // (the parameters first: every argument error is reported without a device)
+  if (!q || !dev_left || !dev_right || !dev_disparity)
+    return arg_failure("amhip_sgbm_disparity_dev: null argument");
+  if (width < 3 || height < 1 || width > 32767 || height > 32767)
+    return arg_failure("amhip_sgbm_disparity_dev: width must be in [3, 32767], height in [1, 32767]");
+  if (q->num_disparities <= 0 || q->num_disparities % 16 != 0 || q->num_disparities > kSgbmMaxD)
+    return arg_failure("amhip_sgbm_disparity_dev: num_disparities must be a positive multiple of 16, <= 256");
+  if (q->block_size > 11 || (q->block_size > 0 && q->block_size % 2 == 0))
+    return arg_failure("amhip_sgbm_disparity_dev: block_size must be odd and <= 11 (0: OpenCV's 5)");
+  if (q->min_disparity < -4096 || q->min_disparity > 4096 || q->pre_filter_cap > 63 ||
+      q->uniqueness_ratio > 100 || q->p1 > 4096 || q->p2 > 4096)
+    return arg_failure("amhip_sgbm_disparity_dev: parameter out of range");
+  if (left_step < (size_t)width || right_step < (size_t)width ||
+      (dev_mask && mask_step < (size_t)width) || disp_step < (size_t)width * sizeof(float) ||
+      (dev_raw && raw_step < (size_t)width * sizeof(int16_t)))
+    return arg_failure("amhip_sgbm_disparity_dev: a row step is smaller than the width");
+  if (disp_step % sizeof(float) != 0 || (dev_raw && raw_step % sizeof(int16_t) != 0))
+    return arg_failure("amhip_sgbm_disparity_dev: output steps must be multiples of the element size");
+  {
+    const int maxD = q->min_disparity + q->num_disparities;
+    const int w1 = width + std::min(q->min_disparity, 0) - std::max(maxD, 0);
+    if (w1 > 0 && w1 <= (q->block_size > 0 ? q->block_size : 5) / 2)
+      return arg_failure("amhip_sgbm_disparity_dev: fewer matchable columns than half the block");
+  }
+  if (!h) return arg_failure("null context");
+  Ctx* c = &h->impl;
+  int rc = ctx_use_device(c);
+  if (rc) return rc;
+
+  // computeDisparitySGBM's preamble (tests/sgbm_reference.py: derived)
+  SgbmDims p;
+  std::memset(&p, 0, sizeof(p));
+  p.W = width;
+  p.H = height;
+  p.minD = q->min_disparity;
+  p.maxD = p.minD + q->num_disparities;
+  p.D = q->num_disparities;
+  p.P1 = q->p1 > 0 ? q->p1 : 2;
+  p.P2 = std::max(q->p2 > 0 ? q->p2 : 5, p.P1 + 1);
+  p.ftzero = std::max(q->pre_filter_cap, 15) | 1;
+  p.uniq = q->uniqueness_ratio >= 0 ? q->uniqueness_ratio : 10;
+  p.disp12 = q->disp_12_max_diff > 0 ? q->disp_12_max_diff : 1;
+  const int win = q->block_size > 0 ? q->block_size : 5;
+  p.SW2 = p.SH2 = win / 2;
+  p.minX1 = std::max(p.maxD, 0);
+  p.maxX1 = width + std::min(p.minD, 0);
+  p.w1 = p.maxX1 - p.minX1;
+  p.invalid = (p.minD - 1) * 16;
+  p.speckle_win = q->speckle_window_size;
+  p.speckle_diff = 16 * q->speckle_range;
+  const bool matched = p.w1 > 0;
+
+  const size_t npix = (size_t)width * height;
+  const size_t vol = matched ? (size_t)height * p.w1 * p.D : 0;
+  const size_t oC = 0, oS = oC + align256(vol * 2), o1 = oS + align256(vol * 4),
+               oK = o1 + align256(npix * 2), oL = oK + align256(npix * 8),
+               oM = oL + align256(npix * 2), oP = oM + align256(npix * 2),
+               oN = oP + align256(npix * 4), oB = oN + align256(npix * 4),
+               total = oB + align256(npix * 4);
+  if ((rc = ensure_bytes(reinterpret_cast<void**>(&c->sgbm_ws), &c->sgbm_ws_cap, total))) return rc;
+  uint8_t* ws = c->sgbm_ws;
+  uint16_t* C = reinterpret_cast<uint16_t*>(ws + oC);
+  int32_t* S = reinterpret_cast<int32_t*>(ws + oS);
+  uint16_t* hsum = reinterpret_cast<uint16_t*>(ws + oS);  // (dead once C is built)
+  int16_t* disp1 = reinterpret_cast<int16_t*>(ws + o1);
+  unsigned long long* key2 = reinterpret_cast<unsigned long long*>(ws + oK);
+  int16_t* lr = reinterpret_cast<int16_t*>(ws + oL);
+  int16_t* med = reinterpret_cast<int16_t*>(ws + oM);
+  int* par = reinterpret_cast<int*>(ws + oP);
+  int* cnt = reinterpret_cast<int*>(ws + oN);
+  int* lab = reinterpret_cast<int*>(ws + oB);
+
+  ScopedTimer t(c, AMHIP_K_STEREO);
+  const dim3 rowgrid((unsigned)((width + 255) / 256), (unsigned)height);
+  if (matched) {
+    AMHIP_TRY(hipMemsetAsync(key2, 0xFF, npix * 8, c->stream));
+    hipLaunchKernelGGL(k_sgbm_hsum, dim3((unsigned)((p.w1 + kSgbmTX - 1) / kSgbmTX), (unsigned)height),
+                       dim3(256), 0, c->stream, p, dev_left, left_step, dev_right, right_step, hsum);
+    hipLaunchKernelGGL(k_sgbm_vsum, dim3((unsigned)(((size_t)p.w1 * p.D + 255) / 256),
+                                         (unsigned)((height + kSgbmVRows - 1) / kSgbmVRows)),
+                       dim3(256), 0, c->stream, p, hsum, C);
+    if (p.D <= 64)
+      launch_paths<1>(c, p, C, S, disp1, key2);
+    else if (p.D <= 128)
+      launch_paths<2>(c, p, C, S, disp1, key2);
+    else if (p.D <= 192)
+      launch_paths<3>(c, p, C, S, disp1, key2);
+    else
+      launch_paths<4>(c, p, C, S, disp1, key2);
+  }
+  // (no match possible: every pixel INVALID_DISP_SCALED; disp1 / key2 are not read)
+  hipLaunchKernelGGL(k_sgbm_lrcheck, rowgrid, dim3(256), 0, c->stream, p, disp1, key2, lr);
+  hipLaunchKernelGGL(k_sgbm_median, rowgrid, dim3(256), 0, c->stream, width, height, lr, med);
+  const bool speckle = q->speckle_window_size > 0;
+  if (speckle) {
+    const unsigned nb = (unsigned)((npix + 255) / 256);
+    hipLaunchKernelGGL(k_sgbm_uf_init, dim3(nb), dim3(256), 0, c->stream, (int)npix, par, cnt);
+    hipLaunchKernelGGL(k_sgbm_uf_union, rowgrid, dim3(256), 0, c->stream, p, med, par);
+    hipLaunchKernelGGL(k_sgbm_uf_count, dim3(nb), dim3(256), 0, c->stream, p, med, par, lab, cnt);
+  }
+  hipLaunchKernelGGL(k_sgbm_final, rowgrid, dim3(256), 0, c->stream, p, med, speckle ? lab : nullptr,
+                     cnt, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step);
+  AMHIP_TRY(hipGetLastError());
+  return AMHIP_OK;
+}
+
+}  // extern "C"

@@ -30,8 +30,8 @@ LAYER_NAMES = ["ortho", "elevation", "elevation_angle", "num_observations",
 
 # amhip_kernel
 (K_DSM_BIN_COUNT, K_DSM_SCAN, K_DSM_SCATTER, K_DSM_GATHER, K_ORTHO, K_MISC,
- K_HALO_SELECT) = range(7)
-NUM_KERNELS = 7
+ K_HALO_SELECT, K_STEREO) = range(8)
+NUM_KERNELS = 8
 
 DIST_NONE, DIST_RADTAN, DIST_EQUIDISTANT = 0, 1, 2
 
@@ -60,6 +60,7 @@ EXPORTS = [
     "amhip_layer_to_image_dev", "amhip_layer_to_image", "amhip_geotiff_write_u8",
     "amhip_grid_map_msg_bytes", "amhip_grid_map_msg_layout", "amhip_io_write_point_cloud_binary",
     "amhip_io_load_point_cloud_binary", "amhip_session_grid_map_msg", "amhip_session_layer_to_image",
+    "amhip_sgbm_default_params", "amhip_sgbm_disparity_dev",
 ]
 
 
@@ -84,6 +85,13 @@ class MosaicDesc(C.Structure):
     """amhip_mosaic_desc"""
     _fields_ = [("width_mosaic_pixels", C.c_int32), ("height_mosaic_pixels", C.c_int32),
                 ("ground_plane_elevation_m", C.c_double), ("origin", C.c_double * 3)]
+
+
+class SgbmParams(C.Structure):
+    """amhip_sgbm_params (BlockMatchingParameters::SGBM)"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "min_disparity", "num_disparities", "pre_filter_cap", "uniqueness_ratio",
+        "speckle_window_size", "speckle_range", "disp_12_max_diff", "p1", "p2", "block_size")]
 
 
 class AmhipError(RuntimeError):
@@ -175,6 +183,11 @@ def load():
         vp, vp, vp, vp, vp, vp]
     lib.amhip_rectify_stereo_pair_dev.argtypes = [vp, f64p, f64p, f64p, f64p, f64p, C.c_int, C.c_int,
                                                   vp, C.c_size_t, vp, C.c_size_t, f64p, f64p, vp, vp, vp, vp]
+    lib.amhip_sgbm_default_params.restype = None
+    lib.amhip_sgbm_default_params.argtypes = [C.POINTER(SgbmParams)]
+    lib.amhip_sgbm_disparity_dev.argtypes = [vp, C.POINTER(SgbmParams), C.c_int, C.c_int,
+                                             vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t,
+                                             vp, C.c_size_t, vp, C.c_size_t]
     lib.amhip_ctx_enable_timing.argtypes = [vp, C.c_int]
     lib.amhip_ctx_timing_reset.argtypes = [vp]
     lib.amhip_ctx_kernel_time.argtypes = [vp, C.c_int, f64p, C.POINTER(C.c_int64)]

@@ -260,8 +260,9 @@ int amhip_ortho_from_pcl_process(amhip_ctx* ctx, const double* host_xyz,
  * row-major 3x3 (StereoRigParameters::K, RectifiedStereoPair::R_G_C), t_G_C1
  * is StereoRigParameters::t_G_C1, baseline RectifiedStereoPair::baseline.
  * dev_count receives the number of valid points (it may exceed `capacity`, the
- * excess is not written).  Asynchronous.  The block matcher (OpenCV BM/SGBM)
- * and the ROS PointCloud2 fill stay the reference's. */
+ * excess is not written).  Asynchronous.  The SGBM block matcher in front of
+ * it is amhip_sgbm_disparity_dev; only OpenCV's BM (use_BM = true) and the ROS
+ * PointCloud2 fill stay the reference's. */
 int amhip_densify_dev(amhip_ctx* ctx, const float* dev_disparity, size_t disp_step,
                       const uint8_t* dev_image_left, size_t img_step, int width,
                       int height, const double* K, double baseline,
@@ -491,7 +492,8 @@ typedef enum amhip_kernel {
   AMHIP_K_ORTHO = 4,         /* per-tile frame cull + per-cell fold/sample */
   AMHIP_K_MISC = 5,          /* memsets / small helpers                    */
   AMHIP_K_HALO_SELECT = 6,   /* multi-GPU: compact the halo points          */
-  AMHIP_NUM_KERNELS = 7
+  AMHIP_K_STEREO = 7,        /* semi-global block matching (all its kernels) */
+  AMHIP_NUM_KERNELS = 8
 } amhip_kernel;
 
 /* ---- stereo::Rectifier::rectifyStereoPair (+ computeMask)
@@ -511,6 +513,32 @@ int amhip_rectify_stereo_pair_dev(amhip_ctx* ctx, const double* K, const double*
                                   const uint8_t* dev_right, size_t right_step, double* R_G_C_out,
                                   double* baseline_out, float* dev_maps, uint8_t* dev_rect_left,
                                   uint8_t* dev_rect_right, uint8_t* dev_mask);
+
+/* ---- stereo::BlockMatchingSGBM::computeDisparityMap
+ *      aerial_mapper_dense_pcl/src/block-matching-sgbm.cpp -- OpenCV's StereoSGBM (MODE_SGBM, 8UC1)
+ *      between amhip_rectify_stereo_pair_dev and amhip_densify_dev --------------------------
+ * BlockMatchingParameters::SGBM (common.h), field for field; amhip_sgbm_default_params fills in its
+ * defaults (1, 80, 35, 10, 100, 20, 0, 120, 250, 9).  40 bytes. */
+typedef struct amhip_sgbm_params {
+  int32_t min_disparity, num_disparities, pre_filter_cap, uniqueness_ratio,
+          speckle_window_size, speckle_range, disp_12_max_diff, p1, p2, block_size;
+} amhip_sgbm_params;
+void amhip_sgbm_default_params(amhip_sgbm_params* out);
+/* dev_left / dev_right: rectified 8UC1 rasters on the GPU, rows *_step bytes apart.  dev_mask (NULL:
+ * none): the rectification mask, pixels where it is 0 get kMaxInvalidDisparity = 1.0f.
+ * dev_disparity: float rows disp_step bytes apart, the map as the wrapper leaves it (CV_16S / 16,
+ * masked); dev_raw (NULL: not wanted): StereoSGBM::compute's CV_16S map (16 * disparity, invalid =
+ * (min_disparity - 1) * 16), raw_step bytes apart.  num_disparities: a multiple of 16 up to 256;
+ * block_size: odd, up to 11 (0: OpenCV's 5); width and height up to 32767.  The rules are those of
+ * tests/sgbm_reference.py, reproduced bit for bit (parity with OpenCV itself is unpinned).
+ * Scratch (about 6 bytes per pixel and disparity) belongs to the context and is kept between calls.
+ * Asynchronous on the context's stream. */
+int amhip_sgbm_disparity_dev(amhip_ctx* ctx, const amhip_sgbm_params* p, int width, int height,
+                             const uint8_t* dev_left, size_t left_step,
+                             const uint8_t* dev_right, size_t right_step,
+                             const uint8_t* dev_mask, size_t mask_step,
+                             float* dev_disparity, size_t disp_step,
+                             int16_t* dev_raw, size_t raw_step);
 
 /* ---- session: one map served through HOST matrices by one or several GPUs ---------------
  *
