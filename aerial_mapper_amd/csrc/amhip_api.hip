@@ -1711,7 +1711,7 @@ const char* amhip_kernel_name(int kernel) {
     case AMHIP_K_HALO_SELECT:
       return "k_halo_select";
     case AMHIP_K_STEREO:
-      return "k_stereo";          // every kernel of amhip_sgbm_disparity_dev
+      return "k_stereo";          // every kernel of amhip_sgbm_disparity_dev / amhip_bm_disparity_dev
     default:
       return "?";
   }

@@ -427,6 +427,160 @@ static void launch_paths(Ctx* c, const SgbmDims& p, const uint16_t* C, int32_t* 
 
 static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
+// ---- block matching (OpenCV's StereoBM, PREFILTER_XSOBEL, 8UC1): tests/bm_reference.py -------
+//   k_bm_prefilter  per pixel: prefilterXSobel of both images (rows in pairs, an odd last row and
+//                   the border columns = cap) -> scratch; FILTERED outside the matched region
+//   k_bm_match      per (32-column tile, 64-row band): the band's prefiltered rows (+ the window's
+//                   rows above / below, the left strip + SW2 halo, the right strip + D - 1) in LDS;
+//                   8 lanes per column, lane g holding d = 8 j + g (j < D / 8); the vertical window sums run
+//                   down the band in registers (entering row added, leaving row subtracted, each
+//                   row's horizontal SAD summed from LDS); texture, winner, uniqueness and subpixel
+//                   by shuffles over the 8 lanes of a column
+// then the SGBM tail: k_sgbm_uf_* (filterSpeckles, speckle_range unscaled) and k_sgbm_final.
+constexpr int kBmTX = 32;        // output columns per k_bm_match workgroup (8 lanes each)
+constexpr int kBmTY = 64;        // output rows per k_bm_match workgroup
+constexpr int kBmMaxSW2 = 15;    // block_size <= 31
+constexpr int kBmRows = kBmTY + 2 * kBmMaxSW2;
+constexpr int kBmLW = kBmTX + 2 * kBmMaxSW2;               // left strip, bytes per row
+constexpr int kBmRW = kBmTX + 2 * kBmMaxSW2 + kSgbmMaxD;   // right strip (>= LW + D - 1)
+
+struct BmDims {
+  int W, H, minD, D, cap, SW2, uniq, texture, lofs, rofs, filtered;
+  int xa, xb, ya, yb;  // the matched region: getValidDisparityROI within [lofs, lofs + width1)
+};
+
+__global__ void __launch_bounds__(256)
+k_bm_prefilter(BmDims p, const uint8_t* __restrict__ left, size_t lstep,
+               const uint8_t* __restrict__ right, size_t rstep, uint8_t* __restrict__ fl,
+               uint8_t* __restrict__ fr, int16_t* __restrict__ raw) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= p.W) return;
+  const size_t i = (size_t)y * p.W + x;
+  uint8_t a = (uint8_t)p.cap, b = (uint8_t)p.cap;
+  // the row pairs stop one row short of an odd H (that row, and columns 0 / W-1, stay cap)
+  if (x > 0 && x < p.W - 1 && y < (p.H & ~1)) {
+    const int yu = y > 0 ? y - 1 : 1, yd = y < p.H - 1 ? y + 1 : p.H - 2;
+    const uint8_t* im[2] = {left, right};
+    const size_t st[2] = {lstep, rstep};
+    uint8_t out[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const uint8_t* r0 = im[k] + (size_t)yu * st[k];
+      const uint8_t* r1 = im[k] + (size_t)y * st[k];
+      const uint8_t* r2 = im[k] + (size_t)yd * st[k];
+      const int s = ((int)r0[x + 1] - (int)r0[x - 1]) + 2 * ((int)r1[x + 1] - (int)r1[x - 1]) +
+                    ((int)r2[x + 1] - (int)r2[x - 1]);
+      out[k] = (uint8_t)(min(max(s, -p.cap), p.cap) + p.cap);
+    }
+    a = out[0];
+    b = out[1];
+  }
+  fl[i] = a;
+  fr[i] = b;
+  if (x < p.xa || x >= p.xb || y < p.ya || y >= p.yb) raw[i] = (int16_t)p.filtered;
+}
+
+// NJ = D / 8: d values per lane
+template <int NJ>
+__global__ void __launch_bounds__(256)
+k_bm_match(BmDims p, const uint8_t* __restrict__ fl, const uint8_t* __restrict__ fr,
+           int16_t* __restrict__ raw) {
+  __shared__ uint8_t sL[kBmRows][kBmLW];
+  __shared__ uint8_t sR[kBmRows][kBmRW];
+  const int SW2 = p.SW2, D = 8 * NJ;
+  const int X0 = p.xa + blockIdx.x * kBmTX;
+  const int y0 = p.ya + blockIdx.y * kBmTY, y1 = min(y0 + kBmTY, p.yb);
+  const int r0 = y0 - SW2, nrows = y1 - y0 + 2 * SW2;  // rows r0 .. r0 + nrows - 1, all inside
+  const int nL = kBmTX + 2 * SW2;
+  const int rmax = p.W - D;                            // the right base column's clamp
+  const int lo = min(max(X0 - SW2 - p.lofs + p.rofs, 0), rmax);
+  const int nR = min(max(X0 + kBmTX - 1 + SW2 - p.lofs + p.rofs, 0), rmax) + D - lo;
+  for (int i = threadIdx.x; i < nrows * nL; i += 256) {
+    const int r = i / nL, k = i - r * nL;
+    sL[r][k] = fl[(size_t)(r0 + r) * p.W + min(max(X0 - SW2 + k, 0), p.W - 1)];
+  }
+  for (int i = threadIdx.x; i < nrows * nR; i += 256) {
+    const int r = i / nR, k = i - r * nR;
+    sR[r][k] = fr[(size_t)(r0 + r) * p.W + lo + k];
+  }
+  __syncthreads();
+  const int xl = threadIdx.x >> 3, g = threadIdx.x & 7;
+  const int X = X0 + xl;
+  const int base = X - p.lofs + p.rofs - lo;  // (right base column of dx) = clamp(base + lo + dx) - lo
+  // one row's contribution (sign +1) and another's (sign -1) to the window sums
+  auto rows = [&](int ra, int rb, bool two, int* v, int& t) {
+    for (int dx = -SW2; dx <= SW2; ++dx) {
+      const int kl = xl + dx + SW2;
+      const int kr = min(max(base + lo + dx, 0), rmax) - lo + g;
+      const int la = sL[ra][kl];
+      t += abs(la - p.cap);
+      if (two) t -= abs((int)sL[rb][kl] - p.cap);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        int s = abs(la - (int)sR[ra][kr + 8 * j]);
+        if (two) s -= abs((int)sL[rb][kl] - (int)sR[rb][kr + 8 * j]);
+        v[j] += s;
+      }
+    }
+  };
+  int vs[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) vs[j] = 0;
+  int tsum = 0;
+  for (int r = 0; r < 2 * SW2; ++r) rows(r, 0, false, vs, tsum);
+  for (int y = y0; y < y1; ++y) {
+    const int rin = y - y0 + 2 * SW2;
+    if (y == y0)
+      rows(rin, 0, false, vs, tsum);
+    else
+      rows(rin, rin - 2 * SW2 - 1, true, vs, tsum);
+    // winner: the first d of the minimum (key = sad << 9 | d)
+    int key = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) key = min(key, (vs[j] << 9) | (8 * j + g));
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) key = min(key, __shfl_xor(key, o, 64));
+    const int minsad = key >> 9, mind = key & 511;
+    const int thresh = minsad + (int)((long long)minsad * p.uniq / 100);
+    const int pi = mind + 1 < D ? mind + 1 : D - 2;  // sad[D] := sad[D-2]
+    const int ni = mind > 0 ? mind - 1 : 1;          // sad[-1] := sad[1]
+    int bad = 0, pv = 0, nv = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int d = 8 * j + g;
+      bad |= (abs(d - mind) > 1 && vs[j] <= thresh) ? 1 : 0;
+      pv += d == pi ? vs[j] : 0;
+      nv += d == ni ? vs[j] : 0;
+    }
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) {
+      bad |= __shfl_xor(bad, o, 64);
+      pv += __shfl_xor(pv, o, 64);
+      nv += __shfl_xor(nv, o, 64);
+    }
+    if (g == 0 && X < p.xb) {
+      int out;
+      if (tsum < p.texture || (p.uniq > 0 && bad)) {
+        out = p.filtered;
+      } else {
+        const int den = pv + nv - 2 * minsad + abs(pv - nv);
+        out = ((D - mind - 1 + p.minD) * 256 + (den != 0 ? (pv - nv) * 256 / den : 0) + 15) >> 4;
+      }
+      raw[(size_t)y * p.W + X] = (int16_t)out;
+    }
+  }
+}
+
+// one instantiation per num_disparities (16 .. 256 in steps of 16)
+template <int NJ = 2>
+static void launch_bm_match(Ctx* c, const BmDims& p, dim3 grid, const uint8_t* fl, const uint8_t* fr,
+                            int16_t* raw) {
+  if constexpr (NJ < 32) {
+    if (p.D != 8 * NJ) return launch_bm_match<NJ + 2>(c, p, grid, fl, fr, raw);
+  }
+  hipLaunchKernelGGL(k_bm_match<NJ>, grid, dim3(256), 0, c->stream, p, fl, fr, raw);
+}
+
 }  // namespace amhip
 
 using namespace amhip;
@@ -554,6 +708,125 @@ int amhip_sgbm_disparity_dev(amhip_ctx* h, const amhip_sgbm_params* q, int width
     hipLaunchKernelGGL(k_sgbm_uf_count, dim3(nb), dim3(256), 0, c->stream, p, med, par, lab, cnt);
   }
   hipLaunchKernelGGL(k_sgbm_final, rowgrid, dim3(256), 0, c->stream, p, med, speckle ? lab : nullptr,
+                     cnt, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step);
+  AMHIP_TRY(hipGetLastError());
+  return AMHIP_OK;
+}
+
+void amhip_bm_default_params(amhip_bm_params* out) {
+  if (!out) return;
+  // BlockMatchingParameters::BM (aerial_mapper_dense_pcl common.h)
+  out->min_disparity = 1;
+  out->num_disparities = 80;
+  out->pre_filter_cap = 31;
+  out->pre_filter_size = 9;
+  out->uniqueness_ratio = 80;
+  out->texture_threshold = 20;
+  out->speckle_window_size = 100;
+  out->speckle_range = 5;
+  out->disp_12_max_diff = 0;
+  out->block_size = 15;
+}
+
+int amhip_bm_disparity_dev(amhip_ctx* h, const amhip_bm_params* q, int width, int height,
+                           const uint8_t* dev_left, size_t left_step, const uint8_t* dev_right,
+                           size_t right_step, const uint8_t* dev_mask, size_t mask_step,
+                           float* dev_disparity, size_t disp_step, int16_t* dev_raw,
+                           size_t raw_step) {
+  // (StereoBM::compute's CV_Asserts on the wrapper's effective parameters, then this
+  // implementation's limits; every argument error is reported without a device)
+  if (!q || !dev_left || !dev_right || !dev_disparity)
+    return arg_failure("amhip_bm_disparity_dev: null argument");
+  if (width < 1 || height < 1 || width > 32767 || height > 32767)
+    return arg_failure("amhip_bm_disparity_dev: width and height must be in [1, 32767]");
+  if (q->num_disparities <= 0 || q->num_disparities % 16 != 0 || q->num_disparities > kSgbmMaxD)
+    return arg_failure("amhip_bm_disparity_dev: num_disparities must be a positive multiple of 16, <= 256");
+  if (q->block_size % 2 == 0 || q->block_size < 5 || q->block_size > 2 * kBmMaxSW2 + 1 ||
+      q->block_size > std::min(width, height))
+    return arg_failure("amhip_bm_disparity_dev: block_size must be odd, in [5, 31] and <= min(width, height)");
+  if (q->pre_filter_size < 1 || q->pre_filter_size > 63)
+    return arg_failure("amhip_bm_disparity_dev: pre_filter_size (the effective preFilterCap) must be in [1, 63]");
+  if (q->texture_threshold < 0)
+    return arg_failure("amhip_bm_disparity_dev: texture_threshold must be >= 0");
+  if (q->uniqueness_ratio < 0)
+    return arg_failure("amhip_bm_disparity_dev: uniqueness_ratio must be >= 0");
+  if (q->min_disparity < -4096 || q->min_disparity > 4096)
+    return arg_failure("amhip_bm_disparity_dev: min_disparity must be in [-4096, 4096]");
+  if (left_step < (size_t)width || right_step < (size_t)width ||
+      (dev_mask && mask_step < (size_t)width) || disp_step < (size_t)width * sizeof(float) ||
+      (dev_raw && raw_step < (size_t)width * sizeof(int16_t)))
+    return arg_failure("amhip_bm_disparity_dev: a row step is smaller than the width");
+  if (disp_step % sizeof(float) != 0 || (dev_raw && raw_step % sizeof(int16_t) != 0))
+    return arg_failure("amhip_bm_disparity_dev: output steps must be multiples of the element size");
+  if (!h) return arg_failure("null context");
+  Ctx* c = &h->impl;
+  int rc = ctx_use_device(c);
+  if (rc) return rc;
+
+  // the wrapper's setters (block-matching-bm.h): preFilterCap = pre_filter_size (the second
+  // setPreFilterCap wins), disp12MaxDiff stays -1; findStereoCorrespondenceBM's preamble and
+  // getValidDisparityROI (tests/bm_reference.py: effective, region)
+  BmDims p;
+  std::memset(&p, 0, sizeof(p));
+  p.W = width;
+  p.H = height;
+  p.minD = q->min_disparity;
+  p.D = q->num_disparities;
+  p.cap = q->pre_filter_size;
+  p.SW2 = q->block_size / 2;
+  p.uniq = q->uniqueness_ratio;
+  p.texture = q->texture_threshold;
+  p.lofs = std::max(p.D - 1 + p.minD, 0);
+  p.rofs = -std::min(p.D - 1 + p.minD, 0);
+  p.filtered = (int)(int16_t)((p.minD - 1) * 16);
+  const int width1 = width - p.rofs - p.D + 1;
+  const int maxD = p.minD + p.D - 1;
+  p.xa = std::max(maxD, 0) + p.SW2;
+  p.xb = std::min(width - p.SW2, p.lofs + width1);
+  p.ya = p.SW2;
+  p.yb = height - p.SW2;
+  if (p.lofs >= width || p.rofs >= width || width1 < 1 || p.xb <= p.xa || p.yb <= p.ya)
+    p.xa = p.xb = p.ya = p.yb = 0;  // nothing matched: FILTERED everywhere
+  const bool matched = p.xb > p.xa;
+
+  const size_t npix = (size_t)width * height;
+  const size_t oL = 0, oR = oL + align256(npix), oD = oR + align256(npix),
+               oP = oD + align256(npix * 2), oN = oP + align256(npix * 4),
+               oB = oN + align256(npix * 4), total = oB + align256(npix * 4);
+  if ((rc = ensure_bytes(reinterpret_cast<void**>(&c->sgbm_ws), &c->sgbm_ws_cap, total))) return rc;
+  uint8_t* ws = c->sgbm_ws;
+  uint8_t* fl = ws + oL;
+  uint8_t* fr = ws + oR;
+  int16_t* disp = reinterpret_cast<int16_t*>(ws + oD);
+  int* par = reinterpret_cast<int*>(ws + oP);
+  int* cnt = reinterpret_cast<int*>(ws + oN);
+  int* lab = reinterpret_cast<int*>(ws + oB);
+
+  // the speckle filter and the final pass are SGBM's, on these fields
+  SgbmDims s;
+  std::memset(&s, 0, sizeof(s));
+  s.W = width;
+  s.H = height;
+  s.invalid = p.filtered;
+  s.speckle_win = q->speckle_window_size;
+  s.speckle_diff = q->speckle_range;  // (StereoBM: unscaled, in 1/16 pixel)
+
+  ScopedTimer t(c, AMHIP_K_STEREO);
+  const dim3 rowgrid((unsigned)((width + 255) / 256), (unsigned)height);
+  hipLaunchKernelGGL(k_bm_prefilter, rowgrid, dim3(256), 0, c->stream, p, dev_left, left_step, dev_right,
+                     right_step, fl, fr, disp);
+  if (matched) {
+    const dim3 grid((unsigned)((p.xb - p.xa + kBmTX - 1) / kBmTX), (unsigned)((p.yb - p.ya + kBmTY - 1) / kBmTY));
+    launch_bm_match(c, p, grid, fl, fr, disp);
+  }
+  const bool speckle = q->speckle_range >= 0 && q->speckle_window_size > 0;
+  if (speckle) {
+    const unsigned nb = (unsigned)((npix + 255) / 256);
+    hipLaunchKernelGGL(k_sgbm_uf_init, dim3(nb), dim3(256), 0, c->stream, (int)npix, par, cnt);
+    hipLaunchKernelGGL(k_sgbm_uf_union, rowgrid, dim3(256), 0, c->stream, s, disp, par);
+    hipLaunchKernelGGL(k_sgbm_uf_count, dim3(nb), dim3(256), 0, c->stream, s, disp, par, lab, cnt);
+  }
+  hipLaunchKernelGGL(k_sgbm_final, rowgrid, dim3(256), 0, c->stream, s, disp, speckle ? lab : nullptr,
                      cnt, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step);
   AMHIP_TRY(hipGetLastError());
   return AMHIP_OK;

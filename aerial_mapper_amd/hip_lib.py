@@ -61,6 +61,7 @@ EXPORTS = [
     "amhip_grid_map_msg_bytes", "amhip_grid_map_msg_layout", "amhip_io_write_point_cloud_binary",
     "amhip_io_load_point_cloud_binary", "amhip_session_grid_map_msg", "amhip_session_layer_to_image",
     "amhip_sgbm_default_params", "amhip_sgbm_disparity_dev",
+    "amhip_bm_default_params", "amhip_bm_disparity_dev",
 ]
 
 
@@ -92,6 +93,13 @@ class SgbmParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "min_disparity", "num_disparities", "pre_filter_cap", "uniqueness_ratio",
         "speckle_window_size", "speckle_range", "disp_12_max_diff", "p1", "p2", "block_size")]
+
+
+class BmParams(C.Structure):
+    """amhip_bm_params (BlockMatchingParameters::BM)"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "min_disparity", "num_disparities", "pre_filter_cap", "pre_filter_size", "uniqueness_ratio",
+        "texture_threshold", "speckle_window_size", "speckle_range", "disp_12_max_diff", "block_size")]
 
 
 class AmhipError(RuntimeError):
@@ -188,6 +196,11 @@ def load():
     lib.amhip_sgbm_disparity_dev.argtypes = [vp, C.POINTER(SgbmParams), C.c_int, C.c_int,
                                              vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t,
                                              vp, C.c_size_t, vp, C.c_size_t]
+    lib.amhip_bm_default_params.restype = None
+    lib.amhip_bm_default_params.argtypes = [C.POINTER(BmParams)]
+    lib.amhip_bm_disparity_dev.argtypes = [vp, C.POINTER(BmParams), C.c_int, C.c_int,
+                                           vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t,
+                                           vp, C.c_size_t, vp, C.c_size_t]
     lib.amhip_ctx_enable_timing.argtypes = [vp, C.c_int]
     lib.amhip_ctx_timing_reset.argtypes = [vp]
     lib.amhip_ctx_kernel_time.argtypes = [vp, C.c_int, f64p, C.POINTER(C.c_int64)]

@@ -710,14 +710,82 @@ def compute_disparity_sgbm(map, image_left, image_right, params=None, mask=None,
     return (disp, rawt) if raw else disp
 
 
+class BmParameters(object):
+    """BlockMatchingParameters::BM (aerial_mapper_dense_pcl common.h), same defaults.  As the
+    reference's wrapper sets them, pre_filter_size becomes OpenCV's preFilterCap (pre_filter_cap is
+    overwritten) and disp_12_max_diff is not used."""
+
+    def __init__(self, min_disparity=1, num_disparities=80, pre_filter_cap=31, pre_filter_size=9,
+                 uniqueness_ratio=80, texture_threshold=20, speckle_window_size=100, speckle_range=5,
+                 disp_12_max_diff=0, block_size=15):
+        self.min_disparity = min_disparity
+        self.num_disparities = num_disparities
+        self.pre_filter_cap = pre_filter_cap
+        self.pre_filter_size = pre_filter_size
+        self.uniqueness_ratio = uniqueness_ratio
+        self.texture_threshold = texture_threshold
+        self.speckle_window_size = speckle_window_size
+        self.speckle_range = speckle_range
+        self.disp_12_max_diff = disp_12_max_diff
+        self.block_size = block_size
+
+    def to_c(self):
+        return L.BmParams(*(int(getattr(self, n)) for n, _ in L.BmParams._fields_))
+
+
+class BlockMatchingParameters(object):
+    """BlockMatchingParameters (aerial_mapper_dense_pcl common.h): use_BM picks the matcher, as
+    stereo::Densifier's constructor does (BM if set, SGBM otherwise)."""
+
+    def __init__(self, use_BM=False, sgbm=None, bm=None):
+        self.use_BM = bool(use_BM)
+        self.sgbm = sgbm if sgbm is not None else SgbmParameters()
+        self.bm = bm if bm is not None else BmParameters()
+
+
+def _stereo_call(fn, map, image_left, image_right, p, mask, raw):
+    import torch
+    for t in (image_left, image_right) + ((mask,) if mask is not None else ()):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.stride(1) == 1
+    H, W = image_left.shape
+    assert tuple(image_right.shape) == (H, W) and (mask is None or tuple(mask.shape) == (H, W))
+    dev = image_left.device
+    disp = torch.empty((H, W), dtype=torch.float32, device=dev)
+    rawt = torch.empty((H, W), dtype=torch.int16, device=dev) if raw else None
+    map.wait_for_torch(image_left)
+    L.check(fn(
+        map.handle, C.byref(p), W, H, C.c_void_p(image_left.data_ptr()), image_left.stride(0),
+        C.c_void_p(image_right.data_ptr()), image_right.stride(0),
+        C.c_void_p(mask.data_ptr()) if mask is not None else None,
+        mask.stride(0) if mask is not None else 0, C.c_void_p(disp.data_ptr()), disp.stride(0) * 4,
+        C.c_void_p(rawt.data_ptr()) if raw else None, rawt.stride(0) * 2 if raw else 0))
+    map.synchronize()
+    return (disp, rawt) if raw else disp
+
+
+def compute_disparity_bm(map, image_left, image_right, params=None, mask=None, raw=False):
+    """stereo::BlockMatchingBM::computeDisparityMap (block-matching-bm.cpp: StereoBM::compute, / 16,
+    the rectification mask) on the GPU of `map`: rectified CUDA torch uint8 tensors (H, W) -> the
+    float32 disparity map (H, W) on the device; with raw=True also OpenCV's CV_16S map (int16).
+    mask (uint8 (H, W), optional): pixels where it is 0 become kMaxInvalidDisparity = 1.0."""
+    p = (params or BmParameters()).to_c()
+    return _stereo_call(L.load().amhip_bm_disparity_dev, map, image_left, image_right, p, mask, raw)
+
+
 def dense_cloud_from_stereo_pair(map, K, R_G_C1, R_G_C2, t_G_C1, t_G_C2, image_left, image_right,
                                  params=None):
-    """stereo::Stereo::processStereoFrame (stereo.cpp) without the ROS publish: rectify -> SGBM
-    (masked with the rectifier's mask) -> densify, all on the GPU of `map`.  image_left /
-    image_right: CUDA torch uint8 (H, W).  Returns (xyz (n, 3) float64, intensities (n,) int32) on
-    the device, ready for Dsm.process / OrthoFromPcl.process."""
+    """stereo::Stereo::processStereoFrame (stereo.cpp) without the ROS publish: rectify -> block
+    matching (masked with the rectifier's mask) -> densify, all on the GPU of `map`.  image_left /
+    image_right: CUDA torch uint8 (H, W).  params: None or SgbmParameters (SGBM), BmParameters (BM),
+    or BlockMatchingParameters (BM if use_BM, as stereo::Densifier picks).  Returns (xyz (n, 3)
+    float64, intensities (n,) int32) on the device, ready for Dsm.process / OrthoFromPcl.process."""
+    if isinstance(params, BlockMatchingParameters):
+        params = params.bm if params.use_BM else params.sgbm
     r = rectify_stereo_pair(map, K, R_G_C1, R_G_C2, t_G_C1, t_G_C2, image_left, image_right)
-    disp = compute_disparity_sgbm(map, r["image_left"], r["image_right"], params, mask=r["mask"])
+    if isinstance(params, BmParameters):
+        disp = compute_disparity_bm(map, r["image_left"], r["image_right"], params, mask=r["mask"])
+    else:
+        disp = compute_disparity_sgbm(map, r["image_left"], r["image_right"], params, mask=r["mask"])
     return densify(map, disp, r["image_left"], K, r["baseline"], r["R_G_C"], t_G_C1)
 
 

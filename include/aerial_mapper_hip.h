@@ -260,9 +260,9 @@ int amhip_ortho_from_pcl_process(amhip_ctx* ctx, const double* host_xyz,
  * row-major 3x3 (StereoRigParameters::K, RectifiedStereoPair::R_G_C), t_G_C1
  * is StereoRigParameters::t_G_C1, baseline RectifiedStereoPair::baseline.
  * dev_count receives the number of valid points (it may exceed `capacity`, the
- * excess is not written).  Asynchronous.  The SGBM block matcher in front of
- * it is amhip_sgbm_disparity_dev; only OpenCV's BM (use_BM = true) and the ROS
- * PointCloud2 fill stay the reference's. */
+ * excess is not written).  Asynchronous.  The block matcher in front of it is
+ * amhip_sgbm_disparity_dev (use_BM = false) or amhip_bm_disparity_dev
+ * (use_BM = true); only the ROS PointCloud2 fill stays the reference's. */
 int amhip_densify_dev(amhip_ctx* ctx, const float* dev_disparity, size_t disp_step,
                       const uint8_t* dev_image_left, size_t img_step, int width,
                       int height, const double* K, double baseline,
@@ -492,7 +492,7 @@ typedef enum amhip_kernel {
   AMHIP_K_ORTHO = 4,         /* per-tile frame cull + per-cell fold/sample */
   AMHIP_K_MISC = 5,          /* memsets / small helpers                    */
   AMHIP_K_HALO_SELECT = 6,   /* multi-GPU: compact the halo points          */
-  AMHIP_K_STEREO = 7,        /* semi-global block matching (all its kernels) */
+  AMHIP_K_STEREO = 7,        /* block matching (SGBM or BM; all its kernels) */
   AMHIP_NUM_KERNELS = 8
 } amhip_kernel;
 
@@ -539,6 +539,37 @@ int amhip_sgbm_disparity_dev(amhip_ctx* ctx, const amhip_sgbm_params* p, int wid
                              const uint8_t* dev_mask, size_t mask_step,
                              float* dev_disparity, size_t disp_step,
                              int16_t* dev_raw, size_t raw_step);
+
+/* ---- stereo::BlockMatchingBM::computeDisparityMap
+ *      aerial_mapper_dense_pcl/src/block-matching-bm.cpp -- OpenCV's StereoBM (PREFILTER_XSOBEL, 8UC1),
+ *      the matcher Densifier picks with BlockMatchingParameters::use_BM = true ------------------------
+ * BlockMatchingParameters::BM (common.h), field for field; amhip_bm_default_params fills in its
+ * defaults (1, 80, 31, 9, 80, 20, 100, 5, 0, 15).  40 bytes. */
+typedef struct amhip_bm_params {
+  int32_t min_disparity, num_disparities, pre_filter_cap, pre_filter_size, uniqueness_ratio,
+          texture_threshold, speckle_window_size, speckle_range, disp_12_max_diff, block_size;
+} amhip_bm_params;
+void amhip_bm_default_params(amhip_bm_params* out);
+/* The wrapper's setters as written (block-matching-bm.h): setPreFilterCap(pre_filter_cap) and then
+ * setPreFilterCap(pre_filter_size), so the effective preFilterCap is pre_filter_size (9 by default)
+ * and pre_filter_cap is unused; preFilterSize keeps OpenCV's 9 (unused by the x-Sobel prefilter);
+ * disp_12_max_diff is never passed (disp12MaxDiff = -1: no left-right check); speckle_range is
+ * passed as is, in 1/16 pixel.  The other fields map one to one.
+ * Arguments as amhip_sgbm_disparity_dev: rectified 8UC1 rasters dev_left / dev_right, the optional
+ * mask (0 -> kMaxInvalidDisparity = 1.0f), the float map (CV_16S / 16, masked) and the optional
+ * StereoBM::compute CV_16S map (16 * disparity, FILTERED = (min_disparity - 1) * 16).
+ * num_disparities: a multiple of 16 up to 256; block_size: odd, in [5, 31], <= min(width, height);
+ * pre_filter_size in [1, 63]; texture_threshold, uniqueness_ratio >= 0; min_disparity in
+ * [-4096, 4096]; width and height in [1, 32767].  The rules are those of tests/bm_reference.py,
+ * reproduced bit for bit (parity with OpenCV itself is unpinned).  Scratch (about 16 bytes per
+ * pixel, no cost volume) is the context's stereo scratch, shared with the SGBM matcher.
+ * Asynchronous on the context's stream. */
+int amhip_bm_disparity_dev(amhip_ctx* ctx, const amhip_bm_params* p, int width, int height,
+                           const uint8_t* dev_left, size_t left_step,
+                           const uint8_t* dev_right, size_t right_step,
+                           const uint8_t* dev_mask, size_t mask_step,
+                           float* dev_disparity, size_t disp_step,
+                           int16_t* dev_raw, size_t raw_step);
 
 /* ---- session: one map served through HOST matrices by one or several GPUs ---------------
  *

@@ -1,6 +1,7 @@
-"""One JSON line: ms of rectify, SGBM (the k_stereo slot), densify and DSM for a 1920x1080 stereo
-pair with the reference's SGBM parameters (BlockMatchingParameters::SGBM), median of --reps runs
-after a warm-up, plus the library's build id.  Usage: python tools/stereo_probe.py [--reps N]"""
+"""One JSON line: ms of rectify, the block matcher (the k_stereo slot), densify and DSM for a 1920x1080
+stereo pair with the reference's parameters of that matcher (BlockMatchingParameters::SGBM, or ::BM
+with --matcher bm), median of --reps runs after a warm-up, plus the library's build id.
+Usage: python tools/stereo_probe.py [--reps N] [--matcher {sgbm,bm}]"""
 import argparse
 import json
 import os
@@ -15,6 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--matcher", choices=("sgbm", "bm"), default="sgbm")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -25,6 +27,13 @@ def main():
     K, R1, R2, t1, t2, left, right = rig(21, W=W, H=H)
     lt, rt = torch.from_numpy(left).cuda(), torch.from_numpy(right).cuda()
     out = {}
+    name = args.matcher
+    if name == "bm":
+        params = A.BmParameters()
+        match = A.compute_disparity_bm
+    else:
+        params = A.SgbmParameters()
+        match = A.compute_disparity_sgbm
     with A.AerialGridMap(A.GridMapSettings(12.0, -4.0, 400.0, 300.0, 0.5)) as m:
         dsm = A.Dsm(A.DsmSettings(1), m)
         runs = []
@@ -36,9 +45,9 @@ def main():
             m.enable_timing(True)
             m.timing_reset()
             t0 = time.perf_counter()
-            disp = A.compute_disparity_sgbm(m, r["image_left"], r["image_right"], mask=r["mask"])
-            ms["sgbm_wall"] = (time.perf_counter() - t0) * 1e3
-            ms["sgbm"] = m.kernel_times()["k_stereo"][0]
+            disp = match(m, r["image_left"], r["image_right"], params, mask=r["mask"])
+            ms[name + "_wall"] = (time.perf_counter() - t0) * 1e3
+            ms[name] = m.kernel_times()["k_stereo"][0]
             m.enable_timing(False)
             t0 = time.perf_counter()
             pts, inten = A.densify(m, disp, r["image_left"], K, r["baseline"], r["R_G_C"], t1)
@@ -52,10 +61,12 @@ def main():
                 runs.append(ms)
         for k in runs[0]:
             out[k] = float(np.median([r[k] for r in runs])) if k != "points" else runs[0][k]
-    out.update({"width": W, "height": H, "num_disparities": 80, "block_size": 9,
-                "reps": args.reps, "build_id": hip_lib.build_id(),
-                "note": "rectify / densify / dsm: wall ms of the synchronous Python calls; sgbm: "
-                        "HIP-event ms of the k_stereo slot (sgbm_wall: the call's wall time)"})
+    out.update({"width": W, "height": H, "num_disparities": params.num_disparities,
+                "block_size": params.block_size, "reps": args.reps, "build_id": hip_lib.build_id(),
+                "note": "rectify / densify / dsm: wall ms of the synchronous Python calls; %s: "
+                        "HIP-event ms of the k_stereo slot (%s_wall: the call's wall time)" % (name, name)})
+    if name == "bm":
+        out["matcher"] = "bm"
     print(json.dumps(out))
 
 
