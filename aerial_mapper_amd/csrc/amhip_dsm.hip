@@ -624,6 +624,27 @@ constexpr int kTileI = 64;
 constexpr int kMaxRegionRows = 96;  // bin rows of a region
 constexpr int kListHdr = 8;         // counters in front of the tile lists
 constexpr int kNumLists = 7;
+// The tile lists of one call: [kListHdr counters] then kNumLists arrays of ntiles tile ids (the device
+// side indexes them by these numbers: wave_append_tile, tile_occupancy_block).  Who writes, who walks:
+enum TileList : int {
+  kListMain = 0,           // occupied class-0 tiles, filled by the pre-pass on sparse calls only; walked by
+                           // the main launch of a sparse call (FP64 or single-precision list kernel)
+  kListClass1 = 1,         // class-1 / class-2 tiles (pre-pass); walked by the list launches with the
+  kListClass2 = 2,         // larger LDS images, FP64 or single precision
+  kListWaveBlock = 3,      // class 3: more points than any LDS image holds (pre-pass); k_dsm_gather_dense
+  kListRedoOwn = 4,        // FP64 redo with an image of cap0 points: class-0 tiles the single-precision main
+                           // launch hands back, or the pre-pass files for it (bin_z, rej_own); FP64 list launch
+  kListRedoBig = 5,        // FP64 redo with the largest image (cap2): tiles the single-precision class launches
+                           // (or a main launch whose own FP64 image fits no CU) hand back, or the pre-pass files
+  kListRedoWaveBlock = 6,  // redo beyond the largest image; k_dsm_gather_dense<false>
+};
+constexpr int kStatRedoUnlisted = 7;  // counter only: pre-classified tiles on NO list (a dense launch takes them)
+struct TileLists {
+  int* base;
+  unsigned ntiles;
+  int* ids(int l) const { return base + kListHdr + (size_t)l * ntiles; }
+  unsigned* count(int l) const { return reinterpret_cast<unsigned*>(base) + l; }
+};
 // s_setreg operand: HW_REG_MODE (id 1), offset 6, width 2 = FP_DENORM for f64 / f16
 constexpr int kHwRegModeFpDenormF64 = 1 | (6 << 6) | ((2 - 1) << 11);
 
@@ -688,13 +709,9 @@ constexpr int kFxMinAdditions = 48;  // a trip of a dense tile brings up to ~20 
 // Clouds are not uniform (overlapping strips, partial coverage): the capacity of
 // the main launch follows the MEAN density, denser tiles go to launches with more
 // LDS per workgroup instead of falling back to the global-memory path.
-//   lists (may be null): [kListHdr counters] then arrays of ntiles ids:
-//     list 0  occupied class-0 tiles (only filled when `list0` -- sparse calls)
-//     list k  class-k tiles (k = 1, 2, 3)
-//     list 4  class-0 tiles the single-precision gather hands to the FP64 kernel
-//             (filled by k_dsm_gather_f32, not here)
-//     list 5  class-1 / class-2 tiles of the single-precision list launches handed to the
-//             FP64 kernel's largest LDS image, list 6: those beyond it (wave-per-block kernel)
+//   lists (may be null): the tile lists (enum TileList): list 0 only when `list0` (sparse calls),
+//     list k for class k = 1, 2, 3; lists 4 .. 6 are filled by the single-precision gathers, and
+//     here only with the tiles that bin_z pre-classifies.
 //   bin_z (may be null; single-precision mode after the three-pass sort): per bin the ordered
 //     keys of its lowest / highest (float-rounded) height, written by the placement pass.  The
 //     tile's region then has a known height range BEFORE anything is staged: a tile whose error
@@ -1966,6 +1983,17 @@ __device__ __forceinline__ void gather_tile_f32(const DsmParams& p, const uint32
   }
 }
 
+// XCD-aware tile order of the dense launches (one workgroup per tile): consecutive tiles
+// (which share halo points) go to the same XCD's L2.  Blocks are dealt
+// round-robin to the 8 XCDs, so XCD x gets the x-th contiguous chunk of the tile
+// list (bijective for any count).
+__device__ __forceinline__ int xcd_tile(int ntiles) {
+  const int b = blockIdx.x;
+  const int xcd = b & 7, k = b >> 3;
+  const int q = ntiles >> 3, r = ntiles & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+}
+
 #ifndef AMHIP_F32_WAVES
 #define AMHIP_F32_WAVES 8
 #endif
@@ -1975,11 +2003,7 @@ k_dsm_gather_f32(DsmParams p, const uint32_t* __restrict__ start,
                  const Pts P, const uint8_t* __restrict__ tile_occ,
                  CellOut o, int* __restrict__ exact_list, unsigned* __restrict__ exact_count) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int ntiles = p.tiles_i * p.tiles_j;
-  const int b = blockIdx.x;
-  const int xcd = b & 7, k = b >> 3;
-  const int q = ntiles >> 3, r = ntiles & 7;
-  const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+  const int tile = xcd_tile(p.tiles_i * p.tiles_j);
   gather_tile_f32<NT, kTileJ, kCap, kVar>(p, start, P, tile_occ, o, tile, smem, 0, exact_list,
                                           exact_count);
 }
@@ -1993,11 +2017,7 @@ k_dsm_gather_f32_wide(DsmParams p, const uint32_t* __restrict__ start,
                       CellOut o, int* __restrict__ exact_list, unsigned* __restrict__ exact_count,
                       int* __restrict__ big_list, unsigned* __restrict__ big_count, int big_np) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int ntiles = p.tiles_i * p.tiles_j;
-  const int b = blockIdx.x;
-  const int xcd = b & 7, k = b >> 3;
-  const int q = ntiles >> 3, r = ntiles & 7;
-  const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+  const int tile = xcd_tile(p.tiles_i * p.tiles_j);
   gather_tile_f32<NT, kTileJ, kCap>(p, start, P, tile_occ, o, tile, smem, 0, exact_list,
                                     exact_count, big_list, big_count, big_np);
 }
@@ -2019,10 +2039,7 @@ k_dsm_gather_f32_list(DsmParams p, const uint32_t* __restrict__ start,
   }
 }
 
-// Dense launch: one workgroup per tile.  XCD-aware tile order: consecutive tiles
-// (which share halo points) go to the same XCD's L2.  Blocks are dealt
-// round-robin to the 8 XCDs, so XCD x gets the x-th contiguous chunk of the tile
-// list (bijective for any count).
+// Dense launch: one workgroup per tile, in the XCD-aware order (xcd_tile).
 // 8 waves per SIMD (64 VGPRs; left to itself the compiler takes 65 = 7 waves, i.e. THREE 512-thread
 // workgroups per CU): the 64 x 16 / 1024-point image is sized so that FOUR fit a CU's LDS, and the
 // fourth hides the other three's staging and epilogue phases -- same box 2.67 -> 2.54 ms per 1e8
@@ -2037,11 +2054,7 @@ k_dsm_gather_tiled(DsmParams p, const uint32_t* __restrict__ start,
                    const Pts P, const uint8_t* __restrict__ tile_occ,
                    CellOut o, int my_class) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int ntiles = p.tiles_i * p.tiles_j;
-  const int b = blockIdx.x;
-  const int xcd = b & 7, k = b >> 3;
-  const int q = ntiles >> 3, r = ntiles & 7;
-  const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+  const int tile = xcd_tile(p.tiles_i * p.tiles_j);
   gather_tile<NT, kTileJ, kCap>(p, start, P, tile_occ, o, tile, smem, my_class);
 }
 
@@ -2051,11 +2064,7 @@ __global__ void __launch_bounds__(NT)
 k_dsm_gather_tiled_knn(DsmParams p, const uint32_t* __restrict__ start, const Pts P,
                        const uint8_t* __restrict__ tile_occ, CellOut o) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int ntiles = p.tiles_i * p.tiles_j;
-  const int b = blockIdx.x;
-  const int xcd = b & 7, k = b >> 3;
-  const int q = ntiles >> 3, r = ntiles & 7;
-  const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+  const int tile = xcd_tile(p.tiles_i * p.tiles_j);
   gather_tile<NT, kTileJ, kCap, kSet>(p, start, P, tile_occ, o, tile, smem, -1);
 }
 
@@ -2263,6 +2272,198 @@ k_range_reduce(const double* __restrict__ part, size_t nparts, unsigned long lon
 // ---------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------
+// Launch of a kernel with dynamic LDS: the kernel's limit is raised to what this launch asks for,
+// then the launch goes onto the context's stream -- both on every launch.  The parameter types come
+// from the kernel's pointer; the arguments convert as in a plain call.
+template <class... P, class... A>
+int launch_lds(Ctx* c, void (*kernel)(P...), unsigned grid, unsigned nt, unsigned lds_bytes, A&&... args) {
+  AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(nt), lds_bytes, c->stream, std::forward<A>(args)...);
+  return AMHIP_OK;
+}
+
+// What the LDS-tiled gather launches of one dsm_run call share (dsm_run decides, launch_gathers<> launches).
+struct GatherPlan {
+  Ctx* c;
+  const DsmParams& p;
+  PtsView pts;        // what dsm_sort left: doubles, records or both
+  CellOut out;
+  TileLists lists;
+  unsigned ntiles;
+  bool f32;           // single-precision mode
+  bool sparse;        // only the occupied tiles are visited, by a fixed grid walking kListMain
+  bool rej_own;       // the FP64 kernel's image of cap0 points fits a CU: redo tiles go to kListRedoOwn
+  bool rej_dense;     // ... and are taken by a dense launch filtering on occ instead of the list
+  bool skip_classes;  // no class launches: the main launch takes every class
+  int cap0;           // points of the main launch's LDS image
+  int cap1, cap2;     // FP64 images of classes 1, 2
+  int capf1, capf2;   // single-precision images of classes 1, 2
+#ifdef AMHIP_TIMING_PROBES
+  int nt;             // tuning knob gather_nt: threads per gather workgroup (512 measured best)
+  int f32_variant;    // tuning knob f32_variant: timing probes of the 64 x 16 / 1024-point instance
+#endif
+  // p with the LDS image resized to `cap` points: the FP64 kernels' 24-byte records, the
+  // single-precision kernels' 16-byte records
+  DsmParams with_cap(int cap) const {
+    DsmParams q = p;
+    q.lds_cap = cap;
+    q.lds_bytes = (unsigned)((int)p.lds_bytes + (cap - cap0) * 24);
+    return q;
+  }
+  DsmParams with_cap_f32(int cap) const {
+    DsmParams q = p;
+    q.lds_cap = cap;
+    q.lds_bytes_f32 = (unsigned)((int)p.lds_bytes_f32 + (cap - cap0) * 16);
+    return q;
+  }
+};
+
+// FP64 dense launch, one workgroup per tile, over the tiles whose occ says `my_class` (-1: every class)
+template <int NT, int kTileJ, int kCap>
+int launch_fp64_dense(const GatherPlan& g, int my_class) {
+  return launch_lds(g.c, k_dsm_gather_tiled<NT, kTileJ, kCap>, g.ntiles, NT, g.p.lds_bytes, g.p,
+                    g.c->bin_start, g.pts, g.c->tile_occ, g.out, my_class);
+}
+
+// FP64 list launch: `list` with an LDS image of `image_cap` points (kCap sizes the instance's
+// registers; the LDS image holds what fits)
+template <int kTileJ, int kCap>
+int launch_fp64_list(const GatherPlan& g, int image_cap, int list, unsigned grid) {
+  const DsmParams q = g.with_cap(image_cap);
+  return launch_lds(g.c, k_dsm_gather_tiled_sparse<512, kTileJ, kCap>, grid, 512, q.lds_bytes, q,
+                    g.c->bin_start, g.pts, g.c->tile_occ, g.lists.ids(list), g.lists.count(list), g.out);
+}
+
+// Single-precision list launch: `list` with an image of `image_cap` points, register instance kCap;
+// tiles it hands back for their height spread go onto list `redo` (FP64 kernel) or, with more than
+// big_np points, onto kListRedoWaveBlock (with_big false: no such list, every one onto `redo`)
+template <int kTileJ, int kCap>
+int launch_f32_list(const GatherPlan& g, int image_cap, int list, unsigned grid, int redo, bool with_big,
+                    int big_np) {
+  const DsmParams q = g.with_cap_f32(image_cap);
+  const TileLists& l = g.lists;
+  return launch_lds(g.c, k_dsm_gather_f32_list<512, kTileJ, kCap>, grid, 512, q.lds_bytes_f32, q,
+                    g.c->bin_start, g.pts, g.c->tile_occ, l.ids(list), l.count(list), g.out, l.ids(redo),
+                    l.count(redo), with_big ? l.ids(kListRedoWaveBlock) : nullptr,
+                    with_big ? l.count(kListRedoWaveBlock) : nullptr, big_np);
+}
+
+#ifdef AMHIP_TIMING_PROBES
+// (timing probes of the 64 x 16 / 1024-point instance: -DAMHIP_TIMING_PROBES builds only)
+template <int kVar>
+int launch_f32_variant(const GatherPlan& g) {
+  return launch_lds(g.c, k_dsm_gather_f32<512, 16, 1024, kVar>, g.ntiles, 512, g.p.lds_bytes_f32, g.p,
+                    g.c->bin_start, g.pts, g.c->tile_occ, g.out, g.lists.ids(kListRedoOwn),
+                    g.lists.count(kListRedoOwn));
+}
+static int launch_f32_probe(const GatherPlan& g) {
+  switch (g.f32_variant) {
+    case 1: return launch_f32_variant<1>(g);
+    case 2: return launch_f32_variant<2>(g);
+    case 5: return launch_f32_variant<5>(g);
+    default: return launch_f32_variant<6>(g);
+  }
+}
+#endif
+
+// The gather launches of one (tile height, LDS point capacity) shape: the main launch of the call's
+// mode (capped / single precision / sparse / dense), then the capacity-class launches.  The shapes:
+// (16, 1024), (16, 2048), (32, 2048) for every mode, (16, 4096) and (16, 7680) for single-precision
+// mains only; every kernel instance the library holds is named here (or in the probes above).
+template <int kTileJ, int kCap>
+int launch_gathers(const GatherPlan& g) {
+  constexpr bool kWide = kCap > 2048;
+  constexpr int kNoLimit = 0x7FFFFFFF;
+  Ctx* const c = g.c;
+  const DsmParams& p = g.p;
+  const TileLists& l = g.lists;
+  int rc;
+  if (p.knn_k > 0) {
+    // the capped mode: one dense launch over the same LDS image (no capacity classes: a
+    // denser tile takes the global bins cell by cell)
+    // (a set of 4 registers for k <= 4 measured the same as the set of 8: the shift's cost follows k)
+    if constexpr (kWide) {
+      return arg_failure("internal: no capped-mode gather for this tile shape");
+    } else {
+      if (p.tile_j != kTileJ || g.cap0 != kCap)
+        return arg_failure("internal: no capped-mode gather for this tile shape");
+      return launch_lds(c, k_dsm_gather_tiled_knn<512, kTileJ, kCap, kMaxKnn>, g.ntiles, 512, p.lds_bytes, p,
+                        c->bin_start, g.pts, c->tile_occ, g.out);
+    }
+  }
+  if constexpr (kWide) {
+    // (make_dsm_params picks 4096 / 7680 only for the single-precision mode)
+    if (!g.f32) return arg_failure("internal: 4096-point tiles outside the single-precision mode");
+    // (rejected tiles: the FP64 kernel with an image of cap0 points while that fits a CU --
+    // kListRedoOwn --, else its largest image -- kListRedoBig -- or the wave-per-block kernel --
+    // kListRedoWaveBlock)
+    const int redo = g.rej_own ? kListRedoOwn : kListRedoBig;
+    const int big_np = g.rej_own ? kNoLimit : g.cap2;
+    if (g.sparse)
+      rc = launch_f32_list<kTileJ, kCap>(g, g.cap0, kListMain, 8192, redo, true, big_np);
+    else
+      rc = launch_lds(c, k_dsm_gather_f32_wide<512, kTileJ, kCap>, g.ntiles, 512, p.lds_bytes_f32, p,
+                      c->bin_start, g.pts, c->tile_occ, g.out, l.ids(redo), l.count(redo),
+                      l.ids(kListRedoWaveBlock), l.count(kListRedoWaveBlock), big_np);
+    if (rc) return rc;
+    if (g.rej_own && (rc = launch_fp64_list<kTileJ, 4096>(g, g.cap0, kListRedoOwn, 4096))) return rc;
+  } else if (g.f32) {
+    // class-0 tiles in single precision (dense or kListMain), then the tiles it handed back
+    // (kListRedoOwn) through the FP64 kernel
+    if (g.sparse)
+      rc = launch_f32_list<kTileJ, kCap>(g, g.cap0, kListMain, 8192, kListRedoOwn, false, kNoLimit);
+#ifdef AMHIP_TIMING_PROBES
+    else if (g.f32_variant && kTileJ == 16 && kCap == 1024)
+      rc = launch_f32_probe(g);
+#endif
+    else
+      rc = launch_lds(c, k_dsm_gather_f32<512, kTileJ, kCap>, g.ntiles, 512, p.lds_bytes_f32, p, c->bin_start,
+                      g.pts, c->tile_occ, g.out, l.ids(kListRedoOwn), l.count(kListRedoOwn));
+    if (rc) return rc;
+    // the FP64 kernel, one workgroup per tile, over the tiles the pre-pass classified for it
+    // (occ = 1 + kListRedoOwn) and nothing else: hardware dispatch and the XCD-aware order instead of a
+    // fixed grid walking kListRedoOwn (28 ns per tile against 37, and no serial list)
+    if (g.rej_dense && (rc = launch_fp64_dense<512, kTileJ, kCap>(g, kListRedoOwn))) return rc;
+    if ((rc = launch_fp64_list<kTileJ, kCap>(g, g.cap0, kListRedoOwn, 4096))) return rc;
+  } else if (g.sparse) {
+    if ((rc = launch_fp64_list<kTileJ, kCap>(g, g.cap0, kListMain, 8192))) return rc;
+  } else {
+    const int main_class = g.skip_classes ? -1 : 0;
+#ifdef AMHIP_TIMING_PROBES   // (gather_nt: the instances the lab build holds besides the 512-thread ones)
+    constexpr bool kHas256 = kCap == 1024 || kTileJ == 32, kHas1024 = kTileJ == 32;
+    if (kHas256 && g.nt == 256) {
+      if constexpr (kHas256) rc = launch_fp64_dense<256, kTileJ, kCap>(g, main_class);
+    } else if (kHas1024 && g.nt == 1024) {
+      if constexpr (kHas1024) rc = launch_fp64_dense<1024, kTileJ, kCap>(g, main_class);
+    } else
+#endif
+      rc = launch_fp64_dense<512, kTileJ, kCap>(g, main_class);
+    if (rc) return rc;
+  }
+  if (g.skip_classes) return AMHIP_OK;  // (nothing: the main launch took every class)
+  if (g.f32) {
+    // single-precision list launches of classes 1, 2: images of capf1 / capf2 points; rejected
+    // tiles -> kListRedoBig (FP64, image cap2) / kListRedoWaveBlock (wave per block)
+    if ((rc = launch_f32_list<kTileJ, 4096>(g, g.capf1, kListClass1, 2048, kListRedoBig, true, g.cap2))) return rc;
+    if ((rc = launch_f32_list<kTileJ, 7680>(g, g.capf2, kListClass2, 1024, kListRedoBig, true, g.cap2))) return rc;
+    return launch_fp64_list<kTileJ, kTileJ == 16 ? 5600 : 5200>(g, g.cap2, kListRedoBig, 1024);
+  }
+  constexpr int kCap1 = kTileJ == 16 ? 2752 : 2432, kCap2 = kTileJ == 16 ? 5600 : 5200;
+  if ((rc = launch_fp64_list<kTileJ, kCap1>(g, std::min(kCap1, g.cap1), kListClass1, 2048))) return rc;
+  return launch_fp64_list<kTileJ, kCap2>(g, std::min(kCap2, g.cap2), kListClass2, 1024);
+}
+
+// (tile height, LDS point capacity) picked by make_dsm_params from the
+// cloud's mean density: 64x16 / 1024 points runs 4 workgroups per CU
+typedef int (*GatherLauncher)(const GatherPlan&);
+static GatherLauncher gather_launcher(int tile_j, int cap0) {
+  if (tile_j == 16 && cap0 == 1024) return launch_gathers<16, 1024>;
+  if (tile_j == 16 && cap0 > 2048) return cap0 == 4096 ? launch_gathers<16, 4096> : launch_gathers<16, 7680>;
+  if (tile_j == 16) return launch_gathers<16, 2048>;
+  return launch_gathers<32, 2048>;
+}
+
 int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
             const DsmParams& p, float* out, unsigned char* mask, unsigned* unfilled,
             bool fill_untouched, float init_value, unsigned long long* zrange,
@@ -2329,14 +2530,14 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
                                   kNumLists * (size_t)ntiles + kListHdr)))
           return rc;
       }
-      unsigned* tile_count = reinterpret_cast<unsigned*>(c->tile_list);
-      int* const lists = c->tile_list;
+      const TileLists lists = {c->tile_list, ntiles};
       const bool f32 = p.fx_ok && !p.pcl_mode && !p.only_unfilled && !mask && !unfilled;
       // Single-precision mode: its records take 16 bytes against the FP64 kernel's 24, so the
       // same two LDS budgets (two workgroups per CU / one) hold more points: classes 1 and 2
       // are cut at capf1 / capf2 and walked by list launches of the single-precision kernel
       // (4096- / 7680-point register instances); what those hand back goes to the FP64
-      // kernel's largest image (list 5) or, beyond it, to the wave-per-block kernel (list 6).
+      // kernel's largest image (kListRedoBig) or, beyond it, to the wave-per-block kernel
+      // (kListRedoWaveBlock).
       const long fixed32 = (long)p.lds_bytes_f32 - ((long)cap0 + 2) * 16;
       auto cap_fit32 = [&](long limit) { return (int)((limit - fixed32) / 16 - 2) & ~1; };
       const int capf1 = std::max(cap0, std::min(4096, cap_fit32(80 * 1024)));
@@ -2349,8 +2550,8 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
 #endif
       // single-precision mode after the three-pass sort: tiles whose height range leaves no room
       // under the error bound go straight onto the FP64 list the kernel would hand them to --
-      // list 4 while the FP64 kernel's image of cap0 points fits a CU (rej_own), else list 5, or
-      // list 6 beyond its largest image
+      // kListRedoOwn while the FP64 kernel's image of cap0 points fits a CU (rej_own), else
+      // kListRedoBig, or kListRedoWaveBlock beyond its largest image
       const bool rej_own = cap0 <= 2048 || ((long)cap0 + 2) * 24 + fixed_bytes <= 150 * 1024;
       const uint2* bin_z = (f32 && c->bin_z_valid) ? reinterpret_cast<const uint2*>(c->bin_z) : nullptr;
       c->last_call_f32 = bin_z != nullptr;  // (its tile counters say how rough the scene is)
@@ -2364,7 +2565,8 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
       bool rej_dense = false;
       if (bin_z && cap0 <= 2048 && !sparse && c->host_tile_stats && prev_ntiles > 0) {
         const volatile unsigned* hs = c->host_tile_stats;
-        const double rejected = (double)hs[4] + (double)hs[5] + (double)hs[6] + (double)hs[7];
+        const double rejected = (double)hs[kListRedoOwn] + (double)hs[kListRedoBig] +
+                                (double)hs[kListRedoWaveBlock] + (double)hs[kStatRedoUnlisted];
         rej_dense = rejected * 10.0 > (double)prev_ntiles;
       }
       // The capacity-class launches behind the main one (denser tiles: classes 1, 2, the wave-per-
@@ -2376,10 +2578,9 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
       for (const int v : {p.rows, p.cols, p.i_off, p.j_off, p.tile_j, p.lds_cap, p.B, p.M, p.w[0], p.pcl_mode, cap1, cap2})
         tsig = (tsig ^ (unsigned long long)(unsigned)v) * 1099511628211ull;
       const volatile unsigned* hst = c->host_tile_stats;
-      const bool skip_classes = !f32 && !sparse && hst && c->tile_stats_sig == tsig && hst[1] == 0u && hst[2] == 0u &&
-                                hst[3] == 0u && !no_launch_skips();
+      const bool skip_classes = !f32 && !sparse && hst && c->tile_stats_sig == tsig && hst[kListClass1] == 0u &&
+                                hst[kListClass2] == 0u && hst[kListWaveBlock] == 0u && !no_launch_skips();
       c->tile_stats_sig = tsig;
-      const int main_class = skip_classes ? -1 : 0;
       ProloguePart pp;
       pp.zpart = c->range_parts ? c->zpart : nullptr;
       pp.nparts = c->range_parts;
@@ -2388,258 +2589,44 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
       pp.nocc = (ntiles + 255) / 256;
       pp.nrange = c->range_parts ? 32u : 0u;
       pp.ticket = c->dev_tickets + 1;
-      // (single-precision mode: its gather kernels still append to lists 4 .. 6 -- copied at the end)
+      // (single-precision mode: its gather kernels still append to the redo lists -- copied at the end)
       pp.host_stats = f32 ? nullptr : c->host_tile_stats;
       c->range_parts = 0;
       hipLaunchKernelGGL(k_dsm_tile_occupancy, dim3(pp.nocc + pp.nrange), dim3(256), 0, c->stream,
-                         p, p.tile_j, c->bin_start, c->tile_occ, lists, sparse ? 1 : 0, ccap0, ccap1, ccap2,
+                         p, p.tile_j, c->bin_start, c->tile_occ, lists.base, sparse ? 1 : 0, ccap0, ccap1, ccap2,
                          bin_z, rej_own ? 1 : 0, cap2, rej_dense ? 1 : 0, pts_view.zref, pp);
+      GatherPlan plan = {c, p, pts_view, cell_out, lists, ntiles, f32, sparse, rej_own, rej_dense, skip_classes,
+                         cap0, cap1, cap2, capf1, capf2};
+#ifdef AMHIP_TIMING_PROBES
+      plan.nt = (int)tuning("gather_nt", 512.0);
+      plan.f32_variant = (int)tuning("f32_variant", 0.0);
+#endif
+      {
+        const int rc = gather_launcher(p.tile_j, cap0)(plan);
+        if (rc) return rc;
+      }
       if (p.knn_k > 0) {
-        // the capped mode: one dense launch over the same LDS image (no capacity classes: a
-        // denser tile takes the global bins cell by cell)
-#define AMHIP_LAUNCH_KNN_(TJ_, CAP_, SET_)                                                       \
-  do {                                                                                        \
-    AMHIP_TRY(hipFuncSetAttribute(                                                            \
-        reinterpret_cast<const void*>(k_dsm_gather_tiled_knn<512, TJ_, CAP_, SET_>),          \
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));                       \
-    hipLaunchKernelGGL((k_dsm_gather_tiled_knn<512, TJ_, CAP_, SET_>), dim3(ntiles), dim3(512), \
-                       p.lds_bytes, c->stream, p, c->bin_start, pts_view, c->tile_occ,       \
-                       cell_out);                                                             \
-  } while (0)
-  // (a set of 4 registers for k <= 4 measured the same as the set of 8: the shift's cost follows k)
-#define AMHIP_LAUNCH_KNN(TJ_, CAP_) AMHIP_LAUNCH_KNN_(TJ_, CAP_, kMaxKnn)
-        if (p.tile_j == 16 && cap0 == 1024) AMHIP_LAUNCH_KNN(16, 1024);
-        else if (p.tile_j == 16 && cap0 == 2048) AMHIP_LAUNCH_KNN(16, 2048);
-        else if (p.tile_j == 32 && cap0 == 2048) AMHIP_LAUNCH_KNN(32, 2048);
-        else return arg_failure("internal: no capped-mode gather for this tile shape");
-#undef AMHIP_LAUNCH_KNN
-#undef AMHIP_LAUNCH_KNN_
         AMHIP_TRY(hipGetLastError());
+        // (known wart, ADVICE: this return leaves host_tile_stats as the previous call wrote them;
+        // the follow-up that refreshes them for the capped mode removes it -- not this change)
         return AMHIP_OK;
       }
-      // tuning knob gather_nt: threads per gather workgroup (tuning knob; 512 measured best)
-#ifdef AMHIP_TIMING_PROBES
-      const int nt = (int)tuning("gather_nt", 512.0);
-#else
-      constexpr int nt = 512;
-      (void)nt;
-#endif
-      auto with_cap = [&](int cap) {
-        DsmParams q = p;
-        q.lds_cap = cap;
-        q.lds_bytes = (unsigned)((int)p.lds_bytes + (cap - cap0) * 24);
-        return q;
-      };
-#define AMHIP_LAUNCH_DENSE(NT_, TJ_, CAP_)                                                    \
-  do {                                                                                        \
-    AMHIP_TRY(hipFuncSetAttribute(                                                            \
-        reinterpret_cast<const void*>(k_dsm_gather_tiled<NT_, TJ_, CAP_>),                    \
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));                       \
-    hipLaunchKernelGGL((k_dsm_gather_tiled<NT_, TJ_, CAP_>), dim3(ntiles), dim3(NT_),         \
-                       p.lds_bytes, c->stream, p, c->bin_start, pts_view, c->tile_occ,       \
-                       cell_out, main_class);                                                 \
-  } while (0)
-      // the FP64 kernel, one workgroup per tile, over the tiles the pre-pass classified for it
-      // (occ = 1 + 4) and nothing else: hardware dispatch and the XCD-aware order instead of a
-      // fixed grid walking list 4 (28 ns per tile against 37, and no serial list)
-#define AMHIP_LAUNCH_REJECTED_DENSE(TJ_, CAP_)                                                \
-  do {                                                                                        \
-    const DsmParams q = with_cap(cap0);                                                       \
-    AMHIP_TRY(hipFuncSetAttribute(                                                            \
-        reinterpret_cast<const void*>(k_dsm_gather_tiled<512, TJ_, CAP_>),                    \
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds_bytes));                       \
-    hipLaunchKernelGGL((k_dsm_gather_tiled<512, TJ_, CAP_>), dim3(ntiles), dim3(512),         \
-                       q.lds_bytes, c->stream, q, c->bin_start, pts_view, c->tile_occ,       \
-                       cell_out, 4);                                                          \
-  } while (0)
-      // FP64 list launch: list LIST_ with an LDS image of CAPV_ points (CAP_ sizes the
-      // instance's registers; the LDS image holds what fits)
-#define AMHIP_LAUNCH_LIST_EX(NT_, TJ_, CAP_, CAPV_, LIST_, GRID_)                             \
-  do {                                                                                        \
-    const DsmParams q = with_cap(CAPV_);                                                      \
-    AMHIP_TRY(hipFuncSetAttribute(                                                            \
-        reinterpret_cast<const void*>(k_dsm_gather_tiled_sparse<NT_, TJ_, CAP_>),             \
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds_bytes));                       \
-    hipLaunchKernelGGL((k_dsm_gather_tiled_sparse<NT_, TJ_, CAP_>), dim3(GRID_), dim3(NT_),   \
-                       q.lds_bytes, c->stream, q, c->bin_start, pts_view, c->tile_occ,       \
-                       lists + kListHdr + (size_t)(LIST_) * ntiles, tile_count + (LIST_),     \
-                       cell_out);                                                             \
-  } while (0)
-#define AMHIP_LAUNCH_LIST(NT_, TJ_, CAP_, CLS_, GRID_)                                        \
-  AMHIP_LAUNCH_LIST_EX(NT_, TJ_, CAP_,                                                        \
-                       ((CLS_) == 0 ? cap0 : std::min((int)(CAP_), (CLS_) == 1 ? cap1 : cap2)), \
-                       CLS_, GRID_)
-      // class-0 tiles in single precision (dense or list 0), then the tiles it handed back
-      // (list 4) through the FP64 kernel
-#define AMHIP_LAUNCH_F32(TJ_, CAP_)                                                           \
-  do {                                                                                        \
-    int* const xl = lists + kListHdr + (size_t)4 * ntiles;                                    \
-    if (sparse) {                                                                             \
-      AMHIP_TRY(hipFuncSetAttribute(                                                          \
-          reinterpret_cast<const void*>(k_dsm_gather_f32_list<512, TJ_, CAP_>),               \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes_f32));                 \
-      hipLaunchKernelGGL((k_dsm_gather_f32_list<512, TJ_, CAP_>), dim3(8192), dim3(512),      \
-                         p.lds_bytes_f32, c->stream, p, c->bin_start, pts_view, c->tile_occ, \
-                         lists + kListHdr, tile_count, cell_out, xl, tile_count + 4,          \
-                         (int*)nullptr, (unsigned*)nullptr, 0x7FFFFFFF);                      \
-    } else if (AMHIP_PROBE_SELECTED(TJ_, CAP_)) {                                             \
-      AMHIP_F32_DENSE(16, 1024, f32_variant);                                                 \
-    } else {                                                                                  \
-      AMHIP_TRY(hipFuncSetAttribute(                                                          \
-          reinterpret_cast<const void*>(k_dsm_gather_f32<512, TJ_, CAP_>),                    \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes_f32));                 \
-      hipLaunchKernelGGL((k_dsm_gather_f32<512, TJ_, CAP_>), dim3(ntiles), dim3(512),         \
-                         p.lds_bytes_f32, c->stream, p, c->bin_start, pts_view, c->tile_occ, \
-                         cell_out, xl, tile_count + 4);                                       \
-    }                                                                                         \
-    if (rej_dense) AMHIP_LAUNCH_REJECTED_DENSE(TJ_, CAP_);                                    \
-    AMHIP_LAUNCH_LIST_EX(512, TJ_, CAP_, cap0, 4, 4096);                                      \
-  } while (0)
-      // (rejected tiles: the FP64 kernel with an image of cap0 points while that fits a CU --
-      // list 4 --, else its largest image -- list 5 -- or the wave-per-block kernel -- list 6)
-#define AMHIP_LAUNCH_F32_WIDE(TJ_, CAP_)                                                      \
-  do {                                                                                        \
-    const bool own = ((long)cap0 + 2) * 24 + fixed_bytes <= 150 * 1024;                       \
-    int* const xl = lists + kListHdr + (size_t)(own ? 4 : 5) * ntiles;                        \
-    unsigned* const xc = tile_count + (own ? 4 : 5);                                          \
-    int* const bl = lists + kListHdr + (size_t)6 * ntiles;                                    \
-    const int bnp = own ? 0x7FFFFFFF : cap2;                                                  \
-    if (sparse) {                                                                             \
-      AMHIP_TRY(hipFuncSetAttribute(                                                          \
-          reinterpret_cast<const void*>(k_dsm_gather_f32_list<512, TJ_, CAP_>),               \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes_f32));                 \
-      hipLaunchKernelGGL((k_dsm_gather_f32_list<512, TJ_, CAP_>), dim3(8192), dim3(512),      \
-                         p.lds_bytes_f32, c->stream, p, c->bin_start, pts_view, c->tile_occ, \
-                         lists + kListHdr, tile_count, cell_out, xl, xc, bl, tile_count + 6,  \
-                         bnp);                                                                \
-    } else {                                                                                  \
-      AMHIP_TRY(hipFuncSetAttribute(                                                          \
-          reinterpret_cast<const void*>(k_dsm_gather_f32_wide<512, TJ_, CAP_>),               \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes_f32));                 \
-      hipLaunchKernelGGL((k_dsm_gather_f32_wide<512, TJ_, CAP_>), dim3(ntiles), dim3(512),    \
-                         p.lds_bytes_f32, c->stream, p, c->bin_start, pts_view, c->tile_occ, \
-                         cell_out, xl, xc, bl, tile_count + 6, bnp);                          \
-    }                                                                                         \
-    if (own) AMHIP_LAUNCH_LIST_EX(512, TJ_, 4096, cap0, 4, 4096);                             \
-  } while (0)
-#ifdef AMHIP_TIMING_PROBES
-      const int f32_variant = (int)tuning("f32_variant", 0.0);
-#define AMHIP_PROBE_SELECTED(TJ_, CAP_) (f32_variant && (TJ_) == 16 && (CAP_) == 1024)
-#else
-      constexpr int f32_variant = 0;
-      (void)f32_variant;
-#define AMHIP_PROBE_SELECTED(TJ_, CAP_) false
-#endif
-      // (timing probes of the 64 x 16 / 1024-point instance: -DAMHIP_TIMING_PROBES builds only)
-#define AMHIP_F32_DENSE_V(V_)                                                                 \
-  do {                                                                                        \
-    AMHIP_TRY(hipFuncSetAttribute(                                                            \
-        reinterpret_cast<const void*>(k_dsm_gather_f32<512, 16, 1024, V_>),                   \
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes_f32));                   \
-    hipLaunchKernelGGL((k_dsm_gather_f32<512, 16, 1024, V_>), dim3(ntiles), dim3(512),        \
-                       p.lds_bytes_f32, c->stream, p, c->bin_start, pts_view, c->tile_occ,   \
-                       cell_out, lists + kListHdr + (size_t)4 * ntiles, tile_count + 4);      \
-  } while (0)
-#ifdef AMHIP_TIMING_PROBES
-#define AMHIP_F32_DENSE(TJ_, CAP_, VAR_)                                                      \
-  do {                                                                                        \
-    if ((VAR_) == 1) AMHIP_F32_DENSE_V(1);                                                    \
-    else if ((VAR_) == 2) AMHIP_F32_DENSE_V(2);                                               \
-    else if ((VAR_) == 5) AMHIP_F32_DENSE_V(5);                                               \
-    else AMHIP_F32_DENSE_V(6);                                                                \
-  } while (0)
-#else
-#define AMHIP_F32_DENSE(TJ_, CAP_, VAR_) do { } while (0)
-#endif
-      // (tile height, LDS point capacity) picked by make_dsm_params from the
-      // cloud's mean density: 64x16 / 1024 points runs 4 workgroups per CU
-      // single-precision list launch of class CLS_ (1, 2): image of CAPV_ points, register
-      // instance CAP_; rejected tiles -> list 5 (FP64, image cap2) / list 6 (wave per block)
-#define AMHIP_LAUNCH_F32_CLASS(TJ_, CAP_, CAPV_, CLS_, GRID_)                                 \
-  do {                                                                                        \
-    DsmParams q = p;                                                                          \
-    q.lds_cap = (CAPV_);                                                                      \
-    q.lds_bytes_f32 = (unsigned)((int)p.lds_bytes_f32 + ((CAPV_) - cap0) * 16);               \
-    AMHIP_TRY(hipFuncSetAttribute(                                                            \
-        reinterpret_cast<const void*>(k_dsm_gather_f32_list<512, TJ_, CAP_>),                 \
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds_bytes_f32));                   \
-    hipLaunchKernelGGL((k_dsm_gather_f32_list<512, TJ_, CAP_>), dim3(GRID_), dim3(512),       \
-                       q.lds_bytes_f32, c->stream, q, c->bin_start, pts_view, c->tile_occ,   \
-                       lists + kListHdr + (size_t)(CLS_) * ntiles, tile_count + (CLS_),       \
-                       cell_out, lists + kListHdr + (size_t)5 * ntiles, tile_count + 5,       \
-                       lists + kListHdr + (size_t)6 * ntiles, tile_count + 6, cap2);          \
-  } while (0)
-      if (p.tile_j == 16 && cap0 == 1024) {
-        if (f32) AMHIP_LAUNCH_F32(16, 1024);
-        else if (sparse) AMHIP_LAUNCH_LIST(512, 16, 1024, 0, 8192);
-#ifdef AMHIP_TIMING_PROBES
-        else if (nt == 256) AMHIP_LAUNCH_DENSE(256, 16, 1024);
-#endif
-        else AMHIP_LAUNCH_DENSE(512, 16, 1024);
-      } else if (p.tile_j == 16 && cap0 > 2048) {
-        // (make_dsm_params picks 4096 / 7680 only for the single-precision mode)
-        if (!f32) return arg_failure("internal: 4096-point tiles outside the single-precision mode");
-        if (cap0 == 4096) AMHIP_LAUNCH_F32_WIDE(16, 4096);
-        else AMHIP_LAUNCH_F32_WIDE(16, 7680);
-      } else if (p.tile_j == 16) {
-        if (f32) AMHIP_LAUNCH_F32(16, 2048);
-        else if (sparse) AMHIP_LAUNCH_LIST(512, 16, 2048, 0, 8192);
-        else AMHIP_LAUNCH_DENSE(512, 16, 2048);
-      } else {
-        if (f32) AMHIP_LAUNCH_F32(32, 2048);
-        else if (sparse) AMHIP_LAUNCH_LIST(512, 32, 2048, 0, 8192);
-#ifdef AMHIP_TIMING_PROBES
-        else if (nt == 256) AMHIP_LAUNCH_DENSE(256, 32, 2048);
-        else if (nt == 1024) AMHIP_LAUNCH_DENSE(1024, 32, 2048);
-#endif
-        else AMHIP_LAUNCH_DENSE(512, 32, 2048);
-      }
-      if (skip_classes) {
-        // (nothing: the main launch took every class)
-      } else if (p.tile_j == 16) {
-        if (f32) {
-          AMHIP_LAUNCH_F32_CLASS(16, 4096, capf1, 1, 2048);
-          AMHIP_LAUNCH_F32_CLASS(16, 7680, capf2, 2, 1024);
-          AMHIP_LAUNCH_LIST_EX(512, 16, 5600, cap2, 5, 1024);
-        } else {
-          AMHIP_LAUNCH_LIST(512, 16, 2752, 1, 2048);
-          AMHIP_LAUNCH_LIST(512, 16, 5600, 2, 1024);
-        }
-      } else {
-        if (f32) {
-          AMHIP_LAUNCH_F32_CLASS(32, 4096, capf1, 1, 2048);
-          AMHIP_LAUNCH_F32_CLASS(32, 7680, capf2, 2, 1024);
-          AMHIP_LAUNCH_LIST_EX(512, 32, 5200, cap2, 5, 1024);
-        } else {
-          AMHIP_LAUNCH_LIST(512, 32, 2432, 1, 2048);
-          AMHIP_LAUNCH_LIST(512, 32, 5200, 2, 1024);
-        }
-      }
-#undef AMHIP_LAUNCH_F32_CLASS
-#undef AMHIP_LAUNCH_DENSE
-#undef AMHIP_LAUNCH_LIST
-#undef AMHIP_LAUNCH_LIST_EX
-#undef AMHIP_LAUNCH_F32
-#undef AMHIP_LAUNCH_F32_WIDE
-#undef AMHIP_F32_DENSE
-#undef AMHIP_F32_DENSE_V
-#undef AMHIP_PROBE_SELECTED
       if (f32)
         hipLaunchKernelGGL(k_dsm_gather_dense<true>, dim3(4096), dim3(256), 0, c->stream, p, p.tile_j,
-                           c->bin_start, pts_view, lists + kListHdr + (size_t)3 * ntiles,
-                           tile_count + 3, cell_out);
+                           c->bin_start, pts_view, lists.ids(kListWaveBlock), lists.count(kListWaveBlock),
+                           cell_out);
       else if (!skip_classes)
         hipLaunchKernelGGL(k_dsm_gather_dense<false>, dim3(4096), dim3(256), 0, c->stream, p, p.tile_j,
-                           c->bin_start, pts_view, lists + kListHdr + (size_t)3 * ntiles,
-                           tile_count + 3, cell_out);
-      // (list 6: tiles the single-precision list launches handed back for their height spread)
+                           c->bin_start, pts_view, lists.ids(kListWaveBlock), lists.count(kListWaveBlock),
+                           cell_out);
+      // (tiles the single-precision list launches handed back for their height spread)
       if (f32)
         hipLaunchKernelGGL(k_dsm_gather_dense<false>, dim3(1024), dim3(256), 0, c->stream, p, p.tile_j,
-                           c->bin_start, pts_view, lists + kListHdr + (size_t)6 * ntiles,
-                           tile_count + 6, cell_out);
+                           c->bin_start, pts_view, lists.ids(kListRedoWaveBlock),
+                           lists.count(kListRedoWaveBlock), cell_out);
       // (what the next call's choice between list and dense launch reads; never waited for)
       if (c->host_tile_stats && f32)   // (FP64 pipeline: the prologue's last workgroup wrote them)
-        AMHIP_TRY(hipMemcpyAsync(c->host_tile_stats, tile_count, kListHdr * sizeof(unsigned),
+        AMHIP_TRY(hipMemcpyAsync(c->host_tile_stats, lists.count(0), kListHdr * sizeof(unsigned),
                                  hipMemcpyDeviceToHost, c->stream));
     } else {
       if (c->range_parts) {
