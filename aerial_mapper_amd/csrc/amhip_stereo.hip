@@ -427,6 +427,12 @@ static void launch_paths(Ctx* c, const SgbmDims& p, const uint16_t* C, int32_t* 
 
 static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
+// The CV_16S map stores 16 * d: the invalid marker (min_disparity - 1) * 16 and the largest value
+// (below (min_disparity + num_disparities) * 16, the subpixel term included) must fit an int16.
+static bool cv16s_holds(int min_disparity, int num_disparities) {
+  return (min_disparity - 1) * 16 >= -32768 && (min_disparity + num_disparities) * 16 <= 32767;
+}
+
 // ---- block matching (OpenCV's StereoBM, PREFILTER_XSOBEL, 8UC1): tests/bm_reference.py -------
 //   k_bm_prefilter  per pixel: prefilterXSobel of both images (rows in pairs, an odd last row and
 //                   the border columns = cap) -> scratch; FILTERED outside the matched region
@@ -619,6 +625,12 @@ int amhip_sgbm_disparity_dev(amhip_ctx* h, const amhip_sgbm_params* q, int width
   if (q->min_disparity < -4096 || q->min_disparity > 4096 || q->pre_filter_cap > 63 ||
       q->uniqueness_ratio > 100 || q->p1 > 4096 || q->p2 > 4096)
     return arg_failure("amhip_sgbm_disparity_dev: parameter out of range");
+  if (!cv16s_holds(q->min_disparity, q->num_disparities))
+    return arg_failure("amhip_sgbm_disparity_dev: the CV_16S map cannot hold this disparity range: "
+                       "min_disparity must be >= -2047 and min_disparity + num_disparities <= 2047");
+  // (the map's values span less than 2^16, so every range >= 4096 acts alike; 16 * range must fit an int)
+  if (q->speckle_range < -4096 || q->speckle_range > 4096)
+    return arg_failure("amhip_sgbm_disparity_dev: speckle_range must be in [-4096, 4096]");
   if (left_step < (size_t)width || right_step < (size_t)width ||
       (dev_mask && mask_step < (size_t)width) || disp_step < (size_t)width * sizeof(float) ||
       (dev_raw && raw_step < (size_t)width * sizeof(int16_t)))
@@ -752,6 +764,9 @@ int amhip_bm_disparity_dev(amhip_ctx* h, const amhip_bm_params* q, int width, in
     return arg_failure("amhip_bm_disparity_dev: uniqueness_ratio must be >= 0");
   if (q->min_disparity < -4096 || q->min_disparity > 4096)
     return arg_failure("amhip_bm_disparity_dev: min_disparity must be in [-4096, 4096]");
+  if (!cv16s_holds(q->min_disparity, q->num_disparities))
+    return arg_failure("amhip_bm_disparity_dev: the CV_16S map cannot hold this disparity range: "
+                       "min_disparity must be >= -2047 and min_disparity + num_disparities <= 2047");
   if (left_step < (size_t)width || right_step < (size_t)width ||
       (dev_mask && mask_step < (size_t)width) || disp_step < (size_t)width * sizeof(float) ||
       (dev_raw && raw_step < (size_t)width * sizeof(int16_t)))

@@ -529,7 +529,11 @@ void amhip_sgbm_default_params(amhip_sgbm_params* out);
  * dev_disparity: float rows disp_step bytes apart, the map as the wrapper leaves it (CV_16S / 16,
  * masked); dev_raw (NULL: not wanted): StereoSGBM::compute's CV_16S map (16 * disparity, invalid =
  * (min_disparity - 1) * 16), raw_step bytes apart.  num_disparities: a multiple of 16 up to 256;
- * block_size: odd, up to 11 (0: OpenCV's 5); width and height up to 32767.  The rules are those of
+ * block_size: odd, up to 11 (0: OpenCV's 5); width and height up to 32767.  min_disparity >= -2047
+ * and min_disparity + num_disparities <= 2047: the CV_16S map must hold the invalid marker and
+ * 16 * the largest disparity, the subpixel term included (nothing wraps inside that range; outside
+ * it the call is AMHIP_ERR_ARG).  speckle_range in [-4096, 4096] (the map spans less than 2^16, so
+ * every range from 4096 on acts alike; a negative one joins nothing).  The rules are those of
  * tests/sgbm_reference.py, reproduced bit for bit (parity with OpenCV itself is unpinned).
  * Scratch (about 6 bytes per pixel and disparity) belongs to the context and is kept between calls.
  * Asynchronous on the context's stream. */
@@ -559,8 +563,10 @@ void amhip_bm_default_params(amhip_bm_params* out);
  * mask (0 -> kMaxInvalidDisparity = 1.0f), the float map (CV_16S / 16, masked) and the optional
  * StereoBM::compute CV_16S map (16 * disparity, FILTERED = (min_disparity - 1) * 16).
  * num_disparities: a multiple of 16 up to 256; block_size: odd, in [5, 31], <= min(width, height);
- * pre_filter_size in [1, 63]; texture_threshold, uniqueness_ratio >= 0; min_disparity in
- * [-4096, 4096]; width and height in [1, 32767].  The rules are those of tests/bm_reference.py,
+ * pre_filter_size in [1, 63]; texture_threshold, uniqueness_ratio >= 0; min_disparity >= -2047 and
+ * min_disparity + num_disparities <= 2047 (what the CV_16S map can hold: FILTERED and 16 * the
+ * largest disparity with its subpixel term; nothing wraps inside that range, outside it the call
+ * is AMHIP_ERR_ARG); width and height in [1, 32767].  The rules are those of tests/bm_reference.py,
  * reproduced bit for bit (parity with OpenCV itself is unpinned).  Scratch (about 16 bytes per
  * pixel, no cost volume) is the context's stereo scratch, shared with the SGBM matcher.
  * Asynchronous on the context's stream. */

@@ -89,6 +89,13 @@ def test_argument_errors_without_a_gpu(L):
     assert "uniqueness_ratio" in err(q=with_(uniqueness_ratio=-1))
     for m in (-4097, 4097):
         assert "min_disparity" in err(q=with_(min_disparity=m))
+    # the CV_16S map holds (min_disparity - 1) * 16 >= -32768 and (min_disparity + D) * 16 <= 32767
+    for D, first_bad, last_ok in ((16, 2032, 2031), (256, 1792, 1791), (16, -2048, -2047),
+                                  (256, -2048, -2047)):
+        assert "CV_16S" in err(q=with_(num_disparities=D, min_disparity=first_bad))
+        assert "null context" in err(q=with_(num_disparities=D, min_disparity=last_ok))
+    # BM passes speckle_range on unscaled: nothing to overflow, any value is accepted
+    assert "null context" in err(q=with_(speckle_range=2 ** 31 - 1))
     for W, H in ((0, 32), (64, 0), (32768, 32), (64, 32768)):
         assert "width and height" in err(W=W, H=H)
     assert "step" in err(ls=63)

@@ -62,6 +62,34 @@ def test_argument_errors_without_a_gpu(L):
     assert "block_size" in err(q=bad)
     bad.block_size = 13
     assert "block_size" in err(q=bad)
+    def with_(**kw):
+        q = L.SgbmParams.from_buffer_copy(bytes(p))
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+    for b_ in (2, 4, 6, 10, 12, 13, 15):
+        assert "block_size" in err(q=with_(block_size=b_))
+    assert "multiple of 16" in err(q=with_(num_disparities=272))
+    assert "multiple of 16" in err(q=with_(num_disparities=-16))
+    for kw in (dict(pre_filter_cap=64), dict(p1=4097), dict(p2=4097), dict(uniqueness_ratio=101),
+               dict(min_disparity=4097), dict(min_disparity=-4097)):
+        assert "out of range" in err(q=with_(**kw))
+    assert "width" in err(W=2, ls=2, rs=2, ds=8)
+    assert "half the block" in err(W=85, ls=85, rs=85, ds=340)   # w1 = 85 - 81 = 4 = block_size / 2
+    # the last accepted value of each passes on to the context check
+    for kw in (dict(pre_filter_cap=63), dict(p1=4096, p2=4096), dict(uniqueness_ratio=100),
+               dict(block_size=11), dict(block_size=0), dict(num_disparities=256),
+               dict(speckle_range=4096), dict(speckle_range=-4096)):
+        assert "null context" in err(q=with_(**kw))
+    # the CV_16S map holds (min_disparity - 1) * 16 >= -32768 and (min_disparity + D) * 16 <= 32767
+    for D, first_bad, last_ok in ((16, 2032, 2031), (256, 1792, 1791), (16, -2048, -2047),
+                                  (256, -2048, -2047)):
+        assert "CV_16S" in err(q=with_(num_disparities=D, min_disparity=first_bad))
+        assert "null context" in err(q=with_(num_disparities=D, min_disparity=last_ok), W=4800, ls=4800,
+                                     rs=4800, ds=19200)
+    for v in (4097, -4097, 2 ** 27, 2 ** 31 - 1, -2 ** 31):
+        assert "speckle_range" in err(q=with_(speckle_range=v))
     assert "step" in err(ls=63)
     assert "step" in err(rs=10)
     assert "step" in err(ds=255)
