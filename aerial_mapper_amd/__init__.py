@@ -10,9 +10,10 @@ from .hip_lib import (AmhipError, Camera, GridDesc, DIST_EQUIDISTANT, DIST_NONE,
 from .mapper import (AerialGridMap, Dsm, DsmSettings, GridMapSettings, HostSession, NCamera,  # noqa: F401
                      OrthoBackwardGrid, OrthoForwardHomography, OrthoForwardHomographySettings,
                      OrthoFromPcl, OrthoFromPclSettings, OrthoSettings, SgbmParameters, BmParameters,
-                     BlockMatchingParameters, compose_T_G_C, compute_disparity_sgbm, compute_disparity_bm, densify, dense_cloud_from_stereo_pair, rectify_stereo_pair)
+                     BlockMatchingParameters, compose_T_G_C, compute_disparity_sgbm, compute_disparity_bm, densify, dense_cloud_from_stereo_pair, rectify_stereo_pair,
+                     Stereo, StereoSettings)
 
 __all__ = ["AerialGridMap", "GridMapSettings", "HostSession", "Dsm", "DsmSettings", "OrthoBackwardGrid",
-           "OrthoSettings", "OrthoForwardHomography", "OrthoForwardHomographySettings", "OrthoFromPcl", "OrthoFromPclSettings", "NCamera", "compose_T_G_C", "densify", "rectify_stereo_pair", "SgbmParameters", "compute_disparity_sgbm", "BmParameters", "BlockMatchingParameters", "compute_disparity_bm", "dense_cloud_from_stereo_pair", "AmhipError", "Camera", "GridDesc",
+           "OrthoSettings", "OrthoForwardHomography", "OrthoForwardHomographySettings", "OrthoFromPcl", "OrthoFromPclSettings", "NCamera", "compose_T_G_C", "densify", "rectify_stereo_pair", "SgbmParameters", "compute_disparity_sgbm", "BmParameters", "BlockMatchingParameters", "compute_disparity_bm", "dense_cloud_from_stereo_pair", "Stereo", "StereoSettings", "AmhipError", "Camera", "GridDesc",
            "make_grid", "cell_position", "LAYER_NAMES", "DIST_NONE", "DIST_RADTAN",
            "DIST_EQUIDISTANT"]

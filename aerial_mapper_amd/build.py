@@ -22,7 +22,7 @@ OBJ_DIR = os.path.join(ROOT, "build", "hip_obj")
 
 HIP_SOURCES = ["amhip_api.hip", "amhip_sort.hip", "amhip_dsm.hip", "amhip_ortho.hip", "amhip_densify.hip",
                "amhip_forward.hip", "amhip_io.hip", "amhip_session.hip", "amhip_rectify.hip", "amhip_export.hip",
-               "amhip_stereo.hip",
+               "amhip_stereo.hip", "amhip_stereo_seq.hip",
                "amhip_hostsum.cc",   # (.cc: host-only, the AVX-512 loop of the session's content sums)
                "amhip_tuning.cc",    # (host-only: the tuning knobs' store, amhip_set_tuning / AMHIP_TUNING)
                "amhip_build_id.cc"]  # (host-only: amhip_build_id(), recompiled whenever anything else is)

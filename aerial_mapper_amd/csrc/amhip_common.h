@@ -360,6 +360,23 @@ int densify_run(Ctx* c, const DensifyParams& p, const float* dev_disparity,
                 const uint8_t* dev_image_left, double* dev_xyz_out, int32_t* dev_intensity_out,
                 size_t capacity, long long* dev_count);
 
+// Append mode (amhip_stereo_seq.hip): the device-resident bookkeeping of one frame sequence.
+// running = points of the sequence so far, base = where the current pair's points start,
+// pairs = pairs in the cloud, skip = the current pair adds nothing (its rectification failed).
+struct SeqState {
+  unsigned long long running, base;
+  unsigned pairs, skip;
+};
+// densify_run at dev_state->running (0 with `replace`), advancing it on the device, plus the pair's
+// PointCloud2 payload (width * height slots of 16 bytes) into dev_pc2
+int densify_append_run(Ctx* c, const DensifyParams& p, const float* dev_disparity,
+                       const uint8_t* dev_image_left, double* dev_xyz, int32_t* dev_intensities,
+                       size_t capacity, SeqState* dev_state, void* dev_pc2, bool replace);
+// aslam MappedUndistorter::processImage for G frames (amhip_forward.hip: k_fwd_undistort), packed
+// output (G x height x width x channels); asynchronous on `stream`
+int undistort_frames_run(hipStream_t stream, const amhip_camera& cam, const uint8_t* dev_frames,
+                         size_t frame_stride, size_t row_step, int channels, int G, uint8_t* dev_out);
+
 // multi-GPU halo selection
 int halo_select_run(Ctx* c, const double* dev_xyz, size_t n, const HaloParams& hp,
                     double* dev_out, unsigned long long* dev_counts);

@@ -326,6 +326,21 @@ k_fwd_undistort(amhip_camera cam, FwdGeom g, const uint8_t* __restrict__ frames,
   }
 }
 
+int undistort_frames_run(hipStream_t stream, const amhip_camera& cam, const uint8_t* dev_frames,
+                         size_t frame_stride, size_t row_step, int channels, int G, uint8_t* dev_out) {
+  FwdGeom g;
+  std::memset(&g, 0, sizeof(g));
+  g.iw = cam.width;
+  g.ih = cam.height;
+  g.ch = channels;
+  g.frame_stride = frame_stride;
+  g.row_step = row_step;
+  hipLaunchKernelGGL(k_fwd_undistort, dim3((unsigned)((g.iw + 255) / 256), (unsigned)g.ih, (unsigned)G),
+                     dim3(256), 0, stream, cam, g, dev_frames, G, dev_out);
+  AMHIP_TRY(hipGetLastError());
+  return AMHIP_OK;
+}
+
 // cv::warpPerspective(INTER_NEAREST, BORDER_CONSTANT) of G frames + addImage's mask,
 // evaluated on every frame's region only.
 __global__ void __launch_bounds__(256)
@@ -756,9 +771,9 @@ static int fwd_feed_frames(Mosaic* m, const double* T_G_C, size_t F, const uint8
     FwdGeom g = g0;
     const uint8_t* src = frames + c.first * frame_stride;
     if (m->cam.distortion != AMHIP_DIST_NONE) {
-      hipLaunchKernelGGL(k_fwd_undistort,
-                         dim3((unsigned)((g.iw + 255) / 256), (unsigned)g.ih, (unsigned)G),
-                         dim3(256), 0, m->stream, m->cam, g, src, G, m->undist);
+      if ((rc = undistort_frames_run(m->stream, m->cam, src, g.frame_stride, g.row_step, ch, G,
+                                     m->undist)))
+        return rc;
       src = m->undist;
       g.frame_stride = fbytes;
       g.row_step = (size_t)g.iw * ch;

@@ -62,6 +62,9 @@ EXPORTS = [
     "amhip_io_load_point_cloud_binary", "amhip_session_grid_map_msg", "amhip_session_layer_to_image",
     "amhip_sgbm_default_params", "amhip_sgbm_disparity_dev",
     "amhip_bm_default_params", "amhip_bm_disparity_dev",
+    "amhip_stereo_default_settings", "amhip_stereo_create", "amhip_stereo_destroy", "amhip_stereo_reset",
+    "amhip_stereo_add_frame", "amhip_stereo_add_frame_dev", "amhip_stereo_add_frames",
+    "amhip_stereo_add_frames_dev", "amhip_stereo_cloud", "amhip_stereo_point_cloud2_dev",
 ]
 
 
@@ -100,6 +103,12 @@ class BmParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "min_disparity", "num_disparities", "pre_filter_cap", "pre_filter_size", "uniqueness_ratio",
         "texture_threshold", "speckle_window_size", "speckle_range", "disp_12_max_diff", "block_size")]
+
+
+class StereoSettings(C.Structure):
+    """amhip_stereo_settings (stereo::Settings + BlockMatchingParameters)"""
+    _fields_ = [("use_every_nth_image", C.c_uint64), ("images_need_undistortion", C.c_int32),
+                ("use_bm", C.c_int32), ("_pad", C.c_int32 * 2), ("sgbm", SgbmParams), ("bm", BmParams)]
 
 
 class AmhipError(RuntimeError):
@@ -201,6 +210,21 @@ def load():
     lib.amhip_bm_disparity_dev.argtypes = [vp, C.POINTER(BmParams), C.c_int, C.c_int,
                                            vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t,
                                            vp, C.c_size_t, vp, C.c_size_t]
+    sp = C.POINTER(StereoSettings)
+    lib.amhip_stereo_default_settings.restype = None
+    lib.amhip_stereo_default_settings.argtypes = [sp]
+    lib.amhip_stereo_create.argtypes = [vp, cp, f64p, sp, C.POINTER(vp)]
+    lib.amhip_stereo_destroy.argtypes = [vp]
+    lib.amhip_stereo_reset.argtypes = [vp]
+    lib.amhip_stereo_add_frame.argtypes = [vp, f64p, vp, C.c_size_t, C.c_int]
+    lib.amhip_stereo_add_frame_dev.argtypes = [vp, f64p, vp, C.c_size_t, C.c_int]
+    lib.amhip_stereo_add_frames.argtypes = [vp, f64p, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int,
+                                            C.c_size_t]
+    lib.amhip_stereo_add_frames_dev.argtypes = [vp, f64p, vp, C.c_size_t, C.c_size_t, C.c_int,
+                                                C.c_size_t]
+    lib.amhip_stereo_cloud.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t),
+                                       C.POINTER(C.c_size_t)]
+    lib.amhip_stereo_point_cloud2_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     lib.amhip_ctx_enable_timing.argtypes = [vp, C.c_int]
     lib.amhip_ctx_timing_reset.argtypes = [vp]
     lib.amhip_ctx_kernel_time.argtypes = [vp, C.c_int, f64p, C.POINTER(C.c_int64)]

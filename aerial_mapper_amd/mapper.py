@@ -789,6 +789,183 @@ def dense_cloud_from_stereo_pair(map, K, R_G_C1, R_G_C2, t_G_C1, t_G_C2, image_l
     return densify(map, disp, r["image_left"], K, r["baseline"], r["R_G_C"], t_G_C1)
 
 
+class StereoSettings(object):
+    """stereo::Settings (aerial_mapper_dense_pcl common.h:31-35), same defaults.
+    show_rectification is accepted and ignored (no GUI)."""
+
+    def __init__(self, use_every_nth_image=1, images_need_undistortion=False, show_rectification=True):
+        self.use_every_nth_image = use_every_nth_image
+        self.images_need_undistortion = images_need_undistortion
+        self.show_rectification = show_rectification
+
+
+def _device_view(ptr, shape, typestr, device, keepalive):
+    import torch
+
+    class _Holder(object):
+        pass
+
+    holder = _Holder()
+    holder.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False),
+                                       "version": 2}
+    holder._keepalive = keepalive
+    return torch.as_tensor(holder, device="cuda:%d" % device)
+
+
+class Stereo(object):
+    """stereo::Stereo (aerial_mapper_dense_pcl stereo.h:42-94, stereo.cpp) over amhip_stereo_*: body
+    poses + 8UC1 frames in, one dense cloud out, on the GPU (and the stream) of `map`.
+
+    add_frames(T_G_Bs, images) empties the cloud and returns the concatenated cloud of every pair of
+    the selected frames; add_frame(T_G_B, image) returns the cloud of the pair this frame makes with
+    its predecessor (empty for the first frame).  Both return (xyz (n, 3) float64, intensities (n,)
+    int32): CUDA tensors that VIEW the object's buffers -- valid until the next add_frame / add_frames
+    / close on this object (clone() what must live longer); ready for Dsm.process /
+    OrthoFromPcl.process without a host copy.  images: a list of host uint8 arrays (H, W), or one CUDA
+    uint8 tensor (F, H, W) ((H, W) for add_frame)."""
+
+    def __init__(self, ncameras, settings=None, block_matching_params=None, map=None):
+        if ncameras is None:
+            raise L.AmhipError(L.ERR_ARG, "CHECK(ncameras_) (stereo.cpp:20)")
+        if map is None:
+            raise L.AmhipError(L.ERR_ARG, "Stereo needs the AerialGridMap whose GPU and stream it runs on")
+        settings = settings or StereoSettings()
+        bmp = block_matching_params or BlockMatchingParameters()
+        self.ncameras, self.settings, self.map = ncameras, settings, map
+        self._lib = L.load()
+        cs = L.StereoSettings()
+        self._lib.amhip_stereo_default_settings(C.byref(cs))
+        nth = int(settings.use_every_nth_image)
+        if nth < 0:
+            raise L.AmhipError(L.ERR_ARG, "use_every_nth_image is a size_t")
+        cs.use_every_nth_image = nth
+        cs.images_need_undistortion = int(bool(settings.images_need_undistortion))
+        cs.use_bm = int(bool(bmp.use_BM))
+        cs.sgbm, cs.bm = bmp.sgbm.to_c(), bmp.bm.to_c()
+        self._h = C.c_void_p()
+        tcb = np.ascontiguousarray(ncameras.T_C_B, np.float64).reshape(7)
+        L.check(self._lib.amhip_stereo_create(map.handle, C.byref(ncameras.camera),
+                                              tcb.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cs),
+                                              C.byref(self._h)))
+        self.pairs = 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.amhip_stereo_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        """A newly constructed object: the next frame is a first frame, the cloud is empty."""
+        L.check(self._lib.amhip_stereo_reset(self._h))
+        self.pairs = 0
+
+    def _check_shape(self, shape):
+        cam = self.ncameras.camera
+        if len(shape) == 3 and shape[2] == 3:
+            raise L.AmhipError(L.ERR_ARG, "8UC3 frames are refused: the reference stores the raw colour "
+                                          "image, which OpenCV's matchers reject (stereo.cpp:131,138)")
+        if len(shape) != 2:
+            raise L.AmhipError(L.ERR_ARG, "Image type not supported (stereo.cpp:123): 8UC1 only")
+        if tuple(shape) != (cam.height, cam.width):
+            raise L.AmhipError(L.ERR_ARG, "image size %s is not the camera's %s"
+                               % (tuple(shape), (cam.height, cam.width)))
+
+    @staticmethod
+    def _host(im):
+        im = np.asarray(im)
+        if im.dtype != np.uint8:
+            raise L.AmhipError(L.ERR_ARG, "Image type not supported (stereo.cpp:123): 8UC1 only")
+        if im.ndim >= 1 and im.strides[-1] != 1:
+            im = np.ascontiguousarray(im)
+        return im
+
+    def _cloud(self):
+        xyz, inten = C.c_void_p(), C.c_void_p()
+        n, pairs = C.c_size_t(), C.c_size_t()
+        L.check(self._lib.amhip_stereo_cloud(self._h, C.byref(xyz), C.byref(inten), C.byref(n),
+                                             C.byref(pairs)))
+        import torch
+        self.pairs = int(pairs.value)
+        dev = self.map.device
+        if n.value == 0:
+            return (torch.empty((0, 3), dtype=torch.float64, device="cuda:%d" % dev),
+                    torch.empty((0,), dtype=torch.int32, device="cuda:%d" % dev))
+        return (_device_view(xyz.value, (n.value, 3), "<f8", dev, self),
+                _device_view(inten.value, (n.value,), "<i4", dev, self))
+
+    def add_frames(self, T_G_Bs, images):
+        """stereo::Stereo::addFrames (stereo.cpp:82-111)."""
+        T = np.ascontiguousarray(T_G_Bs, np.float64).reshape(-1, 7)
+        F = T.shape[0]
+        if len(images) != F:
+            raise L.AmhipError(L.ERR_ARG, "as many poses as images are needed")
+        f64p = C.POINTER(C.c_double)
+        if _is_torch(images):
+            assert images.is_cuda and images.element_size() == 1 and images.dim() == 3
+            if F:
+                self._check_shape(tuple(images.shape[1:]))
+            assert F == 0 or (images.stride(2) == 1 and images.stride(1) >= images.shape[2])
+            self.map.wait_for_torch(images)
+            L.check(self._lib.amhip_stereo_add_frames_dev(
+                self._h, T.ctypes.data_as(f64p), C.c_void_p(images.data_ptr()),
+                images.stride(0) if F else 0, images.stride(1) if F else 0, 1, F))
+            return self._cloud()
+        ptrs = (C.c_void_p * max(F, 1))()
+        steps = (C.c_size_t * max(F, 1))()
+        keep = []
+        for k, im in enumerate(images):
+            im = self._host(im)
+            self._check_shape(im.shape)
+            keep.append(im)
+            ptrs[k] = im.ctypes.data
+            steps[k] = im.strides[0]
+        L.check(self._lib.amhip_stereo_add_frames(self._h, T.ctypes.data_as(f64p), ptrs, steps, 1, F))
+        return self._cloud()
+
+    def add_frame(self, T_G_B, image):
+        """stereo::Stereo::addFrame (stereo.cpp:113-147): the cloud of the pair (previous frame,
+        this frame); empty after the first frame."""
+        T = np.ascontiguousarray(T_G_B, np.float64).reshape(7)
+        f64p = C.POINTER(C.c_double)
+        if _is_torch(image):
+            assert image.is_cuda and image.element_size() == 1
+            self._check_shape(tuple(image.shape))
+            assert image.stride(1) == 1
+            self.map.wait_for_torch(image)
+            L.check(self._lib.amhip_stereo_add_frame_dev(
+                self._h, T.ctypes.data_as(f64p), C.c_void_p(image.data_ptr()), image.stride(0), 1))
+        else:
+            im = self._host(image)
+            self._check_shape(im.shape)
+            L.check(self._lib.amhip_stereo_add_frame(self._h, T.ctypes.data_as(f64p),
+                                                     C.c_void_p(im.ctypes.data), im.strides[0], 1))
+        return self._cloud()
+
+    def point_cloud2(self):
+        """The sensor_msgs::PointCloud2 payload of the last pair (densifier.cpp:53-106): a uint8 CUDA
+        tensor (H, W, 16) viewing the object's buffer -- x, y, z float32 and rgb uint32 per slot,
+        shifted by one slot like the reference's (see amhip_stereo_point_cloud2_dev); overwritten by
+        the next pair."""
+        ptr, nbytes = C.c_void_p(), C.c_size_t()
+        L.check(self._lib.amhip_stereo_point_cloud2_dev(self._h, C.byref(ptr), C.byref(nbytes)))
+        self.map.synchronize()
+        cam = self.ncameras.camera
+        assert nbytes.value == cam.width * cam.height * 16
+        return _device_view(ptr.value, (cam.height, cam.width, 16), "|u1", self.map.device, self)
+
+
 # ---------------------------------------------------------------------------
 # ortho::OrthoForwardHomography
 # ---------------------------------------------------------------------------

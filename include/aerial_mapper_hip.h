@@ -262,7 +262,8 @@ int amhip_ortho_from_pcl_process(amhip_ctx* ctx, const double* host_xyz,
  * dev_count receives the number of valid points (it may exceed `capacity`, the
  * excess is not written).  Asynchronous.  The block matcher in front of it is
  * amhip_sgbm_disparity_dev (use_BM = false) or amhip_bm_disparity_dev
- * (use_BM = true); only the ROS PointCloud2 fill stays the reference's. */
+ * (use_BM = true).  The sensor_msgs::PointCloud2 payload of densifier.cpp:53-106 is filled by the
+ * sequence object below (amhip_stereo_point_cloud2_dev), not by this call. */
 int amhip_densify_dev(amhip_ctx* ctx, const float* dev_disparity, size_t disp_step,
                       const uint8_t* dev_image_left, size_t img_step, int width,
                       int height, const double* K, double baseline,
@@ -576,6 +577,109 @@ int amhip_bm_disparity_dev(amhip_ctx* ctx, const amhip_bm_params* p, int width, 
                            const uint8_t* dev_mask, size_t mask_step,
                            float* dev_disparity, size_t disp_step,
                            int16_t* dev_raw, size_t raw_step);
+
+/* ---- stereo::Stereo: a frame sequence -> one dense cloud
+ *      aerial_mapper_dense_pcl/include/aerial-mapper-dense-pcl/stereo.h:42-94, src/stereo.cpp ----
+ * Images + body poses in, the concatenated cloud of all stereo pairs out, without a host round trip
+ * inside a sequence: every frame is staged (and, if asked for, undistorted) once although it serves
+ * two pairs, each pair runs amhip_rectify_stereo_pair_dev -> the block matcher -> an append-mode
+ * densify whose output position is a point count that lives on the device.
+ *
+ * stereo::Settings (common.h:31-35) + BlockMatchingParameters (common.h:81-110).  show_rectification
+ * has no counterpart (no GUI), nothing is published to ROS.  104 bytes. */
+typedef struct amhip_stereo amhip_stereo;
+typedef struct amhip_stereo_settings {
+  uint64_t use_every_nth_image;     /* 1; 0 divides by zero in the reference: AMHIP_ERR_ARG */
+  int32_t images_need_undistortion; /* 0 */
+  int32_t use_bm;                   /* BlockMatchingParameters::use_BM; 0 = SGBM */
+  int32_t _pad[2];
+  amhip_sgbm_params sgbm;
+  amhip_bm_params bm;
+} amhip_stereo_settings;
+/* Settings' and BlockMatchingParameters' defaults (1, false, use_BM = false, the matchers' own). */
+void amhip_stereo_default_settings(amhip_stereo_settings* out);
+
+/* stereo::Stereo::Stereo (stereo.cpp:12-80).  The object runs on the stream and the scratch of
+ * `ctx` (which must outlive it; one object at a time per context call, like every context call) and
+ * owns two raw frame slots that swap roles, the rectified pair + mask, the disparity map, the cloud,
+ * the running point count and the PointCloud2 payload, plus a second stream on which host frames are
+ * uploaded from pinned staging while the previous pair is still being matched.
+ * cam: camera 0 of the NCamera; K = [fu 0 cu; 0 fv cv; 0 0 1] (:37-40) also when undistorting (the
+ * reference does not switch to the undistorter's output intrinsics).  T_C_B7: get_T_C_B(0).
+ * The parameters of the selected matcher are checked here, by the matcher's own rules
+ * (amhip_sgbm_disparity_dev / amhip_bm_disparity_dev).  Argument errors are reported before the
+ * context is looked at. */
+int amhip_stereo_create(amhip_ctx* ctx, const amhip_camera* cam, const double* T_C_B7,
+                        const amhip_stereo_settings* settings, amhip_stereo** out);
+int amhip_stereo_destroy(amhip_stereo* stereo);
+/* A newly constructed object: first_frame_ = true, the cloud emptied, the payload zeroed. */
+int amhip_stereo_reset(amhip_stereo* stereo);
+
+/* stereo::Stereo::addFrame (stereo.cpp:113-147).  T_G_B7: the body pose.  The camera pose is
+ *   T_G_C = T_G_B * T_C_B^-1 (:43,129-137), amhip_compose_T_G_C's arithmetic, FP64 on the host;
+ *   t_G_C its position, R_G_C the rotation matrix of its quaternion (w, x, y, z) as Eigen's
+ *   toRotationMatrix spells it:  tx = 2x, ty = 2y, tz = 2z, twx = tx w, twy = ty w, twz = tz w,
+ *   txx = tx x, txy = ty x, txz = tz x, tyy = ty y, tyz = tz y, tzz = tz z,
+ *   R = [1 - (tyy + tzz), txy - twz, txz + twy;  txy + twz, 1 - (txx + tzz), tyz - twx;
+ *        txz - twy, tyz + twx, 1 - (txx + tyy)].
+ * The image is 8UC1, camera width x height, rows `step` bytes apart (step >= width).  channels == 3:
+ * the reference converts a gray copy only to pass its own type check and then hands the RAW colour
+ * image to OpenCV's matchers, which refuse it: AMHIP_ERR_ARG.  Any other channel count:
+ * AMHIP_ERR_ARG (LOG(FATAL), :123).  (Value checks come before the object is looked at.)
+ * The first call after creation / reset only stores the frame as "left" and leaves the cloud as it
+ * is; every later call makes one pair with its predecessor and REPLACES the cloud with that pair's
+ * (:178), `pairs` = 1.  With images_need_undistortion the frame goes through the camera's mapped
+ * undistorter (bilinear; the forward mosaic's remap, see amhip_mosaic_*) once, before it is used; a
+ * camera without a distortion model has the identity map and the step is skipped.
+ * The host form copies the image into pinned staging before it returns (the caller may free it);
+ * the _dev form reads dev_image in stream order on the context's stream.  Asynchronous: no
+ * synchronisation of the context's stream, no read-back.  A pair whose baseline is 0
+ * (densifier.cpp:39) is AMHIP_ERR_ARG at once; a zero w of the rectification (rectifier.cpp:93,99) is
+ * found on the device: that pair and every later one add nothing and amhip_stereo_cloud reports
+ * AMHIP_ERR_ARG with the pairs before it.  After a failing call: amhip_stereo_reset. */
+int amhip_stereo_add_frame(amhip_stereo* stereo, const double* T_G_B7, const uint8_t* host_image,
+                           size_t step, int channels);
+int amhip_stereo_add_frame_dev(amhip_stereo* stereo, const double* T_G_B7, const uint8_t* dev_image,
+                               size_t step, int channels);
+
+/* stereo::Stereo::addFrames (stereo.cpp:82-111): the cloud is emptied, frame i is used iff
+ * (i + 1) % use_every_nth_image == 0 (:91-93), every used frame goes through addFrame and the
+ * pairs' clouds are CONCATENATED in order, each in raster order (what amhip_densify_dev emits).
+ * Like the reference this does not touch first_frame_: on a fresh / reset object the first used frame
+ * only becomes "left"; after earlier calls it pairs with the frame left over from them.
+ * Capacity is settled before the first pair (pairs x width x height points worst case, grown once;
+ * AMHIP_ERR_NOMEM if that cannot be had); between the first and the last pair there is no
+ * allocation, no synchronisation of the context's stream and no copy of a count (the block matcher's
+ * scratch is the context's and is sized by the first pair).  The host form waits only for the upload
+ * that last used a staging buffer (two frames back).  The sequence stops at the first failing pair
+ * and keeps the pairs before it.
+ * host_images[i]: frame i, rows steps[i] bytes apart.  _dev: one stack on the GPU, frame i at
+ * dev_frames + i * frame_stride, rows row_step bytes apart. */
+int amhip_stereo_add_frames(amhip_stereo* stereo, const double* T_G_B7xF,
+                            const uint8_t* const* host_images, const size_t* steps, int channels,
+                            size_t F);
+int amhip_stereo_add_frames_dev(amhip_stereo* stereo, const double* T_G_B7xF,
+                                const uint8_t* dev_frames, size_t frame_stride, size_t row_step,
+                                int channels, size_t F);
+
+/* The cloud: the last add_frame's pair, or the last add_frames' sequence.  Synchronises the context
+ * (the ONE read-back of the point count) and returns its sticky status.  dev_xyz (3 n doubles, AoS) /
+ * dev_intensities (n int32): the layout amhip_dsm_process_dev / amhip_ortho_from_pcl_process_dev
+ * take; they stay valid until the next add_frame / add_frames / destroy on the object.  Any output
+ * pointer may be NULL. */
+int amhip_stereo_cloud(amhip_stereo* stereo, const double** dev_xyz, const int32_t** dev_intensities,
+                       size_t* n, size_t* pairs);
+
+/* The sensor_msgs::PointCloud2 payload (point_cloud_ros_msg_.data) of the LAST pair, filled in the
+ * emit pass of that pair (densifier.cpp:53-106, stereo.cpp:46-76): point_step 16, row_step 16 width,
+ * width x height slots of x, y, z as float32 ((float)point_G) and rgb = gray << 16 | gray << 8 | gray
+ * as uint32; invalid pixels hold the quiet-NaN pattern 0x7FC00000 in all four fields.  The reference
+ * advances point_offset BEFORE it writes (:58): pixel k lands in slot k + 1, slot 0 keeps the zeros
+ * of data.resize() and the last pixel's write falls 16 bytes behind the buffer (undefined behaviour
+ * there).  Reproduced: the shift, the zero slot 0; the last pixel is dropped.  All zero before the
+ * first pair.  Overwritten by the next pair like point_cloud_ros_msg_.  In stream order on the
+ * context's stream (amhip_ctx_synchronize before reading it from elsewhere). */
+int amhip_stereo_point_cloud2_dev(amhip_stereo* stereo, const void** dev_data, size_t* bytes);
 
 /* ---- session: one map served through HOST matrices by one or several GPUs ---------------
  *
