@@ -47,6 +47,10 @@ Stereo::~Stereo() {
   if (ctx_) amhip_ctx_destroy(ctx_);
 }
 
+void Stereo::setPairsInFlight(int n) {
+  check_status(amhip_stereo_set_pairs_in_flight(stereo_, n), "Stereo::setPairsInFlight");
+}
+
 static void check_image(const Image& image, const aslam::Camera& camera, const char* where) {
   if (image.channels() != 1 && image.channels() != 3) fatal(where, "Image type not supported");
   if (image.cols != static_cast<int>(camera.imageWidth()) ||

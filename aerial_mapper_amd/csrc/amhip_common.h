@@ -371,7 +371,10 @@ struct SeqState {
 // PointCloud2 payload (width * height slots of 16 bytes) into dev_pc2
 int densify_append_run(Ctx* c, const DensifyParams& p, const float* dev_disparity,
                        const uint8_t* dev_image_left, double* dev_xyz, int32_t* dev_intensities,
-                       size_t capacity, SeqState* dev_state, void* dev_pc2, bool replace);
+                       size_t capacity, SeqState* dev_state, void* dev_pc2, bool replace,
+                       const unsigned* dev_err_word = nullptr);  // (null: the context's own word)
+// the context's stereo scratch holds `batch` pairs of the selected matcher (amhip_stereo.hip)
+int stereo_scratch_reserve(Ctx* c, const amhip_stereo_settings& s, int width, int height, int batch);
 // aslam MappedUndistorter::processImage for G frames (amhip_forward.hip: k_fwd_undistort), packed
 // output (G x height x width x channels); asynchronous on `stream`
 int undistort_frames_run(hipStream_t stream, const amhip_camera& cam, const uint8_t* dev_frames,

@@ -135,7 +135,8 @@ k_densify_emit(DensifyParams p, const float* __restrict__ disparity,
 }
 
 // Append mode, pass 2: the scan of k_densify_scan plus the sequence's bookkeeping.  A pair whose
-// rectification met w == 0 (the sticky device error word) adds nothing: `skip` tells the emit pass.
+// rectification met w == 0 (the sticky device error word, or the copy of it a pair of a group took
+// behind its own rectifier) adds nothing: `skip` tells the emit pass.
 __global__ void __launch_bounds__(kDensifyThreads)
 k_densify_append_scan(uint32_t* __restrict__ block_counts, int nblocks, SeqState* __restrict__ st,
                       const unsigned* __restrict__ dev_err, int replace) {
@@ -211,7 +212,8 @@ k_densify_append_emit(DensifyParams p, const float* __restrict__ disparity,
 
 int densify_append_run(Ctx* c, const DensifyParams& p, const float* dev_disparity,
                        const uint8_t* dev_image_left, double* dev_xyz, int32_t* dev_intensities,
-                       size_t capacity, SeqState* dev_state, void* dev_pc2, bool replace) {
+                       size_t capacity, SeqState* dev_state, void* dev_pc2, bool replace,
+                       const unsigned* dev_err_word) {
   const long long npix = (long long)p.width * p.height;
   const int nblocks = (int)((npix + kDensifyBlock - 1) / kDensifyBlock);
   int rc;
@@ -220,7 +222,8 @@ int densify_append_run(Ctx* c, const DensifyParams& p, const float* dev_disparit
   hipLaunchKernelGGL(k_densify_count, dim3(nblocks), dim3(kDensifyThreads), 0, c->stream, p,
                      dev_disparity, c->scan_partials);
   hipLaunchKernelGGL(k_densify_append_scan, dim3(1), dim3(kDensifyThreads), 0, c->stream,
-                     c->scan_partials, nblocks, dev_state, c->dev_err, replace ? 1 : 0);
+                     c->scan_partials, nblocks, dev_state, dev_err_word ? dev_err_word : c->dev_err,
+                     replace ? 1 : 0);
   hipLaunchKernelGGL(k_densify_append_emit, dim3(nblocks), dim3(kDensifyThreads), 0, c->stream, p,
                      dev_disparity, dev_image_left, c->scan_partials, dev_state, dev_xyz,
                      dev_intensities, (unsigned long long)capacity, static_cast<uint4*>(dev_pc2));

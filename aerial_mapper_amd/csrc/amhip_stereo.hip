@@ -21,8 +21,16 @@
 //                   uniting), then each pixel's root read without writes, region sizes by atomics
 //   k_sgbm_final    small regions -> invalid, CV_16S out, float / 16 with the mask
 // C + S + hsum live in the context's scratch (amhip::Ctx::sgbm_ws), grown on demand.
+//
+// Batches (amhip_*_disparity_batch_dev): blockIdx.z is the pair.  Pair b reads its images and mask
+// and writes its outputs at base + b * batch stride; its scratch is the single-pair layout at
+// b * (scratch bytes of one pair).  Every index a kernel forms (rows, columns, chains, union-find
+// labels, the disp2 keys) is an index into the pair's own arrays, so nothing crosses from one pair
+// into the next, and a batch of one is the single-pair call.
 #include <algorithm>
 #include <cstring>
+#include <string>
+#include <type_traits>
 
 #include "amhip_common.h"
 
@@ -38,6 +46,13 @@ struct SgbmDims {
   int W, H, minD, maxD, D, minX1, maxX1, w1, SW2, SH2;
   int ftzero, P1, P2, uniq, disp12, invalid, speckle_win, speckle_diff;
 };
+
+// pair blockIdx.z of a batch: `stride` bytes from one pair's array to the next pair's
+template <typename T>
+__device__ __forceinline__ T* pair_at(T* p, size_t stride) {
+  using B = typename std::conditional<std::is_const<T>::value, const uint8_t, uint8_t>::type;
+  return reinterpret_cast<T*>(reinterpret_cast<B*>(p) + (size_t)blockIdx.z * stride);
+}
 
 // calcPixelCostBT's channel c (0: x-Sobel through clipTab, 1: raw) of column r of row y, packed
 // with the min / max over it and its half-pixel neighbours: v | v0 << 8 | v1 << 16
@@ -72,7 +87,11 @@ __device__ __forceinline__ int sgbm_bt(unsigned a, unsigned b) {
 
 __global__ void __launch_bounds__(256)
 k_sgbm_hsum(SgbmDims p, const uint8_t* __restrict__ left, size_t lstep,
-            const uint8_t* __restrict__ right, size_t rstep, uint16_t* __restrict__ hsum) {
+            const uint8_t* __restrict__ right, size_t rstep, uint16_t* __restrict__ hsum,
+            size_t lbs, size_t rbs, size_t ws) {
+  left = pair_at(left, lbs);
+  right = pair_at(right, rbs);
+  hsum = pair_at(hsum, ws);
   constexpr int kNL = kSgbmTX + 2 * kSgbmMaxSW2;
   __shared__ unsigned sl[2][kNL];
   __shared__ unsigned sr[2][kNL + kSgbmMaxD];
@@ -111,7 +130,9 @@ k_sgbm_hsum(SgbmDims p, const uint8_t* __restrict__ left, size_t lstep,
 }
 
 __global__ void __launch_bounds__(256)
-k_sgbm_vsum(SgbmDims p, const uint16_t* __restrict__ hsum, uint16_t* __restrict__ C) {
+k_sgbm_vsum(SgbmDims p, const uint16_t* __restrict__ hsum, uint16_t* __restrict__ C, size_t ws) {
+  hsum = pair_at(hsum, ws);
+  C = pair_at(C, ws);
   const size_t plane = (size_t)p.w1 * p.D;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= plane) return;
@@ -143,7 +164,11 @@ __device__ __forceinline__ int wave_min(int v) {
 template <int NJ, int MODE>
 __global__ void __launch_bounds__(256)
 k_sgbm_path(SgbmDims p, int dir, const uint16_t* __restrict__ C, int32_t* __restrict__ S,
-            int16_t* __restrict__ disp1, unsigned long long* __restrict__ key2) {
+            int16_t* __restrict__ disp1, unsigned long long* __restrict__ key2, size_t ws) {
+  C = pair_at(C, ws);
+  S = pair_at(S, ws);
+  disp1 = pair_at(disp1, ws);
+  key2 = pair_at(key2, ws);
   const int lane = threadIdx.x & 63;
   const int chain = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int w1 = p.w1, H = p.H, D = p.D;
@@ -277,7 +302,10 @@ __device__ __forceinline__ int sgbm_disp2(const unsigned long long* __restrict__
 
 __global__ void __launch_bounds__(256)
 k_sgbm_lrcheck(SgbmDims p, const int16_t* __restrict__ disp1,
-               const unsigned long long* __restrict__ key2, int16_t* __restrict__ out) {
+               const unsigned long long* __restrict__ key2, int16_t* __restrict__ out, size_t ws) {
+  disp1 = pair_at(disp1, ws);
+  key2 = pair_at(key2, ws);
+  out = pair_at(out, ws);
   const int X = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
   if (X >= p.W) return;
   const size_t row = (size_t)y * p.W;
@@ -300,7 +328,9 @@ k_sgbm_lrcheck(SgbmDims p, const int16_t* __restrict__ disp1,
 }
 
 __global__ void __launch_bounds__(256)
-k_sgbm_median(int W, int H, const int16_t* __restrict__ in, int16_t* __restrict__ out) {
+k_sgbm_median(int W, int H, const int16_t* __restrict__ in, int16_t* __restrict__ out, size_t ws) {
+  in = pair_at(in, ws);
+  out = pair_at(out, ws);
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
   if (x >= W) return;
   int v[9];
@@ -364,7 +394,9 @@ __device__ __forceinline__ void uf_unite(int* par, int a, int b) {
 }
 
 __global__ void __launch_bounds__(256)
-k_sgbm_uf_init(int n, int* __restrict__ par, int* __restrict__ cnt) {
+k_sgbm_uf_init(int n, int* __restrict__ par, int* __restrict__ cnt, size_t ws) {
+  par = pair_at(par, ws);
+  cnt = pair_at(cnt, ws);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   par[i] = i;
@@ -372,7 +404,9 @@ k_sgbm_uf_init(int n, int* __restrict__ par, int* __restrict__ cnt) {
 }
 
 __global__ void __launch_bounds__(256)
-k_sgbm_uf_union(SgbmDims p, const int16_t* __restrict__ a, int* par) {
+k_sgbm_uf_union(SgbmDims p, const int16_t* __restrict__ a, int* par, size_t ws) {
+  a = pair_at(a, ws);
+  par = pair_at(par, ws);  // (labels are pixel indices of this pair's image alone)
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
   if (x >= p.W) return;
   const int i = y * p.W + x;
@@ -390,7 +424,11 @@ k_sgbm_uf_union(SgbmDims p, const int16_t* __restrict__ a, int* par) {
 
 __global__ void __launch_bounds__(256)
 k_sgbm_uf_count(SgbmDims p, const int16_t* __restrict__ a, const int* __restrict__ par,
-                int* __restrict__ lab, int* __restrict__ cnt) {
+                int* __restrict__ lab, int* __restrict__ cnt, size_t ws) {
+  a = pair_at(a, ws);
+  par = pair_at(par, ws);
+  lab = pair_at(lab, ws);
+  cnt = pair_at(cnt, ws);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= p.W * p.H || a[i] == p.invalid) return;
   const int r = uf_root(par, i);
@@ -401,7 +439,14 @@ k_sgbm_uf_count(SgbmDims p, const int16_t* __restrict__ a, const int* __restrict
 __global__ void __launch_bounds__(256)
 k_sgbm_final(SgbmDims p, const int16_t* __restrict__ med, const int* __restrict__ lab,
              const int* __restrict__ cnt, const uint8_t* __restrict__ mask, size_t mask_step,
-             float* __restrict__ disp, size_t disp_step, int16_t* __restrict__ raw, size_t raw_step) {
+             float* __restrict__ disp, size_t disp_step, int16_t* __restrict__ raw, size_t raw_step,
+             size_t ws, size_t mbs, size_t dbs, size_t wbs) {
+  med = pair_at(med, ws);
+  cnt = pair_at(cnt, ws);
+  if (lab) lab = pair_at(lab, ws);
+  if (mask) mask = pair_at(mask, mbs);
+  if (raw) raw = pair_at(raw, wbs);
+  disp = pair_at(disp, dbs);
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
   if (x >= p.W) return;
   const int i = y * p.W + x;
@@ -414,15 +459,16 @@ k_sgbm_final(SgbmDims p, const int16_t* __restrict__ med, const int* __restrict_
 }
 
 template <int NJ>
-static void launch_paths(Ctx* c, const SgbmDims& p, const uint16_t* C, int32_t* S, int16_t* disp1,
-                         unsigned long long* key2) {
+static void launch_paths(Ctx* c, const SgbmDims& p, unsigned B, size_t ws, const uint16_t* C, int32_t* S,
+                         int16_t* disp1, unsigned long long* key2) {
+  // (the chains of all B pairs in one launch: chains x B waves)
   const unsigned rows = (unsigned)((p.H + 3) / 4), cols = (unsigned)((p.w1 + 3) / 4),
                  diag = (unsigned)((p.H + p.w1 - 1 + 3) / 4);
-  hipLaunchKernelGGL((k_sgbm_path<NJ, 0>), dim3(rows), dim3(256), 0, c->stream, p, 0, C, S, disp1, key2);
-  hipLaunchKernelGGL((k_sgbm_path<NJ, 1>), dim3(cols), dim3(256), 0, c->stream, p, 1, C, S, disp1, key2);
-  hipLaunchKernelGGL((k_sgbm_path<NJ, 1>), dim3(diag), dim3(256), 0, c->stream, p, 2, C, S, disp1, key2);
-  hipLaunchKernelGGL((k_sgbm_path<NJ, 1>), dim3(diag), dim3(256), 0, c->stream, p, 3, C, S, disp1, key2);
-  hipLaunchKernelGGL((k_sgbm_path<NJ, 2>), dim3(rows), dim3(256), 0, c->stream, p, 4, C, S, disp1, key2);
+  hipLaunchKernelGGL((k_sgbm_path<NJ, 0>), dim3(rows, 1, B), dim3(256), 0, c->stream, p, 0, C, S, disp1, key2, ws);
+  hipLaunchKernelGGL((k_sgbm_path<NJ, 1>), dim3(cols, 1, B), dim3(256), 0, c->stream, p, 1, C, S, disp1, key2, ws);
+  hipLaunchKernelGGL((k_sgbm_path<NJ, 1>), dim3(diag, 1, B), dim3(256), 0, c->stream, p, 2, C, S, disp1, key2, ws);
+  hipLaunchKernelGGL((k_sgbm_path<NJ, 1>), dim3(diag, 1, B), dim3(256), 0, c->stream, p, 3, C, S, disp1, key2, ws);
+  hipLaunchKernelGGL((k_sgbm_path<NJ, 2>), dim3(rows, 1, B), dim3(256), 0, c->stream, p, 4, C, S, disp1, key2, ws);
 }
 
 static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -458,7 +504,12 @@ struct BmDims {
 __global__ void __launch_bounds__(256)
 k_bm_prefilter(BmDims p, const uint8_t* __restrict__ left, size_t lstep,
                const uint8_t* __restrict__ right, size_t rstep, uint8_t* __restrict__ fl,
-               uint8_t* __restrict__ fr, int16_t* __restrict__ raw) {
+               uint8_t* __restrict__ fr, int16_t* __restrict__ raw, size_t lbs, size_t rbs, size_t ws) {
+  left = pair_at(left, lbs);
+  right = pair_at(right, rbs);
+  fl = pair_at(fl, ws);
+  fr = pair_at(fr, ws);
+  raw = pair_at(raw, ws);
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
   if (x >= p.W) return;
   const size_t i = (size_t)y * p.W + x;
@@ -490,9 +541,12 @@ k_bm_prefilter(BmDims p, const uint8_t* __restrict__ left, size_t lstep,
 template <int NJ>
 __global__ void __launch_bounds__(256)
 k_bm_match(BmDims p, const uint8_t* __restrict__ fl, const uint8_t* __restrict__ fr,
-           int16_t* __restrict__ raw) {
+           int16_t* __restrict__ raw, size_t ws) {
   __shared__ uint8_t sL[kBmRows][kBmLW];
   __shared__ uint8_t sR[kBmRows][kBmRW];
+  fl = pair_at(fl, ws);
+  fr = pair_at(fr, ws);
+  raw = pair_at(raw, ws);
   const int SW2 = p.SW2, D = 8 * NJ;
   const int X0 = p.xa + blockIdx.x * kBmTX;
   const int y0 = p.ya + blockIdx.y * kBmTY, y1 = min(y0 + kBmTY, p.yb);
@@ -580,11 +634,342 @@ k_bm_match(BmDims p, const uint8_t* __restrict__ fl, const uint8_t* __restrict__
 // one instantiation per num_disparities (16 .. 256 in steps of 16)
 template <int NJ = 2>
 static void launch_bm_match(Ctx* c, const BmDims& p, dim3 grid, const uint8_t* fl, const uint8_t* fr,
-                            int16_t* raw) {
+                            int16_t* raw, size_t ws) {
   if constexpr (NJ < 32) {
-    if (p.D != 8 * NJ) return launch_bm_match<NJ + 2>(c, p, grid, fl, fr, raw);
+    if (p.D != 8 * NJ) return launch_bm_match<NJ + 2>(c, p, grid, fl, fr, raw, ws);
   }
-  hipLaunchKernelGGL(k_bm_match<NJ>, grid, dim3(256), 0, c->stream, p, fl, fr, raw);
+  hipLaunchKernelGGL(k_bm_match<NJ>, grid, dim3(256), 0, c->stream, p, fl, fr, raw, ws);
+}
+
+static int stereo_fail(const char* fn, const char* msg) {
+  return arg_failure((std::string(fn) + ": " + msg).c_str());
+}
+
+// the context's stereo scratch holds `total` bytes (kept between calls; grown, never shrunk)
+static int stereo_scratch(Ctx* c, size_t total) {
+  if (c->sgbm_ws && c->sgbm_ws_cap >= total) return AMHIP_OK;
+  if (c->sgbm_ws) {
+    AMHIP_TRY(hipFree(c->sgbm_ws));  // (waits for the kernels that still use it)
+    c->sgbm_ws = nullptr;
+    c->sgbm_ws_cap = 0;
+  }
+  // grow by 1/8 so that slightly larger follow-up images do not reallocate
+  size_t want = total + total / 8 + 256;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->sgbm_ws), want);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    want = total;
+    e = hipMalloc(reinterpret_cast<void**>(&c->sgbm_ws), want);
+  }
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    c->sgbm_ws = nullptr;
+    set_last_error("stereo matcher: out of device memory for the scratch of the batch");
+    return AMHIP_ERR_NOMEM;
+  }
+  AMHIP_TRY(e);
+  c->sgbm_ws_cap = want;
+  return AMHIP_OK;
+}
+
+// strides between the pairs of a batch, in bytes (unused with one pair)
+struct BatchStrides {
+  size_t left, right, mask, disp, raw;
+};
+
+static int batch_check(const char* fn, int height, int batch, const BatchStrides& bs, size_t left_step,
+                       size_t right_step, bool has_mask, size_t mask_step, size_t disp_step,
+                       bool has_raw, size_t raw_step) {
+  if (batch < 1 || batch > AMHIP_STEREO_MAX_BATCH) return stereo_fail(fn, "batch must be in [1, 16]");
+  const size_t H = (size_t)height;
+  if (bs.left < H * left_step || bs.right < H * right_step || (has_mask && bs.mask < H * mask_step) ||
+      bs.disp < H * disp_step || (has_raw && bs.raw < H * raw_step))
+    return stereo_fail(fn, "a batch stride is smaller than height * row step");
+  if (bs.disp % sizeof(float) != 0 || (has_raw && bs.raw % sizeof(int16_t) != 0))
+    return stereo_fail(fn, "output batch strides must be multiples of the element size");
+  return AMHIP_OK;
+}
+
+// ---- SGBM: the argument rules, the scratch of one pair, the launches -------------------------
+static int sgbm_check(const char* fn, const amhip_sgbm_params* q, int width, int height,
+                      const uint8_t* dev_left, size_t left_step, const uint8_t* dev_right,
+                      size_t right_step, const uint8_t* dev_mask, size_t mask_step,
+                      const float* dev_disparity, size_t disp_step, const int16_t* dev_raw,
+                      size_t raw_step) {
+  // (the parameters first: every argument error is reported without a device)
+  if (!q || !dev_left || !dev_right || !dev_disparity) return stereo_fail(fn, "null argument");
+  if (width < 3 || height < 1 || width > 32767 || height > 32767)
+    return stereo_fail(fn, "width must be in [3, 32767], height in [1, 32767]");
+  if (q->num_disparities <= 0 || q->num_disparities % 16 != 0 || q->num_disparities > kSgbmMaxD)
+    return stereo_fail(fn, "num_disparities must be a positive multiple of 16, <= 256");
+  if (q->block_size > 11 || (q->block_size > 0 && q->block_size % 2 == 0))
+    return stereo_fail(fn, "block_size must be odd and <= 11 (0: OpenCV's 5)");
+  if (q->min_disparity < -4096 || q->min_disparity > 4096 || q->pre_filter_cap > 63 ||
+      q->uniqueness_ratio > 100 || q->p1 > 4096 || q->p2 > 4096)
+    return stereo_fail(fn, "parameter out of range");
+  if (!cv16s_holds(q->min_disparity, q->num_disparities))
+    return stereo_fail(fn, "the CV_16S map cannot hold this disparity range: "
+                           "min_disparity must be >= -2047 and min_disparity + num_disparities <= 2047");
+  // (the map's values span less than 2^16, so every range >= 4096 acts alike; 16 * range must fit an int)
+  if (q->speckle_range < -4096 || q->speckle_range > 4096)
+    return stereo_fail(fn, "speckle_range must be in [-4096, 4096]");
+  if (left_step < (size_t)width || right_step < (size_t)width ||
+      (dev_mask && mask_step < (size_t)width) || disp_step < (size_t)width * sizeof(float) ||
+      (dev_raw && raw_step < (size_t)width * sizeof(int16_t)))
+    return stereo_fail(fn, "a row step is smaller than the width");
+  if (disp_step % sizeof(float) != 0 || (dev_raw && raw_step % sizeof(int16_t) != 0))
+    return stereo_fail(fn, "output steps must be multiples of the element size");
+  {
+    const int maxD = q->min_disparity + q->num_disparities;
+    const int w1 = width + std::min(q->min_disparity, 0) - std::max(maxD, 0);
+    if (w1 > 0 && w1 <= (q->block_size > 0 ? q->block_size : 5) / 2)
+      return stereo_fail(fn, "fewer matchable columns than half the block");
+  }
+  return AMHIP_OK;
+}
+
+// computeDisparitySGBM's preamble (tests/sgbm_reference.py: derived)
+static SgbmDims sgbm_dims(const amhip_sgbm_params* q, int width, int height) {
+  SgbmDims p;
+  std::memset(&p, 0, sizeof(p));
+  p.W = width;
+  p.H = height;
+  p.minD = q->min_disparity;
+  p.maxD = p.minD + q->num_disparities;
+  p.D = q->num_disparities;
+  p.P1 = q->p1 > 0 ? q->p1 : 2;
+  p.P2 = std::max(q->p2 > 0 ? q->p2 : 5, p.P1 + 1);
+  p.ftzero = std::max(q->pre_filter_cap, 15) | 1;
+  p.uniq = q->uniqueness_ratio >= 0 ? q->uniqueness_ratio : 10;
+  p.disp12 = q->disp_12_max_diff > 0 ? q->disp_12_max_diff : 1;
+  const int win = q->block_size > 0 ? q->block_size : 5;
+  p.SW2 = p.SH2 = win / 2;
+  p.minX1 = std::max(p.maxD, 0);
+  p.maxX1 = width + std::min(p.minD, 0);
+  p.w1 = p.maxX1 - p.minX1;
+  p.invalid = (p.minD - 1) * 16;
+  p.speckle_win = q->speckle_window_size;
+  p.speckle_diff = 16 * q->speckle_range;
+  return p;
+}
+
+struct SgbmScratch {
+  size_t oC, oS, o1, oK, oL, oM, oP, oN, oB, total;  // total: one pair's bytes, a multiple of 256
+};
+
+static SgbmScratch sgbm_scratch(const SgbmDims& p) {
+  const size_t npix = (size_t)p.W * p.H;
+  const size_t vol = p.w1 > 0 ? (size_t)p.H * p.w1 * p.D : 0;
+  SgbmScratch o;
+  o.oC = 0;
+  o.oS = o.oC + align256(vol * 2);
+  o.o1 = o.oS + align256(vol * 4);
+  o.oK = o.o1 + align256(npix * 2);
+  o.oL = o.oK + align256(npix * 8);
+  o.oM = o.oL + align256(npix * 2);
+  o.oP = o.oM + align256(npix * 2);
+  o.oN = o.oP + align256(npix * 4);
+  o.oB = o.oN + align256(npix * 4);
+  o.total = o.oB + align256(npix * 4);
+  return o;
+}
+
+static int sgbm_run(Ctx* c, const amhip_sgbm_params* q, int width, int height, int batch,
+                    const BatchStrides& bs, const uint8_t* dev_left, size_t left_step,
+                    const uint8_t* dev_right, size_t right_step, const uint8_t* dev_mask,
+                    size_t mask_step, float* dev_disparity, size_t disp_step, int16_t* dev_raw,
+                    size_t raw_step) {
+  const SgbmDims p = sgbm_dims(q, width, height);
+  const bool matched = p.w1 > 0;
+  const size_t npix = (size_t)width * height;
+  const SgbmScratch o = sgbm_scratch(p);
+  const unsigned B = (unsigned)batch;
+  const size_t wsb = o.total;  // pair b's scratch: the single-pair layout at b * wsb
+  int rc;
+  if ((rc = stereo_scratch(c, wsb * B))) return rc;
+  uint8_t* ws = c->sgbm_ws;
+  uint16_t* C = reinterpret_cast<uint16_t*>(ws + o.oC);
+  int32_t* S = reinterpret_cast<int32_t*>(ws + o.oS);
+  uint16_t* hsum = reinterpret_cast<uint16_t*>(ws + o.oS);  // (dead once C is built)
+  int16_t* disp1 = reinterpret_cast<int16_t*>(ws + o.o1);
+  unsigned long long* key2 = reinterpret_cast<unsigned long long*>(ws + o.oK);
+  int16_t* lr = reinterpret_cast<int16_t*>(ws + o.oL);
+  int16_t* med = reinterpret_cast<int16_t*>(ws + o.oM);
+  int* par = reinterpret_cast<int*>(ws + o.oP);
+  int* cnt = reinterpret_cast<int*>(ws + o.oN);
+  int* lab = reinterpret_cast<int*>(ws + o.oB);
+
+  ScopedTimer t(c, AMHIP_K_STEREO);
+  const dim3 rowgrid((unsigned)((width + 255) / 256), (unsigned)height, B);
+  if (matched) {
+    if (B == 1)
+      AMHIP_TRY(hipMemsetAsync(key2, 0xFF, npix * 8, c->stream));
+    else  // (one row of npix keys per pair, wsb bytes apart)
+      AMHIP_TRY(hipMemset2DAsync(key2, wsb, 0xFF, npix * 8, B, c->stream));
+    hipLaunchKernelGGL(k_sgbm_hsum, dim3((unsigned)((p.w1 + kSgbmTX - 1) / kSgbmTX), (unsigned)height, B),
+                       dim3(256), 0, c->stream, p, dev_left, left_step, dev_right, right_step, hsum,
+                       bs.left, bs.right, wsb);
+    hipLaunchKernelGGL(k_sgbm_vsum, dim3((unsigned)(((size_t)p.w1 * p.D + 255) / 256),
+                                         (unsigned)((height + kSgbmVRows - 1) / kSgbmVRows), B),
+                       dim3(256), 0, c->stream, p, hsum, C, wsb);
+    if (p.D <= 64)
+      launch_paths<1>(c, p, B, wsb, C, S, disp1, key2);
+    else if (p.D <= 128)
+      launch_paths<2>(c, p, B, wsb, C, S, disp1, key2);
+    else if (p.D <= 192)
+      launch_paths<3>(c, p, B, wsb, C, S, disp1, key2);
+    else
+      launch_paths<4>(c, p, B, wsb, C, S, disp1, key2);
+  }
+  // (no match possible: every pixel INVALID_DISP_SCALED; disp1 / key2 are not read)
+  hipLaunchKernelGGL(k_sgbm_lrcheck, rowgrid, dim3(256), 0, c->stream, p, disp1, key2, lr, wsb);
+  hipLaunchKernelGGL(k_sgbm_median, rowgrid, dim3(256), 0, c->stream, width, height, lr, med, wsb);
+  const bool speckle = q->speckle_window_size > 0;
+  if (speckle) {
+    const dim3 nb((unsigned)((npix + 255) / 256), 1, B);
+    hipLaunchKernelGGL(k_sgbm_uf_init, nb, dim3(256), 0, c->stream, (int)npix, par, cnt, wsb);
+    hipLaunchKernelGGL(k_sgbm_uf_union, rowgrid, dim3(256), 0, c->stream, p, med, par, wsb);
+    hipLaunchKernelGGL(k_sgbm_uf_count, nb, dim3(256), 0, c->stream, p, med, par, lab, cnt, wsb);
+  }
+  hipLaunchKernelGGL(k_sgbm_final, rowgrid, dim3(256), 0, c->stream, p, med, speckle ? lab : nullptr,
+                     cnt, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step, wsb, bs.mask,
+                     bs.disp, bs.raw);
+  AMHIP_TRY(hipGetLastError());
+  return AMHIP_OK;
+}
+
+// ---- BM ---------------------------------------------------------------------------------------
+static int bm_check(const char* fn, const amhip_bm_params* q, int width, int height,
+                    const uint8_t* dev_left, size_t left_step, const uint8_t* dev_right,
+                    size_t right_step, const uint8_t* dev_mask, size_t mask_step,
+                    const float* dev_disparity, size_t disp_step, const int16_t* dev_raw,
+                    size_t raw_step) {
+  // (StereoBM::compute's CV_Asserts on the wrapper's effective parameters, then this
+  // implementation's limits; every argument error is reported without a device)
+  if (!q || !dev_left || !dev_right || !dev_disparity) return stereo_fail(fn, "null argument");
+  if (width < 1 || height < 1 || width > 32767 || height > 32767)
+    return stereo_fail(fn, "width and height must be in [1, 32767]");
+  if (q->num_disparities <= 0 || q->num_disparities % 16 != 0 || q->num_disparities > kSgbmMaxD)
+    return stereo_fail(fn, "num_disparities must be a positive multiple of 16, <= 256");
+  if (q->block_size % 2 == 0 || q->block_size < 5 || q->block_size > 2 * kBmMaxSW2 + 1 ||
+      q->block_size > std::min(width, height))
+    return stereo_fail(fn, "block_size must be odd, in [5, 31] and <= min(width, height)");
+  if (q->pre_filter_size < 1 || q->pre_filter_size > 63)
+    return stereo_fail(fn, "pre_filter_size (the effective preFilterCap) must be in [1, 63]");
+  if (q->texture_threshold < 0) return stereo_fail(fn, "texture_threshold must be >= 0");
+  if (q->uniqueness_ratio < 0) return stereo_fail(fn, "uniqueness_ratio must be >= 0");
+  if (q->min_disparity < -4096 || q->min_disparity > 4096)
+    return stereo_fail(fn, "min_disparity must be in [-4096, 4096]");
+  if (!cv16s_holds(q->min_disparity, q->num_disparities))
+    return stereo_fail(fn, "the CV_16S map cannot hold this disparity range: "
+                           "min_disparity must be >= -2047 and min_disparity + num_disparities <= 2047");
+  if (left_step < (size_t)width || right_step < (size_t)width ||
+      (dev_mask && mask_step < (size_t)width) || disp_step < (size_t)width * sizeof(float) ||
+      (dev_raw && raw_step < (size_t)width * sizeof(int16_t)))
+    return stereo_fail(fn, "a row step is smaller than the width");
+  if (disp_step % sizeof(float) != 0 || (dev_raw && raw_step % sizeof(int16_t) != 0))
+    return stereo_fail(fn, "output steps must be multiples of the element size");
+  return AMHIP_OK;
+}
+
+struct BmScratch {
+  size_t oL, oR, oD, oP, oN, oB, total;  // total: one pair's bytes, a multiple of 256
+};
+
+static BmScratch bm_scratch(int width, int height) {
+  const size_t npix = (size_t)width * height;
+  BmScratch o;
+  o.oL = 0;
+  o.oR = o.oL + align256(npix);
+  o.oD = o.oR + align256(npix);
+  o.oP = o.oD + align256(npix * 2);
+  o.oN = o.oP + align256(npix * 4);
+  o.oB = o.oN + align256(npix * 4);
+  o.total = o.oB + align256(npix * 4);
+  return o;
+}
+
+static int bm_run(Ctx* c, const amhip_bm_params* q, int width, int height, int batch,
+                  const BatchStrides& bs, const uint8_t* dev_left, size_t left_step,
+                  const uint8_t* dev_right, size_t right_step, const uint8_t* dev_mask,
+                  size_t mask_step, float* dev_disparity, size_t disp_step, int16_t* dev_raw,
+                  size_t raw_step) {
+  // the wrapper's setters (block-matching-bm.h): preFilterCap = pre_filter_size (the second
+  // setPreFilterCap wins), disp12MaxDiff stays -1; findStereoCorrespondenceBM's preamble and
+  // getValidDisparityROI (tests/bm_reference.py: effective, region)
+  BmDims p;
+  std::memset(&p, 0, sizeof(p));
+  p.W = width;
+  p.H = height;
+  p.minD = q->min_disparity;
+  p.D = q->num_disparities;
+  p.cap = q->pre_filter_size;
+  p.SW2 = q->block_size / 2;
+  p.uniq = q->uniqueness_ratio;
+  p.texture = q->texture_threshold;
+  p.lofs = std::max(p.D - 1 + p.minD, 0);
+  p.rofs = -std::min(p.D - 1 + p.minD, 0);
+  p.filtered = (int)(int16_t)((p.minD - 1) * 16);
+  const int width1 = width - p.rofs - p.D + 1;
+  const int maxD = p.minD + p.D - 1;
+  p.xa = std::max(maxD, 0) + p.SW2;
+  p.xb = std::min(width - p.SW2, p.lofs + width1);
+  p.ya = p.SW2;
+  p.yb = height - p.SW2;
+  if (p.lofs >= width || p.rofs >= width || width1 < 1 || p.xb <= p.xa || p.yb <= p.ya)
+    p.xa = p.xb = p.ya = p.yb = 0;  // nothing matched: FILTERED everywhere
+  const bool matched = p.xb > p.xa;
+
+  const size_t npix = (size_t)width * height;
+  const BmScratch o = bm_scratch(width, height);
+  const unsigned B = (unsigned)batch;
+  const size_t wsb = o.total;  // pair b's scratch: the single-pair layout at b * wsb
+  int rc;
+  if ((rc = stereo_scratch(c, wsb * B))) return rc;
+  uint8_t* ws = c->sgbm_ws;
+  uint8_t* fl = ws + o.oL;
+  uint8_t* fr = ws + o.oR;
+  int16_t* disp = reinterpret_cast<int16_t*>(ws + o.oD);
+  int* par = reinterpret_cast<int*>(ws + o.oP);
+  int* cnt = reinterpret_cast<int*>(ws + o.oN);
+  int* lab = reinterpret_cast<int*>(ws + o.oB);
+
+  // the speckle filter and the final pass are SGBM's, on these fields
+  SgbmDims s;
+  std::memset(&s, 0, sizeof(s));
+  s.W = width;
+  s.H = height;
+  s.invalid = p.filtered;
+  s.speckle_win = q->speckle_window_size;
+  s.speckle_diff = q->speckle_range;  // (StereoBM: unscaled, in 1/16 pixel)
+
+  ScopedTimer t(c, AMHIP_K_STEREO);
+  const dim3 rowgrid((unsigned)((width + 255) / 256), (unsigned)height, B);
+  hipLaunchKernelGGL(k_bm_prefilter, rowgrid, dim3(256), 0, c->stream, p, dev_left, left_step, dev_right,
+                     right_step, fl, fr, disp, bs.left, bs.right, wsb);
+  if (matched) {
+    const dim3 grid((unsigned)((p.xb - p.xa + kBmTX - 1) / kBmTX),
+                    (unsigned)((p.yb - p.ya + kBmTY - 1) / kBmTY), B);
+    launch_bm_match(c, p, grid, fl, fr, disp, wsb);
+  }
+  const bool speckle = q->speckle_range >= 0 && q->speckle_window_size > 0;
+  if (speckle) {
+    const dim3 nb((unsigned)((npix + 255) / 256), 1, B);
+    hipLaunchKernelGGL(k_sgbm_uf_init, nb, dim3(256), 0, c->stream, (int)npix, par, cnt, wsb);
+    hipLaunchKernelGGL(k_sgbm_uf_union, rowgrid, dim3(256), 0, c->stream, s, disp, par, wsb);
+    hipLaunchKernelGGL(k_sgbm_uf_count, nb, dim3(256), 0, c->stream, s, disp, par, lab, cnt, wsb);
+  }
+  hipLaunchKernelGGL(k_sgbm_final, rowgrid, dim3(256), 0, c->stream, s, disp, speckle ? lab : nullptr,
+                     cnt, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step, wsb, bs.mask,
+                     bs.disp, bs.raw);
+  AMHIP_TRY(hipGetLastError());
+  return AMHIP_OK;
+}
+
+int stereo_scratch_reserve(Ctx* c, const amhip_stereo_settings& s, int width, int height, int batch) {
+  const size_t one = s.use_bm ? bm_scratch(width, height).total
+                              : sgbm_scratch(sgbm_dims(&s.sgbm, width, height)).total;
+  return stereo_scratch(c, one * (size_t)batch);
 }
 
 }  // namespace amhip
@@ -613,116 +998,38 @@ int amhip_sgbm_disparity_dev(amhip_ctx* h, const amhip_sgbm_params* q, int width
                              size_t right_step, const uint8_t* dev_mask, size_t mask_step,
                              float* dev_disparity, size_t disp_step, int16_t* dev_raw,
                              size_t raw_step) {
-  // (the parameters first: every argument error is reported without a device)
-  if (!q || !dev_left || !dev_right || !dev_disparity)
-    return arg_failure("amhip_sgbm_disparity_dev: null argument");
-  if (width < 3 || height < 1 || width > 32767 || height > 32767)
-    return arg_failure("amhip_sgbm_disparity_dev: width must be in [3, 32767], height in [1, 32767]");
-  if (q->num_disparities <= 0 || q->num_disparities % 16 != 0 || q->num_disparities > kSgbmMaxD)
-    return arg_failure("amhip_sgbm_disparity_dev: num_disparities must be a positive multiple of 16, <= 256");
-  if (q->block_size > 11 || (q->block_size > 0 && q->block_size % 2 == 0))
-    return arg_failure("amhip_sgbm_disparity_dev: block_size must be odd and <= 11 (0: OpenCV's 5)");
-  if (q->min_disparity < -4096 || q->min_disparity > 4096 || q->pre_filter_cap > 63 ||
-      q->uniqueness_ratio > 100 || q->p1 > 4096 || q->p2 > 4096)
-    return arg_failure("amhip_sgbm_disparity_dev: parameter out of range");
-  if (!cv16s_holds(q->min_disparity, q->num_disparities))
-    return arg_failure("amhip_sgbm_disparity_dev: the CV_16S map cannot hold this disparity range: "
-                       "min_disparity must be >= -2047 and min_disparity + num_disparities <= 2047");
-  // (the map's values span less than 2^16, so every range >= 4096 acts alike; 16 * range must fit an int)
-  if (q->speckle_range < -4096 || q->speckle_range > 4096)
-    return arg_failure("amhip_sgbm_disparity_dev: speckle_range must be in [-4096, 4096]");
-  if (left_step < (size_t)width || right_step < (size_t)width ||
-      (dev_mask && mask_step < (size_t)width) || disp_step < (size_t)width * sizeof(float) ||
-      (dev_raw && raw_step < (size_t)width * sizeof(int16_t)))
-    return arg_failure("amhip_sgbm_disparity_dev: a row step is smaller than the width");
-  if (disp_step % sizeof(float) != 0 || (dev_raw && raw_step % sizeof(int16_t) != 0))
-    return arg_failure("amhip_sgbm_disparity_dev: output steps must be multiples of the element size");
-  {
-    const int maxD = q->min_disparity + q->num_disparities;
-    const int w1 = width + std::min(q->min_disparity, 0) - std::max(maxD, 0);
-    if (w1 > 0 && w1 <= (q->block_size > 0 ? q->block_size : 5) / 2)
-      return arg_failure("amhip_sgbm_disparity_dev: fewer matchable columns than half the block");
-  }
+  int rc = sgbm_check("amhip_sgbm_disparity_dev", q, width, height, dev_left, left_step, dev_right,
+                      right_step, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step);
+  if (rc) return rc;
   if (!h) return arg_failure("null context");
   Ctx* c = &h->impl;
-  int rc = ctx_use_device(c);
+  if ((rc = ctx_use_device(c))) return rc;
+  const BatchStrides one = {0, 0, 0, 0, 0};
+  return sgbm_run(c, q, width, height, 1, one, dev_left, left_step, dev_right, right_step, dev_mask,
+                  mask_step, dev_disparity, disp_step, dev_raw, raw_step);
+}
+
+int amhip_sgbm_disparity_batch_dev(amhip_ctx* h, const amhip_sgbm_params* q, int width, int height,
+                                   int batch, const uint8_t* dev_left, size_t left_step,
+                                   size_t left_batch_stride, const uint8_t* dev_right, size_t right_step,
+                                   size_t right_batch_stride, const uint8_t* dev_mask, size_t mask_step,
+                                   size_t mask_batch_stride, float* dev_disparity, size_t disp_step,
+                                   size_t disp_batch_stride, int16_t* dev_raw, size_t raw_step,
+                                   size_t raw_batch_stride) {
+  static const char* fn = "amhip_sgbm_disparity_batch_dev";
+  int rc = sgbm_check(fn, q, width, height, dev_left, left_step, dev_right, right_step, dev_mask,
+                      mask_step, dev_disparity, disp_step, dev_raw, raw_step);
   if (rc) return rc;
-
-  // computeDisparitySGBM's preamble (tests/sgbm_reference.py: derived)
-  SgbmDims p;
-  std::memset(&p, 0, sizeof(p));
-  p.W = width;
-  p.H = height;
-  p.minD = q->min_disparity;
-  p.maxD = p.minD + q->num_disparities;
-  p.D = q->num_disparities;
-  p.P1 = q->p1 > 0 ? q->p1 : 2;
-  p.P2 = std::max(q->p2 > 0 ? q->p2 : 5, p.P1 + 1);
-  p.ftzero = std::max(q->pre_filter_cap, 15) | 1;
-  p.uniq = q->uniqueness_ratio >= 0 ? q->uniqueness_ratio : 10;
-  p.disp12 = q->disp_12_max_diff > 0 ? q->disp_12_max_diff : 1;
-  const int win = q->block_size > 0 ? q->block_size : 5;
-  p.SW2 = p.SH2 = win / 2;
-  p.minX1 = std::max(p.maxD, 0);
-  p.maxX1 = width + std::min(p.minD, 0);
-  p.w1 = p.maxX1 - p.minX1;
-  p.invalid = (p.minD - 1) * 16;
-  p.speckle_win = q->speckle_window_size;
-  p.speckle_diff = 16 * q->speckle_range;
-  const bool matched = p.w1 > 0;
-
-  const size_t npix = (size_t)width * height;
-  const size_t vol = matched ? (size_t)height * p.w1 * p.D : 0;
-  const size_t oC = 0, oS = oC + align256(vol * 2), o1 = oS + align256(vol * 4),
-               oK = o1 + align256(npix * 2), oL = oK + align256(npix * 8),
-               oM = oL + align256(npix * 2), oP = oM + align256(npix * 2),
-               oN = oP + align256(npix * 4), oB = oN + align256(npix * 4),
-               total = oB + align256(npix * 4);
-  if ((rc = ensure_bytes(reinterpret_cast<void**>(&c->sgbm_ws), &c->sgbm_ws_cap, total))) return rc;
-  uint8_t* ws = c->sgbm_ws;
-  uint16_t* C = reinterpret_cast<uint16_t*>(ws + oC);
-  int32_t* S = reinterpret_cast<int32_t*>(ws + oS);
-  uint16_t* hsum = reinterpret_cast<uint16_t*>(ws + oS);  // (dead once C is built)
-  int16_t* disp1 = reinterpret_cast<int16_t*>(ws + o1);
-  unsigned long long* key2 = reinterpret_cast<unsigned long long*>(ws + oK);
-  int16_t* lr = reinterpret_cast<int16_t*>(ws + oL);
-  int16_t* med = reinterpret_cast<int16_t*>(ws + oM);
-  int* par = reinterpret_cast<int*>(ws + oP);
-  int* cnt = reinterpret_cast<int*>(ws + oN);
-  int* lab = reinterpret_cast<int*>(ws + oB);
-
-  ScopedTimer t(c, AMHIP_K_STEREO);
-  const dim3 rowgrid((unsigned)((width + 255) / 256), (unsigned)height);
-  if (matched) {
-    AMHIP_TRY(hipMemsetAsync(key2, 0xFF, npix * 8, c->stream));
-    hipLaunchKernelGGL(k_sgbm_hsum, dim3((unsigned)((p.w1 + kSgbmTX - 1) / kSgbmTX), (unsigned)height),
-                       dim3(256), 0, c->stream, p, dev_left, left_step, dev_right, right_step, hsum);
-    hipLaunchKernelGGL(k_sgbm_vsum, dim3((unsigned)(((size_t)p.w1 * p.D + 255) / 256),
-                                         (unsigned)((height + kSgbmVRows - 1) / kSgbmVRows)),
-                       dim3(256), 0, c->stream, p, hsum, C);
-    if (p.D <= 64)
-      launch_paths<1>(c, p, C, S, disp1, key2);
-    else if (p.D <= 128)
-      launch_paths<2>(c, p, C, S, disp1, key2);
-    else if (p.D <= 192)
-      launch_paths<3>(c, p, C, S, disp1, key2);
-    else
-      launch_paths<4>(c, p, C, S, disp1, key2);
-  }
-  // (no match possible: every pixel INVALID_DISP_SCALED; disp1 / key2 are not read)
-  hipLaunchKernelGGL(k_sgbm_lrcheck, rowgrid, dim3(256), 0, c->stream, p, disp1, key2, lr);
-  hipLaunchKernelGGL(k_sgbm_median, rowgrid, dim3(256), 0, c->stream, width, height, lr, med);
-  const bool speckle = q->speckle_window_size > 0;
-  if (speckle) {
-    const unsigned nb = (unsigned)((npix + 255) / 256);
-    hipLaunchKernelGGL(k_sgbm_uf_init, dim3(nb), dim3(256), 0, c->stream, (int)npix, par, cnt);
-    hipLaunchKernelGGL(k_sgbm_uf_union, rowgrid, dim3(256), 0, c->stream, p, med, par);
-    hipLaunchKernelGGL(k_sgbm_uf_count, dim3(nb), dim3(256), 0, c->stream, p, med, par, lab, cnt);
-  }
-  hipLaunchKernelGGL(k_sgbm_final, rowgrid, dim3(256), 0, c->stream, p, med, speckle ? lab : nullptr,
-                     cnt, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step);
-  AMHIP_TRY(hipGetLastError());
-  return AMHIP_OK;
+  const BatchStrides bs = {left_batch_stride, right_batch_stride, mask_batch_stride, disp_batch_stride,
+                           raw_batch_stride};
+  if ((rc = batch_check(fn, height, batch, bs, left_step, right_step, dev_mask != nullptr, mask_step,
+                        disp_step, dev_raw != nullptr, raw_step)))
+    return rc;
+  if (!h) return arg_failure("null context");
+  Ctx* c = &h->impl;
+  if ((rc = ctx_use_device(c))) return rc;
+  return sgbm_run(c, q, width, height, batch, bs, dev_left, left_step, dev_right, right_step, dev_mask,
+                  mask_step, dev_disparity, disp_step, dev_raw, raw_step);
 }
 
 void amhip_bm_default_params(amhip_bm_params* out) {
@@ -745,106 +1052,38 @@ int amhip_bm_disparity_dev(amhip_ctx* h, const amhip_bm_params* q, int width, in
                            size_t right_step, const uint8_t* dev_mask, size_t mask_step,
                            float* dev_disparity, size_t disp_step, int16_t* dev_raw,
                            size_t raw_step) {
-  // (StereoBM::compute's CV_Asserts on the wrapper's effective parameters, then this
-  // implementation's limits; every argument error is reported without a device)
-  if (!q || !dev_left || !dev_right || !dev_disparity)
-    return arg_failure("amhip_bm_disparity_dev: null argument");
-  if (width < 1 || height < 1 || width > 32767 || height > 32767)
-    return arg_failure("amhip_bm_disparity_dev: width and height must be in [1, 32767]");
-  if (q->num_disparities <= 0 || q->num_disparities % 16 != 0 || q->num_disparities > kSgbmMaxD)
-    return arg_failure("amhip_bm_disparity_dev: num_disparities must be a positive multiple of 16, <= 256");
-  if (q->block_size % 2 == 0 || q->block_size < 5 || q->block_size > 2 * kBmMaxSW2 + 1 ||
-      q->block_size > std::min(width, height))
-    return arg_failure("amhip_bm_disparity_dev: block_size must be odd, in [5, 31] and <= min(width, height)");
-  if (q->pre_filter_size < 1 || q->pre_filter_size > 63)
-    return arg_failure("amhip_bm_disparity_dev: pre_filter_size (the effective preFilterCap) must be in [1, 63]");
-  if (q->texture_threshold < 0)
-    return arg_failure("amhip_bm_disparity_dev: texture_threshold must be >= 0");
-  if (q->uniqueness_ratio < 0)
-    return arg_failure("amhip_bm_disparity_dev: uniqueness_ratio must be >= 0");
-  if (q->min_disparity < -4096 || q->min_disparity > 4096)
-    return arg_failure("amhip_bm_disparity_dev: min_disparity must be in [-4096, 4096]");
-  if (!cv16s_holds(q->min_disparity, q->num_disparities))
-    return arg_failure("amhip_bm_disparity_dev: the CV_16S map cannot hold this disparity range: "
-                       "min_disparity must be >= -2047 and min_disparity + num_disparities <= 2047");
-  if (left_step < (size_t)width || right_step < (size_t)width ||
-      (dev_mask && mask_step < (size_t)width) || disp_step < (size_t)width * sizeof(float) ||
-      (dev_raw && raw_step < (size_t)width * sizeof(int16_t)))
-    return arg_failure("amhip_bm_disparity_dev: a row step is smaller than the width");
-  if (disp_step % sizeof(float) != 0 || (dev_raw && raw_step % sizeof(int16_t) != 0))
-    return arg_failure("amhip_bm_disparity_dev: output steps must be multiples of the element size");
+  int rc = bm_check("amhip_bm_disparity_dev", q, width, height, dev_left, left_step, dev_right,
+                    right_step, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step);
+  if (rc) return rc;
   if (!h) return arg_failure("null context");
   Ctx* c = &h->impl;
-  int rc = ctx_use_device(c);
+  if ((rc = ctx_use_device(c))) return rc;
+  const BatchStrides one = {0, 0, 0, 0, 0};
+  return bm_run(c, q, width, height, 1, one, dev_left, left_step, dev_right, right_step, dev_mask,
+                mask_step, dev_disparity, disp_step, dev_raw, raw_step);
+}
+
+int amhip_bm_disparity_batch_dev(amhip_ctx* h, const amhip_bm_params* q, int width, int height,
+                                 int batch, const uint8_t* dev_left, size_t left_step,
+                                 size_t left_batch_stride, const uint8_t* dev_right, size_t right_step,
+                                 size_t right_batch_stride, const uint8_t* dev_mask, size_t mask_step,
+                                 size_t mask_batch_stride, float* dev_disparity, size_t disp_step,
+                                 size_t disp_batch_stride, int16_t* dev_raw, size_t raw_step,
+                                 size_t raw_batch_stride) {
+  static const char* fn = "amhip_bm_disparity_batch_dev";
+  int rc = bm_check(fn, q, width, height, dev_left, left_step, dev_right, right_step, dev_mask,
+                    mask_step, dev_disparity, disp_step, dev_raw, raw_step);
   if (rc) return rc;
-
-  // the wrapper's setters (block-matching-bm.h): preFilterCap = pre_filter_size (the second
-  // setPreFilterCap wins), disp12MaxDiff stays -1; findStereoCorrespondenceBM's preamble and
-  // getValidDisparityROI (tests/bm_reference.py: effective, region)
-  BmDims p;
-  std::memset(&p, 0, sizeof(p));
-  p.W = width;
-  p.H = height;
-  p.minD = q->min_disparity;
-  p.D = q->num_disparities;
-  p.cap = q->pre_filter_size;
-  p.SW2 = q->block_size / 2;
-  p.uniq = q->uniqueness_ratio;
-  p.texture = q->texture_threshold;
-  p.lofs = std::max(p.D - 1 + p.minD, 0);
-  p.rofs = -std::min(p.D - 1 + p.minD, 0);
-  p.filtered = (int)(int16_t)((p.minD - 1) * 16);
-  const int width1 = width - p.rofs - p.D + 1;
-  const int maxD = p.minD + p.D - 1;
-  p.xa = std::max(maxD, 0) + p.SW2;
-  p.xb = std::min(width - p.SW2, p.lofs + width1);
-  p.ya = p.SW2;
-  p.yb = height - p.SW2;
-  if (p.lofs >= width || p.rofs >= width || width1 < 1 || p.xb <= p.xa || p.yb <= p.ya)
-    p.xa = p.xb = p.ya = p.yb = 0;  // nothing matched: FILTERED everywhere
-  const bool matched = p.xb > p.xa;
-
-  const size_t npix = (size_t)width * height;
-  const size_t oL = 0, oR = oL + align256(npix), oD = oR + align256(npix),
-               oP = oD + align256(npix * 2), oN = oP + align256(npix * 4),
-               oB = oN + align256(npix * 4), total = oB + align256(npix * 4);
-  if ((rc = ensure_bytes(reinterpret_cast<void**>(&c->sgbm_ws), &c->sgbm_ws_cap, total))) return rc;
-  uint8_t* ws = c->sgbm_ws;
-  uint8_t* fl = ws + oL;
-  uint8_t* fr = ws + oR;
-  int16_t* disp = reinterpret_cast<int16_t*>(ws + oD);
-  int* par = reinterpret_cast<int*>(ws + oP);
-  int* cnt = reinterpret_cast<int*>(ws + oN);
-  int* lab = reinterpret_cast<int*>(ws + oB);
-
-  // the speckle filter and the final pass are SGBM's, on these fields
-  SgbmDims s;
-  std::memset(&s, 0, sizeof(s));
-  s.W = width;
-  s.H = height;
-  s.invalid = p.filtered;
-  s.speckle_win = q->speckle_window_size;
-  s.speckle_diff = q->speckle_range;  // (StereoBM: unscaled, in 1/16 pixel)
-
-  ScopedTimer t(c, AMHIP_K_STEREO);
-  const dim3 rowgrid((unsigned)((width + 255) / 256), (unsigned)height);
-  hipLaunchKernelGGL(k_bm_prefilter, rowgrid, dim3(256), 0, c->stream, p, dev_left, left_step, dev_right,
-                     right_step, fl, fr, disp);
-  if (matched) {
-    const dim3 grid((unsigned)((p.xb - p.xa + kBmTX - 1) / kBmTX), (unsigned)((p.yb - p.ya + kBmTY - 1) / kBmTY));
-    launch_bm_match(c, p, grid, fl, fr, disp);
-  }
-  const bool speckle = q->speckle_range >= 0 && q->speckle_window_size > 0;
-  if (speckle) {
-    const unsigned nb = (unsigned)((npix + 255) / 256);
-    hipLaunchKernelGGL(k_sgbm_uf_init, dim3(nb), dim3(256), 0, c->stream, (int)npix, par, cnt);
-    hipLaunchKernelGGL(k_sgbm_uf_union, rowgrid, dim3(256), 0, c->stream, s, disp, par);
-    hipLaunchKernelGGL(k_sgbm_uf_count, dim3(nb), dim3(256), 0, c->stream, s, disp, par, lab, cnt);
-  }
-  hipLaunchKernelGGL(k_sgbm_final, rowgrid, dim3(256), 0, c->stream, s, disp, speckle ? lab : nullptr,
-                     cnt, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step);
-  AMHIP_TRY(hipGetLastError());
-  return AMHIP_OK;
+  const BatchStrides bs = {left_batch_stride, right_batch_stride, mask_batch_stride, disp_batch_stride,
+                           raw_batch_stride};
+  if ((rc = batch_check(fn, height, batch, bs, left_step, right_step, dev_mask != nullptr, mask_step,
+                        disp_step, dev_raw != nullptr, raw_step)))
+    return rc;
+  if (!h) return arg_failure("null context");
+  Ctx* c = &h->impl;
+  if ((rc = ctx_use_device(c))) return rc;
+  return bm_run(c, q, width, height, batch, bs, dev_left, left_step, dev_right, right_step, dev_mask,
+                mask_step, dev_disparity, disp_step, dev_raw, raw_step);
 }
 
 }  // extern "C"

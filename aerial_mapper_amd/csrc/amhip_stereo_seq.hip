@@ -12,12 +12,22 @@
 //   pairs      rectify -> match -> append, all enqueued on the context's stream; the point count
 //              stays on the device (SeqState) and is read once, by amhip_stereo_cloud.
 //   capacity   settled before the first pair of a sequence (pairs x W x H points).
+//   groups     amhip_stereo_set_pairs_in_flight(n > 1): add_frames takes the used frames in groups of
+//              up to n consecutive pairs -- n + 1 frame slots in rotation (frame j in slot j mod
+//              (n + 1)), the pairs rectified into stacks, ONE batched matcher call, then the appends
+//              pair by pair in order.  Each pair of a group copies the context's sticky error word
+//              behind its own rectifier (stream order), and its append reads that copy: a zero w
+//              silences its own pair and the later ones, never an earlier one.
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <new>
 
 #include "amhip_common.h"
 
 namespace amhip {
+
+constexpr int kSeqMaxSlots = AMHIP_STEREO_MAX_BATCH + 1;
 
 struct Stereo {
   amhip_ctx* ctx = nullptr;
@@ -30,19 +40,24 @@ struct Stereo {
   bool undistort = false;
 
   hipStream_t up_stream = nullptr;
-  hipEvent_t ev_up[2] = {nullptr, nullptr};    // the upload into slot s has finished
-  hipEvent_t ev_free[2] = {nullptr, nullptr};  // the last kernel reading raw[s] has finished
-  bool up_used[2] = {false, false};
-  uint8_t* pin[2] = {nullptr, nullptr};
-  uint8_t* raw[2] = {nullptr, nullptr};
-  uint8_t* und[2] = {nullptr, nullptr};
+  int nslots = 0;                      // frame slots allocated: 2, or (the largest n asked for) + 1
+  int in_flight = 1;                   // pairs per group of add_frames
+  hipEvent_t ev_up[kSeqMaxSlots] = {};    // the upload into slot s has finished
+  hipEvent_t ev_free[kSeqMaxSlots] = {};  // the last kernel reading raw[s] has finished
+  bool up_used[kSeqMaxSlots] = {};
+  uint8_t* pin[kSeqMaxSlots] = {};
+  uint8_t* raw[kSeqMaxSlots] = {};
+  uint8_t* und[kSeqMaxSlots] = {};
 
   bool first_frame = true;
   int left_slot = 0;
   double R1[9] = {}, t1[3] = {};
 
+  // stacks of `stack` rectified pairs, masks and disparity maps, npix elements apart
+  int stack = 0;
   uint8_t *rect_l = nullptr, *rect_r = nullptr, *mask = nullptr;
   float* disp = nullptr;
+  unsigned* flags = nullptr;  // per pair of a group: the device error word behind its rectifier
   double* xyz = nullptr;
   int32_t* inten = nullptr;
   size_t cap = 0;  // points
@@ -102,7 +117,7 @@ static int dev_alloc(void** p, size_t bytes) {
 static void seq_free(Stereo* s) {
   if (s->up_stream) (void)hipStreamSynchronize(s->up_stream);
   if (s->ctx) (void)hipStreamSynchronize(s->ctx->impl.stream);
-  for (int k = 0; k < 2; ++k) {
+  for (int k = 0; k < kSeqMaxSlots; ++k) {
     if (s->ev_up[k]) (void)hipEventDestroy(s->ev_up[k]);
     if (s->ev_free[k]) (void)hipEventDestroy(s->ev_free[k]);
     if (s->pin[k]) (void)hipHostFree(s->pin[k]);
@@ -110,7 +125,7 @@ static void seq_free(Stereo* s) {
     if (s->und[k]) (void)hipFree(s->und[k]);
   }
   if (s->up_stream) (void)hipStreamDestroy(s->up_stream);
-  void* dev[] = {s->rect_l, s->rect_r, s->mask, s->disp, s->xyz, s->inten, s->state, s->pc2};
+  void* dev[] = {s->rect_l, s->rect_r, s->mask, s->disp, s->flags, s->xyz, s->inten, s->state, s->pc2};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   if (s->host_state) (void)hipHostFree(s->host_state);
@@ -137,17 +152,69 @@ static int seq_clear(Stereo* s) {
   return AMHIP_OK;
 }
 
-// One frame of the sequence: stage, undistort, and -- unless it is the first -- run the pair.
-static int seq_push(Stereo* s, const double* T_G_B7, const uint8_t* src, size_t step, bool on_device,
-                    bool replace) {
+// frame slots 0 .. n - 1 exist (events, pinned staging, raw and, if used, undistorted frame)
+static int seq_grow_slots(Stereo* s, int n) {
+  for (int k = s->nslots; k < n; ++k) {
+    AMHIP_TRY(hipEventCreateWithFlags(&s->ev_up[k], hipEventDisableTiming));
+    AMHIP_TRY(hipEventCreateWithFlags(&s->ev_free[k], hipEventDisableTiming));
+    const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&s->pin[k]), s->npix, hipHostMallocDefault);
+    if (e == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      s->pin[k] = nullptr;
+      set_last_error("amhip_stereo: out of pinned host memory");
+      return AMHIP_ERR_NOMEM;
+    }
+    AMHIP_TRY(e);
+    int rc;
+    if ((rc = dev_alloc(reinterpret_cast<void**>(&s->raw[k]), s->npix))) return rc;
+    if (s->undistort && (rc = dev_alloc(reinterpret_cast<void**>(&s->und[k]), s->npix))) return rc;
+    s->nslots = k + 1;  // (a slot that failed half-way is freed with the object)
+  }
+  return AMHIP_OK;
+}
+
+// the stacks hold n rectified pairs, masks and disparity maps (contents are not kept)
+static int seq_grow_stacks(Stereo* s, int n) {
+  if (n <= s->stack) return AMHIP_OK;
+  uint8_t *l = nullptr, *r = nullptr, *m = nullptr;
+  float* d = nullptr;
+  int rc;
+  if ((rc = dev_alloc(reinterpret_cast<void**>(&l), s->npix * n)) ||
+      (rc = dev_alloc(reinterpret_cast<void**>(&r), s->npix * n)) ||
+      (rc = dev_alloc(reinterpret_cast<void**>(&m), s->npix * n)) ||
+      (rc = dev_alloc(reinterpret_cast<void**>(&d), s->npix * n * sizeof(float)))) {
+    void* got[] = {l, r, m, d};
+    for (void* p : got)
+      if (p) (void)hipFree(p);
+    return rc;
+  }
+  // (hipFree waits for the kernels that still use the old stacks)
+  void* old[] = {s->rect_l, s->rect_r, s->mask, s->disp};
+  for (void* p : old)
+    if (p) AMHIP_TRY(hipFree(p));
+  s->rect_l = l;
+  s->rect_r = r;
+  s->mask = m;
+  s->disp = d;
+  s->stack = n;
+  return AMHIP_OK;
+}
+
+// stereo.cpp:129-137: T_G_C = T_G_B * T_B_C, its position and rotation matrix
+static void seq_pose(const Stereo* s, const double* T_G_B7, double R[9], double t[3]) {
+  const HPose T_G_C = hpose_compose(hpose_from7(T_G_B7), s->T_B_C);
+  quat_to_matrix(T_G_C, R);
+  t[0] = T_G_C.tx;
+  t[1] = T_G_C.ty;
+  t[2] = T_G_C.tz;
+}
+
+static const uint8_t* seq_frame(const Stereo* s, int slot) { return s->undistort ? s->und[slot] : s->raw[slot]; }
+
+// a frame into its slot: staged and, if asked for, undistorted -- once, whichever pairs it serves
+static int seq_stage(Stereo* s, int slot, const uint8_t* src, size_t step, bool on_device) {
   Ctx* c = &s->ctx->impl;
   hipStream_t main = c->stream;
-  // stereo.cpp:129-137: T_G_C = T_G_B * T_B_C, its position and rotation matrix
-  const HPose T_G_C = hpose_compose(hpose_from7(T_G_B7), s->T_B_C);
-  double R2[9];
-  quat_to_matrix(T_G_C, R2);
-  const double t2[3] = {T_G_C.tx, T_G_C.ty, T_G_C.tz};
-  const int slot = s->first_frame ? 0 : (s->left_slot ^ 1);
   const size_t W = (size_t)s->W, H = (size_t)s->H;
   if (on_device) {
     AMHIP_TRY(hipMemcpy2DAsync(s->raw[slot], W, src, step, W, H, hipMemcpyDeviceToDevice, main));
@@ -160,45 +227,39 @@ static int seq_push(Stereo* s, const double* T_G_B7, const uint8_t* src, size_t 
     s->up_used[slot] = true;
     AMHIP_TRY(hipStreamWaitEvent(main, s->ev_up[slot], 0));
   }
-  const uint8_t* img[2] = {s->raw[0], s->raw[1]};
   if (s->undistort) {
     ScopedTimer t(c, AMHIP_K_MISC);
     int rc = undistort_frames_run(main, s->cam, s->raw[slot], s->npix, W, 1, 1, s->und[slot]);
     if (rc) return rc;
     AMHIP_TRY(hipEventRecord(s->ev_free[slot], main));
-    img[0] = s->und[0];
-    img[1] = s->und[1];
   }
-  if (s->first_frame) {
-    std::memcpy(s->R1, R2, sizeof(R2));
-    std::memcpy(s->t1, t2, sizeof(t2));
-    s->left_slot = slot;
-    s->first_frame = false;
-    return AMHIP_OK;
-  }
-  const int left = s->left_slot;
-  if (t2[0] == s->t1[0] && t2[1] == s->t1[1] && t2[2] == s->t1[2])
-    return seq_arg_fail("CHECK_NE(baseline, 0.0) (densifier.cpp:39): both frames have the same position");
-  double R_G_C[9], baseline = 0.0;
-  int rc = amhip_rectify_stereo_pair_dev(s->ctx, s->K, s->R1, R2, s->t1, t2, s->W, s->H, img[left], W,
-                                         img[slot], W, R_G_C, &baseline, nullptr, s->rect_l, s->rect_r,
-                                         s->mask);
+  return AMHIP_OK;
+}
+
+// the pair (frame in `left`, pose R1 / t1; frame in `right`, pose R2 / t2) rectified into entry k
+// of the stacks
+static int seq_rectify(Stereo* s, int k, int left, const double* R1, const double* t1, int right,
+                       const double* R2, const double* t2, double* R_G_C, double* baseline) {
+  const size_t W = (size_t)s->W;
+  int rc = amhip_rectify_stereo_pair_dev(s->ctx, s->K, R1, R2, t1, t2, s->W, s->H, seq_frame(s, left), W,
+                                         seq_frame(s, right), W, R_G_C, baseline, nullptr,
+                                         s->rect_l + k * s->npix, s->rect_r + k * s->npix,
+                                         s->mask + k * s->npix);
   if (rc) return rc;
-  // (the next frame is staged into the left frame's slot)
-  if (!s->undistort) AMHIP_TRY(hipEventRecord(s->ev_free[left], main));
-  if (baseline == 0.0) return seq_arg_fail("CHECK_NE(baseline, 0.0) (densifier.cpp:39)");
-  const size_t dstep = W * sizeof(float);
-  rc = s->settings.use_bm
-      ? amhip_bm_disparity_dev(s->ctx, &s->settings.bm, s->W, s->H, s->rect_l, W, s->rect_r, W, s->mask,
-                               W, s->disp, dstep, nullptr, 0)
-      : amhip_sgbm_disparity_dev(s->ctx, &s->settings.sgbm, s->W, s->H, s->rect_l, W, s->rect_r, W,
-                                 s->mask, W, s->disp, dstep, nullptr, 0);
-  if (rc) return rc;
+  // (the slot of a pair's left frame is the next one to be staged into)
+  if (!s->undistort) AMHIP_TRY(hipEventRecord(s->ev_free[left], s->ctx->impl.stream));
+  return AMHIP_OK;
+}
+
+// entry k of the stacks -> the cloud; err_word: the device error word this pair answers to
+static int seq_append(Stereo* s, int k, const double* R_G_C, double baseline, const double* t1,
+                      bool replace, const unsigned* err_word) {
+  const size_t W = (size_t)s->W;
   DensifyParams p;
   std::memset(&p, 0, sizeof(p));
   p.width = s->W;
   p.height = s->H;
-  p.disp_step = dstep;
+  p.disp_step = W * sizeof(float);
   p.img_step = W;
   // stereo projection matrix Q (densifier.cpp:39-46), as amhip_densify_dev builds it
   const double fx = s->K[0], fy = s->K[4], cx = s->K[2], cy = s->K[5];
@@ -207,16 +268,109 @@ static int seq_push(Stereo* s, const double* T_G_B7, const uint8_t* src, size_t 
   p.Q13 = -cy * (fx / fy);
   p.Q23 = fx;
   p.Q32 = 1.0 / baseline;
-  for (int k = 0; k < 9; ++k) p.R[k] = R_G_C[k];
-  for (int k = 0; k < 3; ++k) p.t[k] = s->t1[k];
-  if ((rc = densify_append_run(c, p, s->disp, s->rect_l, s->xyz, s->inten, s->cap, s->state, s->pc2,
-                               replace)))
-    return rc;
+  for (int q = 0; q < 9; ++q) p.R[q] = R_G_C[q];
+  for (int q = 0; q < 3; ++q) p.t[q] = t1[q];
+  return densify_append_run(&s->ctx->impl, p, s->disp + k * s->npix, s->rect_l + k * s->npix, s->xyz,
+                            s->inten, s->cap, s->state, s->pc2, replace, err_word);
+}
+
+static const char kSamePosition[] =
+    "CHECK_NE(baseline, 0.0) (densifier.cpp:39): both frames have the same position";
+static const char kZeroBaseline[] = "CHECK_NE(baseline, 0.0) (densifier.cpp:39)";
+
+// One frame of the sequence: stage, undistort, and -- unless it is the first -- run the pair.
+static int seq_push(Stereo* s, const double* T_G_B7, const uint8_t* src, size_t step, bool on_device,
+                    bool replace) {
+  double R2[9], t2[3];
+  seq_pose(s, T_G_B7, R2, t2);
+  const int slot = s->first_frame ? 0 : (s->left_slot + 1) % s->nslots;
+  int rc;
+  if ((rc = seq_stage(s, slot, src, step, on_device))) return rc;
+  if (s->first_frame) {
+    std::memcpy(s->R1, R2, sizeof(R2));
+    std::memcpy(s->t1, t2, sizeof(t2));
+    s->left_slot = slot;
+    s->first_frame = false;
+    return AMHIP_OK;
+  }
+  if (t2[0] == s->t1[0] && t2[1] == s->t1[1] && t2[2] == s->t1[2]) return seq_arg_fail(kSamePosition);
+  double R_G_C[9], baseline = 0.0;
+  if ((rc = seq_rectify(s, 0, s->left_slot, s->R1, s->t1, slot, R2, t2, R_G_C, &baseline))) return rc;
+  if (baseline == 0.0) return seq_arg_fail(kZeroBaseline);
+  const size_t W = (size_t)s->W, dstep = W * sizeof(float);
+  rc = s->settings.use_bm
+      ? amhip_bm_disparity_dev(s->ctx, &s->settings.bm, s->W, s->H, s->rect_l, W, s->rect_r, W, s->mask,
+                               W, s->disp, dstep, nullptr, 0)
+      : amhip_sgbm_disparity_dev(s->ctx, &s->settings.sgbm, s->W, s->H, s->rect_l, W, s->rect_r, W,
+                                 s->mask, W, s->disp, dstep, nullptr, 0);
+  if (rc) return rc;
+  if ((rc = seq_append(s, 0, R_G_C, baseline, s->t1, replace, nullptr))) return rc;
   // stereo.cpp:142-146: the right frame is the next pair's left frame
   std::memcpy(s->R1, R2, sizeof(R2));
   std::memcpy(s->t1, t2, sizeof(t2));
   s->left_slot = slot;
   return AMHIP_OK;
+}
+
+// g <= in_flight consecutive frames of a sequence whose left frame is in place: g pairs, matched
+// by ONE batched call.  A pair the host refuses (zero baseline) cuts the group in front of it: the
+// pairs before it go through, then the call fails with that pair's error, as frame by frame.
+static int seq_push_group(Stereo* s, const double* const* T_G_B7, const uint8_t* const* src,
+                          const size_t* step, bool on_device, int g) {
+  Ctx* c = &s->ctx->impl;
+  double R[AMHIP_STEREO_MAX_BATCH][9], t[AMHIP_STEREO_MAX_BATCH][3];
+  int m = g;  // pairs that go through
+  const char* refused = nullptr;
+  for (int k = 0; k < g; ++k) {
+    seq_pose(s, T_G_B7[k], R[k], t[k]);
+    const double* tp = k ? t[k - 1] : s->t1;
+    const double d[3] = {t[k][0] - tp[0], t[k][1] - tp[1], t[k][2] - tp[2]};
+    if (t[k][0] == tp[0] && t[k][1] == tp[1] && t[k][2] == tp[2])
+      refused = kSamePosition;
+    else if (std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) == 0.0)  // (the rectifier's baseline)
+      refused = kZeroBaseline;
+    if (refused) {
+      m = k;
+      break;
+    }
+  }
+  const int left0 = s->left_slot;
+  auto slot_of = [&](int k) { return (left0 + 1 + k) % s->nslots; };  // frame k of the group
+  int rc;
+  // (the refused frame is staged too, as frame by frame)
+  for (int k = 0; k < (refused ? m + 1 : m); ++k)
+    if ((rc = seq_stage(s, slot_of(k), src[k], step[k], on_device))) return rc;
+  double R_G_C[AMHIP_STEREO_MAX_BATCH][9], baseline[AMHIP_STEREO_MAX_BATCH];
+  for (int k = 0; k < m; ++k) {
+    if ((rc = seq_rectify(s, k, k ? slot_of(k - 1) : left0, k ? R[k - 1] : s->R1, k ? t[k - 1] : s->t1,
+                          slot_of(k), R[k], t[k], R_G_C[k], &baseline[k])))
+      return rc;
+    // the error word as it stands behind this pair's rectifier (the next pair's comes later)
+    AMHIP_TRY(hipMemcpyAsync(s->flags + k, c->dev_err, sizeof(unsigned), hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (m > 0) {
+    const size_t W = (size_t)s->W, dstep = W * sizeof(float), np = s->npix;
+    rc = s->settings.use_bm
+        ? amhip_bm_disparity_batch_dev(s->ctx, &s->settings.bm, s->W, s->H, m, s->rect_l, W, np, s->rect_r,
+                                       W, np, s->mask, W, np, s->disp, dstep, np * sizeof(float), nullptr, 0, 0)
+        : amhip_sgbm_disparity_batch_dev(s->ctx, &s->settings.sgbm, s->W, s->H, m, s->rect_l, W, np,
+                                         s->rect_r, W, np, s->mask, W, np, s->disp, dstep,
+                                         np * sizeof(float), nullptr, 0, 0);
+    if (rc) return rc;
+    for (int k = 0; k < m; ++k)
+      if ((rc = seq_append(s, k, R_G_C[k], baseline[k], k ? t[k - 1] : s->t1, /*replace=*/false,
+                           s->flags + k)))
+        return rc;
+    std::memcpy(s->R1, R[m - 1], sizeof(s->R1));
+    std::memcpy(s->t1, t[m - 1], sizeof(s->t1));
+    s->left_slot = slot_of(m - 1);
+  }
+  if (refused == kZeroBaseline) {  // (frame by frame the rectifier has run before the baseline is looked at)
+    double Rq[9], bq = 0.0;
+    if ((rc = seq_rectify(s, 0, s->left_slot, s->R1, s->t1, (s->left_slot + 1) % s->nslots, R[m], t[m], Rq, &bq)))
+      return rc;
+  }
+  return refused ? seq_arg_fail(refused) : AMHIP_OK;
 }
 
 static int check_channels(int channels) {
@@ -278,13 +432,33 @@ static int add_many(amhip_stereo* h, const double* T, const uint8_t* const* imag
   if ((rc = ctx_use_device(&s->ctx->impl))) return rc;
   const size_t pairs = used == 0 ? 0 : (s->first_frame ? used - 1 : used);
   if ((rc = seq_reserve(s, pairs * s->npix))) return rc;
+  const size_t n = (size_t)s->in_flight;
+  // (the matcher's scratch for a whole group, before the first pair)
+  if (n > 1 && pairs > 0 &&
+      (rc = stereo_scratch_reserve(&s->ctx->impl, s->settings, s->W, s->H, (int)std::min(n, pairs))))
+    return rc;
   if ((rc = seq_clear(s))) return rc;  // point_cloud->clear() (stereo.cpp:86)
+  const double* gT[AMHIP_STEREO_MAX_BATCH];
+  const uint8_t* gsrc[AMHIP_STEREO_MAX_BATCH];
+  size_t gstep[AMHIP_STEREO_MAX_BATCH];
+  int g = 0;
   for (size_t i = 0; i < F; ++i) {
     if ((i + 1) % nth != 0) continue;  // ++skip % use_every_nth_image == 0 (:93)
     const uint8_t* src = on_device ? dev_frames + i * frame_stride : images[i];
-    if ((rc = seq_push(s, T + 7 * i, src, on_device ? row_step : steps[i], on_device, /*replace=*/false)))
-      return rc;
+    const size_t step = on_device ? row_step : steps[i];
+    if (n == 1 || s->first_frame) {
+      if ((rc = seq_push(s, T + 7 * i, src, step, on_device, /*replace=*/false))) return rc;
+      continue;
+    }
+    gT[g] = T + 7 * i;
+    gsrc[g] = src;
+    gstep[g] = step;
+    if (++g == (int)n) {
+      if ((rc = seq_push_group(s, gT, gsrc, gstep, on_device, g))) return rc;
+      g = 0;
+    }
   }
+  if (g > 0 && (rc = seq_push_group(s, gT, gsrc, gstep, on_device, g))) return rc;  // (the last, shorter group)
   return AMHIP_OK;
 }
 
@@ -343,17 +517,9 @@ int amhip_stereo_create(amhip_ctx* ctx, const amhip_camera* cam, const double* T
     if (_e != hipSuccess) return fail(hip_fail(_e, #expr, __FILE__, __LINE__)); \
   } while (0)
   SEQ_TRY(hipStreamCreateWithFlags(&s->up_stream, hipStreamNonBlocking));
-  for (int k = 0; k < 2; ++k) {
-    SEQ_TRY(hipEventCreateWithFlags(&s->ev_up[k], hipEventDisableTiming));
-    SEQ_TRY(hipEventCreateWithFlags(&s->ev_free[k], hipEventDisableTiming));
-    SEQ_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->pin[k]), s->npix, hipHostMallocDefault));
-    if ((rc = dev_alloc(reinterpret_cast<void**>(&s->raw[k]), s->npix))) return fail(rc);
-    if (s->undistort && (rc = dev_alloc(reinterpret_cast<void**>(&s->und[k]), s->npix))) return fail(rc);
-  }
-  if ((rc = dev_alloc(reinterpret_cast<void**>(&s->rect_l), s->npix))) return fail(rc);
-  if ((rc = dev_alloc(reinterpret_cast<void**>(&s->rect_r), s->npix))) return fail(rc);
-  if ((rc = dev_alloc(reinterpret_cast<void**>(&s->mask), s->npix))) return fail(rc);
-  if ((rc = dev_alloc(reinterpret_cast<void**>(&s->disp), s->npix * sizeof(float)))) return fail(rc);
+  if ((rc = seq_grow_slots(s, 2))) return fail(rc);
+  if ((rc = seq_grow_stacks(s, 1))) return fail(rc);
+  if ((rc = dev_alloc(reinterpret_cast<void**>(&s->flags), AMHIP_STEREO_MAX_BATCH * sizeof(unsigned)))) return fail(rc);
   if ((rc = dev_alloc(reinterpret_cast<void**>(&s->state), sizeof(SeqState)))) return fail(rc);
   if ((rc = dev_alloc(&s->pc2, s->npix * 16))) return fail(rc);
   SEQ_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->host_state), sizeof(SeqState), hipHostMallocDefault));
@@ -382,6 +548,20 @@ int amhip_stereo_reset(amhip_stereo* h) {
   s->left_slot = 0;
   if ((rc = seq_clear(s))) return rc;
   AMHIP_TRY(hipMemsetAsync(s->pc2, 0, s->npix * 16, s->ctx->impl.stream));
+  return AMHIP_OK;
+}
+
+int amhip_stereo_set_pairs_in_flight(amhip_stereo* h, int n) {
+  if (n < 1 || n > AMHIP_STEREO_MAX_BATCH)
+    return seq_arg_fail("amhip_stereo_set_pairs_in_flight: n must be in [1, 16]");
+  if (!h) return seq_arg_fail("null stereo object");
+  Stereo* s = &h->impl;
+  int rc = ctx_use_device(&s->ctx->impl);
+  if (rc) return rc;
+  // (slots and stacks only grow: a frame carried over from earlier calls stays in its slot)
+  if ((rc = seq_grow_slots(s, n + 1))) return rc;
+  if ((rc = seq_grow_stacks(s, n))) return rc;
+  s->in_flight = n;
   return AMHIP_OK;
 }
 

@@ -35,6 +35,8 @@ NUM_KERNELS = 8
 
 DIST_NONE, DIST_RADTAN, DIST_EQUIDISTANT = 0, 1, 2
 
+STEREO_MAX_BATCH = 16   # AMHIP_STEREO_MAX_BATCH
+
 # every symbol include/aerial_mapper_hip.h declares
 EXPORTS = [
     "amhip_abi_version", "amhip_last_error", "amhip_make_grid", "amhip_cell_position",
@@ -62,6 +64,7 @@ EXPORTS = [
     "amhip_io_load_point_cloud_binary", "amhip_session_grid_map_msg", "amhip_session_layer_to_image",
     "amhip_sgbm_default_params", "amhip_sgbm_disparity_dev",
     "amhip_bm_default_params", "amhip_bm_disparity_dev",
+    "amhip_sgbm_disparity_batch_dev", "amhip_bm_disparity_batch_dev", "amhip_stereo_set_pairs_in_flight",
     "amhip_stereo_default_settings", "amhip_stereo_create", "amhip_stereo_destroy", "amhip_stereo_reset",
     "amhip_stereo_add_frame", "amhip_stereo_add_frame_dev", "amhip_stereo_add_frames",
     "amhip_stereo_add_frames_dev", "amhip_stereo_cloud", "amhip_stereo_point_cloud2_dev",
@@ -210,6 +213,11 @@ def load():
     lib.amhip_bm_disparity_dev.argtypes = [vp, C.POINTER(BmParams), C.c_int, C.c_int,
                                            vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t,
                                            vp, C.c_size_t, vp, C.c_size_t]
+    # (per array: pointer, row step, batch stride)
+    batch_io = [vp, C.c_size_t, C.c_size_t] * 5
+    lib.amhip_sgbm_disparity_batch_dev.argtypes = [vp, C.POINTER(SgbmParams), C.c_int, C.c_int, C.c_int] + batch_io
+    lib.amhip_bm_disparity_batch_dev.argtypes = [vp, C.POINTER(BmParams), C.c_int, C.c_int, C.c_int] + batch_io
+    lib.amhip_stereo_set_pairs_in_flight.argtypes = [vp, C.c_int]
     sp = C.POINTER(StereoSettings)
     lib.amhip_stereo_default_settings.restype = None
     lib.amhip_stereo_default_settings.argtypes = [sp]

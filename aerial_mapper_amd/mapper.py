@@ -689,25 +689,13 @@ def compute_disparity_sgbm(map, image_left, image_right, params=None, mask=None,
     """stereo::BlockMatchingSGBM::computeDisparityMap (block-matching-sgbm.cpp: StereoSGBM::compute,
     / 16, the rectification mask) on the GPU of `map`: rectified CUDA torch uint8 tensors (H, W) ->
     the float32 disparity map (H, W) on the device; with raw=True also OpenCV's CV_16S map (int16).
-    mask (uint8 (H, W), optional): pixels where it is 0 become kMaxInvalidDisparity = 1.0."""
-    import torch
-    for t in (image_left, image_right) + ((mask,) if mask is not None else ()):
-        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.stride(1) == 1
-    H, W = image_left.shape
-    assert tuple(image_right.shape) == (H, W) and (mask is None or tuple(mask.shape) == (H, W))
-    dev = image_left.device
-    disp = torch.empty((H, W), dtype=torch.float32, device=dev)
-    rawt = torch.empty((H, W), dtype=torch.int16, device=dev) if raw else None
+    mask (uint8 (H, W), optional): pixels where it is 0 become kMaxInvalidDisparity = 1.0.
+    Stacks (B, H, W) of up to 16 pairs (mask (B, H, W) or None) go through one set of launches
+    (amhip_sgbm_disparity_batch_dev) and give (B, H, W) maps, pair by pair the bits of B calls."""
     p = (params or SgbmParameters()).to_c()
-    map.wait_for_torch(image_left)
-    L.check(L.load().amhip_sgbm_disparity_dev(
-        map.handle, C.byref(p), W, H, C.c_void_p(image_left.data_ptr()), image_left.stride(0),
-        C.c_void_p(image_right.data_ptr()), image_right.stride(0),
-        C.c_void_p(mask.data_ptr()) if mask is not None else None,
-        mask.stride(0) if mask is not None else 0, C.c_void_p(disp.data_ptr()), disp.stride(0) * 4,
-        C.c_void_p(rawt.data_ptr()) if raw else None, rawt.stride(0) * 2 if raw else 0))
-    map.synchronize()
-    return (disp, rawt) if raw else disp
+    lib = L.load()
+    return _stereo_call(lib.amhip_sgbm_disparity_dev, lib.amhip_sgbm_disparity_batch_dev, map, image_left,
+                        image_right, p, mask, raw)
 
 
 class BmParameters(object):
@@ -743,22 +731,29 @@ class BlockMatchingParameters(object):
         self.bm = bm if bm is not None else BmParameters()
 
 
-def _stereo_call(fn, map, image_left, image_right, p, mask, raw):
+def _stereo_call(fn, batch_fn, map, image_left, image_right, p, mask, raw):
     import torch
+    nd = image_left.dim()
+    assert nd in (2, 3), "rectified images are (H, W), or (B, H, W) for a batch"
     for t in (image_left, image_right) + ((mask,) if mask is not None else ()):
-        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.stride(1) == 1
-    H, W = image_left.shape
-    assert tuple(image_right.shape) == (H, W) and (mask is None or tuple(mask.shape) == (H, W))
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == nd and t.stride(-1) == 1
+    shape = tuple(image_left.shape)
+    H, W = shape[-2:]
+    assert tuple(image_right.shape) == shape and (mask is None or tuple(mask.shape) == shape)
     dev = image_left.device
-    disp = torch.empty((H, W), dtype=torch.float32, device=dev)
-    rawt = torch.empty((H, W), dtype=torch.int16, device=dev) if raw else None
+    disp = torch.empty(shape, dtype=torch.float32, device=dev)
+    rawt = torch.empty(shape, dtype=torch.int16, device=dev) if raw else None
     map.wait_for_torch(image_left)
-    L.check(fn(
-        map.handle, C.byref(p), W, H, C.c_void_p(image_left.data_ptr()), image_left.stride(0),
-        C.c_void_p(image_right.data_ptr()), image_right.stride(0),
-        C.c_void_p(mask.data_ptr()) if mask is not None else None,
-        mask.stride(0) if mask is not None else 0, C.c_void_p(disp.data_ptr()), disp.stride(0) * 4,
-        C.c_void_p(rawt.data_ptr()) if raw else None, rawt.stride(0) * 2 if raw else 0))
+
+    def io(t, size):   # pointer, row step and -- for a stack -- batch stride, in bytes
+        if t is None:
+            return [None, 0] + ([0] if nd == 3 else [])
+        return [C.c_void_p(t.data_ptr()), t.stride(-2) * size] + ([t.stride(0) * size] if nd == 3 else [])
+    args = io(image_left, 1) + io(image_right, 1) + io(mask, 1) + io(disp, 4) + io(rawt, 2)
+    if nd == 3:
+        L.check(batch_fn(map.handle, C.byref(p), W, H, shape[0], *args))
+    else:
+        L.check(fn(map.handle, C.byref(p), W, H, *args))
     map.synchronize()
     return (disp, rawt) if raw else disp
 
@@ -767,9 +762,13 @@ def compute_disparity_bm(map, image_left, image_right, params=None, mask=None, r
     """stereo::BlockMatchingBM::computeDisparityMap (block-matching-bm.cpp: StereoBM::compute, / 16,
     the rectification mask) on the GPU of `map`: rectified CUDA torch uint8 tensors (H, W) -> the
     float32 disparity map (H, W) on the device; with raw=True also OpenCV's CV_16S map (int16).
-    mask (uint8 (H, W), optional): pixels where it is 0 become kMaxInvalidDisparity = 1.0."""
+    mask (uint8 (H, W), optional): pixels where it is 0 become kMaxInvalidDisparity = 1.0.
+    Stacks (B, H, W) of up to 16 pairs (mask (B, H, W) or None) go through one set of launches
+    (amhip_bm_disparity_batch_dev) and give (B, H, W) maps, pair by pair the bits of B calls."""
     p = (params or BmParameters()).to_c()
-    return _stereo_call(L.load().amhip_bm_disparity_dev, map, image_left, image_right, p, mask, raw)
+    lib = L.load()
+    return _stereo_call(lib.amhip_bm_disparity_dev, lib.amhip_bm_disparity_batch_dev, map, image_left,
+                        image_right, p, mask, raw)
 
 
 def dense_cloud_from_stereo_pair(map, K, R_G_C1, R_G_C2, t_G_C1, t_G_C2, image_left, image_right,
@@ -822,9 +821,9 @@ class Stereo(object):
     int32): CUDA tensors that VIEW the object's buffers -- valid until the next add_frame / add_frames
     / close on this object (clone() what must live longer); ready for Dsm.process /
     OrthoFromPcl.process without a host copy.  images: a list of host uint8 arrays (H, W), or one CUDA
-    uint8 tensor (F, H, W) ((H, W) for add_frame)."""
+    uint8 tensor (F, H, W) ((H, W) for add_frame).  pairs_in_flight: see set_pairs_in_flight."""
 
-    def __init__(self, ncameras, settings=None, block_matching_params=None, map=None):
+    def __init__(self, ncameras, settings=None, block_matching_params=None, map=None, pairs_in_flight=1):
         if ncameras is None:
             raise L.AmhipError(L.ERR_ARG, "CHECK(ncameras_) (stereo.cpp:20)")
         if map is None:
@@ -848,6 +847,20 @@ class Stereo(object):
                                               tcb.ctypes.data_as(C.POINTER(C.c_double)), C.byref(cs),
                                               C.byref(self._h)))
         self.pairs = 0
+        self.pairs_in_flight = 1
+        if pairs_in_flight != 1:
+            try:
+                self.set_pairs_in_flight(pairs_in_flight)
+            except Exception:
+                self.close()
+                raise
+
+    def set_pairs_in_flight(self, n):
+        """How many stereo pairs add_frames keeps in flight (1 .. 16, default 1): with n > 1 the block
+        matcher serves up to n consecutive pairs per launch.  Results are bit for bit those of n = 1;
+        add_frame is unaffected (amhip_stereo_set_pairs_in_flight)."""
+        L.check(self._lib.amhip_stereo_set_pairs_in_flight(self._h, int(n)))
+        self.pairs_in_flight = int(n)
 
     def close(self):
         if getattr(self, "_h", None):

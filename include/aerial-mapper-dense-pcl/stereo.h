@@ -41,6 +41,10 @@ class Stereo {
   // point_cloud_ros_msg_.data of the last stereo pair (height x width slots of 16 bytes, see
   // amhip_stereo_point_cloud2_dev), downloaded.
   std::vector<uint8_t> pointCloud2Payload() const;
+  // How many stereo pairs addFrames keeps in flight (1 .. 16, default 1): with n > 1 the block
+  // matcher serves up to n consecutive pairs per launch (amhip_stereo_set_pairs_in_flight).  The
+  // cloud is bit for bit that of n = 1.  addFrame is unaffected.
+  void setPairsInFlight(int n);
 
   static constexpr size_t kFrameIdx = 0u;
 

@@ -578,6 +578,36 @@ int amhip_bm_disparity_dev(amhip_ctx* ctx, const amhip_bm_params* p, int width, 
                            float* dev_disparity, size_t disp_step,
                            int16_t* dev_raw, size_t raw_step);
 
+/* ---- several rectified pairs per call (an extension beside the reference's one-pair wrappers) ----
+ * `batch` pairs of one size and one parameter set go through ONE set of launches: pair b reads
+ * dev_left + b * left_batch_stride (bytes; likewise right and mask) and writes dev_disparity +
+ * b * disp_batch_stride and, if wanted, dev_raw + b * raw_batch_stride.  Every rule of the one-pair
+ * call holds per pair, and pair b's result is bit for bit what that call gives for pair b alone:
+ * no step sees across pairs (cost sums, SGBM chains, BM window sums, the median's borders, the
+ * speckle filter's regions and the right-image map all stay inside one image).  batch in
+ * [1, AMHIP_STEREO_MAX_BATCH]; every *_batch_stride >= height * its row step (the mask's only with a
+ * mask, the raw map's only with dev_raw), the output strides multiples of the element size:
+ * otherwise AMHIP_ERR_ARG, reported before the context is looked at like every argument error.
+ * The context's stereo scratch grows to batch x the one-pair size (at 1920 x 1080 and 80
+ * disparities about 1 GB per SGBM pair, 33 MB per BM pair) and is kept; AMHIP_ERR_NOMEM if it cannot
+ * be had.  One pair cannot fill the device (one wave per SGBM chain); several can.  Timed into the
+ * same slot as the one-pair calls (AMHIP_K_STEREO).  Asynchronous on the context's stream. */
+#define AMHIP_STEREO_MAX_BATCH 16
+int amhip_sgbm_disparity_batch_dev(amhip_ctx* ctx, const amhip_sgbm_params* p, int width, int height,
+                                   int batch,
+                                   const uint8_t* dev_left, size_t left_step, size_t left_batch_stride,
+                                   const uint8_t* dev_right, size_t right_step, size_t right_batch_stride,
+                                   const uint8_t* dev_mask, size_t mask_step, size_t mask_batch_stride,
+                                   float* dev_disparity, size_t disp_step, size_t disp_batch_stride,
+                                   int16_t* dev_raw, size_t raw_step, size_t raw_batch_stride);
+int amhip_bm_disparity_batch_dev(amhip_ctx* ctx, const amhip_bm_params* p, int width, int height,
+                                 int batch,
+                                 const uint8_t* dev_left, size_t left_step, size_t left_batch_stride,
+                                 const uint8_t* dev_right, size_t right_step, size_t right_batch_stride,
+                                 const uint8_t* dev_mask, size_t mask_step, size_t mask_batch_stride,
+                                 float* dev_disparity, size_t disp_step, size_t disp_batch_stride,
+                                 int16_t* dev_raw, size_t raw_step, size_t raw_batch_stride);
+
 /* ---- stereo::Stereo: a frame sequence -> one dense cloud
  *      aerial_mapper_dense_pcl/include/aerial-mapper-dense-pcl/stereo.h:42-94, src/stereo.cpp ----
  * Images + body poses in, the concatenated cloud of all stereo pairs out, without a host round trip
@@ -601,7 +631,7 @@ void amhip_stereo_default_settings(amhip_stereo_settings* out);
 
 /* stereo::Stereo::Stereo (stereo.cpp:12-80).  The object runs on the stream and the scratch of
  * `ctx` (which must outlive it; one object at a time per context call, like every context call) and
- * owns two raw frame slots that swap roles, the rectified pair + mask, the disparity map, the cloud,
+ * owns two raw frame slots that swap roles (n + 1 after amhip_stereo_set_pairs_in_flight(n)), the rectified pair + mask, the disparity map, the cloud,
  * the running point count and the PointCloud2 payload, plus a second stream on which host frames are
  * uploaded from pinned staging while the previous pair is still being matched.
  * cam: camera 0 of the NCamera; K = [fu 0 cu; 0 fv cv; 0 0 1] (:37-40) also when undistorting (the
@@ -614,6 +644,20 @@ int amhip_stereo_create(amhip_ctx* ctx, const amhip_camera* cam, const double* T
 int amhip_stereo_destroy(amhip_stereo* stereo);
 /* A newly constructed object: first_frame_ = true, the cloud emptied, the payload zeroed. */
 int amhip_stereo_reset(amhip_stereo* stereo);
+/* How many pairs amhip_stereo_add_frames / _dev keep in flight: n in [1, AMHIP_STEREO_MAX_BATCH],
+ * 1 by default (an extension beside the reference's class; not part of amhip_stereo_settings).  With
+ * n > 1 the used frames are taken in groups of up to n consecutive pairs: each frame is staged and
+ * undistorted once (n + 1 frame slots), the n pairs are rectified into stacks, ONE batched matcher
+ * call serves the group, and the append-mode densify then runs pair by pair in order.  The cloud,
+ * the intensities, the point count, `pairs`, the PointCloud2 payload and every status are bit for
+ * bit those of n = 1: a pair with a zero baseline cuts its group (the pairs before it are kept, the
+ * call fails as at n = 1), and a zero w found on the device silences that pair and every later one,
+ * never an earlier one (each pair of a group has its own copy of the error word, taken in stream
+ * order behind its rectifier).  This call allocates the slots and stacks (AMHIP_ERR_NOMEM if they
+ * cannot be had; the object then keeps its previous n) and waits for the object's work; a frame
+ * carried over from earlier calls is kept.  add_frames settles the matcher's scratch for a whole
+ * group before its first pair.  amhip_stereo_add_frame (one frame at a time) is unaffected. */
+int amhip_stereo_set_pairs_in_flight(amhip_stereo* stereo, int n);
 
 /* stereo::Stereo::addFrame (stereo.cpp:113-147).  T_G_B7: the body pose.  The camera pose is
  *   T_G_C = T_G_B * T_C_B^-1 (:43,129-137), amhip_compose_T_G_C's arithmetic, FP64 on the host;
