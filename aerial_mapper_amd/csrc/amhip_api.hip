@@ -948,7 +948,7 @@ void amhip_ctx_destroy(amhip_ctx* h) {
   for (int l = 0; l < AMHIP_NUM_LAYERS; ++l)
     if (c->layers[l]) (void)hipFree(c->layers[l]);
   void* bufs[] = {c->dev_bbox, c->ortho_list, c->zpart, c->dev_zrange, c->tile_list, c->tile_occ, c->fill_mask, c->stage_values, c->dev_err, c->sorted,       c->rank,        c->bin_start, c->bin_z, c->rec_a, c->rec_b, c->rec16, c->sidx, c->zref, c->zall, c->tmp_points, c->stripe_ws,
-                  c->scan_partials, c->stage_points, c->frame_poses, c->stage_frames, c->sgbm_ws};
+                  c->scan_partials, c->stage_points, c->frame_poses, c->stage_frames, c->stereo_ws};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->host_err) (void)hipHostFree(c->host_err);
@@ -1315,21 +1315,7 @@ int amhip_densify_dev(amhip_ctx* h, const float* dev_disparity, size_t disp_step
   Ctx* c = &h->impl;
   int rc = use_device(c);
   if (rc) return rc;
-  DensifyParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.width = width;
-  p.height = height;
-  p.disp_step = disp_step;
-  p.img_step = img_step;
-  // stereo projection matrix Q (densifier.cpp:39-46), K row-major
-  const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-  p.Q03 = -cx;
-  p.Q11 = fx / fy;
-  p.Q13 = -cy * (fx / fy);
-  p.Q23 = fx;
-  p.Q32 = 1.0 / baseline;
-  for (int k = 0; k < 9; ++k) p.R[k] = R_G_C[k];
-  for (int k = 0; k < 3; ++k) p.t[k] = t_G_C1[k];
+  const DensifyParams p = densify_params(K, baseline, R_G_C, t_G_C1, width, height, disp_step, img_step);
   return densify_run(c, p, dev_disparity, dev_image_left, dev_xyz_out, dev_intensity_out,
                      capacity, reinterpret_cast<long long*>(dev_count));
 }

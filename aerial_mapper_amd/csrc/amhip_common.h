@@ -317,10 +317,10 @@ struct Ctx {
   unsigned long long sort_stats_sig = 0, tile_stats_sig = 0;  // the geometry the pinned counters describe
   unsigned* host_tile_stats = nullptr;  // pinned mirror of the last call's tile-list counters
 
-  // semi-global block matching (amhip_stereo.hip): C, S, the left / right maps, the median and
+  // the stereo matchers (amhip_stereo.hip): the cost volumes or prefiltered images, the maps and
   // the speckle labels of one call, carved out of one block that grows on demand
-  uint8_t* sgbm_ws = nullptr;
-  size_t sgbm_ws_cap = 0;
+  uint8_t* stereo_ws = nullptr;
+  size_t stereo_ws_cap = 0;
 
   // timing
   bool timing = false;
@@ -356,6 +356,25 @@ struct DensifyParams {
   double Q03, Q11, Q13, Q23, Q32;
   double R[9], t[3];
 };
+// the stereo projection matrix Q (densifier.cpp:39-46; K row-major) and the pose of one W x H pair
+inline DensifyParams densify_params(const double* K, double baseline, const double* R_G_C,
+                                    const double* t_G_C1, int width, int height, size_t disp_step,
+                                    size_t img_step) {
+  DensifyParams p = {};
+  p.width = width;
+  p.height = height;
+  p.disp_step = disp_step;
+  p.img_step = img_step;
+  const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+  p.Q03 = -cx;
+  p.Q11 = fx / fy;
+  p.Q13 = -cy * (fx / fy);
+  p.Q23 = fx;
+  p.Q32 = 1.0 / baseline;
+  for (int k = 0; k < 9; ++k) p.R[k] = R_G_C[k];
+  for (int k = 0; k < 3; ++k) p.t[k] = t_G_C1[k];
+  return p;
+}
 int densify_run(Ctx* c, const DensifyParams& p, const float* dev_disparity,
                 const uint8_t* dev_image_left, double* dev_xyz_out, int32_t* dev_intensity_out,
                 size_t capacity, long long* dev_count);
@@ -373,8 +392,32 @@ int densify_append_run(Ctx* c, const DensifyParams& p, const float* dev_disparit
                        const uint8_t* dev_image_left, double* dev_xyz, int32_t* dev_intensities,
                        size_t capacity, SeqState* dev_state, void* dev_pc2, bool replace,
                        const unsigned* dev_err_word = nullptr);  // (null: the context's own word)
-// the context's stereo scratch holds `batch` pairs of the selected matcher (amhip_stereo.hip)
+// What one matcher call reads and writes (amhip_stereo.hip): `batch` pairs of images, pair b at
+// base + b * batch stride.  Steps and strides in bytes; mask and raw may be null.
+struct BatchStrides {
+  size_t left, right, mask, disp, raw;
+};
+struct StereoImages {
+  const uint8_t* left;
+  size_t left_step;
+  const uint8_t* right;
+  size_t right_step;
+  const uint8_t* mask;
+  size_t mask_step;
+  float* disp;
+  size_t disp_step;
+  int16_t* raw;
+  size_t raw_step;
+  int batch;
+  BatchStrides bs;
+};
+// the parameter rules of the selected matcher for width x height images, with the texts of its
+// one-pair export; no context, no device (amhip_stereo.hip)
+int stereo_params_check(const amhip_stereo_settings& s, int width, int height);
+// the context's stereo scratch holds `batch` pairs of the selected matcher
 int stereo_scratch_reserve(Ctx* c, const amhip_stereo_settings& s, int width, int height, int batch);
+// the selected matcher on images and parameters that passed the checks
+int stereo_match(Ctx* c, const amhip_stereo_settings& s, int width, int height, const StereoImages& im);
 // aslam MappedUndistorter::processImage for G frames (amhip_forward.hip: k_fwd_undistort), packed
 // output (G x height x width x channels); asynchronous on `stream`
 int undistort_frames_run(hipStream_t stream, const amhip_camera& cam, const uint8_t* dev_frames,

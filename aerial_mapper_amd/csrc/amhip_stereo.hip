@@ -20,7 +20,8 @@
 //   k_sgbm_uf_*     filterSpeckles: union-find over the 4-connected relation (halving only while
 //                   uniting), then each pixel's root read without writes, region sizes by atomics
 //   k_sgbm_final    small regions -> invalid, CV_16S out, float / 16 with the mask
-// C + S + hsum live in the context's scratch (amhip::Ctx::sgbm_ws), grown on demand.
+// C + S + hsum and the maps live in the context's scratch (amhip::Ctx::stereo_ws), grown on demand;
+// block matching (below) carves its own layout out of the same block.
 //
 // Batches (amhip_*_disparity_batch_dev): blockIdx.z is the pair.  Pair b reads its images and mask
 // and writes its outputs at base + b * batch stride; its scratch is the single-pair layout at
@@ -647,87 +648,119 @@ static int stereo_fail(const char* fn, const char* msg) {
 
 // the context's stereo scratch holds `total` bytes (kept between calls; grown, never shrunk)
 static int stereo_scratch(Ctx* c, size_t total) {
-  if (c->sgbm_ws && c->sgbm_ws_cap >= total) return AMHIP_OK;
-  if (c->sgbm_ws) {
-    AMHIP_TRY(hipFree(c->sgbm_ws));  // (waits for the kernels that still use it)
-    c->sgbm_ws = nullptr;
-    c->sgbm_ws_cap = 0;
+  if (c->stereo_ws && c->stereo_ws_cap >= total) return AMHIP_OK;
+  if (c->stereo_ws) {
+    AMHIP_TRY(hipFree(c->stereo_ws));  // (waits for the kernels that still use it)
+    c->stereo_ws = nullptr;
+    c->stereo_ws_cap = 0;
   }
   // grow by 1/8 so that slightly larger follow-up images do not reallocate
   size_t want = total + total / 8 + 256;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->sgbm_ws), want);
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->stereo_ws), want);
   if (e == hipErrorOutOfMemory) {
     (void)hipGetLastError();
     want = total;
-    e = hipMalloc(reinterpret_cast<void**>(&c->sgbm_ws), want);
+    e = hipMalloc(reinterpret_cast<void**>(&c->stereo_ws), want);
   }
   if (e == hipErrorOutOfMemory) {
     (void)hipGetLastError();
-    c->sgbm_ws = nullptr;
+    c->stereo_ws = nullptr;
     set_last_error("stereo matcher: out of device memory for the scratch of the batch");
     return AMHIP_ERR_NOMEM;
   }
   AMHIP_TRY(e);
-  c->sgbm_ws_cap = want;
+  c->stereo_ws_cap = want;
   return AMHIP_OK;
 }
 
-// strides between the pairs of a batch, in bytes (unused with one pair)
-struct BatchStrides {
-  size_t left, right, mask, disp, raw;
-};
+// ---- the argument rules: each once; stereo_check holds the order in which they are reported ----
+static int params_check(const char* fn, const amhip_sgbm_params& q, int width, int height) {
+  if (width < 3 || height < 1 || width > 32767 || height > 32767)
+    return stereo_fail(fn, "width must be in [3, 32767], height in [1, 32767]");
+  if (q.num_disparities <= 0 || q.num_disparities % 16 != 0 || q.num_disparities > kSgbmMaxD)
+    return stereo_fail(fn, "num_disparities must be a positive multiple of 16, <= 256");
+  if (q.block_size > 11 || (q.block_size > 0 && q.block_size % 2 == 0))
+    return stereo_fail(fn, "block_size must be odd and <= 11 (0: OpenCV's 5)");
+  if (q.min_disparity < -4096 || q.min_disparity > 4096 || q.pre_filter_cap > 63 ||
+      q.uniqueness_ratio > 100 || q.p1 > 4096 || q.p2 > 4096)
+    return stereo_fail(fn, "parameter out of range");
+  if (!cv16s_holds(q.min_disparity, q.num_disparities))
+    return stereo_fail(fn, "the CV_16S map cannot hold this disparity range: "
+                           "min_disparity must be >= -2047 and min_disparity + num_disparities <= 2047");
+  // (the map's values span less than 2^16, so every range >= 4096 acts alike; 16 * range must fit an int)
+  if (q.speckle_range < -4096 || q.speckle_range > 4096)
+    return stereo_fail(fn, "speckle_range must be in [-4096, 4096]");
+  return AMHIP_OK;
+}
 
-static int batch_check(const char* fn, int height, int batch, const BatchStrides& bs, size_t left_step,
-                       size_t right_step, bool has_mask, size_t mask_step, size_t disp_step,
-                       bool has_raw, size_t raw_step) {
-  if (batch < 1 || batch > AMHIP_STEREO_MAX_BATCH) return stereo_fail(fn, "batch must be in [1, 16]");
+// (the one parameter rule that is reported behind the image rules; BM has none)
+static int columns_check(const char* fn, const amhip_sgbm_params& q, int width) {
+  const int maxD = q.min_disparity + q.num_disparities;
+  const int w1 = width + std::min(q.min_disparity, 0) - std::max(maxD, 0);
+  if (w1 > 0 && w1 <= (q.block_size > 0 ? q.block_size : 5) / 2)
+    return stereo_fail(fn, "fewer matchable columns than half the block");
+  return AMHIP_OK;
+}
+static int columns_check(const char*, const amhip_bm_params&, int) { return AMHIP_OK; }
+
+// StereoBM::compute's CV_Asserts on the wrapper's effective parameters, then this implementation's
+// limits
+static int params_check(const char* fn, const amhip_bm_params& q, int width, int height) {
+  if (width < 1 || height < 1 || width > 32767 || height > 32767)
+    return stereo_fail(fn, "width and height must be in [1, 32767]");
+  if (q.num_disparities <= 0 || q.num_disparities % 16 != 0 || q.num_disparities > kSgbmMaxD)
+    return stereo_fail(fn, "num_disparities must be a positive multiple of 16, <= 256");
+  if (q.block_size % 2 == 0 || q.block_size < 5 || q.block_size > 2 * kBmMaxSW2 + 1 ||
+      q.block_size > std::min(width, height))
+    return stereo_fail(fn, "block_size must be odd, in [5, 31] and <= min(width, height)");
+  if (q.pre_filter_size < 1 || q.pre_filter_size > 63)
+    return stereo_fail(fn, "pre_filter_size (the effective preFilterCap) must be in [1, 63]");
+  if (q.texture_threshold < 0) return stereo_fail(fn, "texture_threshold must be >= 0");
+  if (q.uniqueness_ratio < 0) return stereo_fail(fn, "uniqueness_ratio must be >= 0");
+  if (q.min_disparity < -4096 || q.min_disparity > 4096)
+    return stereo_fail(fn, "min_disparity must be in [-4096, 4096]");
+  if (!cv16s_holds(q.min_disparity, q.num_disparities))
+    return stereo_fail(fn, "the CV_16S map cannot hold this disparity range: "
+                           "min_disparity must be >= -2047 and min_disparity + num_disparities <= 2047");
+  return AMHIP_OK;
+}
+
+static int image_check(const char* fn, int width, const StereoImages& im) {
+  const size_t W = (size_t)width;
+  if (im.left_step < W || im.right_step < W || (im.mask && im.mask_step < W) ||
+      im.disp_step < W * sizeof(float) || (im.raw && im.raw_step < W * sizeof(int16_t)))
+    return stereo_fail(fn, "a row step is smaller than the width");
+  if (im.disp_step % sizeof(float) != 0 || (im.raw && im.raw_step % sizeof(int16_t) != 0))
+    return stereo_fail(fn, "output steps must be multiples of the element size");
+  return AMHIP_OK;
+}
+
+static int batch_check(const char* fn, int height, const StereoImages& im) {
+  if (im.batch < 1 || im.batch > AMHIP_STEREO_MAX_BATCH) return stereo_fail(fn, "batch must be in [1, 16]");
   const size_t H = (size_t)height;
-  if (bs.left < H * left_step || bs.right < H * right_step || (has_mask && bs.mask < H * mask_step) ||
-      bs.disp < H * disp_step || (has_raw && bs.raw < H * raw_step))
+  const BatchStrides& bs = im.bs;
+  if (bs.left < H * im.left_step || bs.right < H * im.right_step || (im.mask && bs.mask < H * im.mask_step) ||
+      bs.disp < H * im.disp_step || (im.raw && bs.raw < H * im.raw_step))
     return stereo_fail(fn, "a batch stride is smaller than height * row step");
-  if (bs.disp % sizeof(float) != 0 || (has_raw && bs.raw % sizeof(int16_t) != 0))
+  if (bs.disp % sizeof(float) != 0 || (im.raw && bs.raw % sizeof(int16_t) != 0))
     return stereo_fail(fn, "output batch strides must be multiples of the element size");
   return AMHIP_OK;
 }
 
-// ---- SGBM: the argument rules, the scratch of one pair, the launches -------------------------
-static int sgbm_check(const char* fn, const amhip_sgbm_params* q, int width, int height,
-                      const uint8_t* dev_left, size_t left_step, const uint8_t* dev_right,
-                      size_t right_step, const uint8_t* dev_mask, size_t mask_step,
-                      const float* dev_disparity, size_t disp_step, const int16_t* dev_raw,
-                      size_t raw_step) {
-  // (the parameters first: every argument error is reported without a device)
-  if (!q || !dev_left || !dev_right || !dev_disparity) return stereo_fail(fn, "null argument");
-  if (width < 3 || height < 1 || width > 32767 || height > 32767)
-    return stereo_fail(fn, "width must be in [3, 32767], height in [1, 32767]");
-  if (q->num_disparities <= 0 || q->num_disparities % 16 != 0 || q->num_disparities > kSgbmMaxD)
-    return stereo_fail(fn, "num_disparities must be a positive multiple of 16, <= 256");
-  if (q->block_size > 11 || (q->block_size > 0 && q->block_size % 2 == 0))
-    return stereo_fail(fn, "block_size must be odd and <= 11 (0: OpenCV's 5)");
-  if (q->min_disparity < -4096 || q->min_disparity > 4096 || q->pre_filter_cap > 63 ||
-      q->uniqueness_ratio > 100 || q->p1 > 4096 || q->p2 > 4096)
-    return stereo_fail(fn, "parameter out of range");
-  if (!cv16s_holds(q->min_disparity, q->num_disparities))
-    return stereo_fail(fn, "the CV_16S map cannot hold this disparity range: "
-                           "min_disparity must be >= -2047 and min_disparity + num_disparities <= 2047");
-  // (the map's values span less than 2^16, so every range >= 4096 acts alike; 16 * range must fit an int)
-  if (q->speckle_range < -4096 || q->speckle_range > 4096)
-    return stereo_fail(fn, "speckle_range must be in [-4096, 4096]");
-  if (left_step < (size_t)width || right_step < (size_t)width ||
-      (dev_mask && mask_step < (size_t)width) || disp_step < (size_t)width * sizeof(float) ||
-      (dev_raw && raw_step < (size_t)width * sizeof(int16_t)))
-    return stereo_fail(fn, "a row step is smaller than the width");
-  if (disp_step % sizeof(float) != 0 || (dev_raw && raw_step % sizeof(int16_t) != 0))
-    return stereo_fail(fn, "output steps must be multiples of the element size");
-  {
-    const int maxD = q->min_disparity + q->num_disparities;
-    const int w1 = width + std::min(q->min_disparity, 0) - std::max(maxD, 0);
-    if (w1 > 0 && w1 <= (q->block_size > 0 ? q->block_size : 5) / 2)
-      return stereo_fail(fn, "fewer matchable columns than half the block");
-  }
-  return AMHIP_OK;
+// Every argument error of a matcher call, without a device.  A call with several faults reports the
+// first of: null argument, width / height, the matcher's parameters, row steps, element sizes,
+// SGBM's matchable columns, the batch.
+template <typename Params>
+static int stereo_check(const char* fn, const Params* q, int width, int height, const StereoImages& im) {
+  if (!q || !im.left || !im.right || !im.disp) return stereo_fail(fn, "null argument");
+  int rc;
+  if ((rc = params_check(fn, *q, width, height))) return rc;
+  if ((rc = image_check(fn, width, im))) return rc;
+  if ((rc = columns_check(fn, *q, width))) return rc;
+  return batch_check(fn, height, im);
 }
 
+// ---- SGBM: the scratch of one pair, the launches ----------------------------------------------
 // computeDisparitySGBM's preamble (tests/sgbm_reference.py: derived)
 static SgbmDims sgbm_dims(const amhip_sgbm_params* q, int width, int height) {
   SgbmDims p;
@@ -774,20 +807,39 @@ static SgbmScratch sgbm_scratch(const SgbmDims& p) {
   return o;
 }
 
-static int sgbm_run(Ctx* c, const amhip_sgbm_params* q, int width, int height, int batch,
-                    const BatchStrides& bs, const uint8_t* dev_left, size_t left_step,
-                    const uint8_t* dev_right, size_t right_step, const uint8_t* dev_mask,
-                    size_t mask_step, float* dev_disparity, size_t disp_step, int16_t* dev_raw,
-                    size_t raw_step) {
+// the union-find arrays of the speckle filter in one pair's scratch
+struct SpeckleScratch {
+  int *par, *cnt, *lab;
+};
+
+// The tail of both matchers: filterSpeckles (if `speckle`) over the CV_16S map `map` of every pair,
+// then the final pass into the caller's arrays.  Of s it reads W, H, invalid and the speckle fields.
+static void speckle_and_final(Ctx* c, const SgbmDims& s, bool speckle, const int16_t* map,
+                              const SpeckleScratch& u, size_t wsb, const StereoImages& im) {
+  const unsigned B = (unsigned)im.batch;
+  const size_t npix = (size_t)s.W * s.H;
+  const dim3 rowgrid((unsigned)((s.W + 255) / 256), (unsigned)s.H, B);
+  if (speckle) {
+    const dim3 nb((unsigned)((npix + 255) / 256), 1, B);
+    hipLaunchKernelGGL(k_sgbm_uf_init, nb, dim3(256), 0, c->stream, (int)npix, u.par, u.cnt, wsb);
+    hipLaunchKernelGGL(k_sgbm_uf_union, rowgrid, dim3(256), 0, c->stream, s, map, u.par, wsb);
+    hipLaunchKernelGGL(k_sgbm_uf_count, nb, dim3(256), 0, c->stream, s, map, u.par, u.lab, u.cnt, wsb);
+  }
+  hipLaunchKernelGGL(k_sgbm_final, rowgrid, dim3(256), 0, c->stream, s, map, speckle ? u.lab : nullptr,
+                     u.cnt, im.mask, im.mask_step, im.disp, im.disp_step, im.raw, im.raw_step, wsb,
+                     im.bs.mask, im.bs.disp, im.bs.raw);
+}
+
+static int stereo_run(Ctx* c, const amhip_sgbm_params* q, int width, int height, const StereoImages& im) {
   const SgbmDims p = sgbm_dims(q, width, height);
   const bool matched = p.w1 > 0;
   const size_t npix = (size_t)width * height;
   const SgbmScratch o = sgbm_scratch(p);
-  const unsigned B = (unsigned)batch;
+  const unsigned B = (unsigned)im.batch;
   const size_t wsb = o.total;  // pair b's scratch: the single-pair layout at b * wsb
   int rc;
   if ((rc = stereo_scratch(c, wsb * B))) return rc;
-  uint8_t* ws = c->sgbm_ws;
+  uint8_t* ws = c->stereo_ws;
   uint16_t* C = reinterpret_cast<uint16_t*>(ws + o.oC);
   int32_t* S = reinterpret_cast<int32_t*>(ws + o.oS);
   uint16_t* hsum = reinterpret_cast<uint16_t*>(ws + o.oS);  // (dead once C is built)
@@ -795,9 +847,8 @@ static int sgbm_run(Ctx* c, const amhip_sgbm_params* q, int width, int height, i
   unsigned long long* key2 = reinterpret_cast<unsigned long long*>(ws + o.oK);
   int16_t* lr = reinterpret_cast<int16_t*>(ws + o.oL);
   int16_t* med = reinterpret_cast<int16_t*>(ws + o.oM);
-  int* par = reinterpret_cast<int*>(ws + o.oP);
-  int* cnt = reinterpret_cast<int*>(ws + o.oN);
-  int* lab = reinterpret_cast<int*>(ws + o.oB);
+  const SpeckleScratch u = {reinterpret_cast<int*>(ws + o.oP), reinterpret_cast<int*>(ws + o.oN),
+                            reinterpret_cast<int*>(ws + o.oB)};
 
   ScopedTimer t(c, AMHIP_K_STEREO);
   const dim3 rowgrid((unsigned)((width + 255) / 256), (unsigned)height, B);
@@ -807,8 +858,8 @@ static int sgbm_run(Ctx* c, const amhip_sgbm_params* q, int width, int height, i
     else  // (one row of npix keys per pair, wsb bytes apart)
       AMHIP_TRY(hipMemset2DAsync(key2, wsb, 0xFF, npix * 8, B, c->stream));
     hipLaunchKernelGGL(k_sgbm_hsum, dim3((unsigned)((p.w1 + kSgbmTX - 1) / kSgbmTX), (unsigned)height, B),
-                       dim3(256), 0, c->stream, p, dev_left, left_step, dev_right, right_step, hsum,
-                       bs.left, bs.right, wsb);
+                       dim3(256), 0, c->stream, p, im.left, im.left_step, im.right, im.right_step, hsum,
+                       im.bs.left, im.bs.right, wsb);
     hipLaunchKernelGGL(k_sgbm_vsum, dim3((unsigned)(((size_t)p.w1 * p.D + 255) / 256),
                                          (unsigned)((height + kSgbmVRows - 1) / kSgbmVRows), B),
                        dim3(256), 0, c->stream, p, hsum, C, wsb);
@@ -824,54 +875,12 @@ static int sgbm_run(Ctx* c, const amhip_sgbm_params* q, int width, int height, i
   // (no match possible: every pixel INVALID_DISP_SCALED; disp1 / key2 are not read)
   hipLaunchKernelGGL(k_sgbm_lrcheck, rowgrid, dim3(256), 0, c->stream, p, disp1, key2, lr, wsb);
   hipLaunchKernelGGL(k_sgbm_median, rowgrid, dim3(256), 0, c->stream, width, height, lr, med, wsb);
-  const bool speckle = q->speckle_window_size > 0;
-  if (speckle) {
-    const dim3 nb((unsigned)((npix + 255) / 256), 1, B);
-    hipLaunchKernelGGL(k_sgbm_uf_init, nb, dim3(256), 0, c->stream, (int)npix, par, cnt, wsb);
-    hipLaunchKernelGGL(k_sgbm_uf_union, rowgrid, dim3(256), 0, c->stream, p, med, par, wsb);
-    hipLaunchKernelGGL(k_sgbm_uf_count, nb, dim3(256), 0, c->stream, p, med, par, lab, cnt, wsb);
-  }
-  hipLaunchKernelGGL(k_sgbm_final, rowgrid, dim3(256), 0, c->stream, p, med, speckle ? lab : nullptr,
-                     cnt, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step, wsb, bs.mask,
-                     bs.disp, bs.raw);
+  speckle_and_final(c, p, q->speckle_window_size > 0, med, u, wsb, im);
   AMHIP_TRY(hipGetLastError());
   return AMHIP_OK;
 }
 
 // ---- BM ---------------------------------------------------------------------------------------
-static int bm_check(const char* fn, const amhip_bm_params* q, int width, int height,
-                    const uint8_t* dev_left, size_t left_step, const uint8_t* dev_right,
-                    size_t right_step, const uint8_t* dev_mask, size_t mask_step,
-                    const float* dev_disparity, size_t disp_step, const int16_t* dev_raw,
-                    size_t raw_step) {
-  // (StereoBM::compute's CV_Asserts on the wrapper's effective parameters, then this
-  // implementation's limits; every argument error is reported without a device)
-  if (!q || !dev_left || !dev_right || !dev_disparity) return stereo_fail(fn, "null argument");
-  if (width < 1 || height < 1 || width > 32767 || height > 32767)
-    return stereo_fail(fn, "width and height must be in [1, 32767]");
-  if (q->num_disparities <= 0 || q->num_disparities % 16 != 0 || q->num_disparities > kSgbmMaxD)
-    return stereo_fail(fn, "num_disparities must be a positive multiple of 16, <= 256");
-  if (q->block_size % 2 == 0 || q->block_size < 5 || q->block_size > 2 * kBmMaxSW2 + 1 ||
-      q->block_size > std::min(width, height))
-    return stereo_fail(fn, "block_size must be odd, in [5, 31] and <= min(width, height)");
-  if (q->pre_filter_size < 1 || q->pre_filter_size > 63)
-    return stereo_fail(fn, "pre_filter_size (the effective preFilterCap) must be in [1, 63]");
-  if (q->texture_threshold < 0) return stereo_fail(fn, "texture_threshold must be >= 0");
-  if (q->uniqueness_ratio < 0) return stereo_fail(fn, "uniqueness_ratio must be >= 0");
-  if (q->min_disparity < -4096 || q->min_disparity > 4096)
-    return stereo_fail(fn, "min_disparity must be in [-4096, 4096]");
-  if (!cv16s_holds(q->min_disparity, q->num_disparities))
-    return stereo_fail(fn, "the CV_16S map cannot hold this disparity range: "
-                           "min_disparity must be >= -2047 and min_disparity + num_disparities <= 2047");
-  if (left_step < (size_t)width || right_step < (size_t)width ||
-      (dev_mask && mask_step < (size_t)width) || disp_step < (size_t)width * sizeof(float) ||
-      (dev_raw && raw_step < (size_t)width * sizeof(int16_t)))
-    return stereo_fail(fn, "a row step is smaller than the width");
-  if (disp_step % sizeof(float) != 0 || (dev_raw && raw_step % sizeof(int16_t) != 0))
-    return stereo_fail(fn, "output steps must be multiples of the element size");
-  return AMHIP_OK;
-}
-
 struct BmScratch {
   size_t oL, oR, oD, oP, oN, oB, total;  // total: one pair's bytes, a multiple of 256
 };
@@ -889,11 +898,7 @@ static BmScratch bm_scratch(int width, int height) {
   return o;
 }
 
-static int bm_run(Ctx* c, const amhip_bm_params* q, int width, int height, int batch,
-                  const BatchStrides& bs, const uint8_t* dev_left, size_t left_step,
-                  const uint8_t* dev_right, size_t right_step, const uint8_t* dev_mask,
-                  size_t mask_step, float* dev_disparity, size_t disp_step, int16_t* dev_raw,
-                  size_t raw_step) {
+static int stereo_run(Ctx* c, const amhip_bm_params* q, int width, int height, const StereoImages& im) {
   // the wrapper's setters (block-matching-bm.h): preFilterCap = pre_filter_size (the second
   // setPreFilterCap wins), disp12MaxDiff stays -1; findStereoCorrespondenceBM's preamble and
   // getValidDisparityROI (tests/bm_reference.py: effective, region)
@@ -920,19 +925,17 @@ static int bm_run(Ctx* c, const amhip_bm_params* q, int width, int height, int b
     p.xa = p.xb = p.ya = p.yb = 0;  // nothing matched: FILTERED everywhere
   const bool matched = p.xb > p.xa;
 
-  const size_t npix = (size_t)width * height;
   const BmScratch o = bm_scratch(width, height);
-  const unsigned B = (unsigned)batch;
+  const unsigned B = (unsigned)im.batch;
   const size_t wsb = o.total;  // pair b's scratch: the single-pair layout at b * wsb
   int rc;
   if ((rc = stereo_scratch(c, wsb * B))) return rc;
-  uint8_t* ws = c->sgbm_ws;
+  uint8_t* ws = c->stereo_ws;
   uint8_t* fl = ws + o.oL;
   uint8_t* fr = ws + o.oR;
   int16_t* disp = reinterpret_cast<int16_t*>(ws + o.oD);
-  int* par = reinterpret_cast<int*>(ws + o.oP);
-  int* cnt = reinterpret_cast<int*>(ws + o.oN);
-  int* lab = reinterpret_cast<int*>(ws + o.oB);
+  const SpeckleScratch u = {reinterpret_cast<int*>(ws + o.oP), reinterpret_cast<int*>(ws + o.oN),
+                            reinterpret_cast<int*>(ws + o.oB)};
 
   // the speckle filter and the final pass are SGBM's, on these fields
   SgbmDims s;
@@ -945,23 +948,14 @@ static int bm_run(Ctx* c, const amhip_bm_params* q, int width, int height, int b
 
   ScopedTimer t(c, AMHIP_K_STEREO);
   const dim3 rowgrid((unsigned)((width + 255) / 256), (unsigned)height, B);
-  hipLaunchKernelGGL(k_bm_prefilter, rowgrid, dim3(256), 0, c->stream, p, dev_left, left_step, dev_right,
-                     right_step, fl, fr, disp, bs.left, bs.right, wsb);
+  hipLaunchKernelGGL(k_bm_prefilter, rowgrid, dim3(256), 0, c->stream, p, im.left, im.left_step, im.right,
+                     im.right_step, fl, fr, disp, im.bs.left, im.bs.right, wsb);
   if (matched) {
     const dim3 grid((unsigned)((p.xb - p.xa + kBmTX - 1) / kBmTX),
                     (unsigned)((p.yb - p.ya + kBmTY - 1) / kBmTY), B);
     launch_bm_match(c, p, grid, fl, fr, disp, wsb);
   }
-  const bool speckle = q->speckle_range >= 0 && q->speckle_window_size > 0;
-  if (speckle) {
-    const dim3 nb((unsigned)((npix + 255) / 256), 1, B);
-    hipLaunchKernelGGL(k_sgbm_uf_init, nb, dim3(256), 0, c->stream, (int)npix, par, cnt, wsb);
-    hipLaunchKernelGGL(k_sgbm_uf_union, rowgrid, dim3(256), 0, c->stream, s, disp, par, wsb);
-    hipLaunchKernelGGL(k_sgbm_uf_count, nb, dim3(256), 0, c->stream, s, disp, par, lab, cnt, wsb);
-  }
-  hipLaunchKernelGGL(k_sgbm_final, rowgrid, dim3(256), 0, c->stream, s, disp, speckle ? lab : nullptr,
-                     cnt, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step, wsb, bs.mask,
-                     bs.disp, bs.raw);
+  speckle_and_final(c, s, q->speckle_range >= 0 && q->speckle_window_size > 0, disp, u, wsb, im);
   AMHIP_TRY(hipGetLastError());
   return AMHIP_OK;
 }
@@ -970,6 +964,40 @@ int stereo_scratch_reserve(Ctx* c, const amhip_stereo_settings& s, int width, in
   const size_t one = s.use_bm ? bm_scratch(width, height).total
                               : sgbm_scratch(sgbm_dims(&s.sgbm, width, height)).total;
   return stereo_scratch(c, one * (size_t)batch);
+}
+
+template <typename Params>
+static int params_only_check(const char* fn, const Params& q, int width, int height) {
+  const int rc = params_check(fn, q, width, height);
+  return rc ? rc : columns_check(fn, q, width);
+}
+
+// (under the names of the one-pair exports, whose texts amhip_stereo_create has always reported)
+int stereo_params_check(const amhip_stereo_settings& s, int width, int height) {
+  return s.use_bm ? params_only_check("amhip_bm_disparity_dev", s.bm, width, height)
+                  : params_only_check("amhip_sgbm_disparity_dev", s.sgbm, width, height);
+}
+
+int stereo_match(Ctx* c, const amhip_stereo_settings& s, int width, int height, const StereoImages& im) {
+  return s.use_bm ? stereo_run(c, &s.bm, width, height, im) : stereo_run(c, &s.sgbm, width, height, im);
+}
+
+// what the exports share: every check, the context, its device, the launches
+template <typename Params>
+static int stereo_entry(const char* fn, amhip_ctx* h, const Params* q, int width, int height,
+                        const StereoImages& im) {
+  int rc = stereo_check(fn, q, width, height, im);
+  if (rc) return rc;
+  if (!h) return arg_failure("null context");
+  Ctx* c = &h->impl;
+  if ((rc = ctx_use_device(c))) return rc;
+  return stereo_run(c, q, width, height, im);
+}
+
+// the strides of a one-pair call: one image each (nothing is read at them)
+static BatchStrides one_pair(const StereoImages& im, int height) {
+  const size_t H = (size_t)height;
+  return {H * im.left_step, H * im.right_step, H * im.mask_step, H * im.disp_step, H * im.raw_step};
 }
 
 }  // namespace amhip
@@ -998,15 +1026,10 @@ int amhip_sgbm_disparity_dev(amhip_ctx* h, const amhip_sgbm_params* q, int width
                              size_t right_step, const uint8_t* dev_mask, size_t mask_step,
                              float* dev_disparity, size_t disp_step, int16_t* dev_raw,
                              size_t raw_step) {
-  int rc = sgbm_check("amhip_sgbm_disparity_dev", q, width, height, dev_left, left_step, dev_right,
-                      right_step, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step);
-  if (rc) return rc;
-  if (!h) return arg_failure("null context");
-  Ctx* c = &h->impl;
-  if ((rc = ctx_use_device(c))) return rc;
-  const BatchStrides one = {0, 0, 0, 0, 0};
-  return sgbm_run(c, q, width, height, 1, one, dev_left, left_step, dev_right, right_step, dev_mask,
-                  mask_step, dev_disparity, disp_step, dev_raw, raw_step);
+  StereoImages im = {dev_left, left_step, dev_right, right_step, dev_mask, mask_step, dev_disparity,
+                     disp_step, dev_raw, raw_step, 1, {}};
+  im.bs = one_pair(im, height);
+  return stereo_entry("amhip_sgbm_disparity_dev", h, q, width, height, im);
 }
 
 int amhip_sgbm_disparity_batch_dev(amhip_ctx* h, const amhip_sgbm_params* q, int width, int height,
@@ -1016,20 +1039,11 @@ int amhip_sgbm_disparity_batch_dev(amhip_ctx* h, const amhip_sgbm_params* q, int
                                    size_t mask_batch_stride, float* dev_disparity, size_t disp_step,
                                    size_t disp_batch_stride, int16_t* dev_raw, size_t raw_step,
                                    size_t raw_batch_stride) {
-  static const char* fn = "amhip_sgbm_disparity_batch_dev";
-  int rc = sgbm_check(fn, q, width, height, dev_left, left_step, dev_right, right_step, dev_mask,
-                      mask_step, dev_disparity, disp_step, dev_raw, raw_step);
-  if (rc) return rc;
-  const BatchStrides bs = {left_batch_stride, right_batch_stride, mask_batch_stride, disp_batch_stride,
-                           raw_batch_stride};
-  if ((rc = batch_check(fn, height, batch, bs, left_step, right_step, dev_mask != nullptr, mask_step,
-                        disp_step, dev_raw != nullptr, raw_step)))
-    return rc;
-  if (!h) return arg_failure("null context");
-  Ctx* c = &h->impl;
-  if ((rc = ctx_use_device(c))) return rc;
-  return sgbm_run(c, q, width, height, batch, bs, dev_left, left_step, dev_right, right_step, dev_mask,
-                  mask_step, dev_disparity, disp_step, dev_raw, raw_step);
+  const StereoImages im = {dev_left, left_step, dev_right, right_step, dev_mask, mask_step, dev_disparity,
+                           disp_step, dev_raw, raw_step, batch,
+                           {left_batch_stride, right_batch_stride, mask_batch_stride, disp_batch_stride,
+                            raw_batch_stride}};
+  return stereo_entry("amhip_sgbm_disparity_batch_dev", h, q, width, height, im);
 }
 
 void amhip_bm_default_params(amhip_bm_params* out) {
@@ -1052,15 +1066,10 @@ int amhip_bm_disparity_dev(amhip_ctx* h, const amhip_bm_params* q, int width, in
                            size_t right_step, const uint8_t* dev_mask, size_t mask_step,
                            float* dev_disparity, size_t disp_step, int16_t* dev_raw,
                            size_t raw_step) {
-  int rc = bm_check("amhip_bm_disparity_dev", q, width, height, dev_left, left_step, dev_right,
-                    right_step, dev_mask, mask_step, dev_disparity, disp_step, dev_raw, raw_step);
-  if (rc) return rc;
-  if (!h) return arg_failure("null context");
-  Ctx* c = &h->impl;
-  if ((rc = ctx_use_device(c))) return rc;
-  const BatchStrides one = {0, 0, 0, 0, 0};
-  return bm_run(c, q, width, height, 1, one, dev_left, left_step, dev_right, right_step, dev_mask,
-                mask_step, dev_disparity, disp_step, dev_raw, raw_step);
+  StereoImages im = {dev_left, left_step, dev_right, right_step, dev_mask, mask_step, dev_disparity,
+                     disp_step, dev_raw, raw_step, 1, {}};
+  im.bs = one_pair(im, height);
+  return stereo_entry("amhip_bm_disparity_dev", h, q, width, height, im);
 }
 
 int amhip_bm_disparity_batch_dev(amhip_ctx* h, const amhip_bm_params* q, int width, int height,
@@ -1070,20 +1079,11 @@ int amhip_bm_disparity_batch_dev(amhip_ctx* h, const amhip_bm_params* q, int wid
                                  size_t mask_batch_stride, float* dev_disparity, size_t disp_step,
                                  size_t disp_batch_stride, int16_t* dev_raw, size_t raw_step,
                                  size_t raw_batch_stride) {
-  static const char* fn = "amhip_bm_disparity_batch_dev";
-  int rc = bm_check(fn, q, width, height, dev_left, left_step, dev_right, right_step, dev_mask,
-                    mask_step, dev_disparity, disp_step, dev_raw, raw_step);
-  if (rc) return rc;
-  const BatchStrides bs = {left_batch_stride, right_batch_stride, mask_batch_stride, disp_batch_stride,
-                           raw_batch_stride};
-  if ((rc = batch_check(fn, height, batch, bs, left_step, right_step, dev_mask != nullptr, mask_step,
-                        disp_step, dev_raw != nullptr, raw_step)))
-    return rc;
-  if (!h) return arg_failure("null context");
-  Ctx* c = &h->impl;
-  if ((rc = ctx_use_device(c))) return rc;
-  return bm_run(c, q, width, height, batch, bs, dev_left, left_step, dev_right, right_step, dev_mask,
-                mask_step, dev_disparity, disp_step, dev_raw, raw_step);
+  const StereoImages im = {dev_left, left_step, dev_right, right_step, dev_mask, mask_step, dev_disparity,
+                           disp_step, dev_raw, raw_step, batch,
+                           {left_batch_stride, right_batch_stride, mask_batch_stride, disp_batch_stride,
+                            raw_batch_stride}};
+  return stereo_entry("amhip_bm_disparity_batch_dev", h, q, width, height, im);
 }
 
 }  // extern "C"

@@ -4,22 +4,23 @@
 // Host side only: the kernels are the rectifier's (amhip_rectify.hip), the matchers'
 // (amhip_stereo.hip), the mapped undistorter's (amhip_forward.hip) and the append-mode densify
 // (amhip_densify.hip).  What this file adds is the order of things:
-//   frames     two raw slots that swap roles (frame j lives in slot j & 1): a frame is staged once
-//              and undistorted once although it is the right image of one pair and the left image
-//              of the next.  Host frames go through two pinned buffers and a second stream; the
-//              upload of frame j + 1 waits only for the rectifier of the pair that last read its
-//              slot, so it runs beside the matching of pair j.
-//   pairs      rectify -> match -> append, all enqueued on the context's stream; the point count
-//              stays on the device (SeqState) and is read once, by amhip_stereo_cloud.
-//   capacity   settled before the first pair of a sequence (pairs x W x H points).
-//   groups     amhip_stereo_set_pairs_in_flight(n > 1): add_frames takes the used frames in groups of
-//              up to n consecutive pairs -- n + 1 frame slots in rotation (frame j in slot j mod
-//              (n + 1)), the pairs rectified into stacks, ONE batched matcher call, then the appends
-//              pair by pair in order.  Each pair of a group copies the context's sticky error word
-//              behind its own rectifier (stream order), and its append reads that copy: a zero w
-//              silences its own pair and the later ones, never an earlier one.
+//   frames     nslots raw slots in rotation (frame j of a sequence lives in slot j mod nslots; 2 slots,
+//              or n + 1 once amhip_stereo_set_pairs_in_flight(n) has asked for more): a frame is
+//              staged once and undistorted once although it is the right image of one pair and the
+//              left image of the next.  Host frames go through pinned buffers and a second stream;
+//              the upload of a frame waits only for the rectifier of the pair that last read its
+//              slot, so it runs beside the matching of the pairs before it.
+//   groups     seq_run_group is the one way a pair runs: g consecutive frames behind the left frame
+//              that is in place (add_frame: g = 1; add_frames: groups of up to pairs_in_flight, for
+//              every n) -- each frame staged and its pair rectified into the next entry of the
+//              stacks, ONE matcher call for the g pairs, then the appends pair by pair in order,
+//              all enqueued on the context's stream.  The point count stays on the device
+//              (SeqState) and is read once, by amhip_stereo_cloud.  In a group of more than one,
+//              each pair copies the context's sticky error word behind its own rectifier (stream
+//              order) and its append reads that copy: a zero w silences its own pair and the later
+//              ones, never an earlier one.  A group of one reads the context's word itself.
+//   capacity   settled before the first pair of a call (pairs x W x H points).
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -28,6 +29,17 @@
 namespace amhip {
 
 constexpr int kSeqMaxSlots = AMHIP_STEREO_MAX_BATCH + 1;
+
+// T_G_C of a frame: rotation matrix and position
+struct SeqPose {
+  double R[9], t[3];
+};
+// one frame handed to the sequence: its T_G_B (7 doubles), its rows, `step` bytes apart
+struct SeqFrame {
+  const double* T_G_B7;
+  const uint8_t* src;
+  size_t step;
+};
 
 struct Stereo {
   amhip_ctx* ctx = nullptr;
@@ -51,7 +63,7 @@ struct Stereo {
 
   bool first_frame = true;
   int left_slot = 0;
-  double R1[9] = {}, t1[3] = {};
+  SeqPose left_pose = {};
 
   // stacks of `stack` rectified pairs, masks and disparity maps, npix elements apart
   int stack = 0;
@@ -83,23 +95,6 @@ static void quat_to_matrix(const HPose& p, double R[9]) {
   R[6] = txz - twy;
   R[7] = tyz + twx;
   R[8] = 1.0 - (txx + tyy);
-}
-
-// The selected matcher's own argument check, run without a context: it reports every parameter
-// error before it looks at the context, so "null context" means the parameters passed.
-static int check_matcher_params(const amhip_stereo_settings& s, int W, int H) {
-  const uint8_t* img = reinterpret_cast<const uint8_t*>(&s);  // (never dereferenced: no context)
-  float* out = reinterpret_cast<float*>(const_cast<amhip_stereo_settings*>(&s));
-  const int rc = s.use_bm
-      ? amhip_bm_disparity_dev(nullptr, &s.bm, W, H, img, (size_t)W, img, (size_t)W, nullptr, 0, out,
-                               (size_t)W * sizeof(float), nullptr, 0)
-      : amhip_sgbm_disparity_dev(nullptr, &s.sgbm, W, H, img, (size_t)W, img, (size_t)W, nullptr, 0,
-                                 out, (size_t)W * sizeof(float), nullptr, 0);
-  if (rc == AMHIP_ERR_ARG && std::strstr(amhip_last_error(), "null context")) {
-    set_last_error("");
-    return AMHIP_OK;
-  }
-  return rc;
 }
 
 static int dev_alloc(void** p, size_t bytes) {
@@ -201,26 +196,28 @@ static int seq_grow_stacks(Stereo* s, int n) {
 }
 
 // stereo.cpp:129-137: T_G_C = T_G_B * T_B_C, its position and rotation matrix
-static void seq_pose(const Stereo* s, const double* T_G_B7, double R[9], double t[3]) {
+static SeqPose seq_pose(const Stereo* s, const double* T_G_B7) {
   const HPose T_G_C = hpose_compose(hpose_from7(T_G_B7), s->T_B_C);
-  quat_to_matrix(T_G_C, R);
-  t[0] = T_G_C.tx;
-  t[1] = T_G_C.ty;
-  t[2] = T_G_C.tz;
+  SeqPose p;
+  quat_to_matrix(T_G_C, p.R);
+  p.t[0] = T_G_C.tx;
+  p.t[1] = T_G_C.ty;
+  p.t[2] = T_G_C.tz;
+  return p;
 }
 
 static const uint8_t* seq_frame(const Stereo* s, int slot) { return s->undistort ? s->und[slot] : s->raw[slot]; }
 
 // a frame into its slot: staged and, if asked for, undistorted -- once, whichever pairs it serves
-static int seq_stage(Stereo* s, int slot, const uint8_t* src, size_t step, bool on_device) {
+static int seq_stage(Stereo* s, int slot, const SeqFrame& f, bool on_device) {
   Ctx* c = &s->ctx->impl;
   hipStream_t main = c->stream;
   const size_t W = (size_t)s->W, H = (size_t)s->H;
   if (on_device) {
-    AMHIP_TRY(hipMemcpy2DAsync(s->raw[slot], W, src, step, W, H, hipMemcpyDeviceToDevice, main));
+    AMHIP_TRY(hipMemcpy2DAsync(s->raw[slot], W, f.src, f.step, W, H, hipMemcpyDeviceToDevice, main));
   } else {
     if (s->up_used[slot]) AMHIP_TRY(hipEventSynchronize(s->ev_up[slot]));  // pin[slot] is free again
-    for (size_t v = 0; v < H; ++v) std::memcpy(s->pin[slot] + v * W, src + v * step, W);
+    for (size_t v = 0; v < H; ++v) std::memcpy(s->pin[slot] + v * W, f.src + v * f.step, W);
     AMHIP_TRY(hipStreamWaitEvent(s->up_stream, s->ev_free[slot], 0));
     AMHIP_TRY(hipMemcpyAsync(s->raw[slot], s->pin[slot], s->npix, hipMemcpyHostToDevice, s->up_stream));
     AMHIP_TRY(hipEventRecord(s->ev_up[slot], s->up_stream));
@@ -236,12 +233,12 @@ static int seq_stage(Stereo* s, int slot, const uint8_t* src, size_t step, bool 
   return AMHIP_OK;
 }
 
-// the pair (frame in `left`, pose R1 / t1; frame in `right`, pose R2 / t2) rectified into entry k
+// the pair (frame in slot `left`, pose p1; frame in slot `right`, pose p2) rectified into entry k
 // of the stacks
-static int seq_rectify(Stereo* s, int k, int left, const double* R1, const double* t1, int right,
-                       const double* R2, const double* t2, double* R_G_C, double* baseline) {
+static int seq_rectify(Stereo* s, int k, int left, const SeqPose& p1, int right, const SeqPose& p2,
+                       double* R_G_C, double* baseline) {
   const size_t W = (size_t)s->W;
-  int rc = amhip_rectify_stereo_pair_dev(s->ctx, s->K, R1, R2, t1, t2, s->W, s->H, seq_frame(s, left), W,
+  int rc = amhip_rectify_stereo_pair_dev(s->ctx, s->K, p1.R, p2.R, p1.t, p2.t, s->W, s->H, seq_frame(s, left), W,
                                          seq_frame(s, right), W, R_G_C, baseline, nullptr,
                                          s->rect_l + k * s->npix, s->rect_r + k * s->npix,
                                          s->mask + k * s->npix);
@@ -255,120 +252,66 @@ static int seq_rectify(Stereo* s, int k, int left, const double* R1, const doubl
 static int seq_append(Stereo* s, int k, const double* R_G_C, double baseline, const double* t1,
                       bool replace, const unsigned* err_word) {
   const size_t W = (size_t)s->W;
-  DensifyParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.width = s->W;
-  p.height = s->H;
-  p.disp_step = W * sizeof(float);
-  p.img_step = W;
-  // stereo projection matrix Q (densifier.cpp:39-46), as amhip_densify_dev builds it
-  const double fx = s->K[0], fy = s->K[4], cx = s->K[2], cy = s->K[5];
-  p.Q03 = -cx;
-  p.Q11 = fx / fy;
-  p.Q13 = -cy * (fx / fy);
-  p.Q23 = fx;
-  p.Q32 = 1.0 / baseline;
-  for (int q = 0; q < 9; ++q) p.R[q] = R_G_C[q];
-  for (int q = 0; q < 3; ++q) p.t[q] = t1[q];
+  const DensifyParams p = densify_params(s->K, baseline, R_G_C, t1, s->W, s->H, W * sizeof(float), W);
   return densify_append_run(&s->ctx->impl, p, s->disp + k * s->npix, s->rect_l + k * s->npix, s->xyz,
                             s->inten, s->cap, s->state, s->pc2, replace, err_word);
 }
 
-static const char kSamePosition[] =
-    "CHECK_NE(baseline, 0.0) (densifier.cpp:39): both frames have the same position";
-static const char kZeroBaseline[] = "CHECK_NE(baseline, 0.0) (densifier.cpp:39)";
-
-// One frame of the sequence: stage, undistort, and -- unless it is the first -- run the pair.
-static int seq_push(Stereo* s, const double* T_G_B7, const uint8_t* src, size_t step, bool on_device,
-                    bool replace) {
-  double R2[9], t2[3];
-  seq_pose(s, T_G_B7, R2, t2);
-  const int slot = s->first_frame ? 0 : (s->left_slot + 1) % s->nslots;
+// the first frame of a sequence has no left partner: it is staged and becomes the left frame
+static int seq_first_frame(Stereo* s, const SeqFrame& f, bool on_device) {
   int rc;
-  if ((rc = seq_stage(s, slot, src, step, on_device))) return rc;
-  if (s->first_frame) {
-    std::memcpy(s->R1, R2, sizeof(R2));
-    std::memcpy(s->t1, t2, sizeof(t2));
-    s->left_slot = slot;
-    s->first_frame = false;
-    return AMHIP_OK;
-  }
-  if (t2[0] == s->t1[0] && t2[1] == s->t1[1] && t2[2] == s->t1[2]) return seq_arg_fail(kSamePosition);
-  double R_G_C[9], baseline = 0.0;
-  if ((rc = seq_rectify(s, 0, s->left_slot, s->R1, s->t1, slot, R2, t2, R_G_C, &baseline))) return rc;
-  if (baseline == 0.0) return seq_arg_fail(kZeroBaseline);
-  const size_t W = (size_t)s->W, dstep = W * sizeof(float);
-  rc = s->settings.use_bm
-      ? amhip_bm_disparity_dev(s->ctx, &s->settings.bm, s->W, s->H, s->rect_l, W, s->rect_r, W, s->mask,
-                               W, s->disp, dstep, nullptr, 0)
-      : amhip_sgbm_disparity_dev(s->ctx, &s->settings.sgbm, s->W, s->H, s->rect_l, W, s->rect_r, W,
-                                 s->mask, W, s->disp, dstep, nullptr, 0);
-  if (rc) return rc;
-  if ((rc = seq_append(s, 0, R_G_C, baseline, s->t1, replace, nullptr))) return rc;
-  // stereo.cpp:142-146: the right frame is the next pair's left frame
-  std::memcpy(s->R1, R2, sizeof(R2));
-  std::memcpy(s->t1, t2, sizeof(t2));
-  s->left_slot = slot;
+  if ((rc = seq_stage(s, 0, f, on_device))) return rc;
+  s->left_pose = seq_pose(s, f.T_G_B7);
+  s->left_slot = 0;
+  s->first_frame = false;
   return AMHIP_OK;
 }
 
-// g <= in_flight consecutive frames of a sequence whose left frame is in place: g pairs, matched
-// by ONE batched call.  A pair the host refuses (zero baseline) cuts the group in front of it: the
-// pairs before it go through, then the call fails with that pair's error, as frame by frame.
-static int seq_push_group(Stereo* s, const double* const* T_G_B7, const uint8_t* const* src,
-                          const size_t* step, bool on_device, int g) {
+// g (1 .. stack) consecutive frames of a sequence whose left frame is in place: g pairs, matched by
+// ONE call.  Frame k of the group is staged, then its pair with the frame before it is rectified
+// into entry k.  A pair that is refused -- both frames at one position, or a baseline the rectifier
+// finds to be zero -- cuts the group in front of it: its frame has been staged (and, for the zero
+// baseline, rectified), the pairs before it go through and roll the left frame, then the call fails
+// with that pair's error.  `replace`: the (one) pair replaces the cloud instead of joining it.
+static int seq_run_group(Stereo* s, const SeqFrame* f, int g, bool on_device, bool replace) {
   Ctx* c = &s->ctx->impl;
-  double R[AMHIP_STEREO_MAX_BATCH][9], t[AMHIP_STEREO_MAX_BATCH][3];
-  int m = g;  // pairs that go through
+  SeqPose pose[AMHIP_STEREO_MAX_BATCH + 1];  // pose / slot [k + 1]: frame k; [0]: the left frame
+  int slot[AMHIP_STEREO_MAX_BATCH + 1];
+  double R_G_C[AMHIP_STEREO_MAX_BATCH][9], baseline[AMHIP_STEREO_MAX_BATCH];
+  pose[0] = s->left_pose;
+  slot[0] = s->left_slot;
   const char* refused = nullptr;
-  for (int k = 0; k < g; ++k) {
-    seq_pose(s, T_G_B7[k], R[k], t[k]);
-    const double* tp = k ? t[k - 1] : s->t1;
-    const double d[3] = {t[k][0] - tp[0], t[k][1] - tp[1], t[k][2] - tp[2]};
-    if (t[k][0] == tp[0] && t[k][1] == tp[1] && t[k][2] == tp[2])
-      refused = kSamePosition;
-    else if (std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) == 0.0)  // (the rectifier's baseline)
-      refused = kZeroBaseline;
-    if (refused) {
-      m = k;
+  int m = 0, rc;  // m: pairs that go through
+  for (; m < g; ++m) {
+    const SeqPose& l = pose[m];
+    SeqPose& r = pose[m + 1] = seq_pose(s, f[m].T_G_B7);
+    slot[m + 1] = (slot[m] + 1) % s->nslots;
+    if ((rc = seq_stage(s, slot[m + 1], f[m], on_device))) return rc;
+    if (r.t[0] == l.t[0] && r.t[1] == l.t[1] && r.t[2] == l.t[2]) {
+      refused = "CHECK_NE(baseline, 0.0) (densifier.cpp:39): both frames have the same position";
       break;
     }
-  }
-  const int left0 = s->left_slot;
-  auto slot_of = [&](int k) { return (left0 + 1 + k) % s->nslots; };  // frame k of the group
-  int rc;
-  // (the refused frame is staged too, as frame by frame)
-  for (int k = 0; k < (refused ? m + 1 : m); ++k)
-    if ((rc = seq_stage(s, slot_of(k), src[k], step[k], on_device))) return rc;
-  double R_G_C[AMHIP_STEREO_MAX_BATCH][9], baseline[AMHIP_STEREO_MAX_BATCH];
-  for (int k = 0; k < m; ++k) {
-    if ((rc = seq_rectify(s, k, k ? slot_of(k - 1) : left0, k ? R[k - 1] : s->R1, k ? t[k - 1] : s->t1,
-                          slot_of(k), R[k], t[k], R_G_C[k], &baseline[k])))
-      return rc;
+    baseline[m] = 0.0;
+    if ((rc = seq_rectify(s, m, slot[m], l, slot[m + 1], r, R_G_C[m], &baseline[m]))) return rc;
+    if (baseline[m] == 0.0) {
+      refused = "CHECK_NE(baseline, 0.0) (densifier.cpp:39)";
+      break;
+    }
     // the error word as it stands behind this pair's rectifier (the next pair's comes later)
-    AMHIP_TRY(hipMemcpyAsync(s->flags + k, c->dev_err, sizeof(unsigned), hipMemcpyDeviceToDevice, c->stream));
+    if (g > 1)
+      AMHIP_TRY(hipMemcpyAsync(s->flags + m, c->dev_err, sizeof(unsigned), hipMemcpyDeviceToDevice, c->stream));
   }
   if (m > 0) {
-    const size_t W = (size_t)s->W, dstep = W * sizeof(float), np = s->npix;
-    rc = s->settings.use_bm
-        ? amhip_bm_disparity_batch_dev(s->ctx, &s->settings.bm, s->W, s->H, m, s->rect_l, W, np, s->rect_r,
-                                       W, np, s->mask, W, np, s->disp, dstep, np * sizeof(float), nullptr, 0, 0)
-        : amhip_sgbm_disparity_batch_dev(s->ctx, &s->settings.sgbm, s->W, s->H, m, s->rect_l, W, np,
-                                         s->rect_r, W, np, s->mask, W, np, s->disp, dstep,
-                                         np * sizeof(float), nullptr, 0, 0);
-    if (rc) return rc;
+    const size_t W = (size_t)s->W, np = s->npix;
+    const StereoImages im = {s->rect_l, W, s->rect_r, W, s->mask, W, s->disp, W * sizeof(float), nullptr, 0, m,
+                             {np, np, np, np * sizeof(float), 0}};
+    if ((rc = stereo_match(c, s->settings, s->W, s->H, im))) return rc;
     for (int k = 0; k < m; ++k)
-      if ((rc = seq_append(s, k, R_G_C[k], baseline[k], k ? t[k - 1] : s->t1, /*replace=*/false,
-                           s->flags + k)))
+      if ((rc = seq_append(s, k, R_G_C[k], baseline[k], pose[k].t, replace, g > 1 ? s->flags + k : nullptr)))
         return rc;
-    std::memcpy(s->R1, R[m - 1], sizeof(s->R1));
-    std::memcpy(s->t1, t[m - 1], sizeof(s->t1));
-    s->left_slot = slot_of(m - 1);
-  }
-  if (refused == kZeroBaseline) {  // (frame by frame the rectifier has run before the baseline is looked at)
-    double Rq[9], bq = 0.0;
-    if ((rc = seq_rectify(s, 0, s->left_slot, s->R1, s->t1, (s->left_slot + 1) % s->nslots, R[m], t[m], Rq, &bq)))
-      return rc;
+    // stereo.cpp:142-146: the right frame is the next pair's left frame
+    s->left_pose = pose[m];
+    s->left_slot = slot[m];
   }
   return refused ? seq_arg_fail(refused) : AMHIP_OK;
 }
@@ -380,12 +323,6 @@ static int check_channels(int channels) {
   if (channels != 1) return seq_arg_fail("amhip_stereo: image type not supported (stereo.cpp:123): 8UC1 only");
   return AMHIP_OK;
 }
-
-static int add_one(amhip_stereo* h, const double* T, const uint8_t* image, size_t step, int channels,
-                   bool on_device);
-static int add_many(amhip_stereo* h, const double* T, const uint8_t* const* images,
-                    const size_t* steps, const uint8_t* dev_frames, size_t frame_stride,
-                    size_t row_step, int channels, size_t F);
 
 }  // namespace amhip
 
@@ -404,8 +341,10 @@ static int add_one(amhip_stereo* h, const double* T, const uint8_t* image, size_
   Stereo* s = &h->impl;
   if (step < (size_t)s->W) return seq_arg_fail("amhip_stereo_add_frame: step smaller than the camera's width");
   if ((rc = ctx_use_device(&s->ctx->impl))) return rc;
-  if (!s->first_frame && (rc = seq_reserve(s, s->npix))) return rc;
-  return seq_push(s, T, image, step, on_device, /*replace=*/true);
+  const SeqFrame f = {T, image, step};
+  if (s->first_frame) return seq_first_frame(s, f, on_device);
+  if ((rc = seq_reserve(s, s->npix))) return rc;
+  return seq_run_group(s, &f, 1, on_device, /*replace=*/true);
 }
 
 static int add_many(amhip_stereo* h, const double* T, const uint8_t* const* images,
@@ -438,28 +377,24 @@ static int add_many(amhip_stereo* h, const double* T, const uint8_t* const* imag
       (rc = stereo_scratch_reserve(&s->ctx->impl, s->settings, s->W, s->H, (int)std::min(n, pairs))))
     return rc;
   if ((rc = seq_clear(s))) return rc;  // point_cloud->clear() (stereo.cpp:86)
-  const double* gT[AMHIP_STEREO_MAX_BATCH];
-  const uint8_t* gsrc[AMHIP_STEREO_MAX_BATCH];
-  size_t gstep[AMHIP_STEREO_MAX_BATCH];
+  SeqFrame group[AMHIP_STEREO_MAX_BATCH];
   int g = 0;
   for (size_t i = 0; i < F; ++i) {
     if ((i + 1) % nth != 0) continue;  // ++skip % use_every_nth_image == 0 (:93)
-    const uint8_t* src = on_device ? dev_frames + i * frame_stride : images[i];
-    const size_t step = on_device ? row_step : steps[i];
-    if (n == 1 || s->first_frame) {
-      if ((rc = seq_push(s, T + 7 * i, src, step, on_device, /*replace=*/false))) return rc;
+    const SeqFrame f = {T + 7 * i, on_device ? dev_frames + i * frame_stride : images[i],
+                        on_device ? row_step : steps[i]};
+    if (s->first_frame) {
+      if ((rc = seq_first_frame(s, f, on_device))) return rc;
       continue;
     }
-    gT[g] = T + 7 * i;
-    gsrc[g] = src;
-    gstep[g] = step;
+    group[g] = f;
     if (++g == (int)n) {
-      if ((rc = seq_push_group(s, gT, gsrc, gstep, on_device, g))) return rc;
+      if ((rc = seq_run_group(s, group, g, on_device, /*replace=*/false))) return rc;
       g = 0;
     }
   }
-  if (g > 0 && (rc = seq_push_group(s, gT, gsrc, gstep, on_device, g))) return rc;  // (the last, shorter group)
-  return AMHIP_OK;
+  // (the last, shorter group)
+  return g > 0 ? seq_run_group(s, group, g, on_device, /*replace=*/false) : AMHIP_OK;
 }
 
 }  // namespace amhip
@@ -490,7 +425,7 @@ int amhip_stereo_create(amhip_ctx* ctx, const amhip_camera* cam, const double* T
       cam->distortion != AMHIP_DIST_EQUIDISTANT)
     return seq_arg_fail("amhip_stereo_create: unknown distortion model");
   int rc;
-  if ((rc = check_matcher_params(*settings, cam->width, cam->height))) return rc;
+  if ((rc = stereo_params_check(*settings, cam->width, cam->height))) return rc;
   if (!ctx) return seq_arg_fail("null context");
   if ((rc = ctx_use_device(&ctx->impl))) return rc;
   amhip_stereo* h = new (std::nothrow) amhip_stereo();

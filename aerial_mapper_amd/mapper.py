@@ -857,8 +857,9 @@ class Stereo(object):
 
     def set_pairs_in_flight(self, n):
         """How many stereo pairs add_frames keeps in flight (1 .. 16, default 1): with n > 1 the block
-        matcher serves up to n consecutive pairs per launch.  Results are bit for bit those of n = 1;
-        add_frame is unaffected (amhip_stereo_set_pairs_in_flight)."""
+        matcher serves up to n consecutive pairs per launch (n = 1: groups of one, the same code).
+        Results are bit for bit the same for every n; add_frame is unaffected
+        (amhip_stereo_set_pairs_in_flight)."""
         L.check(self._lib.amhip_stereo_set_pairs_in_flight(self._h, int(n)))
         self.pairs_in_flight = int(n)
 

@@ -645,15 +645,16 @@ int amhip_stereo_destroy(amhip_stereo* stereo);
 /* A newly constructed object: first_frame_ = true, the cloud emptied, the payload zeroed. */
 int amhip_stereo_reset(amhip_stereo* stereo);
 /* How many pairs amhip_stereo_add_frames / _dev keep in flight: n in [1, AMHIP_STEREO_MAX_BATCH],
- * 1 by default (an extension beside the reference's class; not part of amhip_stereo_settings).  With
- * n > 1 the used frames are taken in groups of up to n consecutive pairs: each frame is staged and
- * undistorted once (n + 1 frame slots), the n pairs are rectified into stacks, ONE batched matcher
- * call serves the group, and the append-mode densify then runs pair by pair in order.  The cloud,
- * the intensities, the point count, `pairs`, the PointCloud2 payload and every status are bit for
- * bit those of n = 1: a pair with a zero baseline cuts its group (the pairs before it are kept, the
- * call fails as at n = 1), and a zero w found on the device silences that pair and every later one,
- * never an earlier one (each pair of a group has its own copy of the error word, taken in stream
- * order behind its rectifier).  This call allocates the slots and stacks (AMHIP_ERR_NOMEM if they
+ * 1 by default (an extension beside the reference's class; not part of amhip_stereo_settings).  For
+ * every n the used frames are taken in groups of up to n consecutive pairs, by one piece of code
+ * (n = 1: groups of one, which is also how amhip_stereo_add_frame runs its pair): each frame is
+ * staged and undistorted once (n + 1 frame slots), the pairs of a group are rectified into stacks,
+ * ONE matcher call serves the group, and the append-mode densify then runs pair by pair in order.
+ * The cloud, the intensities, the point count, `pairs`, the PointCloud2 payload and every status
+ * are bit for bit the same for every n: a pair with a zero baseline cuts its group (the pairs
+ * before it are kept, then the call fails), and a zero w found on the device silences that pair and
+ * every later one, never an earlier one (each pair of a group of more than one has its own copy of
+ * the error word, taken in stream order behind its rectifier).  This call allocates the slots and stacks (AMHIP_ERR_NOMEM if they
  * cannot be had; the object then keeps its previous n) and waits for the object's work; a frame
  * carried over from earlier calls is kept.  add_frames settles the matcher's scratch for a whole
  * group before its first pair.  amhip_stereo_add_frame (one frame at a time) is unaffected. */

@@ -293,14 +293,16 @@ def test_add_frames_with_pairs_in_flight(gmap, use_bm, nth):
 
 def test_one_matcher_call_per_group(gmap):
     seq = the_seq()
-    with make(gmap, seq, True, n=4) as st:
-        gmap.enable_timing(True)
-        gmap.timing_reset()
-        st.add_frames(seq.T_G_B, [f for f in seq.frames])
-        times = gmap.kernel_times()
-        gmap.enable_timing(False)
-        assert st.pairs == 6
-    assert times["k_stereo"][1] == 2          # six pairs: a group of four and a group of two
+    # six pairs: six groups of one at n = 1; a group of four and a group of two at n = 4
+    for n, calls in ((1, 6), (4, 2)):
+        with make(gmap, seq, True, n=n) as st:
+            gmap.enable_timing(True)
+            gmap.timing_reset()
+            st.add_frames(seq.T_G_B, [f for f in seq.frames])
+            times = gmap.kernel_times()
+            gmap.enable_timing(False)
+            assert st.pairs == 6
+        assert times["k_stereo"][1] == calls, n
 
 
 def test_undistortion_with_pairs_in_flight(gmap):
@@ -385,3 +387,109 @@ def test_zero_baseline_pair_cuts_its_group(gmap, use_bm):
     assert seen[0][0] == seen[1][0] and "baseline" in seen[0][0]
     assert np.array_equal(seen[1][1][0], np.ascontiguousarray(want_xyz[:ns[0] + ns[1]]).view(np.uint64))
     assert_same_run(seen[1][1], seen[0][1], "the pairs before the failing one")
+
+
+# ---- 9. groups at their edges -----------------------------------------------------------------------
+def chain_prefix(want, pairs):
+    """the first `pairs` pairs of a chain as (xyz bits, intensities)"""
+    k = sum(want[2][:pairs])
+    return np.ascontiguousarray(want[0][:k]).view(np.uint64), want[1][:k]
+
+
+def assert_prefix(run, want, pairs, what):
+    xyz, inten = chain_prefix(want, pairs)
+    assert run[2] == pairs, (what, run[2])
+    assert run[0].shape == xyz.shape and np.array_equal(run[0], xyz), what
+    assert np.array_equal(run[1], inten), what
+
+
+def cloud_counts(st):
+    from aerial_mapper_amd import hip_lib as L
+    num, pairs = C.c_size_t(), C.c_size_t()
+    xyz, inten = C.c_void_p(), C.c_void_p()
+    assert L.load().amhip_stereo_cloud(st._h, C.byref(xyz), C.byref(inten), C.byref(num), C.byref(pairs)) == L.OK
+    return pairs.value, num.value
+
+
+@pytest.mark.parametrize("n", [1, 4])
+@pytest.mark.parametrize("use_bm", [True, False])
+def test_one_frame_then_one_more(gmap, use_bm, n):
+    """A call with one frame: no pair, an empty cloud.  The next call's single frame pairs with the
+    carried one: at n = 4 a carried frame plus a group of one."""
+    seq = the_seq()
+    want = expected(seq, 1, use_bm)
+    with make(gmap, seq, use_bm, n=n) as st:
+        run = snapshot(st, st.add_frames(seq.T_G_B[:1], [seq.frames[0]]))
+        assert run[2] == 0 and run[0].shape[0] == 0 and run[1].shape[0] == 0
+        assert cloud_counts(st) == (0, 0)
+        assert_prefix(snapshot(st, st.add_frames(seq.T_G_B[1:2], [seq.frames[1]])), want, 1, "pair (0, 1)")
+
+
+@pytest.mark.parametrize("n", [1, 4])
+@pytest.mark.parametrize("use_bm", [True, False])
+def test_a_full_group_and_a_full_group_plus_one(gmap, use_bm, n):
+    seq = the_seq()
+    want = expected(seq, 1, use_bm)
+    with make(gmap, seq, use_bm, n=n) as st:
+        for F in (n + 1, n + 2):
+            run = snapshot(st, st.add_frames(seq.T_G_B[:F], [f for f in seq.frames[:F]]))
+            assert_prefix(run, want, F - 1, "%d frames at n = %d" % (F, n))
+            st.reset()
+
+
+@pytest.mark.parametrize("use_bm", [True, False])
+def test_refused_first_pair_of_a_call(gmap, use_bm):
+    """Frames 0 and 1 at one position: no pair goes through, the object recovers after a reset."""
+    A = _A()
+    from aerial_mapper_amd import hip_lib as L
+    seq = the_seq()
+    want = expected(seq, 1, use_bm)
+    T = seq.T_G_B.copy()
+    T[1] = T[0]
+    texts = []
+    for n in (1, 4):
+        with make(gmap, seq, use_bm, n=n) as st:
+            with pytest.raises(A.AmhipError) as ei:
+                st.add_frames(T, [f for f in seq.frames])
+            assert ei.value.status == L.ERR_ARG
+            texts.append(str(ei.value))
+            assert cloud_counts(st) == (0, 0)
+            st.reset()
+            assert_prefix(snapshot(st, st.add_frames(seq.T_G_B, [f for f in seq.frames])), want, 6,
+                          "after the reset, n = %d" % n)
+    assert "CHECK_NE(baseline, 0.0) (densifier.cpp:39): both frames have the same position" in texts[0]
+    assert texts[0] == texts[1]
+
+
+@pytest.mark.parametrize("use_bm", [True, False])
+def test_baseline_that_underflows_to_zero(gmap, use_bm):
+    """Frames 2 and 3 differ by 1e-200 in x: unequal positions whose squared distance underflows, so
+    the rectifier's baseline is exactly 0.0 -- the refusal that is not "same position".  The camera
+    poses are the sequence's own, moved so that frame 2 sits at x = 0, with an identity T_C_B (the
+    composed positions are then the given ones)."""
+    import copy
+    import oracle_ffi as O
+    A = _A()
+    from aerial_mapper_amd import hip_lib as L
+    seq = copy.copy(the_seq())
+    T = O.compose_T_G_C(seq.T_G_B, seq.T_C_B)
+    T[:, 0] -= T[2, 0]
+    T[3] = T[2]
+    T[3, 0] = 1e-200
+    seq.T_G_B, seq.T_C_B = T, np.array([0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0])
+    ts = seq.camera_poses()[1]
+    d = ts[3] - ts[2]
+    assert not np.array_equal(ts[3], ts[2]) and np.sqrt((d * d).sum()) == 0.0
+    want = SB.cpu_chain(seq, [(0, 1), (1, 2)], use_bm, key=("underflow", use_bm))
+    seen = []
+    for n in (1, 4):
+        with make(gmap, seq, use_bm, n=n) as st:
+            with pytest.raises(A.AmhipError) as ei:
+                st.add_frames(seq.T_G_B, [f for f in seq.frames])
+            assert ei.value.status == L.ERR_ARG
+            assert cloud_counts(st) == (2, want[2][0] + want[2][1])
+            seen.append((str(ei.value), snapshot(st, st._cloud())))
+            assert_prefix(seen[-1][1], want, 2, "the pairs before the refused one, n = %d" % n)
+    assert "CHECK_NE(baseline, 0.0) (densifier.cpp:39)" in seen[0][0] and "same position" not in seen[0][0]
+    assert seen[0][0] == seen[1][0]
+    assert_same_run(seen[1][1], seen[0][1], "n = 4 against n = 1")

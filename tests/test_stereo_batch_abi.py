@@ -119,3 +119,70 @@ def test_python_signatures():
     # amhip_stereo_settings is untouched: the knob is not a field of it
     from aerial_mapper_amd import hip_lib
     assert C.sizeof(hip_lib.StereoSettings) == 104
+
+
+# ---- the order in which errors win ------------------------------------------------------------------
+def _two_faults(L, matcher, batched, width=W, left=0x1000, ls=W, ds=4 * W, batch=3, lb=None, q=None):
+    """The text of a call with the given faults, through the one-pair or the batch export (no context)."""
+    lib = L.load()
+    p = L.SgbmParams() if matcher == "sgbm" else L.BmParams()
+    getattr(lib, "amhip_%s_default_params" % matcher)(C.byref(p))
+    p.num_disparities = 16
+    for k, v in (q or {}).items():
+        setattr(p, k, v)
+    img, out = C.c_void_p(left), C.c_void_p(0x2000)   # (never dereferenced: refused first)
+    right = C.c_void_p(0x1000)
+    if batched:
+        fn = getattr(lib, "amhip_%s_disparity_batch_dev" % matcher)
+        rc = fn(None, C.byref(p), width, H, batch, img, ls, H * ls if lb is None else lb, right, W, H * W,
+                None, 0, 0, out, ds, H * ds, None, 0, 0)
+    else:
+        fn = getattr(lib, "amhip_%s_disparity_dev" % matcher)
+        rc = fn(None, C.byref(p), width, H, img, ls, right, W, None, 0, out, ds, None, 0)
+    assert rc == L.ERR_ARG
+    return lib.amhip_last_error().decode()
+
+
+_BAD_BLOCK = {"sgbm": 13, "bm": 4}
+_FEW_COLUMNS = dict(num_disparities=48, min_disparity=14)     # w1 = 64 - 62 = 2 <= 9 / 2
+# (case, faults, {matcher: the text behind "amhip_<matcher>_disparity[_batch]_dev: "}); the texts are
+# those of the commit before the checks were split into one rule each
+_ORDER = [
+    ("null left image + bad num_disparities", lambda m: dict(left=0, q=dict(num_disparities=72)),
+     {"sgbm": "null argument", "bm": "null argument"}),
+    ("bad width + bad block_size", lambda m: dict(width=0, q=dict(block_size=_BAD_BLOCK[m])),
+     {"sgbm": "width must be in [3, 32767], height in [1, 32767]",
+      "bm": "width and height must be in [1, 32767]"}),
+    ("bad block_size + short row step", lambda m: dict(ls=W - 1, q=dict(block_size=_BAD_BLOCK[m])),
+     {"sgbm": "block_size must be odd and <= 11 (0: OpenCV's 5)",
+      "bm": "block_size must be odd, in [5, 31] and <= min(width, height)"}),
+    ("short row step + misaligned disp_step", lambda m: dict(ls=W - 1, ds=4 * W + 2),
+     {"sgbm": "a row step is smaller than the width", "bm": "a row step is smaller than the width"}),
+    ("misaligned disp_step + too few matchable columns", lambda m: dict(ds=4 * W + 2, q=_FEW_COLUMNS),
+     {"sgbm": "output steps must be multiples of the element size"}),
+    ("too few matchable columns + batch 17", lambda m: dict(batch=17, q=_FEW_COLUMNS),
+     {"sgbm": "fewer matchable columns than half the block"}),
+]
+_ORDER_BATCH = [
+    ("batch 17 + short batch stride", dict(batch=17, lb=H * W - 1), "batch must be in [1, 16]"),
+    ("batch 0 + null context", dict(batch=0), "batch must be in [1, 16]"),
+    ("short batch stride + null context", dict(lb=H * W - 1), "a batch stride is smaller than height * row step"),
+]
+
+
+@pytest.mark.parametrize("matcher", ["sgbm", "bm"])
+def test_a_call_with_two_faults_reports_the_same_one_as_before(L, matcher):
+    for batched in (False, True):
+        name = "amhip_%s_disparity_%sdev: " % (matcher, "batch_" if batched else "")
+        for case, faults, want in _ORDER:
+            if matcher not in want:
+                continue
+            kw = faults(matcher)
+            if not batched and "batch" in kw:
+                kw.pop("batch")     # (the one-pair call has the first fault alone)
+            assert _two_faults(L, matcher, batched, **kw) == name + want[matcher], (case, batched)
+    for case, kw, want in _ORDER_BATCH:
+        assert _two_faults(L, matcher, True, **kw) == "amhip_%s_disparity_batch_dev: %s" % (matcher, want), case
+    # without a fault, the missing context is what is left
+    for batched in (False, True):
+        assert _two_faults(L, matcher, batched) == "null context"

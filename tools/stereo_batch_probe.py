@@ -2,14 +2,15 @@
 tests/stereo_sequence.py's generator, device frames, per matcher (BM, SGBM):
   parent      Stereo.add_frames of ANOTHER checkout of this project (--parent-tree: a tree with its own
               built library, e.g. the parent commit), measured by a second process that takes its turn
-              inside every repetition of this one -- the same box, the same minutes;
+              inside every repetition of this one -- the same box, the same minutes; `parent_n8` is
+              that tree with 8 pairs in flight;
   n1 .. n8    Stereo.add_frames of this tree with 1, 2, 4 and 8 pairs in flight.
 The ways take turns inside every repetition (--warmup untimed, --reps timed), each figure is the
 median with min, max and the inter-quartile range; the clock stops when the cloud's size is known on
 the host.  Also: the matcher alone, one batched call of four 1920x1080 pairs against four one-pair
 calls, by HIP events (`matcher_batch4`).
 Usage: python tools/stereo_batch_probe.py [--parent-tree DIR] [--reps 20] [--warmup 3]
-(--serve is the second process's mode: it answers one line per request on stdin.)"""
+(--serve is the second process's mode: it answers one line per request "<matcher> <n>" on stdin.)"""
 import argparse
 import json
 import os
@@ -48,12 +49,16 @@ def timed(torch, st, seq, dev):
     return (time.perf_counter() - t0) * 1e3, n
 
 
+PARENT_WAYS = {"parent": 1, "parent_n8": 8}   # way -> pairs in flight of the other tree
+
+
 def serve(args):
     torch, A, seq, ncam, dev = setup(args.serve, args)
     from aerial_mapper_amd import hip_lib
     with A.AerialGridMap(A.GridMapSettings(0.0, 0.0, 32.0, 32.0, 1.0)) as m:
-        objs = {name: A.Stereo(ncam, A.StereoSettings(), A.BlockMatchingParameters(use_BM=bm), m)
-                for name, bm in (("bm", True), ("sgbm", False))}
+        objs = {"%s %d" % (name, n): A.Stereo(ncam, A.StereoSettings(), A.BlockMatchingParameters(use_BM=bm), m,
+                                              pairs_in_flight=n)
+                for name, bm in (("bm", True), ("sgbm", False)) for n in PARENT_WAYS.values()}
         print(json.dumps({"ready": hip_lib.build_id()}), flush=True)
         for line in sys.stdin:
             name = line.strip()
@@ -122,13 +127,13 @@ def main():
             for name, use_bm in (("bm", True), ("sgbm", False)):
                 bmp = A.BlockMatchingParameters(use_BM=use_bm)
                 objs = {n: A.Stereo(ncam, A.StereoSettings(), bmp, m, pairs_in_flight=n) for n in (1, 2, 4, 8)}
-                ways = (["parent"] if child else []) + ["n%d" % n for n in objs]
+                ways = (list(PARENT_WAYS) if child else []) + ["n%d" % n for n in objs]
                 times = {k: [] for k in ways}
                 counts = set()
                 for rep in range(args.warmup + args.reps):
                     for key in ways:       # (the ways take turns, so that drift hits them alike)
-                        if key == "parent":
-                            child.stdin.write(name + "\n")
+                        if key in PARENT_WAYS:
+                            child.stdin.write("%s %d\n" % (name, PARENT_WAYS[key]))
                             child.stdin.flush()
                             r = json.loads(child.stdout.readline())
                             ms, n = r["ms"], r["points"]
