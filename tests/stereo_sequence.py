@@ -70,6 +70,9 @@ def _texture(x, y, lattice, x0, y0):
     return v + 25.0 * np.sin(0.13 * x) * np.cos(0.11 * y) + 128.0
 
 
+texture = _texture       # (the scene's gray value, for other renderers of the same scene)
+
+
 def distort(kind, d, x, y):
     """aslam's radtan (kind 1) / equidistant (kind 2) distortion of normalised coordinates."""
     if kind == 1:

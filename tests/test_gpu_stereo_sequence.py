@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 import oracle_ffi as O
+import stereo_front_inputs as FI
+import stereo_front_reference as FR
 import stereo_sequence as SS
 
 pytestmark = pytest.mark.gpu
@@ -183,6 +185,9 @@ def test_point_cloud2_payload_of_the_last_pair(gmap, use_bm):
     _, _, ns, last = expected(seq, 1, use_bm)
     want, valid = pc2_restated(last, seq.K, seq.W, seq.H)
     assert valid.sum() == ns[-1]
+    # a second opinion: the payload of tests/stereo_front_reference.py
+    second = FR.densify_full(last["disparity"], last["left"], seq.K, last["baseline"], last["R_G_C"], last["t_G_C1"])
+    assert np.array_equal(second["pc2"], want) and np.array_equal(second["keep"], valid)
     with make(gmap, seq, use_bm) as st:
         before = host(st.point_cloud2())
         assert before.shape == (seq.H, seq.W, 16) and not before.any()
@@ -191,6 +196,7 @@ def test_point_cloud2_payload_of_the_last_pair(gmap, use_bm):
     assert not got[0].any()                                  # slot 0 keeps the zeros
     assert (want[1:, 0] == 0x7FC00000).sum() > 0.2 * seq.W * seq.H > 0   # both kinds of slots occur
     assert np.array_equal(got, want)
+    assert np.array_equal(got, second["pc2"])
 
 
 # ---- 6. row steps and device stacks ----------------------------------------------------------
@@ -328,3 +334,69 @@ def test_timing_goes_to_the_existing_slots(gmap):
         gmap.enable_timing(False)
     assert times["k_stereo"][1] == 2 and times["k_stereo"][0] > 0.0      # one matcher call per pair
     assert times["memset/fill"][1] == 4                                   # (the misc slot) rectify + append per pair
+
+
+# ---- 10. a zero w of the rectification in the middle of a sequence -----------------------------------
+def chain_of(seq, pairs, use_bm):
+    """cpu_chain for 160 x 120 frames: with 80 disparities the matchers leave the left 80 columns
+    invalid, so a pair gives about (160 - 80 - a window) / 160 of its pixels, not cpu_chain's 40 %."""
+    xs, is_, last = [], [], None
+    for (i, j) in pairs:
+        x, it, last = SS.cpu_pair(seq, i, j, use_bm)
+        assert x.shape[0] > 0.3 * seq.W * seq.H
+        xs.append(x)
+        is_.append(it)
+    return np.concatenate(xs), np.concatenate(is_), last
+
+
+def raw_cloud(st):
+    """amhip_stereo_cloud itself -> (status, xyz, intensities, pairs) on the host."""
+    from aerial_mapper_amd import hip_lib as L
+    from aerial_mapper_amd.mapper import _device_view
+    xyz, inten, n, pairs = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+    rc = L.load().amhip_stereo_cloud(st._h, C.byref(xyz), C.byref(inten), C.byref(n), C.byref(pairs))
+    if n.value == 0:
+        return rc, np.zeros((0, 3)), np.zeros(0, np.int32), pairs.value
+    dev = st.map.device
+    return (rc, host(_device_view(xyz.value, (n.value, 3), "<f8", dev, st)).copy(),
+            host(_device_view(inten.value, (n.value,), "<i4", dev, st)).copy(), pairs.value)
+
+
+@pytest.mark.parametrize("use_bm", [True, False])
+def test_zero_w_in_the_third_pair(gmap, use_bm):
+    """What the header promises (amhip_stereo_add_frame, amhip_stereo_set_pairs_in_flight): the zero w
+    is found on the device; that pair and every later one add nothing; amhip_stereo_cloud -- the call
+    that reads the status -- reports AMHIP_ERR_ARG with the rectifier's text and hands out the pairs
+    before it; all of it bit for bit the same for every pairs_in_flight; amhip_stereo_reset recovers.
+    The fourth pair is a GOOD pair (tests/stereo_front_inputs.py): only the sticky error word keeps it
+    out -- in its own group of one (n = 1, 3), in the zero-w pair's group (n = 2), in one group (n = 8)."""
+    A = _A()
+    from aerial_mapper_amd import hip_lib as L
+    seq, good = FI.ZeroWSequence(), FI.ZeroWSequence(turned=False)
+    want_xyz, want_i, last = chain_of(seq, [(0, 1), (1, 2)], use_bm)
+    want_pc2 = FR.densify_full(last["disparity"], last["left"], seq.K, last["baseline"], last["R_G_C"],
+                               last["t_G_C1"])["pc2"]
+    good_xyz, good_i, _ = chain_of(good, SS.pairs_of(5, 1), use_bm)
+    frames = [f for f in seq.frames]
+    with make(gmap, seq, use_bm) as st:
+        for n in (1, 2, 3, 8):
+            what = "pairs_in_flight = %d" % n
+            st.set_pairs_in_flight(n)
+            with pytest.raises(A.AmhipError) as ei:
+                st.add_frames(seq.T_G_B, frames)
+            assert ei.value.status == L.ERR_ARG, what
+            assert "rectifier.cpp:93,99" in str(ei.value) and "w == 0" in str(ei.value), what
+            # (the failing call read and cleared the error word: the cloud is there to be had)
+            rc, xyz, inten, pairs = raw_cloud(st)
+            assert rc == L.OK and pairs == 2, what
+            assert xyz.shape == want_xyz.shape, (what, xyz.shape, want_xyz.shape)
+            assert np.array_equal(xyz.view(np.uint64), want_xyz.view(np.uint64)), what
+            assert np.array_equal(inten, want_i), what
+            # the payload is still the second pair's
+            got_pc2 = host(st.point_cloud2()).reshape(-1, 16).view(np.uint32)
+            assert np.array_equal(got_pc2, want_pc2), what
+            # the documented recovery
+            st.reset()
+            assert_cloud(st.add_frames(good.T_G_B, [f for f in good.frames]), good_xyz, good_i, what + ", after reset")
+            assert st.pairs == 4
+            st.reset()

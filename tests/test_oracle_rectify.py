@@ -9,8 +9,9 @@ import pytest
 import oracle_ffi as O
 
 
-def rig(seed, W=160, H=120, yaw=0.03, base=(6.0, 0.7, -0.4)):
-    """Two nadir-looking cameras ~80 m above ground, a baseline mostly along x."""
+def rig(seed, W=160, H=120, yaw=0.03, base=(6.0, 0.7, -0.4), noise=0.02, pitch2=None):
+    """Two nadir-looking cameras ~80 m above ground, a baseline mostly along x.  noise: sigma of the
+    roll / pitch / yaw noise of both cameras (rad); pitch2: camera 2 turned about its own x axis."""
     rng = np.random.default_rng(seed)
     K = np.array([[150.0, 0.0, (W - 1) / 2.0], [0.0, 150.0, (H - 1) / 2.0], [0.0, 0.0, 1.0]])
 
@@ -21,8 +22,10 @@ def rig(seed, W=160, H=120, yaw=0.03, base=(6.0, 0.7, -0.4)):
         Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
         return Rz @ Ry @ Rx
     down = rot(np.pi, 0.0, 0.0)                    # camera z-axis pointing at the ground
-    R1 = rot(*(rng.normal(0, 0.02, 3))) @ down @ rot(0, 0, yaw)
-    R2 = rot(*(rng.normal(0, 0.02, 3))) @ down @ rot(0, 0, -yaw)
+    R1 = rot(*(rng.normal(0, noise, 3))) @ down @ rot(0, 0, yaw)
+    R2 = rot(*(rng.normal(0, noise, 3))) @ down @ rot(0, 0, -yaw)
+    if pitch2 is not None:
+        R2 = R2 @ rot(pitch2, 0.0, 0.0)
     t1 = np.array([10.0, -4.0, 80.0])
     t2 = t1 + np.array(base)
     yy, xx = np.mgrid[0:H, 0:W]
