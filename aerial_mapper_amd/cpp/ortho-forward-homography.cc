@@ -95,9 +95,15 @@ cv::Mat OrthoForwardHomography::result8() const {
 
 void OrthoForwardHomography::writeOutput() const {
   if (settings_.filename_mosaic_output.empty()) return;
-  // Without OpenCV there is no JPEG encoder: the 8-bit mosaic goes out as a
-  // binary PPM next to the requested name.  A catkin build calls
-  // cv::imwrite(settings_.filename_mosaic_output, result8()) here instead.
+  // cv::imwrite(settings_.filename_mosaic_output, result_) (:126-128, :188): the file the
+  // settings name, encoded on the GPU from the device-resident result_ (clamped to 0..255 as
+  // result8() clamps it; quality 95, libjpeg's defaults).  Like cv::imwrite, a file that cannot
+  // be written is reported and not fatal.
+  const int rc = amhip_mosaic_write_jpeg(mosaic_, 95, settings_.filename_mosaic_output.c_str());
+  if (rc != AMHIP_OK)
+    std::fprintf(stderr, "OrthoForwardHomography: %s not written: %s\n",
+                 settings_.filename_mosaic_output.c_str(), amhip_last_error());
+  // The 8-bit mosaic also goes out as a binary PPM next to it (what the demo tests read back).
   const cv::Mat img = result8();
   const std::string name = settings_.filename_mosaic_output + ".ppm";
   std::FILE* f = std::fopen(name.c_str(), "wb");

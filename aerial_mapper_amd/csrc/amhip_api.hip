@@ -951,6 +951,7 @@ void amhip_ctx_destroy(amhip_ctx* h) {
                   c->scan_partials, c->stage_points, c->frame_poses, c->stage_frames, c->stereo_ws};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  jpeg_scratch_free(&c->jpeg);
   if (c->host_err) (void)hipHostFree(c->host_err);
   if (c->host_tile_stats) (void)hipHostFree(c->host_tile_stats);
   if (c->host_sort_stats) (void)hipHostFree(c->host_sort_stats);

@@ -185,6 +185,37 @@ struct SortSplit {
   unsigned long long* halo_counts;
 };
 
+// The JPEG encoder's scratch (amhip_jpeg.hip), owned by a context or a mosaic, grown on demand and
+// kept: coefficients, bit counts, scan partials and the packed words of one call in `dev`; the
+// header and the two words read back in `pinned`; the raster a layer is turned into before it is
+// encoded in `image`; the file before it goes to the host in `out`.
+struct JpegScratch {
+  uint8_t* dev = nullptr;
+  size_t cap = 0;
+  uint8_t* pinned = nullptr;
+  uint8_t* image = nullptr;
+  size_t image_cap = 0;
+  uint8_t* out = nullptr;
+  size_t out_cap = 0;
+};
+enum { kJpegGray8 = 0, kJpegBgr8 = 1, kJpegBgr16s = 2 };   // 8UC1 / 8UC3 / CV_16SC3 clamped to 0..255
+struct JpegSource {
+  const void* dev;
+  size_t step;     // bytes per row
+  int width, height;
+  int mode;
+};
+void jpeg_scratch_free(JpegScratch* ws);
+int jpeg_scratch_image(JpegScratch* ws, size_t bytes, uint8_t** out);
+// the whole file into dev_out (at most cap bytes, nothing written when it does not fit:
+// AMHIP_ERR_ARG); asynchronous on `stream` up to the read-back of *bytes.  Arguments checked by
+// the callers (jpeg::check_image_args); quality 0 = 95.
+int jpeg_encode_run(hipStream_t stream, JpegScratch* ws, const JpegSource& src, int quality,
+                    uint8_t* dev_out, size_t cap, size_t* bytes);
+// encode, download, write `filename`
+int jpeg_write_run(const char* what, hipStream_t stream, JpegScratch* ws, const JpegSource& src,
+                   int quality, const char* filename);
+
 struct TimedRegion {
   hipEvent_t a, b;
   int slot;
@@ -321,6 +352,7 @@ struct Ctx {
   // the speckle labels of one call, carved out of one block that grows on demand
   uint8_t* stereo_ws = nullptr;
   size_t stereo_ws_cap = 0;
+  JpegScratch jpeg;
 
   // timing
   bool timing = false;

@@ -31,6 +31,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "amhip_common.h"
@@ -79,6 +80,7 @@ struct Mosaic {
   size_t host_frames_cap = 0;
   hipEvent_t frames_event = nullptr;
   bool frames_pending = false;
+  JpegScratch jpeg;                // amhip_mosaic_encode_jpeg_dev / _write_jpeg
 };
 
 static int fwd_arg_fail(const char* msg) {
@@ -942,6 +944,7 @@ int amhip_mosaic_destroy(amhip_mosaic* h) {
                   m->dist,  m->undist,     m->stage,    m->frames};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  jpeg_scratch_free(&m->jpeg);
   if (m->host_frames) (void)hipHostFree(m->host_frames);
   if (m->frames_event) (void)hipEventDestroy(m->frames_event);
   if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
@@ -1051,6 +1054,43 @@ int amhip_mosaic_download(amhip_mosaic* h, int16_t* result, uint8_t* result_mask
   int rc = fwd_use(m);
   if (rc) return rc;
   return fwd_download(m, result, result_mask);
+}
+
+/* cv::imwrite(settings_.filename_mosaic_output, result_) (:126-128, :188) from the device-resident
+ * result_: CV_16SC3 clamped to 0..255 in the block kernel, B G R, 4:2:0 (amhip_jpeg.hip). */
+static JpegSource mosaic_jpeg_source(const Mosaic* m) {
+  const JpegSource src = {m->result16, (size_t)m->desc.width_mosaic_pixels * 3u * sizeof(int16_t),
+                          m->desc.width_mosaic_pixels, m->desc.height_mosaic_pixels, kJpegBgr16s};
+  return src;
+}
+
+static int mosaic_jpeg_check(const char* what, const amhip_mosaic* h, int quality) {
+  if (quality < 0 || quality > 100)
+    return fwd_arg_fail((std::string(what) + ": quality must be 1..100 (0: 95)").c_str());
+  const amhip_mosaic_desc& d = h->impl.desc;
+  if (d.width_mosaic_pixels < 1 || d.height_mosaic_pixels < 1 || d.width_mosaic_pixels > 65535 ||
+      d.height_mosaic_pixels > 65535)
+    return fwd_arg_fail((std::string(what) + ": a JPEG file holds 1 x 1 to 65535 x 65535 pixels").c_str());
+  return AMHIP_OK;
+}
+
+int amhip_mosaic_encode_jpeg_dev(amhip_mosaic* h, int quality, uint8_t* dev_out, size_t cap, size_t* bytes) {
+  if (!h || !dev_out || !bytes) return fwd_arg_fail("amhip_mosaic_encode_jpeg_dev: null argument");
+  int rc = mosaic_jpeg_check("amhip_mosaic_encode_jpeg_dev", h, quality);
+  if (rc) return rc;
+  Mosaic* m = &h->impl;
+  if ((rc = fwd_use(m))) return rc;
+  return jpeg_encode_run(m->stream, &m->jpeg, mosaic_jpeg_source(m), quality, dev_out, cap, bytes);
+}
+
+int amhip_mosaic_write_jpeg(amhip_mosaic* h, int quality, const char* filename) {
+  if (!h || !filename) return fwd_arg_fail("amhip_mosaic_write_jpeg: null argument");
+  int rc = mosaic_jpeg_check("amhip_mosaic_write_jpeg", h, quality);
+  if (rc) return rc;
+  Mosaic* m = &h->impl;
+  if ((rc = fwd_use(m))) return rc;
+  return jpeg_write_run("amhip_mosaic_write_jpeg", m->stream, &m->jpeg, mosaic_jpeg_source(m), quality,
+                        filename);
 }
 
 int amhip_mosaic_device_ptr(amhip_mosaic* h, void** result_16sc3, void** result_mask) {

@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 # tools/gpu_ab.sh; never a different implementation)
 LIB_PATH = os.environ.get("AMHIP_LIB_PATH") or os.path.join(PKG, "lib", "libaerial_mapper_hip.so")
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 # amhip_status
 OK, ERR_ARG, ERR_EXACT_HIT, ERR_ALPHA_NONPOS, ERR_HIP, ERR_NO_DEVICE, ERR_NOMEM, ERR_HALO_OVERFLOW = range(8)
@@ -68,6 +68,8 @@ EXPORTS = [
     "amhip_stereo_default_settings", "amhip_stereo_create", "amhip_stereo_destroy", "amhip_stereo_reset",
     "amhip_stereo_add_frame", "amhip_stereo_add_frame_dev", "amhip_stereo_add_frames",
     "amhip_stereo_add_frames_dev", "amhip_stereo_cloud", "amhip_stereo_point_cloud2_dev",
+    "amhip_jpeg_bound", "amhip_jpeg_encode_dev", "amhip_jpeg_write", "amhip_layer_write_jpeg",
+    "amhip_session_layer_write_jpeg", "amhip_mosaic_encode_jpeg_dev", "amhip_mosaic_write_jpeg",
 ]
 
 
@@ -287,6 +289,17 @@ def load():
                                                C.POINTER(C.c_size_t)]
     lib.amhip_session_layer_to_image.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, vp,
                                                  C.c_size_t]
+    lib.amhip_jpeg_bound.restype = C.c_size_t
+    lib.amhip_jpeg_bound.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.amhip_jpeg_encode_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                          C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.amhip_jpeg_write.argtypes = [vp, C.c_char_p, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                     C.c_int]
+    lib.amhip_layer_write_jpeg.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_char_p]
+    lib.amhip_session_layer_write_jpeg.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                                   C.c_char_p]
+    lib.amhip_mosaic_encode_jpeg_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.amhip_mosaic_write_jpeg.argtypes = [vp, C.c_int, C.c_char_p]
     del u8p
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:

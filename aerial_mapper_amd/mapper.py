@@ -1016,6 +1016,7 @@ class OrthoForwardHomography(object):
         for k in range(3):
             self.desc.origin[k] = settings.origin[k]
         self.handle = C.c_void_p()
+        self.device = int(device)
         L.check(lib.amhip_mosaic_create(C.byref(self.desc), C.byref(ncameras.camera), int(device),
                                         C.byref(self.handle)))
         self._torch_stream = None
@@ -1128,3 +1129,20 @@ class OrthoForwardHomography(object):
         L.check(L.load().amhip_mosaic_download(self.handle, C.c_void_p(res.ctypes.data),
                                                C.c_void_p(mask.ctypes.data)))
         return res, mask
+
+    def write_jpeg(self, filename, quality=95):
+        """cv::imwrite(settings_.filename_mosaic_output, result_) (:126-128, :188): result_ clamped
+        to 0..255, encoded on the device (amhip_mosaic_write_jpeg)."""
+        L.check(L.load().amhip_mosaic_write_jpeg(self.handle, int(quality), str(filename).encode()))
+
+    def encode_jpeg(self, quality=95):
+        """the same file as bytes (amhip_mosaic_encode_jpeg_dev)"""
+        import torch
+        lib = L.load()
+        h, w = self.desc.height_mosaic_pixels, self.desc.width_mosaic_pixels
+        out = torch.empty(lib.amhip_jpeg_bound(w, h, 3), dtype=torch.uint8, device="cuda:%d" % self.device)
+        self._wait_for_torch(out)
+        n = C.c_size_t()
+        L.check(lib.amhip_mosaic_encode_jpeg_dev(self.handle, int(quality), C.c_void_p(out.data_ptr()),
+                                                 out.numel(), C.byref(n)))
+        return out[:n.value].cpu().numpy().tobytes()

@@ -82,7 +82,7 @@ int main(int argc, char** argv) {
   settings.ground_plane_elevation_m = ground;
   settings.width_mosaic_pixels = N;
   settings.height_mosaic_pixels = N;
-  settings.filename_mosaic_output = "/tmp/demo_forward_mosaic";
+  // (filename_mosaic_output keeps the reference's default, /tmp/result.jpg)
   const double t0 = now_s();
   ortho::OrthoForwardHomography mosaic(ncameras, settings);
   if (settings.batch) {
@@ -95,8 +95,9 @@ int main(int argc, char** argv) {
   size_t covered = 0;
   for (uint8_t m : mosaic.result_mask()) covered += m != 0;
   std::printf("%s: %d frames %dx%d -> %dx%d mosaic in %.1f ms (host images, PCIe included), "
-              "%.1f %% covered, written to %s.ppm\n",
+              "%.1f %% covered, written to %s (JPEG, encoded on the GPU) and %s.ppm\n",
               incremental ? "updateOrthomosaic x F" : "batch", F, W, H, N, N, (t1 - t0) * 1e3,
-              100.0 * covered / (static_cast<double>(N) * N), settings.filename_mosaic_output.c_str());
+              100.0 * covered / (static_cast<double>(N) * N), settings.filename_mosaic_output.c_str(),
+              settings.filename_mosaic_output.c_str());
   return covered > 0 ? 0 : 1;
 }

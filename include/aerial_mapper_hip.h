@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define AMHIP_ABI_VERSION 1
+#define AMHIP_ABI_VERSION 2
 
 typedef enum amhip_status {
   AMHIP_OK = 0,
@@ -395,6 +395,14 @@ int amhip_mosaic_update_dev(amhip_mosaic* mosaic, const double* T_G_C7, const vo
                             size_t row_step, int channels);
 int amhip_mosaic_download(amhip_mosaic* mosaic, int16_t* result_16sc3, uint8_t* result_mask);
 int amhip_mosaic_device_ptr(amhip_mosaic* mosaic, void** result_16sc3, void** result_mask);
+/* cv::imwrite(settings_.filename_mosaic_output, result_) (:126-128, :188): the device-resident
+ * result_ (CV_16SC3, clamped to 0..255 in the kernel) as a baseline JPEG file, see amhip_jpeg_*
+ * below.  _encode_jpeg_dev leaves the file in device memory (at most cap bytes; *bytes = its size;
+ * a file that does not fit: AMHIP_ERR_ARG, nothing written), _write_jpeg downloads and writes it.
+ * quality 1..100, 0 = 95 (OpenCV's default). */
+int amhip_mosaic_encode_jpeg_dev(amhip_mosaic* mosaic, int quality, uint8_t* dev_out, size_t cap,
+                                 size_t* bytes);
+int amhip_mosaic_write_jpeg(amhip_mosaic* mosaic, int quality, const char* filename);
 /* The image -> mosaic homography of one frame (row-major 3x3, M[8] = 1); host
  * arithmetic only.  batch_quirk != 0: batch()'s offsets. */
 int amhip_mosaic_homography(const amhip_mosaic_desc* desc, const amhip_camera* cam,
@@ -449,6 +457,31 @@ int amhip_layer_to_image_dev(amhip_ctx* ctx, int layer, int bgr, float lower, fl
                              uint8_t* dev_image, size_t step);
 int amhip_layer_to_image(amhip_ctx* ctx, int layer, int bgr, float lower, float upper,
                          uint8_t* host_image, size_t step);
+
+/* ---- JPEG, encoded on the GPU ------------------------------------------------------------------
+ * The file libjpeg writes for cv::imwrite(name, image) at quality q (save_orthomosaic_jpg /
+ * orthomosaic_jpg_filename of the ortho::Settings, filename_mosaic_output of the forward mosaic):
+ * baseline sequential DCT, 8 bit, the standard Huffman tables, one scan, no restart markers; JFIF
+ * 1.01 header; 8UC1 as one component, 8UC3 (B, G, R) as Y Cb Cr 4:2:0.  Byte for byte what
+ * libjpeg-turbo writes through Pillow's save(quality=q, subsampling=2, optimize=False)
+ * (tests/golden/jpeg/).  width, height 1..65535; channels 1 or 3; quality 1..100, 0 = 95.
+ * Argument errors are reported before the context is looked at.
+ *   amhip_jpeg_bound       worst-case size of the file (0 for arguments out of range)
+ *   amhip_jpeg_encode_dev  device pixels (rows `step` bytes apart) -> the file in dev_out, at most
+ *                          cap bytes; *bytes = the file's size.  A file larger than cap gives
+ *                          AMHIP_ERR_ARG and nothing is written.  Runs on the context's stream,
+ *                          asynchronously up to the one read-back of *bytes.
+ *   amhip_jpeg_write       encode (host or device pixels), download, write `filename`
+ *   amhip_layer_write_jpeg amhip_layer_to_image_dev into scratch, then the encoder
+ * A file that cannot be opened or written is AMHIP_ERR_ARG with errno's text (amhip_status has no
+ * I/O code; the GeoTiff and point-cloud writers do the same). */
+size_t amhip_jpeg_bound(int width, int height, int channels);
+int amhip_jpeg_encode_dev(amhip_ctx* ctx, const uint8_t* dev_pixels, size_t step, int width, int height,
+                          int channels, int quality, uint8_t* dev_out, size_t cap, size_t* bytes);
+int amhip_jpeg_write(amhip_ctx* ctx, const char* filename, const uint8_t* pixels, int on_device,
+                     size_t step, int width, int height, int channels, int quality);
+int amhip_layer_write_jpeg(amhip_ctx* ctx, int layer, int bgr, float lower, float upper, int quality,
+                           const char* filename);
 
 /* The GeoTiff container io::AerialMapperIO::toGeoTiff / writeDataToDEMGeoTiffColor produce with
  * GDAL (aerial_mapper_io/src/aerial-mapper-io.cc:349-509), without GDAL: classic little-endian
@@ -821,6 +854,9 @@ int amhip_session_grid_map_msg(amhip_session* s, uint64_t stamp_ns, const char* 
 /* amhip_layer_to_image for the whole map of a session (every window on its own device). */
 int amhip_session_layer_to_image(amhip_session* s, int layer, int bgr, float lower, float upper,
                                  uint8_t* host_image, size_t step);
+/* amhip_layer_write_jpeg for the whole map of a session, from the assembled image. */
+int amhip_session_layer_write_jpeg(amhip_session* s, int layer, int bgr, float lower, float upper,
+                                   int quality, const char* filename);
 
 /* ---- tuning knobs: the ONE door for switches that select among correct implementations ----------
  * (tests force every path through them, A-B timing flips them; none is needed in normal use).
