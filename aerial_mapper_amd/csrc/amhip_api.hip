@@ -884,6 +884,7 @@ int amhip_ctx_create_window(const amhip_grid_desc* grid, int i0, int j0, int row
   c->win_j0 = j0;
   c->win_rows = rows;
   c->win_cols = cols;
+  c->windowed = rows != grid->rows || cols != grid->cols;
   c->cells = static_cast<size_t>(rows) * static_cast<size_t>(cols);
   // reference-identical by default; FAST is opt-in (setter, or AMHIP_DSM_FAST=1 for hosts that
   // cannot be recompiled; AMHIP_DSM_EXACT=1 wins over it)
@@ -1765,6 +1766,12 @@ int amhip_ctx_dsm_stats(amhip_ctx* h, int64_t* points_binned, int64_t* num_bins,
   }
   if (num_bins) *num_bins = c->last_num_bins;
   if (bin_cells) *bin_cells = c->last_bin_cells;
+  return AMHIP_OK;
+}
+
+int amhip_ctx_dsm_sort_pipeline(amhip_ctx* h, int32_t* pipeline) {
+  if (!h || !pipeline) return arg_fail("amhip_ctx_dsm_sort_pipeline: null argument");
+  *pipeline = h->impl.last_sort_pipeline;
   return AMHIP_OK;
 }
 

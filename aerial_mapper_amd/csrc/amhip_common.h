@@ -225,6 +225,7 @@ struct Ctx {
   amhip_grid_desc grid;       // the (global) map
   int win_i0 = 0, win_j0 = 0; // window of it this context owns
   int win_rows = 0, win_cols = 0;
+  bool windowed = false;      // created as a proper part of the map (a tile of a tiling)
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
@@ -333,6 +334,7 @@ struct Ctx {
   int64_t last_points_binned = 0;
   int64_t last_num_bins = 0;
   int32_t last_bin_cells = 0;
+  int last_sort_pipeline = -1;    // AMHIP_SORT_* of the last dsm_sort (-1: none yet)
   int64_t last_ntiles = 0;        // gather tiles of the last call (0: not the LDS-tiled gather)
   // Launch bookkeeping (round 5): what the sort's single-workgroup kernel resets for the gather
   // (SortAux), where the scatter waves' height partials end, the ticket of the count pass's

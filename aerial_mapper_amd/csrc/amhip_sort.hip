@@ -514,13 +514,29 @@ k_dsm_p3_reduce_scan(const uint32_t* __restrict__ hist_rows, int nrows, uint32_t
 // Passes 1 and 2.  kFirst: chunk of the input cloud, key k1, values/centre
 // handling of the reference; else: chunk of one k1 partition, key k2.
 // vb: the chunk.
-template <bool kFirst>
+//
+// kRuns (the run pipeline, DESIGN.md 4.1: no count pass, no global positions): the chunk's sorted
+// image goes back COMPACT -- pass 1 at the chunk's own base, pass 2 at its segment's place in the k1
+// partition -- and the pass leaves, per (key, chunk), where the key's run lies inside the image
+// (offset << 16 | length).  Pass 2 reads its segment -- kP3Chunk consecutive points of the
+// partition's logical order, which is the order of the source chunks -- through pass 1's run table.
+struct RunTabs {
+  uint32_t* run1;   // [k1][chunk], row stride r1s: offset << 16 | length of the chunk's k1 run
+  uint32_t* pre1;   // [k1][chunk], row stride p1s: exclusive prefix of the lengths; [g1] = the total
+  uint32_t* seg1;   // [k1][segment], row stride p1s: the chunk that holds the segment's first point
+  uint32_t* run2;   // sub-partition (k1, k2): row of its partition's segments at blk2[k1] * n2 + k2 * nseg
+  uint32_t* pre2;   // same layout: exclusive prefix of the lengths
+  uint32_t g1, r1s, p1s;
+};
+constexpr int kRunsCache = 2048;   // runs of a pass-2 segment kept in LDS (more: searched in memory)
+
+template <bool kFirst, bool kRuns = false>
 __device__ __forceinline__ void p3_scatter_body(const unsigned vb, const double* __restrict__ src,
                                                 const int32_t* __restrict__ values, size_t n,
                                                 const DsmParams& p, const uint32_t* __restrict__ start1,
                                                 const uint32_t* __restrict__ blk2,
                                                 uint32_t* __restrict__ cursor, double* __restrict__ dst,
-                                                double* __restrict__ zpart) {
+                                                double* __restrict__ zpart, const RunTabs rt = RunTabs{}) {
   extern __shared__ double s_pts[];                                       // 3 * kP3Chunk
   uint32_t* s_dest = reinterpret_cast<uint32_t*>(s_pts + 3 * kP3Chunk);   // kP3Chunk
   uint32_t* s_cnt = s_dest + kP3Chunk;                                    // kP3MaxKeys
@@ -530,6 +546,7 @@ __device__ __forceinline__ void p3_scatter_body(const unsigned vb, const double*
   const int tid = threadIdx.x;
   int nkeys;
   size_t c0, c1;
+  uint32_t part = 0, seg = 0, nseg = 0;   // kRuns, pass 2: the k1 partition, the segment of it, its segments
   if (kFirst) {
     c0 = (size_t)vb * kP3Chunk;
     c1 = min(c0 + (size_t)kP3Chunk, n);
@@ -546,8 +563,61 @@ __device__ __forceinline__ void p3_scatter_body(const unsigned vb, const double*
     c0 = (size_t)start1[lo] + (size_t)(b - blk2[lo]) * kP3Chunk;
     c1 = min(c0 + (size_t)kP3Chunk, (size_t)start1[lo + 1]);
     nkeys = p.p3_n2;
-    cursor += (size_t)lo * p.p3_n2;
+    if (!kRuns) cursor += (size_t)lo * p.p3_n2;
+    if (kRuns) {
+      part = lo;
+      seg = b - blk2[lo];
+      nseg = blk2[lo + 1] - blk2[lo];
+    }
   }
+  // kRuns, pass 2: the runs that cover the segment -- those of the chunks [ca, ca + nr) -- as
+  // (first point of the run in the segment, its address in the source); the table lies in the
+  // points' image, which nothing touches before every load's address is known
+  uint32_t* const s_rpre = reinterpret_cast<uint32_t*>(s_pts);   // kRunsCache
+  uint32_t* const s_rsrc = s_rpre + kRunsCache;                  // kRunsCache
+  const uint32_t* prow = nullptr;
+  const uint32_t* rrow = nullptr;
+  uint32_t l0 = 0, ca = 0, nr = 0;
+  bool cached = false;
+  if (kRuns && !kFirst) {
+    if (c1 <= c0) return;
+    prow = rt.pre1 + (size_t)part * rt.p1s;
+    rrow = rt.run1 + (size_t)part * rt.r1s;
+    const uint32_t* srow = rt.seg1 + (size_t)part * rt.p1s;
+    l0 = seg * (uint32_t)kP3Chunk;
+    ca = min(srow[seg], rt.g1 - 1u);
+    // (up to the chunk of the NEXT segment's first point: it may hold this one's last points)
+    const uint32_t cb = seg + 1u < nseg ? min(srow[seg + 1u], rt.g1 - 1u) : rt.g1 - 1u;
+    nr = cb >= ca ? cb - ca + 1u : 1u;
+    cached = nr <= (uint32_t)kRunsCache;
+    if (cached) {
+      for (uint32_t i = tid; i < nr; i += kP3Threads) {
+        const uint32_t c = ca + i, pre = prow[c];
+        const uint32_t at = max(pre, l0);  // (the first run may begin in the segment before)
+        s_rpre[i] = at - l0;
+        s_rsrc[i] = c * (uint32_t)kP3Chunk + (rrow[c] >> 16) + (at - pre);
+      }
+    }
+  }
+  // point j of the segment -> its row in the source: the LAST run that begins at or before j
+  // (empty runs share their successor's beginning); run 0 begins at 0
+  auto run_src = [&](uint32_t j) -> size_t {
+    uint32_t a = 0, b = nr;
+    if (cached) {
+      while (b - a > 1u) {
+        const uint32_t mid = (a + b) >> 1;
+        if (s_rpre[mid] <= j) a = mid; else b = mid;
+      }
+      return (size_t)s_rsrc[a] + (j - s_rpre[a]);
+    }
+    const uint32_t g = l0 + j;
+    while (b - a > 1u) {
+      const uint32_t mid = (a + b) >> 1;
+      if (prow[ca + mid] <= g) a = mid; else b = mid;
+    }
+    const uint32_t c = ca + a, pre = prow[c];
+    return (size_t)c * kP3Chunk + (rrow[c] >> 16) + (g - min(pre, g));
+  };
   if (tid < kP3MaxKeys) s_cnt[tid] = 0;
   __syncthreads();
   double px[kP3PerThread], py[kP3PerThread], pz[kP3PerThread];
@@ -557,7 +627,8 @@ __device__ __forceinline__ void p3_scatter_body(const unsigned vb, const double*
   if (c1 <= c0) return;
 #pragma unroll
   for (int k = 0; k < kP3PerThread; ++k) {
-    const size_t ld = min(c0 + tid + (size_t)k * kP3Threads, c1 - 1);
+    size_t ld = min(c0 + tid + (size_t)k * kP3Threads, c1 - 1);
+    if (kRuns && !kFirst) ld = min(run_src((uint32_t)(ld - c0)), n - 1);
     px[k] = src[3 * ld + 0];
     py[k] = src[3 * ld + 1];
     pz[k] = src[3 * ld + 2];
@@ -601,9 +672,17 @@ __device__ __forceinline__ void p3_scatter_body(const unsigned vb, const double*
     const unsigned ex = block_excl_scan<kP3Threads>(c, &total, s_scan);
     if (tid < nkeys) {
       s_off[tid] = ex;
-      // (the reservation's round trip to the counter runs under the placement below: its
-      // result is only stored -- and so only awaited -- after it)
-      if (c) my_base = atomicAdd(&cursor[tid], c);
+      if (kRuns) {
+        // (every entry, the empty runs too: the tables are never cleared)
+        if (kFirst)
+          rt.run1[(size_t)tid * rt.r1s + vb] = (ex << 16) | c;
+        else
+          rt.run2[(size_t)blk2[part] * nkeys + (size_t)tid * nseg + seg] = (ex << 16) | c;
+      } else if (c) {
+        // (the reservation's round trip to the counter runs under the placement below: its
+        // result is only stored -- and so only awaited -- after it)
+        my_base = atomicAdd(&cursor[tid], c);
+      }
     }
     if (tid == 0) s_scan[23] = total;
   }
@@ -616,12 +695,18 @@ __device__ __forceinline__ void p3_scatter_body(const unsigned vb, const double*
       s_pts[3 * q + 0] = px[k];
       s_pts[3 * q + 1] = py[k];
       s_pts[3 * q + 2] = pz[k];
-      s_dest[q] = slot[k];
+      if (!kRuns) s_dest[q] = slot[k];
     }
   }
-  if (tid < nkeys) s_base[tid] = my_base;
+  if (!kRuns && tid < nkeys) s_base[tid] = my_base;
   __syncthreads();
   const uint32_t ne = 3u * s_scan[23];
+  if (kRuns) {
+    // the image is in key order already: one contiguous, fully coalesced range
+    double* out = dst + 3 * (kFirst ? c0 : (size_t)start1[part] + (size_t)seg * kP3Chunk);
+    for (uint32_t e = tid; e < ne; e += kP3Threads) out[e] = s_pts[e];
+    return;
+  }
   for (uint32_t e = tid; e < ne; e += kP3Threads) {
     const uint32_t q = e / 3u;
     const uint32_t d = s_dest[q];
@@ -639,6 +724,128 @@ k_dsm_p3_scatter(const double* __restrict__ src, const int32_t* __restrict__ val
   p3_scatter_body<kFirst>(blockIdx.x, src, values, n, p, start1, blk2, cursor, dst, zpart);
 }
 
+// ---------------------------------------------------------------------------
+// the run pipeline (tuning key sort_runs, the default where a call is eligible): local sorts, runs
+// gathered on the read side -- no count pass, no global atomics
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kP3Threads)
+k_dsm_runs_sort1(const double* __restrict__ src, const int32_t* __restrict__ values, size_t n,
+                 DsmParams p, double* __restrict__ dst, double* __restrict__ zpart, RunTabs rt) {
+  p3_scatter_body<true, true>(blockIdx.x, src, values, n, p, nullptr, nullptr, nullptr, dst, zpart, rt);
+}
+
+__global__ void __launch_bounds__(kP3Threads)
+k_dsm_runs_sort2(const double* __restrict__ src, size_t n, DsmParams p,
+                 const uint32_t* __restrict__ start1, const uint32_t* __restrict__ blk2,
+                 double* __restrict__ dst, RunTabs rt) {
+  p3_scatter_body<false, true>(blockIdx.x, src, nullptr, n, p, start1, blk2, nullptr, dst, nullptr, rt);
+}
+
+// Scan 1: workgroup k1 turns its row of pass 1's run lengths into exclusive prefixes (four chunks
+// per thread and round) and notes, for every segment of kP3Chunk points of the partition, the
+// chunk its first point comes from (a run is at most one chunk long: it holds at most one such
+// point); the workgroup that finishes last (a ticket, as in k_dsm_p3_reduce_scan) lays the
+// partitions out: start1, blk2 -- and resets what SortAux names.
+__global__ void __launch_bounds__(1024)
+k_dsm_runs_scan1(RunTabs rt, int n1, uint32_t* __restrict__ tot1, uint32_t* __restrict__ start1,
+                 uint32_t* __restrict__ blk2, unsigned chunk, SortAux aux, unsigned* __restrict__ ticket) {
+  __shared__ unsigned lds[1024 / 64 + 1];
+  __shared__ unsigned s_last;
+  const int tid = threadIdx.x;
+  const uint32_t k1 = blockIdx.x;
+  const uint32_t* row = rt.run1 + (size_t)k1 * rt.r1s;
+  uint32_t* out = rt.pre1 + (size_t)k1 * rt.p1s;
+  uint32_t* seg = rt.seg1 + (size_t)k1 * rt.p1s;
+  unsigned carry = 0;
+  for (uint32_t base = 0; base < rt.g1; base += 4096u) {
+    const uint32_t i0 = base + 4u * tid;   // (rows are padded to a multiple of four chunks)
+    uint4 w = make_uint4(0u, 0u, 0u, 0u);
+    if (i0 < rt.g1) w = *reinterpret_cast<const uint4*>(row + i0);
+    unsigned v[4] = {w.x & 0xFFFFu, w.y & 0xFFFFu, w.z & 0xFFFFu, w.w & 0xFFFFu};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (i0 + q >= rt.g1) v[q] = 0u;
+    unsigned total;
+    unsigned run = carry + block_excl_scan<1024>(v[0] + v[1] + v[2] + v[3], &total, lds);
+    unsigned pre[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      pre[q] = run;
+      if (v[q]) {
+        const unsigned m = (run + chunk - 1u) / chunk;
+        if (m * chunk < run + v[q] && m < rt.g1) seg[m] = i0 + q;
+      }
+      run += v[q];
+    }
+    if (i0 < rt.g1) *reinterpret_cast<uint4*>(out + i0) = make_uint4(pre[0], pre[1], pre[2], pre[3]);
+    carry += total;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    out[rt.g1] = carry;
+    tot1[k1] = carry;
+    __threadfence();
+    s_last = atomicAdd(ticket, 1u) == gridDim.x - 1u ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  if (tid == 0) *ticket = 0u;
+  aux_reset(aux);
+  const unsigned t = tid < n1 ? tot1[tid] : 0u;
+  unsigned total;
+  const unsigned ex = block_excl_scan<1024>(t, &total, lds);
+  if (tid < n1) start1[tid] = ex;
+  if (tid == 0) start1[n1] = total;
+  const unsigned exb = block_excl_scan<1024>((t + chunk - 1u) / chunk, &total, lds);
+  if (tid < n1) blk2[tid] = exb;
+  if (tid == 0) blk2[n1] = total;
+}
+
+// Scan 2: a wave per (k1, k2) sub-partition sums its runs over the partition's segments (and leaves
+// their exclusive prefixes for the placement), 256 runs per round with all loads in flight; then
+// one workgroup makes the plan the counting pipeline's scan makes -- p3_scan_body -- from the sums.
+// (Two launches, no ticket: a ticket needs a device-scope fence in every one of ~2000 workgroups,
+// each of which writes the L2 back -- 0.10 ms measured against 0.03 + 0.02 for the pair.)
+__global__ void __launch_bounds__(1024)
+k_dsm_runs_scan2(RunTabs rt, uint32_t* __restrict__ cnt, int n1, int n2, const uint32_t* __restrict__ blk2) {
+  const int nk = n1 * n2;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int sp = (int)blockIdx.x * 16 + wid; sp < nk; sp += (int)gridDim.x * 16) {
+    const int k1 = sp / n2, k2 = sp - k1 * n2;
+    const uint32_t b0 = blk2[k1], nseg = blk2[k1 + 1] - b0;
+    const size_t at = (size_t)b0 * n2 + (size_t)k2 * nseg;
+    const uint32_t* row = rt.run2 + at;
+    uint32_t* out = rt.pre2 + at;
+    unsigned run = 0;   // (wave-uniform)
+    for (uint32_t i0 = 0; i0 < nseg; i0 += 256u) {
+      unsigned v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const uint32_t i = i0 + 64u * q + lane;
+        v[q] = i < nseg ? row[i] & 0xFFFFu : 0u;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const uint32_t i = i0 + 64u * q + lane;
+        const unsigned incl = wave_incl_scan(v[q], lane);
+        if (i < nseg) out[i] = run + incl - v[q];
+        run += __shfl(incl, 63, 64);
+      }
+    }
+    if (lane == 0) cnt[sp] = run;
+  }
+}
+
+__global__ void __launch_bounds__(1024)
+k_dsm_runs_plan2(const uint32_t* __restrict__ cnt, int n1, int n2,
+                 uint32_t* __restrict__ start2, uint32_t* __restrict__ cursor2,
+                 uint32_t* __restrict__ start1, uint32_t* __restrict__ cursor1,
+                 uint32_t* __restrict__ blk2, unsigned cap_small, unsigned cap_big,
+                 uint32_t* __restrict__ big_list, unsigned chunk) {
+  p3_scan_body(cnt, n1, n2, start2, cursor2, start1, cursor1, blk2, cap_small, cap_big, big_list, chunk, nullptr);
+}
+
 // Pass 3: one workgroup per (k1, k2) sub-partition.
 // bin_z (may be null): per bin the ordered keys (zkey_of) of its lowest / highest float-rounded
 // height -- the occupancy pre-pass of the single-precision gather reads them (amhip_dsm.hip)
@@ -646,18 +853,91 @@ __device__ __forceinline__ uint32_t place_zkey(double z) {
   const uint32_t b = __float_as_uint((float)z);
   return (b >> 31) ? ~b : (b | 0x80000000u);
 }
-template <int THREADS, int PER>
+// Where point idx of a sub-partition [g0, g1) lies in the placement's source.  The counting
+// pipeline: at idx.  The run pipeline (kRuns): the sub-partition is the sequence of its runs in
+// the segments of its k1 partition (pass 2 left one run per segment, scan 2 their prefixes);
+// point j = idx - g0 lies in the LAST run that begins at or before j.  Rows of up to kPlaceRunsCache
+// segments are searched in LDS (cfg3: ~150), longer ones in memory -- any length is served.
+constexpr int kPlaceRunsCache = 512;
+template <bool kRuns>
+struct PlaceSource {
+  const uint32_t* pre;
+  const uint32_t* run;
+  const uint32_t* s_pre;
+  const uint32_t* s_run;
+  uint32_t nseg, base, g0;
+  bool cached;
+  // every thread of the workgroup; a barrier has to follow before the first look-up
+  __device__ __forceinline__ void init(const RunTabs& rt, const uint32_t* __restrict__ start1,
+                                       const uint32_t* __restrict__ blk2, int n2, int k1, int k2,
+                                       uint32_t g0_, uint32_t* s_cache, int threads) {
+    if (!kRuns) return;
+    const uint32_t b0 = blk2[k1];
+    nseg = blk2[k1 + 1] - b0;
+    const size_t at = (size_t)b0 * n2 + (size_t)k2 * nseg;
+    pre = rt.pre2 + at;
+    run = rt.run2 + at;
+    base = start1[k1];
+    g0 = g0_;
+    cached = nseg <= (uint32_t)kPlaceRunsCache;
+    s_pre = s_cache;
+    s_run = s_cache + kPlaceRunsCache;
+    if (cached)
+      for (uint32_t i = threadIdx.x; i < nseg; i += threads) {
+        s_cache[i] = pre[i];
+        s_cache[kPlaceRunsCache + i] = run[i];
+      }
+  }
+  // The rows of points [0, cnt) of the sub-partition, one word each (cached lists only; after
+  // init()'s barrier, a barrier before the first read): a thread per run.  What the register-
+  // resident paths use instead of a search per point.
+  __device__ __forceinline__ void expand(uint32_t* s_rows, uint32_t cnt, int threads) const {
+    for (uint32_t r = threadIdx.x; r < nseg; r += threads) {
+      const uint32_t b = s_pre[r], w = s_run[r];
+      const uint32_t row = base + r * (uint32_t)kP3Chunk + (w >> 16);
+      for (uint32_t q = 0, len = w & 0xFFFFu; q < len && b + q < cnt; ++q) s_rows[b + q] = row + q;
+    }
+  }
+  __device__ __forceinline__ size_t operator()(size_t idx) const {
+    if (!kRuns) return idx;
+    const uint32_t j = (uint32_t)idx - g0;
+    uint32_t a = 0, b = nseg;
+    if (cached) {
+      while (b - a > 1u) {
+        const uint32_t mid = (a + b) >> 1;
+        if (s_pre[mid] <= j) a = mid; else b = mid;
+      }
+      return (size_t)base + (size_t)a * kP3Chunk + (s_run[a] >> 16) + (j - min(s_pre[a], j));
+    }
+    while (b - a > 1u) {
+      const uint32_t mid = (a + b) >> 1;
+      if (pre[mid] <= j) a = mid; else b = mid;
+    }
+    return (size_t)base + (size_t)a * kP3Chunk + (run[a] >> 16) + (j - min(pre[a], j));
+  }
+};
+// (what the run pipeline's placement kernels get on top of the counting pipeline's arguments)
+struct PlaceRuns {
+  RunTabs rt;
+  const uint32_t* start1;
+  const uint32_t* blk2;
+  size_t n;   // rows of the source: an address is clamped to it
+};
+
+template <int THREADS, int PER, bool kRuns = false>
 __device__ __forceinline__ void place_subpartition(const double* __restrict__ src, const DsmParams& p,
                                                    int cap, const uint32_t* __restrict__ start2,
                                                    uint32_t* __restrict__ bin_start,
                                                    double* __restrict__ sorted, int sp,
                                                    unsigned skip_lo, unsigned skip_hi,
-                                                   uint2* __restrict__ bin_z) {
+                                                   uint2* __restrict__ bin_z,
+                                                   const PlaceRuns pr = PlaceRuns{}) {
   extern __shared__ double s_pts[];                                  // 3 * cap
   uint32_t* s_bins = reinterpret_cast<uint32_t*>(s_pts + 3 * cap);   // p3_w
   uint32_t* s_scan = s_bins + p.p3_w;                                // 24
   uint32_t* s_zlo = s_scan + 24;                                     // p3_w (bin_z only)
   uint32_t* s_zhi = s_zlo + p.p3_w;                                  // p3_w
+  uint32_t* s_cache = s_scan + 24 + (bin_z ? 2 * p.p3_w : 0);        // 2 * kPlaceRunsCache (kRuns only)
   const int tid = threadIdx.x;
   const int k1 = sp / p.p3_n2, k2 = sp - k1 * p.p3_n2;
   const int rr = k2 / p.p3_c;
@@ -675,10 +955,20 @@ __device__ __forceinline__ void place_subpartition(const double* __restrict__ sr
       s_zhi[k] = 0u;
     }
   }
+  PlaceSource<kRuns> at;
+  at.init(pr.rt, pr.start1, pr.blk2, p.p3_n2, k1, k2, g0, s_cache, THREADS);
+  auto row_of = [&](size_t idx) -> size_t { return kRuns ? min(at(idx), pr.n - 1) : idx; };
   __syncthreads();
   // (skip_lo, skip_hi]: sub-partitions the other launch takes
   if ((g1 - g0) > skip_lo && (g1 - g0) <= skip_hi) return;
   const bool in_lds = (int)(g1 - g0) <= cap && cap <= THREADS * PER;
+  // (kRuns: the points' rows spelled out in the image, which is free until the placement)
+  const bool mapped = kRuns && in_lds && at.cached;
+  const uint32_t* const s_rows = reinterpret_cast<const uint32_t*>(s_pts);
+  if (mapped) {
+    at.expand(reinterpret_cast<uint32_t*>(s_pts), g1 - g0, THREADS);
+    __syncthreads();
+  }
   // the sub-partition is read ONCE: a thread keeps its points (<= 8) in
   // registers between the count and the placement
   double px[PER], py[PER], pz[PER];
@@ -688,7 +978,8 @@ __device__ __forceinline__ void place_subpartition(const double* __restrict__ sr
     if (g1 > g0) {
 #pragma unroll
       for (int k = 0; k < PER; ++k) {
-        const size_t ld = min(g0 + tid + (uint32_t)k * THREADS, g1 - 1);
+        const uint32_t at_k = min(g0 + tid + (uint32_t)k * THREADS, g1 - 1);
+        const size_t ld = mapped ? min((size_t)s_rows[at_k - g0], pr.n - 1) : row_of(at_k);
         px[k] = src[3 * ld + 0];
         py[k] = src[3 * ld + 1];
         pz[k] = src[3 * ld + 2];
@@ -713,7 +1004,8 @@ __device__ __forceinline__ void place_subpartition(const double* __restrict__ sr
   } else {
     for (uint32_t idx = g0 + tid; idx < g1; idx += THREADS) {
       int bx, by;
-      point_bin_xy(p, src[3 * (size_t)idx + 0], src[3 * (size_t)idx + 1], &bx, &by);
+      const size_t ld = row_of(idx);
+      point_bin_xy(p, src[3 * ld + 0], src[3 * ld + 1], &bx, &by);
       atomicAdd(&s_bins[bx - bx0], 1u);
     }
   }
@@ -743,9 +1035,10 @@ __device__ __forceinline__ void place_subpartition(const double* __restrict__ sr
   if (!in_lds) {
     // over-full sub-partition (clustered cloud): second read, direct placement
     for (uint32_t idx = g0 + tid; idx < g1; idx += THREADS) {
-      const double x = src[3 * (size_t)idx + 0];
-      const double y = src[3 * (size_t)idx + 1];
-      const double z = src[3 * (size_t)idx + 2];
+      const size_t ld = row_of(idx);
+      const double x = src[3 * ld + 0];
+      const double y = src[3 * ld + 1];
+      const double z = src[3 * ld + 2];
       int bx, by;
       point_bin_xy(p, x, y, &bx, &by);
       const size_t o = (size_t)g0 + atomicAdd(&s_bins[bx - bx0], 1u);
@@ -793,12 +1086,13 @@ __device__ __forceinline__ void place_subpartition(const double* __restrict__ sr
 // single bin larger than the image (hundreds of points per cell) is placed directly.
 // kRec: 20-byte records in, 16-byte records + rows out (place_records' formats).
 // ---------------------------------------------------------------------------
-template <int THREADS, bool kRec, int PER>
+template <int THREADS, bool kRec, int PER, bool kRuns = false>
 __device__ __forceinline__ void place_rounds(const void* __restrict__ src_v, const DsmParams& p, int cap,
                                              const uint32_t* __restrict__ start2,
                                              uint32_t* __restrict__ bin_start, double* __restrict__ sorted,
                                              uint4* __restrict__ rec16, uint32_t* __restrict__ sidx,
-                                             uint2* __restrict__ bin_z, int sp) {
+                                             uint2* __restrict__ bin_z, int sp,
+                                             const PlaceRuns pr = PlaceRuns{}) {
   // PER > 0: the sub-partition holds at most THREADS * PER points and a thread keeps its PER of
   // them in REGISTERS from the one read to the last round (configs[3] on one GPU: 13.3 K points
   // per sub-partition, 14 per thread); PER == 0: any size, every round re-reads it (from the L2).
@@ -811,6 +1105,7 @@ __device__ __forceinline__ void place_rounds(const void* __restrict__ src_v, con
   uint32_t* s_scan = s_cur + p.p3_w;                                    // 24
   uint32_t* s_zlo = s_scan + 24;                                        // p3_w (bin_z only)
   uint32_t* s_zhi = s_zlo + p.p3_w;                                     // p3_w
+  uint32_t* s_cache = s_zhi + p.p3_w;                                   // 2 * kPlaceRunsCache (kRuns only)
   const double* srcd = reinterpret_cast<const double*>(src_v);
   const uint32_t* srcw = reinterpret_cast<const uint32_t*>(src_v);
   const int tid = threadIdx.x;
@@ -828,12 +1123,15 @@ __device__ __forceinline__ void place_rounds(const void* __restrict__ src_v, con
       s_zlo[k] = 0xFFFFFFFFu;
       s_zhi[k] = 0u;
     }
+  PlaceSource<kRuns> at;
+  at.init(pr.rt, pr.start1, pr.blk2, p.p3_n2, k1, k2, g0, s_cache, THREADS);
+  auto row_of = [&](size_t idx) -> size_t { return kRuns ? min(at(idx), pr.n - 1) : idx; };
   __syncthreads();
-  // the bin of sorted point idx (PER == 0)
-  auto bin_of = [&](uint32_t idx) -> int {
-    if (kRec) return div_by((int)(srcw[(size_t)kRecWords * idx] & 0xFFFFu), p.B, p.mul_B) - bx0;
+  // the bin of the point in row ld of the source (PER == 0)
+  auto bin_of = [&](size_t ld) -> int {
+    if (kRec) return div_by((int)(srcw[(size_t)kRecWords * ld] & 0xFFFFu), p.B, p.mul_B) - bx0;
     int bx, by;
-    point_bin_xy(p, srcd[3 * (size_t)idx + 0], srcd[3 * (size_t)idx + 1], &bx, &by);
+    point_bin_xy(p, srcd[3 * ld + 0], srcd[3 * ld + 1], &bx, &by);
     return bx - bx0;
   };
   // register-resident points (PER > 0): all loads first, branch-free (rows past the end re-read
@@ -845,7 +1143,7 @@ __device__ __forceinline__ void place_rounds(const void* __restrict__ src_v, con
     if (g1 > g0) {
 #pragma unroll
       for (int k = 0; k < kRegs; ++k) {
-        const size_t ld = min(g0 + tid + (uint32_t)k * THREADS, g1 - 1);
+        const size_t ld = row_of(min(g0 + tid + (uint32_t)k * THREADS, g1 - 1));
         if (kRec) {
 #pragma unroll
           for (int t = 0; t < kRecWords; ++t) rw[k][t] = srcw[(size_t)kRecWords * ld + t];
@@ -878,7 +1176,8 @@ __device__ __forceinline__ void place_rounds(const void* __restrict__ src_v, con
     }
   } else {
     // ---- histogram (first read) ----
-    for (uint32_t idx = g0 + tid; idx < g1; idx += THREADS) {
+    for (uint32_t i = g0 + tid; i < g1; i += THREADS) {
+      const size_t idx = row_of(i);
       const int b = bin_of(idx);
       atomicAdd(&s_bins[b], 1u);
       if (bin_z) {
@@ -955,7 +1254,8 @@ __device__ __forceinline__ void place_rounds(const void* __restrict__ src_v, con
         }
       }
     } else {
-      for (uint32_t idx = g0 + tid; idx < g1; idx += THREADS) {
+      for (uint32_t i = g0 + tid; i < g1; i += THREADS) {
+        const size_t idx = row_of(i);
         const int bb = bin_of(idx);
         if (bb < lo_bin || bb >= hi_bin) continue;
         const uint32_t q = atomicAdd(&s_cur[bb], 1u);
@@ -1027,6 +1327,41 @@ k_dsm_p3_place_big(const double* __restrict__ src, DsmParams p,
     else
       place_subpartition<kP3BigThreads, kP3BigPer>(src, p, kP3BigCap, start2, bin_start, sorted, sp, 0u,
                                                    0u, bin_z);
+    __syncthreads();
+  }
+}
+
+// The run pipeline's placement: the same two kernels, the sub-partition read through its run list.
+__global__ void __launch_bounds__(kP3PlaceThreads)
+k_dsm_runs_place(const double* __restrict__ src, DsmParams p, int cap,
+                 const uint32_t* __restrict__ start2, uint32_t* __restrict__ bin_start,
+                 double* __restrict__ sorted, unsigned skip_lo, unsigned skip_hi,
+                 uint2* __restrict__ bin_z, const uint32_t* __restrict__ big_list,
+                 unsigned* __restrict__ host_big, PlaceRuns pr) {
+  if (host_big && blockIdx.x == 0 && threadIdx.x == 0) host_big[0] = big_list[0];
+  place_subpartition<kP3PlaceThreads, kP3PlacePer, true>(src, p, cap, start2, bin_start, sorted,
+                                                         (int)blockIdx.x, skip_lo, skip_hi, bin_z, pr);
+}
+
+__global__ void __launch_bounds__(kP3BigThreads)
+k_dsm_runs_place_big(const double* __restrict__ src, DsmParams p,
+                     const uint32_t* __restrict__ start2, uint32_t* __restrict__ bin_start,
+                     double* __restrict__ sorted, const uint32_t* __restrict__ big_list,
+                     uint2* __restrict__ bin_z, int cap_rounds, unsigned rounds_above, unsigned reg_max,
+                     PlaceRuns pr) {
+  const unsigned count = big_list[0];
+  for (unsigned k = blockIdx.x; k < count; k += gridDim.x) {
+    const int sp = (int)big_list[1 + k];
+    const uint32_t cnt = start2[sp + 1] - start2[sp];
+    if (cnt > rounds_above && cnt <= min(reg_max, (unsigned)(kP3BigThreads * kP3RoundsPer)))
+      place_rounds<kP3BigThreads, false, kP3RoundsPer, true>(src, p, cap_rounds, start2, bin_start, sorted,
+                                                             nullptr, nullptr, bin_z, sp, pr);
+    else if (cnt > rounds_above)
+      place_rounds<kP3BigThreads, false, 0, true>(src, p, cap_rounds, start2, bin_start, sorted, nullptr,
+                                                  nullptr, bin_z, sp, pr);
+    else
+      place_subpartition<kP3BigThreads, kP3BigPer, true>(src, p, kP3BigCap, start2, bin_start, sorted, sp,
+                                                         0u, 0u, bin_z, pr);
     __syncthreads();
   }
 }
@@ -1651,6 +1986,108 @@ static unsigned long long sort_geometry_signature(const DsmParams& p) {
 static int dsm_sort_impl(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
                          const DsmParams& p, unsigned long long* zrange, const SortSplit* split);
 
+// The run pipeline: local sort of every chunk -> scan 1 -> local sort of every segment of a k1
+// partition, its runs gathered -> scan 2 (the plan) -> placement through the run lists.
+// Buffers as in the counting pipeline: c->sorted, c->tmp_points, c->sorted.
+static int dsm_sort_runs(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
+                         const DsmParams& p, double* zpart, const SortAux& aux, unsigned long long geo_sig) {
+  const int n1 = p.p3_n1, n2 = p.p3_n2, nk = n1 * n2;
+  const size_t g1 = (n + kP3Chunk - 1) / kP3Chunk;   // chunks of pass 1; pass 2 has at most g1 + n1 segments
+  const size_t r1s = (g1 + 3) & ~(size_t)3, p1s = r1s + 4;
+  auto up4 = [](size_t w) { return (w + 3) & ~(size_t)3; };
+  const size_t plan_words = up4(4 * (size_t)nk + 4 * (size_t)n1 + 64);
+  const size_t rows2 = (g1 + (size_t)n1) * (size_t)n2;
+  const size_t ws_words = plan_words + up4((size_t)n1) + (size_t)n1 * (r1s + 2 * p1s) + 2 * up4(rows2) + 16;
+  int rc;
+  if ((rc = ensure_capacity(&c->tmp_points, &c->tmp_points_cap, 3 * n))) return rc;
+  if ((rc = ensure_capacity(&c->stripe_ws, &c->stripe_ws_cap, ws_words))) return rc;
+  uint32_t* cnt = c->stripe_ws;
+  uint32_t* start2 = cnt + nk;       // nk + 1
+  uint32_t* cursor2 = start2 + nk + 1;
+  uint32_t* start1 = cursor2 + nk;   // n1 + 1
+  uint32_t* cursor1 = start1 + n1 + 1;
+  uint32_t* blk2 = cursor1 + n1;     // n1 + 1
+  uint32_t* big_list = blk2 + n1 + 1;  // [count] + up to nk sub-partition ids
+  uint32_t* tot1 = c->stripe_ws + plan_words;
+  RunTabs rt;
+  rt.run1 = tot1 + up4((size_t)n1);
+  rt.pre1 = rt.run1 + (size_t)n1 * r1s;
+  rt.seg1 = rt.pre1 + (size_t)n1 * p1s;
+  rt.run2 = rt.seg1 + (size_t)n1 * p1s;
+  rt.pre2 = rt.run2 + up4(rows2);
+  rt.g1 = (uint32_t)g1;
+  rt.r1s = (uint32_t)r1s;
+  rt.p1s = (uint32_t)p1s;
+  const size_t lds_sort = (size_t)kP3Chunk * 28 + (3 * kP3MaxKeys + 32) * sizeof(uint32_t);
+  static_assert(2 * kRunsCache * sizeof(uint32_t) <= (size_t)kP3Chunk * 24, "the run table lies in the points' image");
+  AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_runs_sort1),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort));
+  AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_runs_sort2),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort));
+  {
+    ScopedTimer t(c, AMHIP_K_DSM_SCATTER);
+    hipLaunchKernelGGL(k_dsm_runs_sort1, dim3((unsigned)g1), dim3(kP3Threads), lds_sort, c->stream,
+                       dev_xyz, dev_values, n, p, c->sorted, zpart, rt);
+    c->range_parts = g1 * (kP3Threads / 64);
+    AMHIP_TRY(hipGetLastError());
+  }
+  {
+    ScopedTimer t(c, AMHIP_K_DSM_BIN_COUNT);
+    hipLaunchKernelGGL(k_dsm_runs_scan1, dim3((unsigned)n1), dim3(1024), 0, c->stream, rt, n1, tot1,
+                       start1, blk2, (unsigned)kP3Chunk, aux, c->dev_tickets + 2);
+    c->aux_done = true;
+    AMHIP_TRY(hipGetLastError());
+  }
+  {
+    ScopedTimer t(c, AMHIP_K_DSM_SCATTER);
+    hipLaunchKernelGGL(k_dsm_runs_sort2, dim3((unsigned)(g1 + n1)), dim3(kP3Threads), lds_sort, c->stream,
+                       c->sorted, n, p, start1, blk2, c->tmp_points, rt);
+    AMHIP_TRY(hipGetLastError());
+  }
+  {
+    ScopedTimer t(c, AMHIP_K_DSM_BIN_COUNT);
+    const unsigned grid = (unsigned)std::min<size_t>(((size_t)nk + 15) / 16, 2048);
+    hipLaunchKernelGGL(k_dsm_runs_scan2, dim3(grid), dim3(1024), 0, c->stream, rt, cnt, n1, n2,
+                       (const uint32_t*)blk2);
+    hipLaunchKernelGGL(k_dsm_runs_plan2, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)cnt, n1, n2,
+                       start2, cursor2, start1, cursor1, blk2, (unsigned)p.p3_cap, (unsigned)kP3BigCap,
+                       big_list, (unsigned)kP3Chunk);
+    AMHIP_TRY(hipGetLastError());
+  }
+  {
+    ScopedTimer t(c, AMHIP_K_DSM_SCAN);
+    // (the launch policy of the counting pipeline's placement, word for word)
+    const PlaceRuns pr = {rt, start1, blk2, n};
+    uint2* bin_z = nullptr;
+    const size_t cache = 2 * (size_t)kPlaceRunsCache * sizeof(uint32_t);
+    const size_t lds = (size_t)p.p3_cap * 24 + ((size_t)p.p3_w + 32) * sizeof(uint32_t) + cache;
+    AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_runs_place),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const bool want_big = !(c->sort_stats_sig == geo_sig && c->host_sort_stats && c->host_sort_stats[0] == 0u) ||
+                          no_launch_skips();
+    c->sort_stats_sig = geo_sig;
+    hipLaunchKernelGGL(k_dsm_runs_place, dim3((unsigned)nk), dim3(kP3PlaceThreads), lds, c->stream,
+                       c->tmp_points, p, p.p3_cap, start2, c->bin_start, c->sorted,
+                       want_big ? (unsigned)p.p3_cap : 0xFFFFFFFFu, 0xFFFFFFFFu, bin_z,
+                       (const uint32_t*)big_list, c->host_sort_stats, pr);
+    const size_t tables = (4 * (size_t)p.p3_w + 64) * sizeof(uint32_t) + cache;
+    int cap_rounds = (int)std::min<size_t>(kP3BigCap, (kLdsMaxBytes - tables) / 24);
+    unsigned rounds_above = kP3BigCap, reg_max = 0xFFFFFFFFu;
+    p3_rounds_knob(&cap_rounds, &rounds_above, &reg_max);
+    const size_t lds_big = std::max((size_t)kP3BigCap * 24 + ((size_t)p.p3_w + 32) * sizeof(uint32_t) + cache,
+                                    (size_t)cap_rounds * 24 + tables);
+    AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_runs_place_big),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big));
+    if (want_big)
+      hipLaunchKernelGGL(k_dsm_runs_place_big, dim3(256), dim3(kP3BigThreads), lds_big, c->stream,
+                         c->tmp_points, p, start2, c->bin_start, c->sorted, big_list, bin_z, cap_rounds,
+                         rounds_above, reg_max, pr);
+    c->bin_z_valid = false;
+    AMHIP_TRY(hipGetLastError());
+  }
+  return AMHIP_OK;
+}
+
 int dsm_sort(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
              const DsmParams& p, unsigned long long* zrange, const SortSplit* split) {
   const int rc = dsm_sort_impl(c, dev_xyz, dev_values, n, p, zrange, split);
@@ -1705,6 +2142,7 @@ static int dsm_sort_impl(Ctx* c, const double* dev_xyz, const int32_t* dev_value
 
   const bool force_one_level = force_one_level_;
   const bool three_pass = p.p3_n1 > 0 && !force_one_level;
+  c->last_sort_pipeline = AMHIP_SORT_ONE_LEVEL;
   if (split && split->phase == 1 && !three_pass)  // small clouds: selection in a pass of its own
     return halo_select_run(c, dev_xyz, split->n_prefix, split->hp, split->halo_out,
                            split->halo_counts);
@@ -1721,6 +2159,16 @@ static int dsm_sort_impl(Ctx* c, const double* dev_xyz, const int32_t* dev_value
     const size_t g_a = count_grid(n_a), g_b = n > n_a ? count_grid(n - n_a) : 0;
     const size_t gcount = g_a + g_b;
     int rc;
+    // The run pipeline serves the doubles of a whole, untiled context; the records
+    // (their zref has to exist before the first is written), tiled calls and windows (the halo
+    // selection rides on the count pass), and clouds whose rows do not fit the run tables' 32-bit
+    // addresses with room to spare keep the counting pipeline (so do column blocks of more than
+    // 2048 bins: the run lists' 4 KB of LDS have to fit next to the big placement's image).
+    // tuning key sort_runs=0: always.
+    const bool runs = !rec && !split && !c->windowed && n <= ((size_t)1 << 27) && n1 <= kP3MaxKeys &&
+                      n2 <= kP3MaxKeys && p.p3_w <= 2048 && tuning("sort_runs", 1.0) != 0.0;
+    c->last_sort_pipeline = runs ? AMHIP_SORT_RUNS : AMHIP_SORT_COUNT;
+    if (runs) return dsm_sort_runs(c, dev_xyz, dev_values, n, p, zpart, aux, geo_sig);
     if (rec) {
       if ((rc = ensure_capacity(&c->rec_a, &c->rec_a_cap, (size_t)kRecWords * n + 16))) return rc;
       if ((rc = ensure_capacity(&c->rec_b, &c->rec_b_cap, (size_t)kRecWords * n + 16))) return rc;

@@ -17,7 +17,7 @@ namespace {
 const char* const kKeys[] = {
     // sort
     "sort_one_level", "p3_min_points", "p3_target", "p3_cap", "p3_rounds_cap", "p3_rounds_reread",
-    "no_launch_skips",
+    "no_launch_skips", "sort_runs",
     // DSM gather
     "dsm_canon_all", "knn_global_bins", "dsm_no_rough_switch", "dsm_no_subwindow", "eager_reset",
     // mosaic

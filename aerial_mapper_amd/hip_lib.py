@@ -47,7 +47,7 @@ EXPORTS = [
     "amhip_densify_dev", "amhip_rectify_stereo_pair_dev", "amhip_halo_select_dev", "amhip_dsm_tiled_begin_dev",
     "amhip_dsm_tiled_finish_dev", "amhip_compose_T_G_C", "amhip_ortho_backward_process_dev",
     "amhip_ortho_backward_process", "amhip_ctx_enable_timing", "amhip_ctx_timing_reset",
-    "amhip_ctx_kernel_time", "amhip_kernel_name", "amhip_ctx_dsm_stats", "amhip_ctx_dsm_gather_stats", "amhip_ctx_order_after", "amhip_session_last_profile", "amhip_build_id", "amhip_set_tuning", "amhip_get_tuning", "amhip_default_dsm_precision",
+    "amhip_ctx_kernel_time", "amhip_kernel_name", "amhip_ctx_dsm_stats", "amhip_ctx_dsm_sort_pipeline", "amhip_ctx_dsm_gather_stats", "amhip_ctx_order_after", "amhip_session_last_profile", "amhip_build_id", "amhip_set_tuning", "amhip_get_tuning", "amhip_default_dsm_precision",
     "amhip_mosaic_create", "amhip_mosaic_destroy", "amhip_mosaic_set_stream",
     "amhip_mosaic_synchronize", "amhip_mosaic_reset", "amhip_mosaic_batch",
     "amhip_mosaic_batch_dev", "amhip_mosaic_update", "amhip_mosaic_update_dev",
@@ -249,6 +249,7 @@ def load():
     lib.amhip_ctx_dsm_gather_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.amhip_ctx_dsm_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                         C.POINTER(C.c_int32)]
+    lib.amhip_ctx_dsm_sort_pipeline.argtypes = [vp, C.POINTER(C.c_int32)]
     mp = C.POINTER(MosaicDesc)
     lib.amhip_mosaic_create.argtypes = [mp, cp, C.c_int, C.POINTER(vp)]
     lib.amhip_mosaic_destroy.argtypes = [vp]

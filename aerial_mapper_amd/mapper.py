@@ -234,7 +234,12 @@ class AerialGridMap(object):
     def dsm_stats(self):
         a, b, c = C.c_int64(), C.c_int64(), C.c_int32()
         L.check(self._lib.amhip_ctx_dsm_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return {"points_binned": a.value, "num_bins": b.value, "bin_cells": c.value}
+        s = C.c_int32()
+        L.check(self._lib.amhip_ctx_dsm_sort_pipeline(self._h, C.byref(s)))
+        # (which binning sort the last call took: None before the first call)
+        pipeline = {0: "one-level", 1: "count", 2: "runs"}.get(s.value)
+        return {"points_binned": a.value, "num_bins": b.value, "bin_cells": c.value,
+                "sort_pipeline": pipeline}
 
     def dsm_gather_stats(self):
         """amhip_ctx_dsm_gather_stats: where the gather tiles of the last DSM call went."""

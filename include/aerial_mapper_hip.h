@@ -828,6 +828,13 @@ const char* amhip_kernel_name(int kernel);
  * filter, number of bins, bin edge in cells. */
 int amhip_ctx_dsm_stats(amhip_ctx* ctx, int64_t* points_binned,
                         int64_t* num_bins, int32_t* bin_cells);
+/* Which binning sort the last amhip_dsm_process* / amhip_ortho_from_pcl_process* of the context took
+ * (host bookkeeping, no synchronisation): -1 none yet, 0 the one-level counting sort, 1 the
+ * three-pass sort with its count pass, 2 the three-pass sort on runs (tuning key sort_runs). */
+#define AMHIP_SORT_ONE_LEVEL 0
+#define AMHIP_SORT_COUNT 1
+#define AMHIP_SORT_RUNS 2
+int amhip_ctx_dsm_sort_pipeline(amhip_ctx* ctx, int32_t* pipeline);
 
 /* Where the gather tiles of the last amhip_dsm_process* went (synchronises): out8[0..6] = tiles
  * on the lists of the tiled gather -- [0] occupied class-0 tiles (sparse calls only), [1] / [2]
@@ -872,6 +879,9 @@ int amhip_session_layer_write_jpeg(amhip_session* s, int layer, int bgr, float l
  *                             forced at test size: image of n points / re-reading instead of registers
  *   no_launch_skips           launch every capacity-class / big-list kernel whatever the previous
  *                             call's counters say
+ *   sort_runs (1)             the three-pass sort without its count pass (local sorts, runs gathered)
+ *                             where the call is eligible: FP64 point pipeline, whole untiled context,
+ *                             at most 2^27 points; 0: the counting pipeline everywhere
  *   dsm_canon_all             every FP64 quotient goes through the order-independent double-double sums
  *   knn_global_bins           the optional k-cap mode on the plain global-bins kernel (default: LDS-tiled)
  *   dsm_no_rough_switch       the single-precision mode stays in its own pipeline on rough scenes

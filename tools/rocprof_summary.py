@@ -120,9 +120,10 @@ def main():
     if a.traffic_json and a.fetch and a.write:
         import json
         slot = lambda k: ("k_dsm_gather" if k.startswith("k_dsm_gather") else
-                          "k_dsm_p3_scatter" if k.startswith("k_dsm_p3_scatter") else
-                          "k_dsm_p3_place" if k.startswith("k_dsm_p3_place") else
-                          "k_dsm_p3_count" if k.startswith(("k_dsm_p3_count", "k_dsm_p3_reduce", "k_dsm_p3_scan")) else
+                          "k_dsm_p3_scatter" if k.startswith(("k_dsm_p3_scatter", "k_dsm_runs_sort")) else
+                          "k_dsm_p3_place" if k.startswith(("k_dsm_p3_place", "k_dsm_runs_place")) else
+                          "k_dsm_p3_count" if k.startswith(("k_dsm_p3_count", "k_dsm_p3_reduce", "k_dsm_p3_scan",
+                                                            "k_dsm_runs_scan", "k_dsm_runs_plan")) else
                           "k_ortho_backward" if k.startswith("k_ortho_backward") else k)
         fetch, write = pmc_rows(a.fetch, "FETCH_SIZE"), pmc_rows(a.write, "WRITE_SIZE")
         # one bench step = ONE launch of the sort's count pass and of the main gather instance;
