@@ -1,4 +1,4 @@
-// io::AerialMapperIO's text loaders over the C ABI
+// io::AerialMapperIO's text and image loaders over the C ABI
 // (see include/aerial-mapper-io/aerial-mapper-io.h).
 #include "aerial-mapper-io/aerial-mapper-io.h"
 
@@ -11,6 +11,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <memory>
+#include <string>
 #include <vector>
 
 #include "shim_common.h"
@@ -33,6 +35,8 @@ struct MappedFile {
     if (p == MAP_FAILED) return;
     data = static_cast<const char*>(p);
     size = static_cast<size_t>(st.st_size);
+    ::close(fd);   // (the mapping stays: loadImagesFromFile maps one file per pose, any number of them)
+    fd = -1;
   }
   ~MappedFile() {
     if (data) ::munmap(const_cast<char*>(data), size);
@@ -96,6 +100,58 @@ void AerialMapperIO::loadPointCloudFromFile(
     AlignedType<std::vector, Eigen::Vector3d>::type* point_cloud_xyz) {
   std::vector<int> intensities;
   loadPointCloudFromFile(filename_point_cloud, point_cloud_xyz, &intensities);
+}
+
+// aerial-mapper-io.cc:207-227: cv::imread(filename_base + std::to_string(i) + ".jpg") per pose
+void AerialMapperIO::loadImagesFromFileToDevice(const std::string& filename_base, size_t num_poses,
+                                                bool load_colored_images, uint8_t** dev_frames,
+                                                int* width, int* height, size_t* row_step,
+                                                size_t* frame_stride) {
+  if (!dev_frames || !width || !height || !row_step || !frame_stride)
+    amhip_shim::fatal("loadImagesFromFile", "CHECK(images)");
+  if (num_poses == 0) amhip_shim::fatal("loadImagesFromFile", "no poses: no images to load");
+  std::vector<std::unique_ptr<MappedFile> > mapped;
+  std::vector<const uint8_t*> files;
+  std::vector<size_t> lens;
+  for (size_t i = 0; i < num_poses; ++i) {
+    const std::string name = filename_base + std::to_string(i) + ".jpg";
+    mapped.emplace_back(new MappedFile(name));
+    if (!mapped.back()->data)
+      amhip_shim::fatal("loadImagesFromFile", ("cannot read " + name).c_str());
+    files.push_back(reinterpret_cast<const uint8_t*>(mapped.back()->data));
+    lens.push_back(mapped.back()->size);
+  }
+  amhip_shim::check_status(
+      amhip_io_decode_jpeg_frames(device_index(), files.data(), lens.data(), num_poses,
+                                  load_colored_images ? 1 : 0, dev_frames, width, height, row_step,
+                                  frame_stride),
+      "loadImagesFromFile");
+}
+
+void AerialMapperIO::loadImagesFromFile(const std::string& filename_base, size_t num_poses,
+                                        Images* images, bool load_colored_images) {
+  if (!images) amhip_shim::fatal("loadImagesFromFile", "CHECK(images)");
+  uint8_t* dev = nullptr;
+  int w = 0, h = 0;
+  size_t row_step = 0, frame_stride = 0;
+  loadImagesFromFileToDevice(filename_base, num_poses, load_colored_images, &dev, &w, &h, &row_step,
+                             &frame_stride);
+  const int ch = load_colored_images ? 3 : 1;
+  std::vector<uint8_t> host(num_poses * frame_stride);
+  amhip_shim::check_status(amhip_io_download_frames(dev, host.size(), host.data()), "loadImagesFromFile");
+  amhip_io_free(dev);
+  for (size_t i = 0; i < num_poses; ++i) {
+#if AERIAL_MAPPER_REAL_DEPS
+    cv::Mat image(h, w, load_colored_images ? CV_8UC3 : CV_8UC1);
+#else
+    cv::Mat image(h, w, ch);
+#endif
+    for (int y = 0; y < h; ++y)
+      std::memcpy(image.data + static_cast<size_t>(y) * image.step,
+                  host.data() + i * frame_stride + static_cast<size_t>(y) * row_step,
+                  static_cast<size_t>(w) * ch);
+    images->push_back(image);   // (the reference push_back()s: append)
+  }
 }
 
 void AerialMapperIO::loadPosesFromFileStandard(const std::string& filename, Poses* T_G_Bs) {

@@ -1,0 +1,592 @@
+// amhip_jpeg_decode.hip -- baseline JPEG frames, decoded on the GPU: what
+// io::AerialMapperIO::loadImagesFromFile (aerial-mapper-io.cc:207-227) gets from cv::imread, one
+// file per pose.  The bar is bit identity with libjpeg at its defaults (JDCT_ISLOW, fancy
+// upsampling); tests/jpeg_decode_reference.py restates every rule and is pinned to libjpeg's own
+// pixels (tests/golden/jpeg_decode/).  The header parser, the per-frame descriptor and the Huffman
+// decode tables are host code (amhip_jpeg_decode_host.h).
+//
+// Three kernels per group of frames, on the default stream; the statuses are read back once:
+//   1. k_jpegd_entropy  one wave per frame.  The walk through the scan (Huffman codes, 0xFF 0x00,
+//                       RSTn, DC prediction) is sequential and wave-uniform: every value it
+//                       branches on is broadcast from the first lane, so it runs on the scalar unit;
+//                       the lanes stage 1024 file bytes at a time into LDS (16 per lane, each load
+//                       checked against the scan's end), hold the frame's four Huffman tables there,
+//                       and flush every finished block as one 128-byte row of int16 coefficients in
+//                       natural order (lane k writes the coefficient of zigzag position k).  Blocks are stored plane by
+//                       plane, not in scan order.  Parallelism is across the frames of the call.
+//   2. k_jpegd_idct     jpeg_idct_islow, the mirror of k_jpeg_blocks: eight lanes per block, a lane
+//                       dequantises and transforms a column, the block goes through LDS, the same
+//                       lane transforms a row, adds 128 and clamps.  colored == 0: only Y blocks,
+//                       written straight into the cropped output frame.  Otherwise whole-block
+//                       component planes.
+//   3. k_jpegd_colour   one lane per output pixel: the upsampling rule the frame's sampling selects
+//                       (jdsample.c: fullsize, h2v1 fancy, h2v2 fancy, replication when the chroma
+//                       plane is at most 2 samples wide) and ycc_rgb_convert -> B, G, R.  A gray
+//                       file is replicated.
+//
+// Bounds: the walk decodes exactly the frame's blocks; a block takes one DC symbol and at most 63 AC
+// symbols (every AC symbol moves the coefficient index forward by at least one); a code takes at
+// most 16 - 8 steps of the maxcode loop; a refill takes at most 8 bytes.  No byte at or behind the
+// scan's end is loaded: they read as 0.  An undefined code, a run past coefficient 63, a wrong or
+// missing RSTn and a scan that ends early set the frame's status word and end the walk.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "amhip_common.h"
+#include "amhip_jpeg_decode_host.h"
+#include "amhip_tuning.h"
+
+namespace amhip {
+
+namespace {
+
+using jpegd::Frame;
+using jpegd::HuffTable;
+
+constexpr int kWindow = 1024;            // file bytes in LDS (16 per lane)
+constexpr int kIdctBlocks = 32;          // k_jpegd_idct: 256 lanes, 8 per block
+// MB of coefficients per group of frames (tuning knob jpegd_coef_budget_mb).  Groups run one after
+// another and each takes as long as its longest scan, so the default holds the demo flags' 249 frames
+// of 1920 x 1080 in one group (1.0 GB gray, 1.5 GB 4:2:0, planes half as much again).
+constexpr double kCoefBudgetMB = 4096.0;
+constexpr size_t kGroupFrames = 32768;   // (grid.y / grid.z of the per-frame launches)
+
+struct Zigzag {
+  uint8_t at[64];
+};
+constexpr Zigzag make_zigzag() {
+  Zigzag z = {};
+  for (int k = 0; k < 64; ++k) z.at[k] = jpeg::kZigzag[k];
+  return z;
+}
+__constant__ Zigzag d_zigzag = make_zigzag();
+
+__device__ __forceinline__ uint32_t uni(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// The bit reader of one frame (jpeg_fill_bit_buffer, jdhuff.c).  Everything in here is the same
+// in every lane.
+struct Reader {
+  const uint8_t* files;
+  uint8_t* win;        // LDS, kWindow bytes
+  uint64_t pos, end;   // next unread byte; the scan's end (EOI)
+  uint64_t wbase;      // file offset of win[0]
+  uint64_t acc;        // the low `nbits` bits are unread, MSB first
+  int nbits;
+  int fake;            // of those, zero bits fed behind a marker or the end (always the last ones)
+  uint32_t err;
+
+  __device__ __forceinline__ void stage(uint64_t at, int lane) {
+    __syncthreads();
+    wbase = at;
+#pragma unroll
+    for (int i = 0; i < kWindow / 64; ++i) {
+      const uint64_t q = at + (uint64_t)(lane + 64 * i);
+      win[lane + 64 * i] = q < end ? files[q] : (uint8_t)0;   // (never a byte at or behind `end`)
+    }
+    __syncthreads();
+  }
+
+  // at least 32 unread bits behind this (a code takes at most 16, a value at most 15)
+  __device__ __forceinline__ void fill(int lane) {
+    while (nbits <= 56) {   // (at most 8 rounds)
+      uint32_t b = 0;
+      if (pos >= end) {
+        fake += 8;
+      } else {
+        if (pos < wbase || pos + 2 > wbase + kWindow) stage(pos, lane);
+        b = uni(win[pos - wbase]);
+        if (b == 0xFF) {
+          const uint32_t b2 = pos + 1 < end ? uni(win[pos + 1 - wbase]) : 0xD9u;
+          if (b2 == 0) {
+            pos += 2;   // 0xFF 0x00 is one data byte
+          } else {
+            b = 0;      // a marker: it stays where it is, zero bits are fed
+            fake += 8;
+          }
+        } else {
+          pos += 1;
+        }
+      }
+      acc = (acc << 8) | b;
+      nbits += 8;
+    }
+  }
+  __device__ __forceinline__ uint32_t peek(int n) const {
+    return (uint32_t)(acc >> (nbits - n)) & ((1u << n) - 1u);
+  }
+  __device__ __forceinline__ void drop(int n) {
+    nbits -= n;
+    if (nbits < fake) err = jpegd::kEndsEarly;
+  }
+  // jpeg_huff_decode: the lookahead table, then the maxcode loop for codes longer than 8 bits
+  __device__ __forceinline__ uint32_t symbol(const HuffTable* t) {
+    const uint32_t e = uni(t->look[peek(jpegd::kLookahead)]);
+    if (e) {
+      drop((int)(e >> 8));
+      return e & 255u;
+    }
+    int l = jpegd::kLookahead + 1;
+    while (l <= 16 && (int32_t)peek(l) > (int32_t)uni((uint32_t)t->maxcode[l])) ++l;   // (at most 8 rounds)
+    if (l > 16) {
+      err = jpegd::kBadCode;
+      return 0;
+    }
+    const uint32_t code = peek(l);
+    drop(l);
+    return uni(t->huffval[(code + (uint32_t)uni((uint32_t)t->valoffset[l])) & 255u]);
+  }
+  // HUFF_EXTEND: a value below 2^(s-1) is negative
+  __device__ __forceinline__ int32_t receive_extend(int s) {
+    const int32_t v = (int32_t)peek(s);
+    drop(s);
+    return v < (1 << (s - 1)) ? v - ((1 << s) - 1) : v;
+  }
+};
+
+__global__ __launch_bounds__(64) void k_jpegd_entropy(const uint8_t* __restrict__ files,
+                                                      const Frame* __restrict__ frames, size_t first_frame,
+                                                      int16_t* __restrict__ coef, uint32_t* __restrict__ status) {
+  __shared__ HuffTable tbl[4];   // dc 0, dc 1, ac 0, ac 1
+  __shared__ uint8_t win[kWindow];
+  __shared__ int16_t blk[64];
+  const int lane = threadIdx.x;
+  const int natural = d_zigzag.at[lane];   // jpeg_natural_order of this lane's zigzag position
+  const size_t fi = first_frame + blockIdx.x;
+  const Frame* f = frames + fi;
+  {
+    static_assert(sizeof(HuffTable) % 4 == 0 && offsetof(Frame, dc) % 4 == 0, "tables are copied by words");
+    static_assert(offsetof(Frame, ac) == offsetof(Frame, dc) + 2 * sizeof(HuffTable), "dc and ac are adjacent");
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(f->dc);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(tbl);
+    for (int i = lane; i < (int)(4 * sizeof(HuffTable) / 4); i += 64) dst[i] = src[i];
+    blk[lane] = 0;
+  }
+  const int ncomp = (int)uni((uint32_t)f->ncomp);
+  const uint32_t mcux = uni((uint32_t)f->mcux), mcuy = uni((uint32_t)f->mcuy);
+  const uint32_t restart = uni((uint32_t)f->restart);
+  const uint64_t coef_base = f->coef_base;
+  Reader r;
+  r.files = files;
+  r.win = win;
+  r.pos = f->scan_begin;
+  r.end = f->scan_end;
+  r.acc = 0;
+  r.nbits = 0;
+  r.fake = 0;
+  r.err = 0;
+  r.stage(r.pos, lane);   // (its barriers cover the tables too)
+
+  uint32_t pred[3] = {0, 0, 0};   // (wraps instead of overflowing on a corrupt file)
+  uint32_t todo = restart, next_rst = 0;
+  uint32_t mx = 0, my = 0;
+  const uint32_t nmcu = mcux * mcuy;
+  for (uint32_t mcu = 0; mcu < nmcu && !r.err; ++mcu) {
+    if (restart) {
+      if (todo == 0) {
+        // process_restart: the bits left of the byte are dropped, the next two bytes must be the
+        // expected RSTn, the predictors go back to 0
+        r.acc = 0;
+        r.nbits = 0;
+        r.fake = 0;
+        bool ok = r.pos + 1 < r.end;
+        if (ok) {
+          if (r.pos < r.wbase || r.pos + 2 > r.wbase + kWindow) r.stage(r.pos, lane);
+          ok = uni(win[r.pos - r.wbase]) == 0xFFu && uni(win[r.pos + 1 - r.wbase]) == 0xD0u + next_rst;
+        }
+        if (!ok) {
+          r.err = jpegd::kBadRestart;
+          break;
+        }
+        r.pos += 2;
+        next_rst = (next_rst + 1) & 7u;
+        pred[0] = pred[1] = pred[2] = 0;
+        todo = restart;
+      }
+      --todo;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (c >= ncomp) break;
+      const uint32_t ch = uni((uint32_t)f->comp_h[c]), cv = uni((uint32_t)f->comp_v[c]);
+      const uint32_t bw = uni((uint32_t)f->comp_bw[c]);
+      const HuffTable* dc = &tbl[uni((uint32_t)f->td[c]) & 1u];
+      const HuffTable* ac = &tbl[2 + (uni((uint32_t)f->ta[c]) & 1u)];
+      const uint32_t nb = ch * cv;   // (1, 2 or 4)
+      for (uint32_t k4 = 0; k4 < nb && !r.err; ++k4) {
+        const uint32_t bx = k4 % ch, by = k4 / ch;
+        r.fill(lane);
+        const uint32_t s = r.symbol(dc) & 15u;
+        if (s) pred[c] += (uint32_t)r.receive_extend((int)s);
+        if (lane == 0) blk[0] = (int16_t)pred[c];
+        int k = 1;
+        while (k < 64 && !r.err) {   // (every round moves k forward: at most 63)
+          r.fill(lane);
+          const uint32_t rs = r.symbol(ac);
+          const int run = (int)(rs >> 4), size = (int)(rs & 15u);
+          if (size == 0) {
+            if (run != 15) break;   // EOB
+            k += 16;                // ZRL
+            continue;
+          }
+          k += run;
+          if (k > 63) {
+            r.err = jpegd::kRunPast63;
+            break;
+          }
+          const int32_t v = r.receive_extend(size);
+          if (lane == 0) blk[k] = (int16_t)v;   // (zigzag position: the flush puts it in its place)
+          ++k;
+        }
+        // the finished block: one 128-byte row, lane k writes the coefficient of zigzag position k
+        const uint64_t b = coef_base + f->comp_base[c] + (uint64_t)(my * cv + by) * bw + (mx * ch + bx);
+        __syncthreads();
+        coef[b * 64 + natural] = blk[lane];
+        blk[lane] = 0;
+        __syncthreads();
+      }
+      if (r.err) break;
+    }
+    if (++mx == mcux) {
+      mx = 0;
+      ++my;
+    }
+  }
+  if (!r.err && r.pos != r.end) r.err = jpegd::kBytesLeft;
+  if (lane == 0) status[fi] = r.err;
+}
+
+// jpeg_idct_islow's constants (jidctint.c): CONST_BITS = 13, PASS1_BITS = 2
+constexpr int kConstBits = 13, kPass1Bits = 2;
+constexpr int64_t F_0_298 = 2446, F_0_390 = 3196, F_0_541 = 4433, F_0_765 = 6270, F_0_899 = 7373,
+                  F_1_175 = 9633, F_1_501 = 12299, F_1_847 = 15137, F_1_961 = 16069, F_2_053 = 16819,
+                  F_2_562 = 20995, F_3_072 = 25172;
+
+// one pass of jpeg_idct_islow over d[0..7]; DESCALE by `shift` (rounding half up).  64-bit like the
+// C code's JLONG, so that coefficients no real encoder writes cannot overflow.
+__device__ __forceinline__ void idct_1d(int64_t d[8], int shift) {
+  int64_t z1 = (d[2] + d[6]) * F_0_541;
+  const int64_t tmp2 = z1 + d[6] * (-F_1_847);
+  const int64_t tmp3 = z1 + d[2] * F_0_765;
+  const int64_t tmp0 = (d[0] + d[4]) * ((int64_t)1 << kConstBits);
+  const int64_t tmp1 = (d[0] - d[4]) * ((int64_t)1 << kConstBits);
+  const int64_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  int64_t t0 = d[7], t1 = d[5], t2 = d[3], t3 = d[1];
+  z1 = t0 + t3;
+  int64_t z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
+  const int64_t z5 = (z3 + z4) * F_1_175;
+  t0 *= F_0_298;
+  t1 *= F_2_053;
+  t2 *= F_3_072;
+  t3 *= F_1_501;
+  z1 *= -F_0_899;
+  z2 *= -F_2_562;
+  z3 *= -F_1_961;
+  z4 *= -F_0_390;
+  z3 += z5;
+  z4 += z5;
+  t0 += z1 + z3;
+  t1 += z2 + z4;
+  t2 += z2 + z3;
+  t3 += z1 + z4;
+  const int64_t half = (int64_t)1 << (shift - 1);
+  d[0] = (tmp10 + t3 + half) >> shift;
+  d[7] = (tmp10 - t3 + half) >> shift;
+  d[1] = (tmp11 + t2 + half) >> shift;
+  d[6] = (tmp11 - t2 + half) >> shift;
+  d[2] = (tmp12 + t1 + half) >> shift;
+  d[5] = (tmp12 - t1 + half) >> shift;
+  d[3] = (tmp13 + t0 + half) >> shift;
+  d[4] = (tmp13 - t0 + half) >> shift;
+}
+
+__global__ __launch_bounds__(256) void k_jpegd_idct(const Frame* __restrict__ frames, size_t first_frame,
+                                                    const int16_t* __restrict__ coef,
+                                                    uint8_t* __restrict__ planes, uint8_t* __restrict__ out,
+                                                    size_t frame_stride, size_t row_step, int colored) {
+  __shared__ int32_t tile[kIdctBlocks][64 + 8];   // (+8: rows of neighbouring blocks on other banks)
+  const size_t fi = first_frame + blockIdx.y;
+  const Frame* f = frames + fi;
+  const int slot = threadIdx.x >> 3, j = threadIdx.x & 7;
+  const uint32_t b = blockIdx.x * kIdctBlocks + slot;
+  const uint32_t nblocks = colored ? f->comp_base[f->ncomp] : f->comp_base[1];
+  const bool live = b < nblocks;
+  int c = 0;
+  if (live) c = b >= f->comp_base[2] && f->ncomp == 3 ? 2 : (b >= f->comp_base[1] ? 1 : 0);
+  int64_t d[8];
+  if (live) {
+    // columns: lane j holds column j, dequantised
+    const int16_t* src = coef + (f->coef_base + b) * 64;
+    const uint16_t* q = f->quant[c];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) d[r] = (int64_t)((int32_t)src[r * 8 + j] * (int32_t)q[r * 8 + j]);
+    idct_1d(d, kConstBits - kPass1Bits);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) tile[slot][r * 8 + j] = (int32_t)d[r];
+  }
+  __syncthreads();
+  if (!live) return;
+  // rows: lane j holds row j
+#pragma unroll
+  for (int i = 0; i < 8; ++i) d[i] = tile[slot][j * 8 + i];
+  idct_1d(d, kConstBits + kPass1Bits + 3);
+  uint8_t px[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int64_t v = d[i] + 128;
+    px[i] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+  }
+  const uint32_t local = b - f->comp_base[c];
+  const uint32_t bw = (uint32_t)f->comp_bw[c];
+  const uint32_t by = local / bw, bx = local % bw;
+  if (!colored) {
+    const uint32_t y = by * 8 + j;
+    if (y >= (uint32_t)f->height) return;
+    uint8_t* dst = out + fi * frame_stride + (size_t)y * row_step;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint32_t x = bx * 8 + i;
+      if (x < (uint32_t)f->width) dst[x] = px[i];
+    }
+  } else {
+    // whole blocks: the plane is bw * 8 wide and comp_bh * 8 high
+    uint8_t* dst = planes + f->plane_base + (size_t)f->comp_base[c] * 64 +
+                   ((size_t)by * 8 + j) * ((size_t)bw * 8) + (size_t)bx * 8;
+    uint2 w;
+    w.x = px[0] | (px[1] << 8) | (px[2] << 16) | ((uint32_t)px[3] << 24);
+    w.y = px[4] | (px[5] << 8) | (px[6] << 16) | ((uint32_t)px[7] << 24);
+    *reinterpret_cast<uint2*>(dst) = w;
+  }
+}
+
+// one chroma sample at output pixel (x, y) (jdsample.c).  p: the component's plane, pw bytes per
+// row; dw x dh: its real samples (the rest of the plane is block padding).
+__device__ __forceinline__ int upsampled(const uint8_t* p, size_t pw, int dw, int dh, int hmax, int vmax,
+                                         int x, int y) {
+  if (hmax == 1) return p[(size_t)y * pw + x];   // fullsize_upsample
+  const int k = x >> 1;
+  if (dw <= 2) return p[(size_t)(vmax == 2 ? y >> 1 : y) * pw + k];   // h2v1_upsample / h2v2_upsample
+  if (vmax == 1) {
+    // h2v1_fancy_upsample
+    const uint8_t* row = p + (size_t)y * pw;
+    const int a = row[k];
+    if (x & 1) return k == dw - 1 ? a : (3 * a + row[k + 1] + 2) >> 2;
+    return k == 0 ? a : (3 * a + row[k - 1] + 1) >> 2;
+  }
+  // h2v2_fancy_upsample: the nearer row 3 : 1 the other; the first and the last real row are their
+  // own neighbours
+  const int r = y >> 1;
+  int nb = (y & 1) ? r + 1 : r - 1;
+  nb = nb < 0 ? 0 : nb > dh - 1 ? dh - 1 : nb;
+  const uint8_t* r0 = p + (size_t)r * pw;
+  const uint8_t* r1 = p + (size_t)nb * pw;
+  const int cs = 3 * r0[k] + r1[k];
+  if (x & 1) return k == dw - 1 ? (4 * cs + 7) >> 4 : (3 * cs + 3 * r0[k + 1] + r1[k + 1] + 7) >> 4;
+  return k == 0 ? (4 * cs + 8) >> 4 : (3 * cs + 3 * r0[k - 1] + r1[k - 1] + 8) >> 4;
+}
+
+__device__ __forceinline__ uint8_t clamp8(int v) {
+  return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+}
+
+__global__ __launch_bounds__(256) void k_jpegd_colour(const Frame* __restrict__ frames, size_t first_frame,
+                                                      const uint8_t* __restrict__ planes,
+                                                      uint8_t* __restrict__ out, size_t frame_stride,
+                                                      size_t row_step) {
+  const size_t fi = first_frame + blockIdx.z;
+  const Frame* f = frames + fi;
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= f->width || y >= f->height) return;
+  const uint8_t* base = planes + f->plane_base;
+  const size_t pw0 = (size_t)f->comp_bw[0] * 8;
+  const int Y = base[(size_t)y * pw0 + x];
+  uint8_t* dst = out + fi * frame_stride + (size_t)y * row_step + 3 * (size_t)x;
+  if (f->ncomp == 1) {
+    dst[0] = dst[1] = dst[2] = (uint8_t)Y;
+    return;
+  }
+  const int hmax = f->hmax, vmax = f->vmax;
+  const int dw = (f->width + hmax - 1) / hmax, dh = (f->height + vmax - 1) / vmax;
+  const size_t pw1 = (size_t)f->comp_bw[1] * 8;
+  const int cb = upsampled(base + (size_t)f->comp_base[1] * 64, pw1, dw, dh, hmax, vmax, x, y) - 128;
+  const int cr = upsampled(base + (size_t)f->comp_base[2] * 64, pw1, dw, dh, hmax, vmax, x, y) - 128;
+  // ycc_rgb_convert (jdcolor.c): FIX(1.40200), FIX(1.77200), FIX(0.34414), FIX(0.71414); >> is arithmetic
+  const int R = Y + ((91881 * cr + 32768) >> 16);
+  const int B = Y + ((116130 * cb + 32768) >> 16);
+  const int G = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
+  dst[0] = clamp8(B);
+  dst[1] = clamp8(G);
+  dst[2] = clamp8(R);
+}
+
+struct DevBuf {
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  int alloc(size_t bytes) {
+    AMHIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
+    return AMHIP_OK;
+  }
+  template <typename T>
+  T* as() {
+    return static_cast<T*>(p);
+  }
+  void* release() {
+    void* q = p;
+    p = nullptr;
+    return q;
+  }
+};
+
+int fail_arg(const std::string& msg) {
+  set_last_error("amhip_io_decode_jpeg_frames: " + msg);
+  return AMHIP_ERR_ARG;
+}
+
+}  // namespace
+
+int io_decode_jpeg_frames(int device, const uint8_t* const* files, const size_t* lens, size_t F, int colored,
+                          uint8_t** dev_frames, int* width, int* height, size_t* row_step,
+                          size_t* frame_stride) {
+  // ---- everything the host can see, before any device is touched ---------------------------
+  std::vector<Frame> frames(F);
+  std::vector<size_t> file_at(F);
+  size_t total = 0;
+  char text[160];
+  for (size_t i = 0; i < F; ++i) {
+    if (!files[i]) return fail_arg("frame " + std::to_string(i) + ": null file");
+    if (!jpegd::parse(files[i], lens[i], &frames[i], text, sizeof(text)))
+      return fail_arg("frame " + std::to_string(i) + ": " + text);
+    if (frames[i].width != frames[0].width || frames[i].height != frames[0].height)
+      return fail_arg("frame " + std::to_string(i) + " is " + std::to_string(frames[i].width) + " x " +
+                      std::to_string(frames[i].height) + ", frame 0 is " + std::to_string(frames[0].width) +
+                      " x " + std::to_string(frames[0].height));
+    file_at[i] = total;
+    frames[i].scan_begin += total;
+    frames[i].scan_end += total;
+    total += lens[i];
+  }
+  const int W = frames[0].width, H = frames[0].height, ch = colored ? 3 : 1;
+  // groups of consecutive frames whose coefficients fit the budget (at least one frame each)
+  std::vector<size_t> group_begin;
+  const double budget_mb = tuning("jpegd_coef_budget_mb", kCoefBudgetMB);
+  const size_t budget = (size_t)((budget_mb >= 0.0 && budget_mb <= 1048576.0 ? budget_mb : kCoefBudgetMB) * 1048576.0);
+  size_t max_blocks = 0, max_idct = 0;
+  {
+    size_t blocks = 0, count = 0;
+    for (size_t i = 0; i < F; ++i) {
+      const size_t nb = frames[i].comp_base[frames[i].ncomp];
+      if (i == 0 || (blocks + nb) * 128 > budget || count == kGroupFrames) {
+        group_begin.push_back(i);
+        blocks = 0;
+        count = 0;
+      }
+      frames[i].coef_base = blocks;
+      frames[i].plane_base = blocks * 64;
+      blocks += nb;
+      ++count;
+      max_blocks = std::max(max_blocks, blocks);
+      max_idct = std::max(max_idct, (size_t)(colored ? nb : frames[i].comp_base[1]));
+    }
+    group_begin.push_back(F);
+  }
+  // ---- the device ----------------------------------------------------------------------------
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    set_last_error("no HIP device available (libaerial_mapper_hip has no CPU fallback)");
+    return AMHIP_ERR_NO_DEVICE;
+  }
+  if (device < 0 || device >= ndev) return fail_arg("bad device index");
+  AMHIP_TRY(hipSetDevice(device));
+  hipStream_t stream = nullptr;   // the default stream: this entry point is synchronous
+  const size_t rstep = (size_t)W * ch, fstride = rstep * (size_t)H;
+  DevBuf bytes, desc, coef, planes, status, out;
+  int rc;
+  if ((rc = bytes.alloc(total))) return rc;
+  if ((rc = desc.alloc(F * sizeof(Frame)))) return rc;
+  if ((rc = coef.alloc(max_blocks * 128))) return rc;
+  if (colored && (rc = planes.alloc(max_blocks * 64))) return rc;
+  if ((rc = status.alloc(F * sizeof(uint32_t)))) return rc;
+  if ((rc = out.alloc(F * fstride))) return rc;
+  for (size_t i = 0; i < F; ++i)
+    AMHIP_TRY(hipMemcpyAsync(bytes.as<uint8_t>() + file_at[i], files[i], lens[i], hipMemcpyHostToDevice, stream));
+  AMHIP_TRY(hipMemcpyAsync(desc.p, frames.data(), F * sizeof(Frame), hipMemcpyHostToDevice, stream));
+  AMHIP_TRY(hipMemsetAsync(status.p, 0, F * sizeof(uint32_t), stream));
+  const Frame* dframes = desc.as<Frame>();
+  for (size_t g = 0; g + 1 < group_begin.size(); ++g) {
+    const size_t first = group_begin[g], n = group_begin[g + 1] - first;
+    hipLaunchKernelGGL(k_jpegd_entropy, dim3((unsigned)n), dim3(64), 0, stream, bytes.as<uint8_t>(), dframes,
+                       first, coef.as<int16_t>(), status.as<uint32_t>());
+    hipLaunchKernelGGL(k_jpegd_idct, dim3((unsigned)((max_idct + kIdctBlocks - 1) / kIdctBlocks), (unsigned)n),
+                       dim3(256), 0, stream, dframes, first, coef.as<int16_t>(), planes.as<uint8_t>(),
+                       out.as<uint8_t>(), fstride, rstep, colored ? 1 : 0);
+    if (colored)
+      hipLaunchKernelGGL(k_jpegd_colour, dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)n), dim3(256),
+                         0, stream, dframes, first, planes.as<uint8_t>(), out.as<uint8_t>(), fstride, rstep);
+    AMHIP_TRY(hipGetLastError());
+  }
+  std::vector<uint32_t> st(F);
+  AMHIP_TRY(hipMemcpyAsync(st.data(), status.p, F * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  AMHIP_TRY(hipStreamSynchronize(stream));
+  for (size_t i = 0; i < F; ++i)
+    if (st[i]) return fail_arg("frame " + std::to_string(i) + ": " + jpegd::status_text(st[i]));
+  *dev_frames = static_cast<uint8_t*>(out.release());
+  *width = W;
+  *height = H;
+  *row_step = rstep;
+  *frame_stride = fstride;
+  return AMHIP_OK;
+}
+
+}  // namespace amhip
+
+extern "C" {
+
+int amhip_jpeg_info(const uint8_t* file, size_t len, int* width, int* height, int* channels) {
+  if (!file || !width || !height || !channels) {
+    amhip::set_last_error("amhip_jpeg_info: null argument");
+    return AMHIP_ERR_ARG;
+  }
+  amhip::jpegd::Frame f;
+  char text[160];
+  if (!amhip::jpegd::parse(file, len, &f, text, sizeof(text))) {
+    amhip::set_last_error(std::string("amhip_jpeg_info: ") + text);
+    return AMHIP_ERR_ARG;
+  }
+  *width = f.width;
+  *height = f.height;
+  *channels = f.ncomp;
+  return AMHIP_OK;
+}
+
+int amhip_io_decode_jpeg_frames(int device, const uint8_t* const* files, const size_t* lens, size_t F, int colored,
+                                uint8_t** dev_frames, int* width, int* height, size_t* row_step,
+                                size_t* frame_stride) {
+  if (dev_frames) *dev_frames = nullptr;
+  if (!files || !lens || !dev_frames || !width || !height || !row_step || !frame_stride) {
+    amhip::set_last_error("amhip_io_decode_jpeg_frames: null argument");
+    return AMHIP_ERR_ARG;
+  }
+  if (F == 0) {
+    amhip::set_last_error("amhip_io_decode_jpeg_frames: no frames (F = 0)");
+    return AMHIP_ERR_ARG;
+  }
+  return amhip::io_decode_jpeg_frames(device, files, lens, F, colored, dev_frames, width, height, row_step,
+                                      frame_stride);
+}
+
+int amhip_io_download_frames(const uint8_t* dev_frames, size_t num_bytes, uint8_t* host_frames) {
+  if (num_bytes == 0) return AMHIP_OK;
+  if (!dev_frames || !host_frames) {
+    amhip::set_last_error("amhip_io_download_frames: null argument");
+    return AMHIP_ERR_ARG;
+  }
+  AMHIP_TRY(hipMemcpy(host_frames, dev_frames, num_bytes, hipMemcpyDeviceToHost));
+  return AMHIP_OK;
+}
+
+}  // extern "C"

@@ -70,6 +70,7 @@ EXPORTS = [
     "amhip_stereo_add_frames_dev", "amhip_stereo_cloud", "amhip_stereo_point_cloud2_dev",
     "amhip_jpeg_bound", "amhip_jpeg_encode_dev", "amhip_jpeg_write", "amhip_layer_write_jpeg",
     "amhip_session_layer_write_jpeg", "amhip_mosaic_encode_jpeg_dev", "amhip_mosaic_write_jpeg",
+    "amhip_jpeg_info", "amhip_io_decode_jpeg_frames", "amhip_io_download_frames",
 ]
 
 
@@ -301,6 +302,11 @@ def load():
                                                    C.c_char_p]
     lib.amhip_mosaic_encode_jpeg_dev.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.amhip_mosaic_write_jpeg.argtypes = [vp, C.c_int, C.c_char_p]
+    lib.amhip_jpeg_info.argtypes = [C.c_char_p, C.c_size_t] + [C.POINTER(C.c_int)] * 3
+    lib.amhip_io_decode_jpeg_frames.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                                C.c_int, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    lib.amhip_io_download_frames.argtypes = [vp, C.c_size_t, vp]
     del u8p
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:

@@ -1,8 +1,11 @@
-"""io::AerialMapperIO's text formats (aerial-mapper-io.cc:103-121,309-347).
+"""io::AerialMapperIO's loaders (aerial-mapper-io.cc:103-121,207-227,309-347).
 
 `load_point_cloud_text` tokenises and parses the `x y z intensity` file on the
 GPU (amhip_io.hip) and leaves the cloud in HBM, ready for Dsm.process /
-OrthoFromPcl.process; `load_poses_text` reads the small pose file on the host.
+OrthoFromPcl.process; `load_poses_text` reads the small pose file on the host;
+`load_images` / `decode_jpeg_frames` decode the frames' JPEG files on the GPU
+(amhip_jpeg_decode.hip) and leave them in HBM as one stack, ready for
+OrthoBackwardGrid.process, OrthoForwardHomography.batch and Stereo.add_frames.
 """
 import ctypes as C
 import mmap
@@ -111,3 +114,80 @@ def load_poses_text(filename):
     if n == 0:
         raise L.AmhipError(L.ERR_ARG, "No poses loaded.")
     return np.asarray(vals[:7 * n], np.float64).reshape(n, 7)
+
+
+class DeviceFrames(object):
+    """A stack of decoded frames resident in HBM: .frames is a torch CUDA uint8 tensor (F, H, W)
+    or (F, H, W, 3) (B, G, R) sharing the library's allocation."""
+
+    def __init__(self, ptr, num_frames, width, height, channels, row_step, frame_stride, device):
+        self._ptr = ptr
+        self.num_frames, self.width, self.height, self.channels = int(num_frames), int(width), int(height), int(channels)
+        self.row_step, self.frame_stride = int(row_step), int(frame_stride)
+        self.device = device
+
+    @property
+    def frames(self):
+        import torch
+
+        class _Holder(object):
+            pass
+
+        shape = (self.num_frames, self.height, self.width) + ((3,) if self.channels == 3 else ())
+        strides = (self.frame_stride, self.row_step) + ((3, 1) if self.channels == 3 else (1,))
+        h = _Holder()
+        h.__cuda_array_interface__ = {"shape": shape, "typestr": "|u1", "strides": strides,
+                                      "data": (int(self._ptr), False), "version": 2}
+        h._keepalive = self
+        return torch.as_tensor(h, device="cuda:%d" % self.device)
+
+    def to_host(self):
+        """-> numpy uint8 (F, H, W) or (F, H, W, 3)"""
+        shape = (self.num_frames, self.height, self.width) + ((3,) if self.channels == 3 else ())
+        out = np.empty((self.num_frames, self.frame_stride), np.uint8)
+        if out.size:
+            L.check(L.load().amhip_io_download_frames(C.c_void_p(self._ptr), out.size, C.c_void_p(out.ctypes.data)))
+        rows = out[:, :self.height * self.row_step].reshape(self.num_frames, self.height, self.row_step)
+        return np.ascontiguousarray(rows[:, :, :self.width * self.channels]).reshape(shape)
+
+    def close(self):
+        if L is None or not getattr(self, "_ptr", None):
+            return        # (nothing to free, or the interpreter is shutting down)
+        L.load().amhip_io_free(C.c_void_p(self._ptr))
+        self._ptr = None
+
+    __del__ = close
+
+
+def jpeg_info(data):
+    """-> (width, height, channels) of a JPEG file's bytes; raises for a file the decoder refuses."""
+    data = bytes(data)
+    w, h, ch = C.c_int(), C.c_int(), C.c_int()
+    L.check(L.load().amhip_jpeg_info(data, len(data), C.byref(w), C.byref(h), C.byref(ch)))
+    return w.value, h.value, ch.value
+
+
+def decode_jpeg_frames(files, colored=False, device=0):
+    """files: list of bytes, each one baseline JPEG file of the same width and height -> DeviceFrames
+    (colored=False: 8UC1, of a colour file its Y plane; colored=True: 8UC3 B, G, R)."""
+    lib = L.load()
+    files = [f if isinstance(f, bytes) else bytes(f) for f in files]
+    n = len(files)
+    ptrs = (C.c_char_p * max(n, 1))(*files)
+    lens = (C.c_size_t * max(n, 1))(*[len(f) for f in files])
+    out = C.c_void_p()
+    w, h = C.c_int(), C.c_int()
+    row, stride = C.c_size_t(), C.c_size_t()
+    L.check(lib.amhip_io_decode_jpeg_frames(int(device), ptrs, lens, n, 1 if colored else 0, C.byref(out),
+                                            C.byref(w), C.byref(h), C.byref(row), C.byref(stride)))
+    return DeviceFrames(out.value, n, w.value, h.value, 3 if colored else 1, row.value, stride.value, int(device))
+
+
+def load_images(filename_base, num_poses, colored=False, device=0):
+    """io::AerialMapperIO::loadImagesFromFile: reads <filename_base><i>.jpg, i = 0..num_poses-1, and
+    decodes them on the GPU -> DeviceFrames.  A missing or refused file raises."""
+    files = []
+    for i in range(int(num_poses)):
+        with open("%s%d.jpg" % (filename_base, i), "rb") as f:
+            files.append(f.read())
+    return decode_jpeg_frames(files, colored, device)

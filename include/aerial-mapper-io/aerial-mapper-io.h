@@ -7,8 +7,11 @@
 //   subtractOriginFromPoses.
 //   toGeoTiff / writeDataToDEMGeoTiffColor (:349-509) -- the same files without
 //     GDAL (amhip_geotiff_write_u8: baseline TIFF + GeoTIFF tags).
-// The image / camera-rig loaders (OpenCV imread, aslam YAML) and the format
-// converters stay the reference's.
+//   loadImagesFromFile (:207-227) -- the cv::imread("<prefix><i>.jpg") per pose as one
+//     batched baseline JPEG decoder on the GPU (amhip_io_decode_jpeg_frames): the pixels
+//     libjpeg gives at its defaults; EXIF orientation is not applied; no imshow.
+// The .png overload of the image loader, the camera-rig loader (aslam YAML) and the
+// format converters stay the reference's.
 #ifndef AERIAL_MAPPER_HIP_IO_TYPES_H_
 #define AERIAL_MAPPER_HIP_IO_TYPES_H_
 
@@ -43,6 +46,11 @@ class AerialMapperIO {
 
   void subtractOriginFromPoses(const Eigen::Vector3d& origin, Poses* T_G_Bs);
 
+  // <filename_base><i>.jpg, i = 0 .. num_poses - 1, decoded on the GPU and appended to *images
+  // (8UC1, or 8UC3 B, G, R).  A missing or undecodable file is fatal.
+  void loadImagesFromFile(const std::string& filename_base, size_t num_poses, Images* images,
+                          bool load_colored_images = false);
+
   void writeDataToDEMGeoTiffColor(const cv::Mat& ortho_image, const Eigen::Vector2d& xy,
                                   const std::string& geotiff_filename);
 
@@ -54,6 +62,13 @@ class AerialMapperIO {
   // release both with amhip_io_free().
   void loadPointCloudFromFileToDevice(const std::string& filename_point_cloud, double** dev_xyz,
                                       int32_t** dev_intensities, size_t* num_points);
+
+  // --- extension: keep the decoded frames in HBM as one stack (frame f at *dev_frames + f *
+  // *frame_stride, rows *row_step bytes apart: the layout amhip_ortho_backward_process_dev,
+  // amhip_mosaic_batch_dev and amhip_stereo_add_frames_dev take); release with amhip_io_free().
+  void loadImagesFromFileToDevice(const std::string& filename_base, size_t num_poses,
+                                  bool load_colored_images, uint8_t** dev_frames, int* width, int* height,
+                                  size_t* row_step, size_t* frame_stride);
 
   // --- extension: the same cloud as a binary file (amhip_io_write_point_cloud_binary) and its
   // loader, staged through pinned buffers straight into HBM.

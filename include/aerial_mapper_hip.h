@@ -440,6 +440,36 @@ int amhip_io_download_point_cloud(const double* dev_xyz, const int32_t* dev_inte
                                   size_t n, double* host_xyz, int32_t* host_intensities);
 int amhip_io_free(void* dev_ptr);
 
+/* ---- io::AerialMapperIO::loadImagesFromFile (aerial-mapper-io.cc:207-227): the frames' JPEG files,
+ *      decoded on the GPU ------------------------------------------------------------------------
+ * What cv::imread gives through libjpeg at its defaults (JDCT_ISLOW, fancy upsampling), bit for bit
+ * libjpeg-turbo's pixels (tests/golden/jpeg_decode/); parity with OpenCV itself is adopted, unpinned,
+ * and EXIF orientation is not applied.  Accepted: baseline sequential DCT (SOF0), 8 bit, Huffman, one
+ * scan; one component, or Y Cb Cr with Y sampled 1x1, 2x1 or 2x2 and chroma 1x1; 8-bit quantisation
+ * tables; Huffman table ids 0 and 1 of any content; optional DRI; APPn / COM skipped; width and
+ * height 1..65535.  Everything else (progressive, arithmetic, 12 bit, 4 components, other sampling
+ * factors, 16-bit DQT, several scans, Adobe transform 0 or component ids R G B, missing tables, no
+ * SOI / SOS / EOI) is AMHIP_ERR_ARG with a text naming the marker or field, reported before any
+ * device is touched.  A scan that does not decode (undefined code, run past coefficient 63, wrong or
+ * missing RSTn, early end) is found on the device: AMHIP_ERR_ARG naming the frame, *dev_frames = NULL.
+ * The scan ends at the first EOI behind it; whatever follows that EOI (thumbnails, padding, a second image) is
+ * ignored, as libjpeg ignores it.  Stricter than libjpeg, which only warns: 0xFF fill bytes in front of an RSTn
+ * marker, and bytes left between the last block and EOI, are errors here.  Scratch is bounded by decoding in groups
+ * of frames (tuning key jpegd_coef_budget_mb). */
+/* host only: parses up to SOS, applies every rule above; channels = components in the file (1 or 3) */
+int amhip_jpeg_info(const uint8_t* file, size_t len, int* width, int* height, int* channels);
+/* F files in host memory -> ONE stack of frames in HBM, frame f at *dev_frames + f * *frame_stride, rows *row_step
+ * bytes apart: the layout amhip_ortho_backward_process_dev, amhip_mosaic_batch_dev and amhip_stereo_add_frames_dev
+ * take.  colored == 0: 8UC1 (a gray file as it is, of a colour file its Y plane); colored != 0: 8UC3 B, G, R (a gray
+ * file replicated).  All files must have the width and height of file 0 (else AMHIP_ERR_ARG naming the frame).
+ * Released with amhip_io_free().  Like the other amhip_io_* calls it takes a device, not a context: the mains load
+ * frames before a map exists.  Scratch lives for the call. */
+int amhip_io_decode_jpeg_frames(int device, const uint8_t* const* files, const size_t* lens, size_t F, int colored,
+                                uint8_t** dev_frames, int* width, int* height, size_t* row_step, size_t* frame_stride);
+/* num_bytes of such a stack (or of a part of it) into host memory: what the drop-in loadImagesFromFile fills its
+ * cv::Mats from.  Synchronous. */
+int amhip_io_download_frames(const uint8_t* dev_frames, size_t num_bytes, uint8_t* host_frames);
+
 /* ---- what leaves the map: images, GeoTiff, grid_map_msgs, binary clouds
  *      (the formats either side of the path) ------------------
  * grid_map_cv, grid_map_ros, GDAL and roscpp are not part of the reference tree; the adopted
@@ -892,6 +922,8 @@ int amhip_session_layer_write_jpeg(amhip_session* s, int layer, int bgr, float l
  *                             no small-batch pre-cull / dispatch every tile of a large map instead of a
  *                             list of visible ones
  *   no_distorted_cull, no_distorted_prune, distorted_square_cull   cameras with a distortion model
+ *   jpegd_coef_budget_mb (4096)  amhip_io_decode_jpeg_frames: MB of coefficient scratch per group of frames;
+ *                             groups run one after another (a small value forces several groups)
  *   session_always_copy, session_threads, session_scalar_sums, session_no_partial,
  *   session_serial_sums       device content sums always before the downloads (round 5's order)
  *   session_verify_partial, session_trace          amhip_session: every matrix both ways on every
