@@ -27,8 +27,12 @@
 // Bounds: the walk decodes exactly the frame's blocks; a block takes one DC symbol and at most 63 AC
 // symbols (every AC symbol moves the coefficient index forward by at least one); a code takes at
 // most 16 - 8 steps of the maxcode loop; a refill takes at most 8 bytes.  No byte at or behind the
-// scan's end is loaded: they read as 0.  An undefined code, a run past coefficient 63, a wrong or
-// missing RSTn and a scan that ends early set the frame's status word and end the walk.
+// scan's end is loaded: they read as 0.  A run of 0xFF fill bytes, in front of a stuffed 0x00 or of
+// an RSTn, is followed no further than the scan's end, and so is the search for the RSTn at the end
+// of an interval.  An undefined code, a run past coefficient 63, a wrong or missing RSTn and a scan
+// that ends early set the frame's status word and end the walk; bytes between the end of an
+// interval's data and its RSTn, or between the last block and the EOI, are skipped, as libjpeg
+// skips them.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -78,6 +82,7 @@ struct Reader {
   int fake;            // of those, zero bits fed behind a marker or the end (always the last ones)
   uint32_t err;
 
+  // (a refill asks for pos and pos + 1 at once; a walk along fill bytes for one byte at a time)
   __device__ __forceinline__ void stage(uint64_t at, int lane) {
     __syncthreads();
     wbase = at;
@@ -87,6 +92,27 @@ struct Reader {
       win[lane + 64 * i] = q < end ? files[q] : (uint8_t)0;   // (never a byte at or behind `end`)
     }
     __syncthreads();
+  }
+
+  // the byte at file offset q < end, through the window
+  __device__ __forceinline__ uint32_t byte_at(uint64_t q, int lane) {
+    if (q < wbase || q >= wbase + kWindow) stage(q, lane);
+    return uni(win[q - wbase]);
+  }
+  // next_marker (jdmarker.c): `at` holds a 0xFF; -> the offset of the first byte behind the run of
+  // 0xFF that starts there (at most `end`), and that byte in *code (0xD9 at the end: the EOI).  All
+  // but the last 0xFF of the run are fill bytes (T.81 B.1.1.2).
+  __device__ __forceinline__ uint64_t behind_ff(uint64_t at, int lane, uint32_t* code) {
+    uint64_t k = at + 1;
+    uint32_t c = 0xD9u;
+    while (k < end) {   // (bounded by the scan's end)
+      c = byte_at(k, lane);
+      if (c != 0xFFu) break;
+      c = 0xD9u;
+      ++k;
+    }
+    *code = c;
+    return k;
   }
 
   // at least 32 unread bits behind this (a code takes at most 16, a value at most 15)
@@ -99,9 +125,10 @@ struct Reader {
         if (pos < wbase || pos + 2 > wbase + kWindow) stage(pos, lane);
         b = uni(win[pos - wbase]);
         if (b == 0xFF) {
-          const uint32_t b2 = pos + 1 < end ? uni(win[pos + 1 - wbase]) : 0xD9u;
+          uint32_t b2;
+          const uint64_t k = behind_ff(pos, lane, &b2);
           if (b2 == 0) {
-            pos += 2;   // 0xFF 0x00 is one data byte
+            pos = k + 1;   // 0xFF ... 0xFF 0x00 is one data byte 0xFF
           } else {
             b = 0;      // a marker: it stays where it is, zero bits are fed
             fake += 8;
@@ -186,21 +213,29 @@ __global__ __launch_bounds__(64) void k_jpegd_entropy(const uint8_t* __restrict_
   for (uint32_t mcu = 0; mcu < nmcu && !r.err; ++mcu) {
     if (restart) {
       if (todo == 0) {
-        // process_restart: the bits left of the byte are dropped, the next two bytes must be the
-        // expected RSTn, the predictors go back to 0
+        // process_restart: the bits left of the byte are dropped; read_restart_marker: the next
+        // marker (next_marker skips what is no 0xFF, and 0xFF 0x00; then any number of 0xFF and the
+        // code) must be the expected RSTn; the predictors go back to 0.  p only moves forward and
+        // never past the scan's end, where the code reads as EOI.
         r.acc = 0;
         r.nbits = 0;
         r.fake = 0;
-        bool ok = r.pos + 1 < r.end;
-        if (ok) {
-          if (r.pos < r.wbase || r.pos + 2 > r.wbase + kWindow) r.stage(r.pos, lane);
-          ok = uni(win[r.pos - r.wbase]) == 0xFFu && uni(win[r.pos + 1 - r.wbase]) == 0xD0u + next_rst;
+        uint64_t p = r.pos, k = r.end;
+        uint32_t code = 0xD9u;
+        while (p < r.end) {
+          if (r.byte_at(p, lane) != 0xFFu) {
+            ++p;
+            continue;
+          }
+          k = r.behind_ff(p, lane, &code);
+          if (code != 0u) break;
+          p = k + 1;
         }
-        if (!ok) {
+        if (p >= r.end || code != 0xD0u + next_rst) {
           r.err = jpegd::kBadRestart;
           break;
         }
-        r.pos += 2;
+        r.pos = k + 1;
         next_rst = (next_rst + 1) & 7u;
         pred[0] = pred[1] = pred[2] = 0;
         todo = restart;
@@ -254,7 +289,8 @@ __global__ __launch_bounds__(64) void k_jpegd_entropy(const uint8_t* __restrict_
       ++my;
     }
   }
-  if (!r.err && r.pos != r.end) r.err = jpegd::kBytesLeft;
+  // (what lies between the last block and the EOI is skipped, as next_marker skips it with a
+  // warning: the host parser has seen that no other marker is among it)
   if (lane == 0) status[fi] = r.err;
 }
 

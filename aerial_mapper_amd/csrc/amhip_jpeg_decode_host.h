@@ -6,8 +6,10 @@
 //
 // Accepted: baseline sequential DCT (SOF0), 8 bit, Huffman, one scan; one component, or Y Cb Cr
 // with Y sampled 1x1, 2x1 or 2x2 and chroma 1x1; 8-bit quantisation tables; Huffman table ids 0
-// and 1; optional DRI; APPn / COM skipped; bytes behind EOI ignored.  Everything else is refused with a text that names the
-// marker or field.  Every read is checked against the file's length.
+// and 1; optional DRI; APPn / COM skipped; 0xFF fill bytes in front of any marker, in the header
+// and in the scan (where a run of 0xFF followed by 0x00 is one data byte 0xFF); any bytes between
+// the last block and EOI; bytes behind EOI ignored.  Everything else is refused with a text that
+// names the marker or field.  Every read is checked against the file's length.
 #ifndef AMHIP_JPEG_DECODE_HOST_H_
 #define AMHIP_JPEG_DECODE_HOST_H_
 
@@ -271,7 +273,8 @@ enum Status : uint32_t {
   kRunPast63 = 2,      // a run past coefficient 63
   kBadRestart = 3,     // a wrong or missing RSTn
   kEndsEarly = 4,      // the scan ends before its last block
-  kBytesLeft = 5,      // bytes left behind the last block
+  // (5 was "bytes left behind the last block": libjpeg skips them, and so does the walk.  Retired,
+  // not reused.)
 };
 
 inline const char* status_text(uint32_t s) {
@@ -281,7 +284,6 @@ inline const char* status_text(uint32_t s) {
     case kRunPast63: return "a run past coefficient 63";
     case kBadRestart: return "a wrong or missing RSTn marker";
     case kEndsEarly: return "the scan ends before its last block";
-    case kBytesLeft: return "bytes left behind the last block";
   }
   return "unknown status";
 }

@@ -453,9 +453,11 @@ int amhip_io_free(void* dev_ptr);
  * device is touched.  A scan that does not decode (undefined code, run past coefficient 63, wrong or
  * missing RSTn, early end) is found on the device: AMHIP_ERR_ARG naming the frame, *dev_frames = NULL.
  * The scan ends at the first EOI behind it; whatever follows that EOI (thumbnails, padding, a second image) is
- * ignored, as libjpeg ignores it.  Stricter than libjpeg, which only warns: 0xFF fill bytes in front of an RSTn
- * marker, and bytes left between the last block and EOI, are errors here.  Scratch is bounded by decoding in groups
- * of frames (tuning key jpegd_coef_budget_mb). */
+ * ignored, as libjpeg ignores it.  As in libjpeg, any number of 0xFF fill bytes may stand in front of a marker
+ * (a run of 0xFF followed by 0x00 is one data byte 0xFF), and bytes between the end of a restart interval's data
+ * and its RSTn, or between the last block and EOI, are skipped.  Stricter than libjpeg, which only warns: a wrong
+ * RSTn index and a scan that ends early are errors here.  Scratch is bounded by decoding in groups of frames
+ * (tuning key jpegd_coef_budget_mb). */
 /* host only: parses up to SOS, applies every rule above; channels = components in the file (1 or 3) */
 int amhip_jpeg_info(const uint8_t* file, size_t len, int* width, int* height, int* channels);
 /* F files in host memory -> ONE stack of frames in HBM, frame f at *dev_frames + f * *frame_stride, rows *row_step

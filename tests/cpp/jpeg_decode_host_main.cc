@@ -2,8 +2,8 @@
 // amhip_jpeg_decode_host.h: header parser, per-frame descriptor, Huffman decode tables) as a
 // stand-alone program.  tests/test_jpeg_decode_host.py builds it with -fsanitize=address,undefined,
 // runs it, and compares what it prints with tests/jpeg_decode_reference.py.
-//   jpeg_decode_host_main desc <file>...            -> per file the descriptor and its tables, or
-//                                                      "refused <text>"
+//   jpeg_decode_host_main desc <file>...            -> per file the descriptor, its tables and the
+//                                                      marks of its scan, or "refused <text>"
 //   jpeg_decode_host_main fuzz <seed> <count> <file>...
 //        -> per file `count` seeded mutations of its header (one byte changed, or the file cut
 //           short), each parsed from a heap buffer of exactly its size; prints "<ok> <refused>"
@@ -36,6 +36,30 @@ static void print_table(const char* name, const HuffTable& t) {
   std::printf("\n%s.huffval", name);
   for (int i = 0; i < 256; ++i) std::printf(" %u", t.huffval[i]);
   std::printf("\n");
+}
+
+// What the entropy kernel relies on when it follows a run of 0xFF inside the scan: the scan ends
+// at a 0xFF whose run leads to EOI inside the file, and every run of 0xFF in front of that is
+// followed, still inside the scan, by 0x00 (a stuffed byte) or an RSTn.  Counts the RSTn, the
+// stuffed bytes and the fill bytes (all but the last 0xFF of a run); false: a bound is broken.
+static bool scan_marks(const uint8_t* file, size_t n, const Frame& f, long* rst, long* stuffed, long* fill) {
+  *rst = *stuffed = *fill = 0;
+  if (f.scan_begin > f.scan_end || f.scan_end + 2 > n || file[f.scan_end] != 0xFF) return false;
+  size_t e = (size_t)f.scan_end;
+  while (e < n && file[e] == 0xFF) ++e;
+  if (e >= n || file[e] != 0xD9) return false;
+  for (size_t p = (size_t)f.scan_begin; p < f.scan_end; ++p) {
+    if (file[p] != 0xFF) continue;
+    size_t k = p + 1;
+    while (k < f.scan_end && file[k] == 0xFF) ++k;
+    if (k >= f.scan_end) return false;
+    if (file[k] == 0x00) ++*stuffed;
+    else if (file[k] >= 0xD0 && file[k] <= 0xD7) ++*rst;
+    else return false;
+    *fill += (long)(k - p - 1);
+    p = k;
+  }
+  return true;
 }
 
 static uint64_t next(uint64_t* s) {   // splitmix64
@@ -71,6 +95,12 @@ int main(int argc, char** argv) {
         std::printf("\n");
       }
       std::printf("blocks %u\n", f.comp_base[f.ncomp]);
+      long rst, stuffed, fill;
+      if (!scan_marks(exact.data(), exact.size(), f, &rst, &stuffed, &fill)) {
+        std::printf("bad scan bounds accepted\n");
+        return 1;
+      }
+      std::printf("marks %ld %ld %ld\n", rst, stuffed, fill);
       for (int c = 0; c < f.ncomp; ++c) {
         char name[16];
         std::snprintf(name, sizeof(name), "dc%d", f.td[c]);
@@ -84,7 +114,7 @@ int main(int argc, char** argv) {
   if (!std::strcmp(argv[1], "fuzz") && argc >= 5) {
     uint64_t seed = std::strtoull(argv[2], nullptr, 10);
     const int count = std::atoi(argv[3]);
-    long ok = 0, refused = 0;
+    long ok = 0, refused = 0, rst, stuffed, fill;
     for (int a = 4; a < argc; ++a) {
       std::vector<uint8_t> file;
       if (!read_file(argv[a], &file)) return 1;
@@ -109,7 +139,8 @@ int main(int argc, char** argv) {
         if (parse(buf, n, &f, text, sizeof(text))) {
           // what the kernels rely on
           if (f.scan_begin > f.scan_end || f.scan_end + 2 > n || f.mcux < 1 || f.mcuy < 1 ||
-              (f.ncomp != 1 && f.ncomp != 3) || f.comp_base[f.ncomp] == 0) {
+              (f.ncomp != 1 && f.ncomp != 3) || f.comp_base[f.ncomp] == 0 ||
+              !scan_marks(buf, n, f, &rst, &stuffed, &fill)) {
             std::printf("bad descriptor accepted\n");
             return 1;
           }

@@ -9,7 +9,10 @@ tests/test_jpeg_decode_reference.py compares bit for bit.  This module is the ya
 decoder (aerial_mapper_amd/csrc/amhip_jpeg_decode.hip).
 
 Not restated: the C code's wraparound of samples beyond the range table (corrupt coefficients);
-samples are clamped.  EXIF orientation is not applied.
+samples are clamped, as libjpeg-turbo's SIMD IDCT clamps them (pinned up to an IDCT output of
++-1303 by the fixtures of tests/golden/jpeg_decode/streams/; beyond that the SIMD code's 16-bit
+intermediates leave the plain rule).  EXIF orientation is not applied.  Deliberately stricter than
+libjpeg, which warns and goes on: a scan that ends early, a wrong RSTn index.
 """
 import numpy as np
 
@@ -230,6 +233,14 @@ class Counters(object):
         self.restarts = 0         # RSTn markers passed
         self.rst_wraps = 0        # ... of which n went from 7 back to 0
         self.stuffed = 0          # 0xFF 0x00 pairs read as one byte
+        self.fill_bytes = 0       # 0xFF fill bytes skipped in front of a stuffed 0x00 or an RSTn
+        self.before_rst = 0       # bytes skipped between the end of an interval's data and its RSTn
+        self.trailing = 0         # bytes between the last block and EOI (libjpeg warns and skips them)
+        self.slow_by_length = np.zeros(17, np.int64)   # slow codes of each length 9..16
+        self.max_dc_size = self.max_ac_size = 0        # the largest SSSS seen (merge with max, not +)
+        self.at_63 = 0            # coefficients stored at zigzag 63 (such a block has no EOB)
+        self.zrls = 0             # ZRL symbols
+        self.zrl_past_63 = 0      # ZRLs that carry the index past 63 (the block ends there)
 
 
 def entropy_decode(data, h, counters=None):
@@ -243,8 +254,9 @@ def entropy_decode(data, h, counters=None):
     zz = [int(v) for v in ZIGZAG]
 
     def fill():
-        # jpeg_fill_bit_buffer: 0xFF 0x00 is one data byte; at a marker (or behind the end) no
-        # byte is consumed and zero bits are fed
+        # jpeg_fill_bit_buffer: a run of 0xFF and then 0x00 is one data byte 0xFF (all but the last
+        # 0xFF of the run are fill bytes, T.81 B.1.1.2); at a marker (or behind the end) no byte is
+        # consumed and zero bits are fed.  The run is followed no further than the scan's end.
         while st["nbits"] <= 56:
             pos = st["pos"]
             b = 0
@@ -253,10 +265,14 @@ def entropy_decode(data, h, counters=None):
             else:
                 b = data[pos]
                 if b == 0xFF:
-                    b2 = data[pos + 1] if pos + 1 < end else 0xD9
+                    k = pos + 1
+                    while k < end and data[k] == 0xFF:
+                        k += 1
+                    b2 = data[k] if k < end else 0xD9
                     if b2 == 0:
-                        st["pos"] = pos + 2
+                        st["pos"] = k + 1
                         cnt.stuffed += 1
+                        cnt.fill_bytes += k - pos - 1
                     else:
                         b = 0
                         st["fake"] += 8
@@ -284,6 +300,7 @@ def entropy_decode(data, h, counters=None):
             l += 1
         if l > 16:
             raise Corrupt("undefined Huffman code")
+        cnt.slow_by_length[l] += 1
         code = peek(l)
         drop(l)
         return t.huffval[(code + t.valoffset[l]) & 255]
@@ -301,13 +318,34 @@ def entropy_decode(data, h, counters=None):
         for mx in range(mcux):
             if h.restart:
                 if todo == 0:
-                    # process_restart: discard the bits left of the byte, the marker must be the
-                    # next RSTn, predictors back to 0
+                    # process_restart: discard the bits left of the byte; read_restart_marker /
+                    # next_marker: skip to the next marker (bytes that are not 0xFF, 0xFF 0x00 pairs:
+                    # "extraneous bytes", a warning; then any number of 0xFF and the code), which
+                    # must be the next RSTn; predictors back to 0.  Stricter than libjpeg in one
+                    # thing: a wrong index is an error (jpeg_resync_to_restart guesses and goes on).
                     st["acc"] = st["nbits"] = st["fake"] = 0
-                    pos = st["pos"]
-                    if not (pos + 1 < end and data[pos] == 0xFF and data[pos + 1] == 0xD0 + next_rst):
+                    pos, code = st["pos"], None
+                    while pos < end:
+                        if data[pos] != 0xFF:
+                            pos += 1
+                            cnt.before_rst += 1
+                            continue
+                        k = pos + 1
+                        while k < end and data[k] == 0xFF:
+                            k += 1
+                        if k >= end:
+                            break
+                        if data[k] != 0:
+                            code = data[k]
+                            break
+                        cnt.before_rst += 1          # (a stuffed 0xFF among them)
+                        cnt.stuffed += 1
+                        cnt.fill_bytes += k - pos - 1
+                        pos = k + 1
+                    if code != 0xD0 + next_rst:
                         raise Corrupt("wrong or missing RST%d" % next_rst)
-                    st["pos"] = pos + 2
+                    cnt.fill_bytes += k - pos - 1
+                    st["pos"] = k + 1
                     cnt.restarts += 1
                     next_rst = (next_rst + 1) & 7
                     cnt.rst_wraps += next_rst == 0
@@ -322,6 +360,7 @@ def entropy_decode(data, h, counters=None):
                         row = planes[ci][my * v + by, mx * hh + bx]
                         fill()
                         s = symbol(dc)
+                        cnt.max_dc_size = max(cnt.max_dc_size, s)
                         if s:
                             fill()
                             pred[ci] += receive_extend(s)
@@ -334,15 +373,20 @@ def entropy_decode(data, h, counters=None):
                             if s == 0:
                                 if r != 15:
                                     break      # EOB
-                                k += 16        # ZRL
+                                k += 16        # ZRL (past 63: the loop ends, as decode_mcu's does)
+                                cnt.zrls += 1
+                                cnt.zrl_past_63 += k > 63
                                 continue
                             k += r
                             if k > 63:
                                 raise Corrupt("run past coefficient 63")
+                            cnt.max_ac_size = max(cnt.max_ac_size, s)
+                            cnt.at_63 += k == 63
                             row[zz[k]] = receive_extend(s)
                             k += 1
-    if st["pos"] != end:
-        raise Corrupt("bytes left behind the last block")
+    # what lies between the last block and EOI is skipped whatever it is (next_marker: "extraneous
+    # bytes before marker", a warning); the header parser has seen that no other marker is among it
+    cnt.trailing += end - st["pos"]
     cnt.scan_bits_left = st["nbits"] - st["fake"]
     return planes
 
@@ -383,6 +427,7 @@ def _idct_1d(d, shift):
 class IdctCounters(object):
     def __init__(self):
         self.clamped_low = self.clamped_high = 0
+        self.lowest = self.highest = 0   # extremes of the IDCT's output before + 128 (merge with min / max)
 
 
 def idct_islow(coef, qtable, counters=None):
@@ -393,6 +438,8 @@ def idct_islow(coef, qtable, counters=None):
     ws = _idct_1d(d, CONST_BITS - PASS1_BITS)                         # columns: along the row index
     px = _idct_1d(ws.swapaxes(-1, -2), CONST_BITS + PASS1_BITS + 3).swapaxes(-1, -2) + 128
     if counters is not None:
+        counters.lowest = min(counters.lowest, int(px.min()) - 128)
+        counters.highest = max(counters.highest, int(px.max()) - 128)
         counters.clamped_low += int((px < 0).sum())
         counters.clamped_high += int((px > 255).sum())
     return np.clip(px, 0, 255)

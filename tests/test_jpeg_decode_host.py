@@ -49,12 +49,11 @@ def _records(text):
     return out
 
 
-def test_descriptors_and_tables_equal_the_restatement(exe):
-    names = DI.fixture_names()
-    recs = _records(_run(exe, "desc", *[DI.fixture_path(n) for n in names]))
+def _check_descriptors(names, recs, bytes_of):
     assert len(recs) == len(names)
     for name, r in zip(names, recs):
-        h = D.parse_header(DI.fixture_bytes(name))
+        assert "refused" not in r, (name, r)
+        h = D.parse_header(bytes_of(name))
         hmax, vmax, mcux, mcuy, samp = D.layout(h)
         assert r["size"] == [h.width, h.height, h.channels], name
         assert r["mcu"] == [hmax, vmax, mcux, mcuy, h.restart], name
@@ -73,6 +72,52 @@ def test_descriptors_and_tables_equal_the_restatement(exe):
                 assert r[key + ".valoffset"] == t.valoffset, (name, key)
                 assert r[key + ".huffval"] == t.huffval, (name, key)
         assert r["blocks"] == [base], name
+        # the marks of the scan, counted from its bytes, are those the restatement's walk meets
+        c = D.Counters()
+        D.entropy_decode(bytes_of(name), h, c)
+        assert r["marks"] == [c.restarts, c.stuffed, c.fill_bytes], name
+
+
+def test_descriptors_and_tables_equal_the_restatement(exe):
+    names = DI.fixture_names()
+    recs = _records(_run(exe, "desc", *[DI.fixture_path(n) for n in names]))
+    _check_descriptors(names, recs, DI.fixture_bytes)
+
+
+def test_every_stream_is_accepted_and_its_descriptor_equals_the_restatement(exe, tmp_path):
+    """the second family: header and scan rewrites, hand-coded scans, flat quantisation tables and
+    Pillow's further shapes; scan bounds, tables and marks as the restatement has them"""
+    names = DI.stream_names()
+    paths = []
+    for n in names:
+        if n in DI.BUILT_NOT_COMMITTED:
+            p = tmp_path / (n + ".jpg")
+            p.write_bytes(DI.stream_bytes(n))
+            paths.append(str(p))
+        else:
+            paths.append(DI.stream_path(n))
+    extra = {"ff_ff_00_at_619": DI.ff_ff_00_at_619()[0], "run_past_63": DI.run_past_63()}
+    for n, data in extra.items():
+        p = tmp_path / (n + ".jpg")
+        p.write_bytes(data)
+        paths.append(str(p))
+    recs = _records(_run(exe, "desc", *paths))
+    assert len(recs) == 170 + 2
+    _check_descriptors(names, recs[:170], DI.stream_bytes)
+    for (n, data), r in zip(extra.items(), recs[170:]):
+        h = D.parse_header(data)
+        assert r["scan"] == [h.scan_begin, h.scan_end] and r["size"] == [h.width, h.height, h.channels], n
+    # fill bytes in front of EOI lie outside the scan: it ends at the first 0xFF of the run
+    a = _records(_run(exe, "desc", DI.stream_path("b_fill_before_eoi_420"), DI.fixture_path("noise_33x15_420_q95_rst1")))
+    assert a[0]["scan"] == a[1]["scan"]
+
+
+def test_mutated_headers_of_the_streams_end_in_ok_or_a_refusal(exe):
+    """169 files x 10 seeded mutations, as below: rearranged and hand-written headers under the sanitizers"""
+    names = [n for n in DI.stream_names() if n not in DI.BUILT_NOT_COMMITTED]
+    ok, refused = (int(x) for x in _run(exe, "fuzz", 20261019, 10, *[DI.stream_path(n) for n in names]).split())
+    assert ok + refused == 169 * 10
+    assert ok > 20 and refused > 400
 
 
 def test_every_refusal_is_refused_with_a_text(exe, tmp_path):

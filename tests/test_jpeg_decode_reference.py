@@ -1,7 +1,13 @@
 """CPU: tests/jpeg_decode_reference.py (the yardstick of the GPU JPEG decoder) against libjpeg's own
 pixels: the .npz beside every fixture of tests/golden/jpeg_decode/ (what libjpeg-turbo decoded when
 the fixtures were written), Pillow directly on the 576 files of tests/golden/jpeg/ where Pillow is
-present, and tests/jpeg_reference.py's coefficients.  And that the fixtures reach every branch."""
+present, and tests/jpeg_reference.py's coefficients.  And that the fixtures reach every branch.
+The same for the second family, tests/golden/jpeg_decode/streams/: stream shapes no encoder of
+ours writes (jpeg_decode_inputs.stream_names())."""
+import glob
+import os
+
+
 import numpy as np
 import pytest
 
@@ -152,3 +158,155 @@ def test_corrupt_scans_are_found():
         D.parse_header(data)
         with pytest.raises(D.Corrupt):
             D.decode(data)
+
+
+# ---------------------------------------------------------------------------
+# the second family: every legal stream shape (tests/golden/jpeg_decode/streams/)
+# ---------------------------------------------------------------------------
+
+
+def _merge(total, one):
+    """counters of one file into the family's: max_* / highest by max, lowest by min, the rest summed"""
+    for part in ("entropy", "idct", "sample"):
+        a, b = getattr(total, part), getattr(one, part)
+        for k, v in vars(b).items():
+            if k.startswith("max_") or k == "highest":
+                setattr(a, k, max(getattr(a, k, 0), v))
+            elif k == "lowest":
+                setattr(a, k, min(getattr(a, k, 0), v))
+            else:
+                setattr(a, k, getattr(a, k, 0) + v)
+
+
+@pytest.fixture(scope="module")
+def streams():
+    """every stream decoded once: {name: Decoded}, the family's counters, {name: counters}"""
+    total, per_file, out = D.AllCounters(), {}, {}
+    for name in DI.stream_names():
+        c = D.AllCounters()
+        out[name] = D.decode(DI.stream_bytes(name), c)
+        per_file[name] = c
+        _merge(total, c)
+    return out, total, per_file
+
+
+def test_stream_list_is_the_committed_one_and_small():
+    names = DI.stream_names()
+    assert len(names) == len(set(names)) == 170
+    assert len(DI.stream_rewrites()) == 66 and len(DI.pillow_specs()) == 104
+    jpg = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(DI.STREAMS, "*.jpg")))
+    npz = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(DI.STREAMS, "*.npz")))
+    assert npz == sorted(names)
+    assert jpg == sorted(n for n in names if n not in DI.BUILT_NOT_COMMITTED)
+    sizes = [os.path.getsize(f) for f in glob.glob(os.path.join(DI.STREAMS, "*"))]
+    assert max(sizes) < 25 * 1024 and sum(sizes) < 512 * 1024
+    for n in jpg:
+        assert os.path.getsize(DI.stream_path(n)) < 16 * 1024, n
+
+
+def test_rewrites_and_hand_coded_scans_are_the_committed_bytes():
+    """groups a to d are derived from committed fixtures without an encoder: the derivation gives
+    the very bytes libjpeg-turbo decoded when the .npz files were written"""
+    for name, data in DI.stream_rewrites().items():
+        if name not in DI.BUILT_NOT_COMMITTED:
+            with open(DI.stream_path(name), "rb") as f:
+                assert f.read() == data, name
+
+
+def test_restatement_equals_libjpeg_on_every_stream(streams):
+    out = streams[0]
+    assert len(out) == 170
+    for name, d in out.items():
+        gray, bgr = DI.stream_pixels(name)
+        assert d.gray.dtype == np.uint8 and d.gray.shape == gray.shape and d.bgr.shape == bgr.shape, name
+        assert np.array_equal(d.gray, gray), (name, int((d.gray != gray).sum()))
+        assert np.array_equal(d.bgr, bgr), (name, int((d.bgr != bgr).sum()))
+
+
+def test_header_rewrites_give_the_pixels_of_their_base(streams):
+    out = streams[0]
+    n = 0
+    for tag, base in DI.HEADER_BASES.items():
+        gray, bgr = DI.fixture_pixels(base)
+        for name in DI.same_picture_variants(tag):
+            n += 1
+            assert np.array_equal(out[name].gray, gray) and np.array_equal(out[name].bgr, bgr), name
+    assert n == len(DI.header_rewrites()) == 34
+    # ... and so does a fill byte where libjpeg-turbo's fast path strays from libjpeg's rule
+    data, base = DI.ff_ff_00_at_619()
+    d = D.decode(data)
+    gray, bgr = DI.fixture_pixels(base)
+    assert np.array_equal(d.gray, gray) and np.array_equal(d.bgr, bgr)
+
+
+def test_streams_reach_what_the_encoder_fixtures_do_not(streams):
+    out, c, per_file = streams
+    e = c.entropy
+    # a slow code of every length 9..16 (the ladder tables), in one file and on the whole
+    assert all(per_file["c_ladder_every_length"].entropy.slow_by_length[9:17] > 0)
+    assert all(e.slow_by_length[9:17] > 0) and e.slow_by_length[:9].sum() == 0
+    assert e.slow_by_length.sum() == e.slow_codes
+    # the largest sizes a baseline scan may hold, both signs of each
+    assert e.max_dc_size == 11 and e.max_ac_size == 10
+    dc = out["c_dc_category_11"].coefs[0][0, :, 0]
+    assert list(dc[:4]) == [2047, 0, -2047, 0]
+    at63 = out["c_ac_size_10_at_63"].coefs[0][0, :, 63]
+    assert list(at63[:4]) == [1023, -1023, 512, -512]
+    # 63 coefficients and no EOB; three ZRL and a coefficient at 63; a ZRL past 63 ends the block
+    full = out["c_63_coefficients_no_eob"].coefs[0][0]
+    assert all((full[k][1:] != 0).all() for k in range(3)) and per_file["c_63_coefficients_no_eob"].entropy.at_63 == 3
+    pe = per_file["c_three_zrl_then_63"].entropy
+    assert pe.at_63 == 2 and pe.zrls == 6
+    assert list(out["c_three_zrl_then_63"].coefs[0][0, :3, 63]) == [1, 0, -1]
+    pe = per_file["c_zrl_past_63"].entropy
+    assert pe.zrl_past_63 == 2 and pe.zrls == 8 and pe.at_63 == 0
+    # (the blocks behind them are where they belong: the predictor goes 25, -25, 0, 9)
+    assert list(out["c_zrl_past_63"].coefs[0][0, :5, 0]) == [25, -25, 0, 9, 9]
+    # fill bytes in front of RSTn and of a stuffed byte, stuffed bytes, bytes in front of EOI
+    assert e.stuffed > 0 and e.fill_bytes > 0 and e.trailing > 0
+    assert per_file["b_fill3_before_one_rst"].entropy.fill_bytes == 3
+    pe = per_file["b_fill2_before_every_rst_gray"].entropy
+    assert pe.restarts == 50 and pe.fill_bytes == 100 and pe.rst_wraps == 6
+    assert per_file["b_ff_ff_00_444"].entropy.fill_bytes == 1
+    pe = per_file["b_ff_ff_ff_00_everywhere_444"].entropy
+    assert pe.fill_bytes == 2 * pe.stuffed > 0
+    # bytes between an interval's data and its RSTn, beyond what a refill has read ahead
+    assert [per_file["b_bytes_%d_before_one_rst" % n].entropy.before_rst for n in (1, 9, 20)] == [0, 2, 13]
+    assert per_file["b_bytes_before_every_rst_gray"].entropy.before_rst >= 4 * 2
+    pe = per_file["b_bytes_with_ff_00_before_rst"].entropy
+    assert pe.before_rst > 0 and pe.fill_bytes == 1
+    # (a refill reads up to 7 bytes ahead: of 8, 9 and 20 bytes 1, 2 and 13 are left unread)
+    assert [per_file["b_trailing_%d_420" % n].entropy.trailing for n in (1, 7, 8, 9, 20)] == [0, 0, 1, 2, 13]
+    # a restart counter that wraps past RST7 in a Pillow-written file of one row of MCUs
+    pe = per_file["e_random_2049x1_422_q30_rst1"].entropy
+    assert pe.restarts == 128 and pe.rst_wraps == 16
+    # DRI without RSTn: an interval longer than the scan
+    for name in ("a_dri_60000_444", "a_dri_60000_420", "e_random_32x16_444_q100_rst60000"):
+        assert out[name].header.restart == 60000 and per_file[name].entropy.restarts == 0, name
+    assert out["a_dri_0_444"].header.restart == 0
+    # clamping on both sides, and IDCT output up to the edge of the contract (+-1303) and not beyond
+    assert c.idct.clamped_low > 0 and c.idct.clamped_high > 0
+    assert c.idct.lowest == -1303 and 1100 < c.idct.highest <= 1303
+    for q, lo in ((8, -652), (16, -1303)):
+        assert per_file["d_quant_all_%d_gray" % q].idct.lowest == lo
+    # every upsampling rule; replication at dw <= 2 for both subsamplings
+    s = c.sample
+    assert s.replicated and s.h2v1_fancy and s.h2v2_fancy and s.fullsize
+    for size in ("2x1", "1x2", "3x1", "4x1"):
+        for samp in ("422", "420"):
+            ps = per_file["e_random_%s_%s_q30" % (size, samp)].sample
+            assert ps.replicated == 2 and not ps.h2v1_fancy and not ps.h2v2_fancy, (size, samp)
+    assert per_file["e_random_5x3_422_q30"].sample.h2v1_fancy == 2
+    assert per_file["e_random_5x3_420_q30"].sample.h2v2_fancy == 2
+    assert per_file["e_random_2049x1_444_q30"].sample.fullsize == 2
+    # a file's own Huffman tables
+    assert out["e_random_32x16_444_q100_opt"].header.huff[(1, 0)].bits != J.AC_LUM_BITS
+
+
+def test_a_run_past_coefficient_63_is_corrupt():
+    data = DI.run_past_63()
+    assert DI.sof0_size(data) == (DI.HAND_W, DI.HAND_H)
+    D.parse_header(data)
+    with pytest.raises(D.Corrupt) as ei:
+        D.decode(data)
+    assert DI.CORRUPT_REASONS["run past 63"] in str(ei.value)

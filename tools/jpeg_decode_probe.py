@@ -11,7 +11,9 @@ The result also goes to profiles/jpeg_decode_probe_<build id>.json (--out FILE: 
 The split between the three kernels comes from a kernel trace of a fresh process:
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o t -- python tools/jpeg_decode_probe.py --trace-target
 (its *_kernel_stats.csv lists the k_jpegd_* kernels; DESIGN 4.11 quotes it).
-Usage: python tools/jpeg_decode_probe.py [--reps N] [--frames N] [--distinct N] [--out FILE] [--trace-target]"""
+--no-pillow leaves column (c) out: for timing two builds of the library in turn (AMHIP_LIB_PATH names
+the other one), where Pillow's seconds per run buy nothing.
+Usage: python tools/jpeg_decode_probe.py [--reps N] [--frames N] [--distinct N] [--out FILE] [--no-pillow] [--trace-target]"""
 import argparse
 import io
 import json
@@ -48,6 +50,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--no-pillow", action="store_true", help="do not time Pillow beside the GPU")
     ap.add_argument("--trace-target", action="store_true",
                     help="only decode both stacks twice (the program to run under a kernel trace)")
     args = ap.parse_args()
@@ -58,9 +61,11 @@ def main():
         from PIL import Image
     except ImportError:
         Image = None
+    if args.no_pillow:
+        Image = None
     out = {"build_id": hip_lib.build_id(), "reps": args.reps, "warmup": 3, "frames": args.frames,
            "distinct_frames": args.distinct, "width": args.width, "height": args.height,
-           "pillow": "measured" if Image else "not available"}
+           "pillow": "measured" if Image else "left out" if args.no_pillow else "not available"}
     stacks = {}
     with A.AerialGridMap(A.GridMapSettings(0.0, 0.0, 32.0, 32.0, 1.0), device=0) as m:
         for name, ch in (("gray", 1), ("colour_420", 3)):
