@@ -128,6 +128,61 @@ void AerialMapperIO::loadImagesFromFileToDevice(const std::string& filename_base
       "loadImagesFromFile");
 }
 
+namespace {
+
+// a stack in HBM -> cv::Mats appended to *images; frees the stack
+void append_downloaded(uint8_t* dev, size_t num_poses, int w, int h, size_t row_step, size_t frame_stride,
+                       bool load_colored_images, Images* images);
+
+}  // namespace
+
+// aerial-mapper-io.cc:229-249: cv::imread(directory + image_names[i] + ".png") per name
+void AerialMapperIO::loadImagesFromFileToDevice(const std::string& directory,
+                                                const std::vector<std::string>& image_names,
+                                                bool load_colored_images, uint8_t** dev_frames,
+                                                int* width, int* height, size_t* row_step,
+                                                size_t* frame_stride) {
+  if (!dev_frames || !width || !height || !row_step || !frame_stride)
+    amhip_shim::fatal("loadImagesFromFile", "CHECK(images)");
+  if (image_names.empty()) amhip_shim::fatal("loadImagesFromFile", "no image names: no images to load");
+  std::vector<std::unique_ptr<MappedFile> > mapped;
+  std::vector<const uint8_t*> files;
+  std::vector<size_t> lens;
+  for (size_t i = 0; i < image_names.size(); ++i) {
+    const std::string name = directory + image_names[i] + ".png";
+    mapped.emplace_back(new MappedFile(name));
+    if (!mapped.back()->data)
+      amhip_shim::fatal("loadImagesFromFile", ("cannot read " + name).c_str());
+    files.push_back(reinterpret_cast<const uint8_t*>(mapped.back()->data));
+    lens.push_back(mapped.back()->size);
+  }
+  const int rc = amhip_io_decode_png_frames(device_index(), files.data(), lens.data(), files.size(),
+                                            load_colored_images ? 1 : 0, dev_frames, width, height,
+                                            row_step, frame_stride);
+  if (rc != AMHIP_OK) {
+    // the library names the frame; the caller knows files: name the file as well
+    const std::string text = amhip_last_error();
+    const size_t at = text.find("frame ");
+    std::string file;
+    if (at != std::string::npos) {
+      const size_t k = static_cast<size_t>(std::strtoul(text.c_str() + at + 6, nullptr, 10));
+      if (k < image_names.size()) file = " (" + directory + image_names[k] + ".png)";
+    }
+    amhip_shim::fatal("loadImagesFromFile", (text + file).c_str());
+  }
+}
+
+void AerialMapperIO::loadImagesFromFile(const std::string& directory, std::vector<std::string> image_names,
+                                        Images* images, bool load_colored_images) {
+  if (!images) amhip_shim::fatal("loadImagesFromFile", "CHECK(images)");
+  uint8_t* dev = nullptr;
+  int w = 0, h = 0;
+  size_t row_step = 0, frame_stride = 0;
+  loadImagesFromFileToDevice(directory, image_names, load_colored_images, &dev, &w, &h, &row_step,
+                             &frame_stride);
+  append_downloaded(dev, image_names.size(), w, h, row_step, frame_stride, load_colored_images, images);
+}
+
 void AerialMapperIO::loadImagesFromFile(const std::string& filename_base, size_t num_poses,
                                         Images* images, bool load_colored_images) {
   if (!images) amhip_shim::fatal("loadImagesFromFile", "CHECK(images)");
@@ -136,6 +191,13 @@ void AerialMapperIO::loadImagesFromFile(const std::string& filename_base, size_t
   size_t row_step = 0, frame_stride = 0;
   loadImagesFromFileToDevice(filename_base, num_poses, load_colored_images, &dev, &w, &h, &row_step,
                              &frame_stride);
+  append_downloaded(dev, num_poses, w, h, row_step, frame_stride, load_colored_images, images);
+}
+
+namespace {
+
+void append_downloaded(uint8_t* dev, size_t num_poses, int w, int h, size_t row_step, size_t frame_stride,
+                       bool load_colored_images, Images* images) {
   const int ch = load_colored_images ? 3 : 1;
   std::vector<uint8_t> host(num_poses * frame_stride);
   amhip_shim::check_status(amhip_io_download_frames(dev, host.size(), host.data()), "loadImagesFromFile");
@@ -153,6 +215,8 @@ void AerialMapperIO::loadImagesFromFile(const std::string& filename_base, size_t
     images->push_back(image);   // (the reference push_back()s: append)
   }
 }
+
+}  // namespace
 
 void AerialMapperIO::loadPosesFromFileStandard(const std::string& filename, Poses* T_G_Bs) {
   if (!T_G_Bs) amhip_shim::fatal("loadPosesFromFileStandard", "CHECK(T_G_Bs)");

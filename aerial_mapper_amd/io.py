@@ -183,6 +183,41 @@ def decode_jpeg_frames(files, colored=False, device=0):
     return DeviceFrames(out.value, n, w.value, h.value, 3 if colored else 1, row.value, stride.value, int(device))
 
 
+def png_info(data):
+    """-> (width, height, channels) of a PNG file's bytes (channels 1 for gray and gray + alpha, else 3);
+    raises for a file the decoder refuses."""
+    data = bytes(data)
+    w, h, ch = C.c_int(), C.c_int(), C.c_int()
+    L.check(L.load().amhip_png_info(data, len(data), C.byref(w), C.byref(h), C.byref(ch)))
+    return w.value, h.value, ch.value
+
+
+def decode_png_frames(files, colored=False, device=0):
+    """files: list of bytes, each one 8-bit non-interlaced PNG file of the same width and height ->
+    DeviceFrames (colored=False: 8UC1; colored=True: 8UC3 B, G, R; alpha dropped)."""
+    lib = L.load()
+    files = [f if isinstance(f, bytes) else bytes(f) for f in files]
+    n = len(files)
+    ptrs = (C.c_char_p * max(n, 1))(*files)
+    lens = (C.c_size_t * max(n, 1))(*[len(f) for f in files])
+    out = C.c_void_p()
+    w, h = C.c_int(), C.c_int()
+    row, stride = C.c_size_t(), C.c_size_t()
+    L.check(lib.amhip_io_decode_png_frames(int(device), ptrs, lens, n, 1 if colored else 0, C.byref(out),
+                                           C.byref(w), C.byref(h), C.byref(row), C.byref(stride)))
+    return DeviceFrames(out.value, n, w.value, h.value, 3 if colored else 1, row.value, stride.value, int(device))
+
+
+def load_images_named(directory, image_names, colored=False, device=0):
+    """io::AerialMapperIO::loadImagesFromFile(directory, image_names, ..): reads <directory><name>.png
+    for every name and decodes them on the GPU -> DeviceFrames.  A missing or refused file raises."""
+    files = []
+    for name in image_names:
+        with open("%s%s.png" % (directory, name), "rb") as f:
+            files.append(f.read())
+    return decode_png_frames(files, colored, device)
+
+
 def load_images(filename_base, num_poses, colored=False, device=0):
     """io::AerialMapperIO::loadImagesFromFile: reads <filename_base><i>.jpg, i = 0..num_poses-1, and
     decodes them on the GPU -> DeviceFrames.  A missing or refused file raises."""

@@ -10,8 +10,12 @@
 //   loadImagesFromFile (:207-227) -- the cv::imread("<prefix><i>.jpg") per pose as one
 //     batched baseline JPEG decoder on the GPU (amhip_io_decode_jpeg_frames): the pixels
 //     libjpeg gives at its defaults; EXIF orientation is not applied; no imshow.
-// The .png overload of the image loader, the camera-rig loader (aslam YAML) and the
-// format converters stay the reference's.
+//   loadImagesFromFile(directory, image_names, ..) (:229-249) -- the
+//     cv::imread("<directory><name>.png") per name as one batched PNG decoder on the GPU
+//     (amhip_io_decode_png_frames): inflate as zlib defines it, the pixels Pillow gives; 8 bit,
+//     not interlaced; gray from a colour file by libpng's rgb_to_gray rule (adopted, unpinned);
+//     no imshow.
+// The camera-rig loader (aslam YAML) and the format converters stay the reference's.
 #ifndef AERIAL_MAPPER_HIP_IO_TYPES_H_
 #define AERIAL_MAPPER_HIP_IO_TYPES_H_
 
@@ -51,6 +55,11 @@ class AerialMapperIO {
   void loadImagesFromFile(const std::string& filename_base, size_t num_poses, Images* images,
                           bool load_colored_images = false);
 
+  // <directory><name>.png for every name, decoded on the GPU and appended to *images (8UC1, or
+  // 8UC3 B, G, R).  A missing or refused file is fatal and named.
+  void loadImagesFromFile(const std::string& directory, std::vector<std::string> image_names,
+                          Images* images, bool load_colored_images = false);
+
   void writeDataToDEMGeoTiffColor(const cv::Mat& ortho_image, const Eigen::Vector2d& xy,
                                   const std::string& geotiff_filename);
 
@@ -67,6 +76,12 @@ class AerialMapperIO {
   // *frame_stride, rows *row_step bytes apart: the layout amhip_ortho_backward_process_dev,
   // amhip_mosaic_batch_dev and amhip_stereo_add_frames_dev take); release with amhip_io_free().
   void loadImagesFromFileToDevice(const std::string& filename_base, size_t num_poses,
+                                  bool load_colored_images, uint8_t** dev_frames, int* width, int* height,
+                                  size_t* row_step, size_t* frame_stride);
+
+  // --- extension: the same for the .png overload.
+  void loadImagesFromFileToDevice(const std::string& directory,
+                                  const std::vector<std::string>& image_names,
                                   bool load_colored_images, uint8_t** dev_frames, int* width, int* height,
                                   size_t* row_step, size_t* frame_stride);
 

@@ -472,6 +472,36 @@ int amhip_io_decode_jpeg_frames(int device, const uint8_t* const* files, const s
  * cv::Mats from.  Synchronous. */
 int amhip_io_download_frames(const uint8_t* dev_frames, size_t num_bytes, uint8_t* host_frames);
 
+/* ---- io::AerialMapperIO::loadImagesFromFile(directory, image_names, ..) (aerial-mapper-io.cc:229-249):
+ *      the frames' PNG files, decoded on the GPU ------------------------------------------------------
+ * What cv::imread gives through libpng: inflate as zlib defines it and the pixels Pillow gives, bit for
+ * bit (tests/golden/png_decode/).  Accepted: bit depth 8; colour types 0 (gray), 2 (RGB), 3 (palette),
+ * 4 (gray + alpha), 6 (RGBA); not interlaced; width and height 1..65535; any number of consecutive IDAT
+ * chunks (they are joined into one zlib stream on the host); ancillary chunks skipped unread, tRNS and
+ * gAMA included; bytes behind IEND ignored.  Refused with AMHIP_ERR_ARG and a text naming the field or
+ * chunk, before any device is touched: bit depths 1, 2, 4, 16; Adam7; a bad CRC on IHDR, PLTE, IDAT or
+ * IEND; a missing PLTE, IDAT or IEND; an IDAT behind another chunk that interrupted the run; a truncated
+ * chunk; a length that runs past the file; a zlib header other than CM 8, CINFO <= 7, FDICT 0 with a
+ * valid FCHECK.  Found on the device (AMHIP_ERR_ARG naming the frame and the reason, *dev_frames = NULL):
+ * an undefined Huffman code, an over-subscribed or incomplete set of code lengths (but for the distance
+ * code of one symbol RFC 1951 allows), a dynamic header out of range, block type 3, LEN != ~NLEN, a
+ * distance behind the first output byte, a stream that ends early, output shorter or longer than the
+ * scanlines, a filter type above 4, an Adler-32 mismatch, a palette index outside PLTE.  Stricter than
+ * libpng, which only warns: surplus inflated data is an error.  Laxer than a strict zlib: a distance up
+ * to 32768 is taken whatever CINFO declares.  Alpha is dropped.  colored == 0 on a colour file: libpng's
+ * png_set_rgb_to_gray(.., 0.299, 0.587) as cv::imread sets it up, (9797 R + 19234 G + 3737 B) >> 15,
+ * gAMA ignored -- this one rule is adopted, unpinned.  Scratch (the streams, the raw scanlines) lives for
+ * the call and is bounded by decoding in groups of frames (tuning key pngd_raw_budget_mb). */
+/* host only: applies every host rule above; channels = 1 for colour types 0 and 4, else 3 */
+int amhip_png_info(const uint8_t* file, size_t len, int* width, int* height, int* channels); /* host only; 1 or 3 */
+/* The contract of amhip_io_decode_jpeg_frames: F files in host memory -> ONE stack in HBM, tight rows
+ * (*row_step = width * channels, *frame_stride = height * *row_step).  colored == 0: 8UC1; colored != 0:
+ * 8UC3 B, G, R (gray replicated, palette through PLTE).  All files must have the width and height of file
+ * 0 (else AMHIP_ERR_ARG naming the frame); colour types may differ.  Released with amhip_io_free();
+ * amhip_io_download_frames works on the result. */
+int amhip_io_decode_png_frames(int device, const uint8_t* const* files, const size_t* lens, size_t F, int colored,
+                               uint8_t** dev_frames, int* width, int* height, size_t* row_step, size_t* frame_stride);
+
 /* ---- what leaves the map: images, GeoTiff, grid_map_msgs, binary clouds
  *      (the formats either side of the path) ------------------
  * grid_map_cv, grid_map_ros, GDAL and roscpp are not part of the reference tree; the adopted
@@ -926,6 +956,8 @@ int amhip_session_layer_write_jpeg(amhip_session* s, int layer, int bgr, float l
  *   no_distorted_cull, no_distorted_prune, distorted_square_cull   cameras with a distortion model
  *   jpegd_coef_budget_mb (4096)  amhip_io_decode_jpeg_frames: MB of coefficient scratch per group of frames;
  *                             groups run one after another (a small value forces several groups)
+ *   pngd_raw_budget_mb (4096)  amhip_io_decode_png_frames: MB of raw scanlines per group of frames; groups run
+ *                             one after another, at least one frame each
  *   session_always_copy, session_threads, session_scalar_sums, session_no_partial,
  *   session_serial_sums       device content sums always before the downloads (round 5's order)
  *   session_verify_partial, session_trace          amhip_session: every matrix both ways on every
