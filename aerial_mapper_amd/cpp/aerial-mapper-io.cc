@@ -102,63 +102,44 @@ void AerialMapperIO::loadPointCloudFromFile(
   loadPointCloudFromFile(filename_point_cloud, point_cloud_xyz, &intensities);
 }
 
-// aerial-mapper-io.cc:207-227: cv::imread(filename_base + std::to_string(i) + ".jpg") per pose
-void AerialMapperIO::loadImagesFromFileToDevice(const std::string& filename_base, size_t num_poses,
-                                                bool load_colored_images, uint8_t** dev_frames,
-                                                int* width, int* height, size_t* row_step,
-                                                size_t* frame_stride) {
-  if (!dev_frames || !width || !height || !row_step || !frame_stride)
-    amhip_shim::fatal("loadImagesFromFile", "CHECK(images)");
-  if (num_poses == 0) amhip_shim::fatal("loadImagesFromFile", "no poses: no images to load");
-  std::vector<std::unique_ptr<MappedFile> > mapped;
-  std::vector<const uint8_t*> files;
-  std::vector<size_t> lens;
-  for (size_t i = 0; i < num_poses; ++i) {
-    const std::string name = filename_base + std::to_string(i) + ".jpg";
-    mapped.emplace_back(new MappedFile(name));
-    if (!mapped.back()->data)
-      amhip_shim::fatal("loadImagesFromFile", ("cannot read " + name).c_str());
-    files.push_back(reinterpret_cast<const uint8_t*>(mapped.back()->data));
-    lens.push_back(mapped.back()->size);
-  }
-  amhip_shim::check_status(
-      amhip_io_decode_jpeg_frames(device_index(), files.data(), lens.data(), num_poses,
-                                  load_colored_images ? 1 : 0, dev_frames, width, height, row_step,
-                                  frame_stride),
-      "loadImagesFromFile");
-}
-
 namespace {
 
-// a stack in HBM -> cv::Mats appended to *images; frees the stack
-void append_downloaded(uint8_t* dev, size_t num_poses, int w, int h, size_t row_step, size_t frame_stride,
-                       bool load_colored_images, Images* images);
+typedef int (*DecodeFrames)(int, const uint8_t* const*, const size_t*, size_t, int, uint8_t**, int*, int*,
+                            size_t*, size_t*);
 
-}  // namespace
+// aerial-mapper-io.cc:207-227: cv::imread(filename_base + std::to_string(i) + ".jpg") per pose
+std::vector<std::string> jpg_names(const std::string& filename_base, size_t num_poses) {
+  std::vector<std::string> names;
+  for (size_t i = 0; i < num_poses; ++i) names.push_back(filename_base + std::to_string(i) + ".jpg");
+  return names;
+}
 
 // aerial-mapper-io.cc:229-249: cv::imread(directory + image_names[i] + ".png") per name
-void AerialMapperIO::loadImagesFromFileToDevice(const std::string& directory,
-                                                const std::vector<std::string>& image_names,
-                                                bool load_colored_images, uint8_t** dev_frames,
-                                                int* width, int* height, size_t* row_step,
-                                                size_t* frame_stride) {
+std::vector<std::string> png_names(const std::string& directory, const std::vector<std::string>& image_names) {
+  std::vector<std::string> names;
+  for (const std::string& name : image_names) names.push_back(directory + name + ".png");
+  return names;
+}
+
+// every file mapped and handed to the decoder: one stack in HBM
+void decode_files(const std::vector<std::string>& names, const char* none, DecodeFrames decode,
+                  bool load_colored_images, uint8_t** dev_frames, int* width, int* height, size_t* row_step,
+                  size_t* frame_stride) {
   if (!dev_frames || !width || !height || !row_step || !frame_stride)
     amhip_shim::fatal("loadImagesFromFile", "CHECK(images)");
-  if (image_names.empty()) amhip_shim::fatal("loadImagesFromFile", "no image names: no images to load");
+  if (names.empty()) amhip_shim::fatal("loadImagesFromFile", none);
   std::vector<std::unique_ptr<MappedFile> > mapped;
   std::vector<const uint8_t*> files;
   std::vector<size_t> lens;
-  for (size_t i = 0; i < image_names.size(); ++i) {
-    const std::string name = directory + image_names[i] + ".png";
+  for (const std::string& name : names) {
     mapped.emplace_back(new MappedFile(name));
     if (!mapped.back()->data)
       amhip_shim::fatal("loadImagesFromFile", ("cannot read " + name).c_str());
     files.push_back(reinterpret_cast<const uint8_t*>(mapped.back()->data));
     lens.push_back(mapped.back()->size);
   }
-  const int rc = amhip_io_decode_png_frames(device_index(), files.data(), lens.data(), files.size(),
-                                            load_colored_images ? 1 : 0, dev_frames, width, height,
-                                            row_step, frame_stride);
+  const int rc = decode(device_index(), files.data(), lens.data(), files.size(), load_colored_images ? 1 : 0,
+                        dev_frames, width, height, row_step, frame_stride);
   if (rc != AMHIP_OK) {
     // the library names the frame; the caller knows files: name the file as well
     const std::string text = amhip_last_error();
@@ -166,43 +147,25 @@ void AerialMapperIO::loadImagesFromFileToDevice(const std::string& directory,
     std::string file;
     if (at != std::string::npos) {
       const size_t k = static_cast<size_t>(std::strtoul(text.c_str() + at + 6, nullptr, 10));
-      if (k < image_names.size()) file = " (" + directory + image_names[k] + ".png)";
+      if (k < names.size()) file = " (" + names[k] + ")";
     }
     amhip_shim::fatal("loadImagesFromFile", (text + file).c_str());
   }
 }
 
-void AerialMapperIO::loadImagesFromFile(const std::string& directory, std::vector<std::string> image_names,
-                                        Images* images, bool load_colored_images) {
+// ... downloaded and appended to *images as cv::Mats
+void load_files(const std::vector<std::string>& names, const char* none, DecodeFrames decode,
+                bool load_colored_images, Images* images) {
   if (!images) amhip_shim::fatal("loadImagesFromFile", "CHECK(images)");
   uint8_t* dev = nullptr;
   int w = 0, h = 0;
   size_t row_step = 0, frame_stride = 0;
-  loadImagesFromFileToDevice(directory, image_names, load_colored_images, &dev, &w, &h, &row_step,
-                             &frame_stride);
-  append_downloaded(dev, image_names.size(), w, h, row_step, frame_stride, load_colored_images, images);
-}
-
-void AerialMapperIO::loadImagesFromFile(const std::string& filename_base, size_t num_poses,
-                                        Images* images, bool load_colored_images) {
-  if (!images) amhip_shim::fatal("loadImagesFromFile", "CHECK(images)");
-  uint8_t* dev = nullptr;
-  int w = 0, h = 0;
-  size_t row_step = 0, frame_stride = 0;
-  loadImagesFromFileToDevice(filename_base, num_poses, load_colored_images, &dev, &w, &h, &row_step,
-                             &frame_stride);
-  append_downloaded(dev, num_poses, w, h, row_step, frame_stride, load_colored_images, images);
-}
-
-namespace {
-
-void append_downloaded(uint8_t* dev, size_t num_poses, int w, int h, size_t row_step, size_t frame_stride,
-                       bool load_colored_images, Images* images) {
+  decode_files(names, none, decode, load_colored_images, &dev, &w, &h, &row_step, &frame_stride);
   const int ch = load_colored_images ? 3 : 1;
-  std::vector<uint8_t> host(num_poses * frame_stride);
+  std::vector<uint8_t> host(names.size() * frame_stride);
   amhip_shim::check_status(amhip_io_download_frames(dev, host.size(), host.data()), "loadImagesFromFile");
   amhip_io_free(dev);
-  for (size_t i = 0; i < num_poses; ++i) {
+  for (size_t i = 0; i < names.size(); ++i) {
 #if AERIAL_MAPPER_REAL_DEPS
     cv::Mat image(h, w, load_colored_images ? CV_8UC3 : CV_8UC1);
 #else
@@ -216,7 +179,38 @@ void append_downloaded(uint8_t* dev, size_t num_poses, int w, int h, size_t row_
   }
 }
 
+const char kNoPoses[] = "no poses: no images to load";
+const char kNoNames[] = "no image names: no images to load";
+
 }  // namespace
+
+void AerialMapperIO::loadImagesFromFileToDevice(const std::string& filename_base, size_t num_poses,
+                                                bool load_colored_images, uint8_t** dev_frames,
+                                                int* width, int* height, size_t* row_step,
+                                                size_t* frame_stride) {
+  decode_files(jpg_names(filename_base, num_poses), kNoPoses, amhip_io_decode_jpeg_frames, load_colored_images,
+               dev_frames, width, height, row_step, frame_stride);
+}
+
+void AerialMapperIO::loadImagesFromFileToDevice(const std::string& directory,
+                                                const std::vector<std::string>& image_names,
+                                                bool load_colored_images, uint8_t** dev_frames,
+                                                int* width, int* height, size_t* row_step,
+                                                size_t* frame_stride) {
+  decode_files(png_names(directory, image_names), kNoNames, amhip_io_decode_png_frames, load_colored_images,
+               dev_frames, width, height, row_step, frame_stride);
+}
+
+void AerialMapperIO::loadImagesFromFile(const std::string& directory, std::vector<std::string> image_names,
+                                        Images* images, bool load_colored_images) {
+  load_files(png_names(directory, image_names), kNoNames, amhip_io_decode_png_frames, load_colored_images, images);
+}
+
+void AerialMapperIO::loadImagesFromFile(const std::string& filename_base, size_t num_poses,
+                                        Images* images, bool load_colored_images) {
+  load_files(jpg_names(filename_base, num_poses), kNoPoses, amhip_io_decode_jpeg_frames, load_colored_images,
+             images);
+}
 
 void AerialMapperIO::loadPosesFromFileStandard(const std::string& filename, Poses* T_G_Bs) {
   if (!T_G_Bs) amhip_shim::fatal("loadPosesFromFileStandard", "CHECK(T_G_Bs)");

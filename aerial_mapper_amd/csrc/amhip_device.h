@@ -4,7 +4,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+
 namespace amhip {
+
+// the first active lane's v in every lane: what a wave-uniform walk branches on (readfirstlane, so
+// the compiler keeps it in a scalar register)
+__device__ __forceinline__ uint32_t uni(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
 
 // ---------------------------------------------------------------------------
 // wave / workgroup scans

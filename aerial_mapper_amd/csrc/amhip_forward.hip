@@ -34,7 +34,7 @@
 #include <string>
 #include <vector>
 
-#include "amhip_common.h"
+#include "amhip_frame_stack.h"
 
 namespace amhip {
 
@@ -881,20 +881,14 @@ int amhip_mosaic_create(const amhip_mosaic_desc* desc, const amhip_camera* cam, 
   if (desc->width_mosaic_pixels <= 0 || desc->height_mosaic_pixels <= 0 || cam->width <= 0 ||
       cam->height <= 0)
     return fwd_arg_fail("amhip_mosaic_create: empty mosaic or image");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    set_last_error("no HIP device available (libaerial_mapper_hip has no CPU fallback)");
-    return AMHIP_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) return fwd_arg_fail("amhip_mosaic_create: bad device index");
+  int rc = open_device(device, "amhip_mosaic_create");
+  if (rc) return rc;
   amhip_mosaic* h = new amhip_mosaic();
   Mosaic* m = &h->impl;
   m->desc = *desc;
   m->cam = *cam;
   m->device = device;
   m->pixels = (size_t)desc->width_mosaic_pixels * (size_t)desc->height_mosaic_pixels;
-  int rc = AMHIP_OK;
   do {
     if ((rc = fwd_use(m))) break;
     hipError_t e = hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking);

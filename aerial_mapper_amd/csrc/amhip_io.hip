@@ -35,7 +35,7 @@
 #include <string>
 #include <vector>
 
-#include "amhip_common.h"
+#include "amhip_frame_stack.h"
 #include "amhip_pow5_table.h"
 
 namespace amhip {
@@ -467,26 +467,6 @@ k_io_keep_emit(const double* __restrict__ xyz, const int32_t* __restrict__ inten
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    AMHIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
-    return AMHIP_OK;
-  }
-  template <typename T>
-  T* as() {
-    return static_cast<T*>(p);
-  }
-  void* release() {
-    void* q = p;
-    p = nullptr;
-    return q;
-  }
-};
-
 int io_fail(const char* msg) {
   set_last_error(msg);
   return AMHIP_ERR_ARG;
@@ -496,14 +476,8 @@ int io_fail(const char* msg) {
 
 int io_parse_point_cloud(int device, const char* host_text, size_t len, double** out_xyz,
                          int32_t** out_inten, size_t* out_n, size_t* out_slow) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    set_last_error("no HIP device available (libaerial_mapper_hip has no CPU fallback)");
-    return AMHIP_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) return io_fail("amhip_io: bad device index");
-  AMHIP_TRY(hipSetDevice(device));
+  int rc;
+  if ((rc = open_device(device, "amhip_io"))) return rc;
   *out_xyz = nullptr;
   *out_inten = nullptr;
   *out_n = 0;
@@ -513,7 +487,6 @@ int io_parse_point_cloud(int device, const char* host_text, size_t len, double**
   const size_t nblk = (len + kIoChunk - 1) / kIoChunk;
   if (nblk >= 0xFFFFFFFFull) return io_fail("amhip_io: text larger than 16 TB");
   DevBuf text, counts, total, table;
-  int rc;
   if ((rc = text.alloc(len + 16))) return rc;
   if ((rc = counts.alloc((nblk + 1) * sizeof(uint32_t)))) return rc;
   if ((rc = total.alloc(4 * sizeof(unsigned long long)))) return rc;

@@ -37,9 +37,9 @@
 #include <string>
 #include <vector>
 
-#include "amhip_common.h"
+#include "amhip_device.h"
+#include "amhip_frame_stack.h"
 #include "amhip_jpeg_decode_host.h"
-#include "amhip_tuning.h"
 
 namespace amhip {
 
@@ -50,11 +50,6 @@ using jpegd::HuffTable;
 
 constexpr int kWindow = 1024;            // file bytes in LDS (16 per lane)
 constexpr int kIdctBlocks = 32;          // k_jpegd_idct: 256 lanes, 8 per block
-// MB of coefficients per group of frames (tuning knob jpegd_coef_budget_mb).  Groups run one after
-// another and each takes as long as its longest scan, so the default holds the demo flags' 249 frames
-// of 1920 x 1080 in one group (1.0 GB gray, 1.5 GB 4:2:0, planes half as much again).
-constexpr double kCoefBudgetMB = 4096.0;
-constexpr size_t kGroupFrames = 32768;   // (grid.y / grid.z of the per-frame launches)
 
 struct Zigzag {
   uint8_t at[64];
@@ -65,10 +60,6 @@ constexpr Zigzag make_zigzag() {
   return z;
 }
 __constant__ Zigzag d_zigzag = make_zigzag();
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
 
 // The bit reader of one frame (jpeg_fill_bit_buffer, jdhuff.c).  Everything in here is the same
 // in every lane.
@@ -457,162 +448,88 @@ __global__ __launch_bounds__(256) void k_jpegd_colour(const Frame* __restrict__ 
   dst[2] = clamp8(R);
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
+// The codec description of decode_frame_stack (amhip_frame_stack.h): files are uploaded as they are,
+// one behind the other; a frame costs its coefficients, 128 bytes per block.
+struct JpegStack {
+  using Frame = jpegd::Frame;
+  static constexpr const char* kDecode = "amhip_io_decode_jpeg_frames";
+  static constexpr const char* kInfo = "amhip_jpeg_info";
+  // MB of coefficients per group of frames.  Groups run one after another and each takes as long as
+  // its longest scan, so the default holds the demo flags' 249 frames of 1920 x 1080 in one group
+  // (1.0 GB gray, 1.5 GB 4:2:0, planes half as much again).
+  static constexpr const char* kBudgetKey = "jpegd_coef_budget_mb";
+  static constexpr double kBudgetMB = 4096.0;
+  static constexpr size_t kGroupFrames = 32768;   // (grid.y / grid.z of the per-frame launches)
+
+  static bool info(const uint8_t* file, size_t len, int* width, int* height, int* channels, char* err,
+                   size_t errcap) {
+    Frame f;
+    if (!jpegd::parse(file, len, &f, err, errcap)) return false;
+    *width = f.width;
+    *height = f.height;
+    *channels = f.ncomp;
+    return true;
   }
-  int alloc(size_t bytes) {
-    AMHIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
+  static const char* status_text(uint32_t s) { return jpegd::status_text(s); }
+
+  size_t total = 0;      // bytes of the files so far
+  size_t max_idct = 0;   // most blocks k_jpegd_idct transforms in one frame
+  DevBuf bytes, coef, planes;
+
+  bool parse(const uint8_t* file, size_t len, Frame* f, char* err, size_t errcap) {
+    if (!jpegd::parse(file, len, f, err, errcap)) return false;
+    f->scan_begin += total;
+    f->scan_end += total;
+    total += len;
+    return true;
+  }
+  size_t cost_bytes(const Frame& f) const { return (size_t)f.comp_base[f.ncomp] * 128; }
+  void place(Frame* f, size_t base_bytes, int colored) {
+    f->coef_base = base_bytes / 128;
+    f->plane_base = f->coef_base * 64;
+    max_idct = std::max(max_idct, (size_t)(colored ? f->comp_base[f->ncomp] : f->comp_base[1]));
+  }
+  int upload(const uint8_t* const* files, const size_t* lens, size_t F, size_t max_group_bytes, int colored,
+             hipStream_t stream) {
+    int rc;
+    if ((rc = bytes.alloc(total))) return rc;
+    if ((rc = coef.alloc(max_group_bytes))) return rc;
+    if (colored && (rc = planes.alloc(max_group_bytes / 2))) return rc;
+    size_t at = 0;
+    for (size_t i = 0; i < F; ++i) {
+      AMHIP_TRY(hipMemcpyAsync(bytes.as<uint8_t>() + at, files[i], lens[i], hipMemcpyHostToDevice, stream));
+      at += lens[i];
+    }
     return AMHIP_OK;
   }
-  template <typename T>
-  T* as() {
-    return static_cast<T*>(p);
-  }
-  void* release() {
-    void* q = p;
-    p = nullptr;
-    return q;
+  void launch_group(size_t first, size_t n, const StackLaunch<Frame>& s) {
+    hipLaunchKernelGGL(k_jpegd_entropy, dim3((unsigned)n), dim3(64), 0, s.stream, bytes.as<uint8_t>(), s.frames,
+                       first, coef.as<int16_t>(), s.status);
+    hipLaunchKernelGGL(k_jpegd_idct, dim3((unsigned)((max_idct + kIdctBlocks - 1) / kIdctBlocks), (unsigned)n),
+                       dim3(256), 0, s.stream, s.frames, first, coef.as<int16_t>(), planes.as<uint8_t>(), s.out,
+                       s.frame_stride, s.row_step, s.colored);
+    if (s.colored)
+      hipLaunchKernelGGL(k_jpegd_colour, dim3((unsigned)((s.width + 255) / 256), (unsigned)s.height, (unsigned)n),
+                         dim3(256), 0, s.stream, s.frames, first, planes.as<uint8_t>(), s.out, s.frame_stride,
+                         s.row_step);
   }
 };
 
-int fail_arg(const std::string& msg) {
-  set_last_error("amhip_io_decode_jpeg_frames: " + msg);
-  return AMHIP_ERR_ARG;
-}
-
 }  // namespace
-
-int io_decode_jpeg_frames(int device, const uint8_t* const* files, const size_t* lens, size_t F, int colored,
-                          uint8_t** dev_frames, int* width, int* height, size_t* row_step,
-                          size_t* frame_stride) {
-  // ---- everything the host can see, before any device is touched ---------------------------
-  std::vector<Frame> frames(F);
-  std::vector<size_t> file_at(F);
-  size_t total = 0;
-  char text[160];
-  for (size_t i = 0; i < F; ++i) {
-    if (!files[i]) return fail_arg("frame " + std::to_string(i) + ": null file");
-    if (!jpegd::parse(files[i], lens[i], &frames[i], text, sizeof(text)))
-      return fail_arg("frame " + std::to_string(i) + ": " + text);
-    if (frames[i].width != frames[0].width || frames[i].height != frames[0].height)
-      return fail_arg("frame " + std::to_string(i) + " is " + std::to_string(frames[i].width) + " x " +
-                      std::to_string(frames[i].height) + ", frame 0 is " + std::to_string(frames[0].width) +
-                      " x " + std::to_string(frames[0].height));
-    file_at[i] = total;
-    frames[i].scan_begin += total;
-    frames[i].scan_end += total;
-    total += lens[i];
-  }
-  const int W = frames[0].width, H = frames[0].height, ch = colored ? 3 : 1;
-  // groups of consecutive frames whose coefficients fit the budget (at least one frame each)
-  std::vector<size_t> group_begin;
-  const double budget_mb = tuning("jpegd_coef_budget_mb", kCoefBudgetMB);
-  const size_t budget = (size_t)((budget_mb >= 0.0 && budget_mb <= 1048576.0 ? budget_mb : kCoefBudgetMB) * 1048576.0);
-  size_t max_blocks = 0, max_idct = 0;
-  {
-    size_t blocks = 0, count = 0;
-    for (size_t i = 0; i < F; ++i) {
-      const size_t nb = frames[i].comp_base[frames[i].ncomp];
-      if (i == 0 || (blocks + nb) * 128 > budget || count == kGroupFrames) {
-        group_begin.push_back(i);
-        blocks = 0;
-        count = 0;
-      }
-      frames[i].coef_base = blocks;
-      frames[i].plane_base = blocks * 64;
-      blocks += nb;
-      ++count;
-      max_blocks = std::max(max_blocks, blocks);
-      max_idct = std::max(max_idct, (size_t)(colored ? nb : frames[i].comp_base[1]));
-    }
-    group_begin.push_back(F);
-  }
-  // ---- the device ----------------------------------------------------------------------------
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    set_last_error("no HIP device available (libaerial_mapper_hip has no CPU fallback)");
-    return AMHIP_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) return fail_arg("bad device index");
-  AMHIP_TRY(hipSetDevice(device));
-  hipStream_t stream = nullptr;   // the default stream: this entry point is synchronous
-  const size_t rstep = (size_t)W * ch, fstride = rstep * (size_t)H;
-  DevBuf bytes, desc, coef, planes, status, out;
-  int rc;
-  if ((rc = bytes.alloc(total))) return rc;
-  if ((rc = desc.alloc(F * sizeof(Frame)))) return rc;
-  if ((rc = coef.alloc(max_blocks * 128))) return rc;
-  if (colored && (rc = planes.alloc(max_blocks * 64))) return rc;
-  if ((rc = status.alloc(F * sizeof(uint32_t)))) return rc;
-  if ((rc = out.alloc(F * fstride))) return rc;
-  for (size_t i = 0; i < F; ++i)
-    AMHIP_TRY(hipMemcpyAsync(bytes.as<uint8_t>() + file_at[i], files[i], lens[i], hipMemcpyHostToDevice, stream));
-  AMHIP_TRY(hipMemcpyAsync(desc.p, frames.data(), F * sizeof(Frame), hipMemcpyHostToDevice, stream));
-  AMHIP_TRY(hipMemsetAsync(status.p, 0, F * sizeof(uint32_t), stream));
-  const Frame* dframes = desc.as<Frame>();
-  for (size_t g = 0; g + 1 < group_begin.size(); ++g) {
-    const size_t first = group_begin[g], n = group_begin[g + 1] - first;
-    hipLaunchKernelGGL(k_jpegd_entropy, dim3((unsigned)n), dim3(64), 0, stream, bytes.as<uint8_t>(), dframes,
-                       first, coef.as<int16_t>(), status.as<uint32_t>());
-    hipLaunchKernelGGL(k_jpegd_idct, dim3((unsigned)((max_idct + kIdctBlocks - 1) / kIdctBlocks), (unsigned)n),
-                       dim3(256), 0, stream, dframes, first, coef.as<int16_t>(), planes.as<uint8_t>(),
-                       out.as<uint8_t>(), fstride, rstep, colored ? 1 : 0);
-    if (colored)
-      hipLaunchKernelGGL(k_jpegd_colour, dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)n), dim3(256),
-                         0, stream, dframes, first, planes.as<uint8_t>(), out.as<uint8_t>(), fstride, rstep);
-    AMHIP_TRY(hipGetLastError());
-  }
-  std::vector<uint32_t> st(F);
-  AMHIP_TRY(hipMemcpyAsync(st.data(), status.p, F * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  AMHIP_TRY(hipStreamSynchronize(stream));
-  for (size_t i = 0; i < F; ++i)
-    if (st[i]) return fail_arg("frame " + std::to_string(i) + ": " + jpegd::status_text(st[i]));
-  *dev_frames = static_cast<uint8_t*>(out.release());
-  *width = W;
-  *height = H;
-  *row_step = rstep;
-  *frame_stride = fstride;
-  return AMHIP_OK;
-}
 
 }  // namespace amhip
 
 extern "C" {
 
 int amhip_jpeg_info(const uint8_t* file, size_t len, int* width, int* height, int* channels) {
-  if (!file || !width || !height || !channels) {
-    amhip::set_last_error("amhip_jpeg_info: null argument");
-    return AMHIP_ERR_ARG;
-  }
-  amhip::jpegd::Frame f;
-  char text[160];
-  if (!amhip::jpegd::parse(file, len, &f, text, sizeof(text))) {
-    amhip::set_last_error(std::string("amhip_jpeg_info: ") + text);
-    return AMHIP_ERR_ARG;
-  }
-  *width = f.width;
-  *height = f.height;
-  *channels = f.ncomp;
-  return AMHIP_OK;
+  return amhip::image_info<amhip::JpegStack>(file, len, width, height, channels);
 }
 
 int amhip_io_decode_jpeg_frames(int device, const uint8_t* const* files, const size_t* lens, size_t F, int colored,
                                 uint8_t** dev_frames, int* width, int* height, size_t* row_step,
                                 size_t* frame_stride) {
-  if (dev_frames) *dev_frames = nullptr;
-  if (!files || !lens || !dev_frames || !width || !height || !row_step || !frame_stride) {
-    amhip::set_last_error("amhip_io_decode_jpeg_frames: null argument");
-    return AMHIP_ERR_ARG;
-  }
-  if (F == 0) {
-    amhip::set_last_error("amhip_io_decode_jpeg_frames: no frames (F = 0)");
-    return AMHIP_ERR_ARG;
-  }
-  return amhip::io_decode_jpeg_frames(device, files, lens, F, colored, dev_frames, width, height, row_step,
-                                      frame_stride);
+  return amhip::decode_frame_stack<amhip::JpegStack>(device, files, lens, F, colored, dev_frames, width, height,
+                                                     row_step, frame_stride);
 }
 
 int amhip_io_download_frames(const uint8_t* dev_frames, size_t num_bytes, uint8_t* host_frames) {

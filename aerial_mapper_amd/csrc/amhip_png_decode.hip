@@ -33,9 +33,9 @@
 #include <string>
 #include <vector>
 
-#include "amhip_common.h"
+#include "amhip_device.h"
+#include "amhip_frame_stack.h"
 #include "amhip_png_decode_host.h"
-#include "amhip_tuning.h"
 
 namespace amhip {
 
@@ -49,11 +49,6 @@ constexpr int kFlush = 4096;             // bytes that leave the ring at a time
 constexpr int kLitBits = 10, kDistBits = 8;   // peeked bits of the two lookup tables
 constexpr int kMaxLit = 288, kMaxDist = 32;
 constexpr uint32_t kAdlerMod = 65521u;
-// MB of raw scanlines per group of frames (tuning knob pngd_raw_budget_mb).  Groups run one after
-// another and each takes as long as its longest stream, so the default holds the demo flags' 249
-// frames of 1920 x 1080 in one group (0.5 GB gray, 1.5 GB RGB).
-constexpr double kRawBudgetMB = 4096.0;
-constexpr size_t kGroupFrames = 32768;   // (grid.z of the per-pixel launch)
 
 struct Tables {
   uint16_t len_base[32], len_extra[32], dist_base[32], dist_extra[32];
@@ -83,10 +78,6 @@ constexpr Tables make_tables() {
   return t;
 }
 __constant__ Tables d_tables = make_tables();
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
 
 // One prefix code in LDS: a lookup table over the next `bits` bits of the stream (entry = symbol |
 // length << 9, 0: no code that short), and for the longer codes the count per length and the
@@ -640,164 +631,84 @@ __global__ __launch_bounds__(256) void k_pngd_pixels(const Frame* __restrict__ f
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    AMHIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
-    return AMHIP_OK;
-  }
-  template <typename T>
-  T* as() {
-    return static_cast<T*>(p);
-  }
-  void* release() {
-    void* q = p;
-    p = nullptr;
-    return q;
-  }
-};
-
-int fail_arg(const std::string& msg) {
-  set_last_error("amhip_io_decode_png_frames: " + msg);
-  return AMHIP_ERR_ARG;
-}
-
 size_t round16(size_t n) {
   return (n + 15) & ~(size_t)15;
 }
 
-}  // namespace
+// The codec description of decode_frame_stack (amhip_frame_stack.h): every frame's IDAT payloads are
+// joined into one zlib stream at a multiple of 16; a frame costs its raw scanlines, rounded up to 16.
+struct PngStack {
+  using Frame = pngd::Frame;
+  static constexpr const char* kDecode = "amhip_io_decode_png_frames";
+  static constexpr const char* kInfo = "amhip_png_info";
+  // MB of raw scanlines per group of frames.  Groups run one after another and each takes as long as
+  // its longest stream, so the default holds the demo flags' 249 frames of 1920 x 1080 in one group
+  // (0.5 GB gray, 1.5 GB RGB).
+  static constexpr const char* kBudgetKey = "pngd_raw_budget_mb";
+  static constexpr double kBudgetMB = 4096.0;
+  static constexpr size_t kGroupFrames = 32768;   // (grid.z of the per-pixel launch)
 
-int io_decode_png_frames(int device, const uint8_t* const* files, const size_t* lens, size_t F, int colored,
-                         uint8_t** dev_frames, int* width, int* height, size_t* row_step, size_t* frame_stride) {
-  // ---- everything the host can see, before any device is touched ---------------------------
-  std::vector<Frame> frames(F);
-  std::vector<uint8_t> streams;   // every frame's IDAT payloads as one zlib stream, each at a multiple of 16
-  char text[160];
-  {
-    pngd::Parsed parsed;
-    for (size_t i = 0; i < F; ++i) {
-      if (!files[i]) return fail_arg("frame " + std::to_string(i) + ": null file");
-      if (!pngd::parse(files[i], lens[i], &parsed, text, sizeof(text)))
-        return fail_arg("frame " + std::to_string(i) + ": " + text);
-      frames[i] = parsed.f;
-      if (frames[i].width != frames[0].width || frames[i].height != frames[0].height)
-        return fail_arg("frame " + std::to_string(i) + " is " + std::to_string(frames[i].width) + " x " +
-                        std::to_string(frames[i].height) + ", frame 0 is " + std::to_string(frames[0].width) +
-                        " x " + std::to_string(frames[0].height));
-      const size_t at = streams.size();
-      streams.resize(at + round16(parsed.zlen), 0);
-      pngd::concat(files[i], parsed, streams.data() + at);
-      frames[i].stream_begin += at;
-      frames[i].stream_end += at;
-    }
+  static bool info(const uint8_t* file, size_t len, int* width, int* height, int* channels, char* err,
+                   size_t errcap) {
+    pngd::Parsed p;
+    if (!pngd::parse(file, len, &p, err, errcap)) return false;
+    *width = p.f.width;
+    *height = p.f.height;
+    *channels = (p.f.colour_type == 0 || p.f.colour_type == 4) ? 1 : 3;
+    return true;
   }
-  const int W = frames[0].width, H = frames[0].height, ch = colored ? 3 : 1;
-  // groups of consecutive frames whose raw scanlines fit the budget (at least one frame each)
-  std::vector<size_t> group_begin;
-  const double budget_mb = tuning("pngd_raw_budget_mb", kRawBudgetMB);
-  const size_t budget = (size_t)((budget_mb >= 0.0 && budget_mb <= 1048576.0 ? budget_mb : kRawBudgetMB) * 1048576.0);
-  size_t max_raw = 0;
-  {
-    size_t bytes = 0, count = 0;
-    for (size_t i = 0; i < F; ++i) {
-      const size_t need = round16((size_t)frames[i].raw_len);
-      if (i == 0 || bytes + need > budget || count == kGroupFrames) {
-        group_begin.push_back(i);
-        bytes = 0;
-        count = 0;
-      }
-      frames[i].raw_base = bytes;
-      bytes += need;
-      ++count;
-      max_raw = std::max(max_raw, bytes);
-    }
-    group_begin.push_back(F);
+  static const char* status_text(uint32_t s) { return pngd::status_text(s); }
+
+  std::vector<uint8_t> streams;   // every frame's zlib stream, each at a multiple of 16
+  pngd::Parsed parsed;
+  DevBuf bytes, raw;
+
+  bool parse(const uint8_t* file, size_t len, Frame* f, char* err, size_t errcap) {
+    if (!pngd::parse(file, len, &parsed, err, errcap)) return false;
+    const size_t at = streams.size();
+    streams.resize(at + round16(parsed.zlen), 0);
+    pngd::concat(file, parsed, streams.data() + at);
+    *f = parsed.f;
+    f->stream_begin += at;
+    f->stream_end += at;
+    return true;
   }
-  // ---- the device ----------------------------------------------------------------------------
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    set_last_error("no HIP device available (libaerial_mapper_hip has no CPU fallback)");
-    return AMHIP_ERR_NO_DEVICE;
+  size_t cost_bytes(const Frame& f) const { return round16((size_t)f.raw_len); }
+  void place(Frame* f, size_t base_bytes, int /*colored*/) { f->raw_base = base_bytes; }
+  int upload(const uint8_t* const*, const size_t*, size_t, size_t max_group_bytes, int /*colored*/,
+             hipStream_t stream) {
+    int rc;
+    if ((rc = bytes.alloc(streams.size()))) return rc;
+    if ((rc = raw.alloc(max_group_bytes))) return rc;
+    AMHIP_TRY(hipMemcpyAsync(bytes.p, streams.data(), streams.size(), hipMemcpyHostToDevice, stream));
+    return AMHIP_OK;
   }
-  if (device < 0 || device >= ndev) return fail_arg("bad device index");
-  AMHIP_TRY(hipSetDevice(device));
-  hipStream_t stream = nullptr;   // the default stream: this entry point is synchronous
-  const size_t rstep = (size_t)W * ch, fstride = rstep * (size_t)H;
-  DevBuf bytes, desc, raw, status, out;
-  int rc;
-  if ((rc = bytes.alloc(streams.size()))) return rc;
-  if ((rc = desc.alloc(F * sizeof(Frame)))) return rc;
-  if ((rc = raw.alloc(max_raw))) return rc;
-  if ((rc = status.alloc(F * sizeof(uint32_t)))) return rc;
-  if ((rc = out.alloc(F * fstride))) return rc;
-  AMHIP_TRY(hipMemcpyAsync(bytes.p, streams.data(), streams.size(), hipMemcpyHostToDevice, stream));
-  AMHIP_TRY(hipMemcpyAsync(desc.p, frames.data(), F * sizeof(Frame), hipMemcpyHostToDevice, stream));
-  AMHIP_TRY(hipMemsetAsync(status.p, 0, F * sizeof(uint32_t), stream));
-  const Frame* dframes = desc.as<Frame>();
-  for (size_t g = 0; g + 1 < group_begin.size(); ++g) {
-    const size_t first = group_begin[g], n = group_begin[g + 1] - first;
-    hipLaunchKernelGGL(k_pngd_inflate, dim3((unsigned)n), dim3(64), 0, stream, bytes.as<uint8_t>(), dframes, first,
-                       raw.as<uint8_t>(), status.as<uint32_t>());
-    hipLaunchKernelGGL(k_pngd_unfilter, dim3((unsigned)n), dim3(64), 0, stream, dframes, first, raw.as<uint8_t>(),
-                       status.as<uint32_t>());
-    hipLaunchKernelGGL(k_pngd_pixels, dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)n), dim3(256), 0,
-                       stream, dframes, first, raw.as<uint8_t>(), out.as<uint8_t>(), fstride, rstep, colored ? 1 : 0,
-                       status.as<uint32_t>());
-    AMHIP_TRY(hipGetLastError());
+  void launch_group(size_t first, size_t n, const StackLaunch<Frame>& s) {
+    hipLaunchKernelGGL(k_pngd_inflate, dim3((unsigned)n), dim3(64), 0, s.stream, bytes.as<uint8_t>(), s.frames,
+                       first, raw.as<uint8_t>(), s.status);
+    hipLaunchKernelGGL(k_pngd_unfilter, dim3((unsigned)n), dim3(64), 0, s.stream, s.frames, first,
+                       raw.as<uint8_t>(), s.status);
+    hipLaunchKernelGGL(k_pngd_pixels, dim3((unsigned)((s.width + 255) / 256), (unsigned)s.height, (unsigned)n),
+                       dim3(256), 0, s.stream, s.frames, first, raw.as<uint8_t>(), s.out, s.frame_stride,
+                       s.row_step, s.colored, s.status);
   }
-  std::vector<uint32_t> st(F);
-  AMHIP_TRY(hipMemcpyAsync(st.data(), status.p, F * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  AMHIP_TRY(hipStreamSynchronize(stream));
-  for (size_t i = 0; i < F; ++i)
-    if (st[i]) return fail_arg("frame " + std::to_string(i) + ": " + pngd::status_text(st[i]));
-  *dev_frames = static_cast<uint8_t*>(out.release());
-  *width = W;
-  *height = H;
-  *row_step = rstep;
-  *frame_stride = fstride;
-  return AMHIP_OK;
-}
+};
+
+}  // namespace
 
 }  // namespace amhip
 
 extern "C" {
 
 int amhip_png_info(const uint8_t* file, size_t len, int* width, int* height, int* channels) {
-  if (!file || !width || !height || !channels) {
-    amhip::set_last_error("amhip_png_info: null argument");
-    return AMHIP_ERR_ARG;
-  }
-  amhip::pngd::Parsed p;
-  char text[160];
-  if (!amhip::pngd::parse(file, len, &p, text, sizeof(text))) {
-    amhip::set_last_error(std::string("amhip_png_info: ") + text);
-    return AMHIP_ERR_ARG;
-  }
-  *width = p.f.width;
-  *height = p.f.height;
-  *channels = (p.f.colour_type == 0 || p.f.colour_type == 4) ? 1 : 3;
-  return AMHIP_OK;
+  return amhip::image_info<amhip::PngStack>(file, len, width, height, channels);
 }
 
 int amhip_io_decode_png_frames(int device, const uint8_t* const* files, const size_t* lens, size_t F, int colored,
                                uint8_t** dev_frames, int* width, int* height, size_t* row_step,
                                size_t* frame_stride) {
-  if (dev_frames) *dev_frames = nullptr;
-  if (!files || !lens || !dev_frames || !width || !height || !row_step || !frame_stride) {
-    amhip::set_last_error("amhip_io_decode_png_frames: null argument");
-    return AMHIP_ERR_ARG;
-  }
-  if (F == 0) {
-    amhip::set_last_error("amhip_io_decode_png_frames: no frames (F = 0)");
-    return AMHIP_ERR_ARG;
-  }
-  return amhip::io_decode_png_frames(device, files, lens, F, colored, dev_frames, width, height, row_step,
-                                     frame_stride);
+  return amhip::decode_frame_stack<amhip::PngStack>(device, files, lens, F, colored, dev_frames, width, height,
+                                                    row_step, frame_stride);
 }
 
 }  // extern "C"

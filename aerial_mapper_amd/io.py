@@ -1,11 +1,14 @@
-"""io::AerialMapperIO's loaders (aerial-mapper-io.cc:103-121,207-227,309-347).
+"""io::AerialMapperIO's loaders (aerial-mapper-io.cc:103-121,207-249,309-347).
 
 `load_point_cloud_text` tokenises and parses the `x y z intensity` file on the
 GPU (amhip_io.hip) and leaves the cloud in HBM, ready for Dsm.process /
 OrthoFromPcl.process; `load_poses_text` reads the small pose file on the host;
-`load_images` / `decode_jpeg_frames` decode the frames' JPEG files on the GPU
-(amhip_jpeg_decode.hip) and leave them in HBM as one stack, ready for
-OrthoBackwardGrid.process, OrthoForwardHomography.batch and Stereo.add_frames.
+`load_images` / `decode_jpeg_frames` decode the frames' JPEG files
+(`<base><i>.jpg`, amhip_jpeg_decode.hip) and `load_images_named` /
+`decode_png_frames` their PNG files (`<directory><name>.png`,
+amhip_png_decode.hip) on the GPU; both leave them in HBM as one stack in the
+same layout (DeviceFrames), ready for OrthoBackwardGrid.process,
+OrthoForwardHomography.batch and Stereo.add_frames.
 """
 import ctypes as C
 import mmap
@@ -14,6 +17,22 @@ import os
 import numpy as np
 
 from . import hip_lib as L
+
+
+def _device_view(owner, ptr, shape, typestr, strides, device):
+    """A torch CUDA tensor over the library's allocation at `ptr` (strides None: packed); the tensor
+    keeps `owner`, which frees the allocation, alive."""
+    import torch
+
+    class _Holder(object):
+        pass
+
+    h = _Holder()
+    h.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 2}
+    if strides is not None:
+        h.__cuda_array_interface__["strides"] = strides
+    h._keepalive = owner
+    return torch.as_tensor(h, device="cuda:%d" % device)
 
 
 class DeviceCloud(object):
@@ -26,25 +45,15 @@ class DeviceCloud(object):
         self.device = device
         self.strtod_tokens = int(strtod_tokens)
 
-    def _view(self, ptr, shape, typestr):
-        import torch
-
-        class _Holder(object):
-            pass
-
-        h = _Holder()
-        h.__cuda_array_interface__ = {"shape": shape, "typestr": typestr,
-                                      "data": (int(ptr), False), "version": 2}
-        h._keepalive = self
-        return torch.as_tensor(h, device="cuda:%d" % self.device)
-
     @property
     def xyz(self):
-        return self._view(self._xyz_ptr, (self.n, 3), "<f8") if self.n else None
+        return _device_view(self, self._xyz_ptr, (self.n, 3), "<f8", None, self.device) if self.n else None
 
     @property
     def intensities(self):
-        return self._view(self._inten_ptr, (self.n,), "<i4") if self.n and self._inten_ptr else None
+        if not (self.n and self._inten_ptr):
+            return None
+        return _device_view(self, self._inten_ptr, (self.n,), "<i4", None, self.device)
 
     def to_host(self):
         xyz = np.empty((self.n, 3), np.float64)
@@ -128,18 +137,9 @@ class DeviceFrames(object):
 
     @property
     def frames(self):
-        import torch
-
-        class _Holder(object):
-            pass
-
         shape = (self.num_frames, self.height, self.width) + ((3,) if self.channels == 3 else ())
         strides = (self.frame_stride, self.row_step) + ((3, 1) if self.channels == 3 else (1,))
-        h = _Holder()
-        h.__cuda_array_interface__ = {"shape": shape, "typestr": "|u1", "strides": strides,
-                                      "data": (int(self._ptr), False), "version": 2}
-        h._keepalive = self
-        return torch.as_tensor(h, device="cuda:%d" % self.device)
+        return _device_view(self, self._ptr, shape, "|u1", strides, self.device)
 
     def to_host(self):
         """-> numpy uint8 (F, H, W) or (F, H, W, 3)"""
@@ -159,53 +159,48 @@ class DeviceFrames(object):
     __del__ = close
 
 
-def jpeg_info(data):
-    """-> (width, height, channels) of a JPEG file's bytes; raises for a file the decoder refuses."""
+def _image_info(symbol, data):
     data = bytes(data)
     w, h, ch = C.c_int(), C.c_int(), C.c_int()
-    L.check(L.load().amhip_jpeg_info(data, len(data), C.byref(w), C.byref(h), C.byref(ch)))
+    L.check(getattr(L.load(), symbol)(data, len(data), C.byref(w), C.byref(h), C.byref(ch)))
     return w.value, h.value, ch.value
+
+
+def _decode_frames(symbol, files, colored, device):
+    lib = L.load()
+    files = [f if isinstance(f, bytes) else bytes(f) for f in files]
+    n = len(files)
+    ptrs = (C.c_char_p * max(n, 1))(*files)
+    lens = (C.c_size_t * max(n, 1))(*[len(f) for f in files])
+    out = C.c_void_p()
+    w, h = C.c_int(), C.c_int()
+    row, stride = C.c_size_t(), C.c_size_t()
+    L.check(getattr(lib, symbol)(int(device), ptrs, lens, n, 1 if colored else 0, C.byref(out),
+                                 C.byref(w), C.byref(h), C.byref(row), C.byref(stride)))
+    return DeviceFrames(out.value, n, w.value, h.value, 3 if colored else 1, row.value, stride.value, int(device))
+
+
+def jpeg_info(data):
+    """-> (width, height, channels) of a JPEG file's bytes; raises for a file the decoder refuses."""
+    return _image_info("amhip_jpeg_info", data)
 
 
 def decode_jpeg_frames(files, colored=False, device=0):
     """files: list of bytes, each one baseline JPEG file of the same width and height -> DeviceFrames
     (colored=False: 8UC1, of a colour file its Y plane; colored=True: 8UC3 B, G, R)."""
-    lib = L.load()
-    files = [f if isinstance(f, bytes) else bytes(f) for f in files]
-    n = len(files)
-    ptrs = (C.c_char_p * max(n, 1))(*files)
-    lens = (C.c_size_t * max(n, 1))(*[len(f) for f in files])
-    out = C.c_void_p()
-    w, h = C.c_int(), C.c_int()
-    row, stride = C.c_size_t(), C.c_size_t()
-    L.check(lib.amhip_io_decode_jpeg_frames(int(device), ptrs, lens, n, 1 if colored else 0, C.byref(out),
-                                            C.byref(w), C.byref(h), C.byref(row), C.byref(stride)))
-    return DeviceFrames(out.value, n, w.value, h.value, 3 if colored else 1, row.value, stride.value, int(device))
+    return _decode_frames("amhip_io_decode_jpeg_frames", files, colored, device)
 
 
 def png_info(data):
     """-> (width, height, channels) of a PNG file's bytes (channels 1 for gray and gray + alpha, else 3);
     raises for a file the decoder refuses."""
-    data = bytes(data)
-    w, h, ch = C.c_int(), C.c_int(), C.c_int()
-    L.check(L.load().amhip_png_info(data, len(data), C.byref(w), C.byref(h), C.byref(ch)))
-    return w.value, h.value, ch.value
+    return _image_info("amhip_png_info", data)
 
 
 def decode_png_frames(files, colored=False, device=0):
     """files: list of bytes, each one 8-bit non-interlaced PNG file of the same width and height ->
     DeviceFrames (colored=False: 8UC1; colored=True: 8UC3 B, G, R; alpha dropped)."""
-    lib = L.load()
-    files = [f if isinstance(f, bytes) else bytes(f) for f in files]
-    n = len(files)
-    ptrs = (C.c_char_p * max(n, 1))(*files)
-    lens = (C.c_size_t * max(n, 1))(*[len(f) for f in files])
-    out = C.c_void_p()
-    w, h = C.c_int(), C.c_int()
-    row, stride = C.c_size_t(), C.c_size_t()
-    L.check(lib.amhip_io_decode_png_frames(int(device), ptrs, lens, n, 1 if colored else 0, C.byref(out),
-                                           C.byref(w), C.byref(h), C.byref(row), C.byref(stride)))
-    return DeviceFrames(out.value, n, w.value, h.value, 3 if colored else 1, row.value, stride.value, int(device))
+    return _decode_frames("amhip_io_decode_png_frames", files, colored, device)
 
 
 def load_images_named(directory, image_names, colored=False, device=0):
