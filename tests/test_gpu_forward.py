@@ -2,9 +2,13 @@
 amhip_mosaic_*) against the CPU oracle (oracle/amo_forward.cc) and the
 committed golden fixtures.  The mosaic is integer data (CV_16SC3 + CV_8U mask):
 the bar is bit-exact."""
+import ctypes as C
+import functools
+
 import numpy as np
 import pytest
 
+import forward_undistort_cases as U
 import golden_io as G
 import oracle_ffi as O
 import scenarios as S
@@ -42,6 +46,90 @@ def _assert_same(got, want, what):
         bad = np.argwhere(got != want)
         raise AssertionError("%s: %d differing entries, first at %s: %s != %s" % (
             what, bad.shape[0], bad[0], got[tuple(bad[0])], want[tuple(bad[0])]))
+
+
+def _distorted(kind, F, ch, seed, salt, batch=True, **how):
+    """camera `kind` of forward_undistort_cases, its mosaic, F poses over it and F hashed frames"""
+    cam = U.camera(kind)
+    desc = U.mosaic_for(cam)
+    poses = U.nadir_poses(cam, F, seed, center=U.batch_center(desc) if batch else (0.0, 0.0), **how)
+    return cam, desc, poses, synth.make_frames(F, cam.height, cam.width, ch, salt=salt)
+
+
+@functools.lru_cache(maxsize=None)
+def _camera_conditions(kind):
+    cam = U.camera(kind)
+    if kind in U.PINCUSHION:
+        U.assert_reaches_border(cam)                # (a)
+    if cam.distortion == O.DIST_EQUIDISTANT:
+        U.assert_atan_robust(cam)                   # (b)
+    return True
+
+
+def _assert_conditions(kind, cam, desc, poses, quirk=True):
+    """conditions (a) to (c) of forward_undistort_cases for a case that compares bit for bit"""
+    assert _camera_conditions(kind)
+    assert all(U.seen_whole(cam, desc, poses, quirk))      # (c)
+
+
+def _T_G_C(mosaic, poses):
+    from aerial_mapper_amd.mapper import compose_T_G_C
+    return np.ascontiguousarray(
+        compose_T_G_C(np.asarray(poses, np.float64).reshape(-1, 7), mosaic.ncameras.T_C_B))
+
+
+def _f64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _raw_batch_dev(mosaic, poses, ptr, frame_stride, row_step, ch):
+    """amhip_mosaic_batch_dev as a C caller reaches it (the wrapper takes dense tensors only)"""
+    from aerial_mapper_amd import hip_lib as L
+    T = _T_G_C(mosaic, poses)
+    rc = L.load().amhip_mosaic_batch_dev(mosaic.handle, _f64p(T), T.shape[0], C.c_void_p(ptr),
+                                         frame_stride, row_step, ch)
+    return rc, L.last_error()
+
+
+def _raw_update_dev(mosaic, pose, ptr, row_step, ch):
+    from aerial_mapper_amd import hip_lib as L
+    T = _T_G_C(mosaic, pose)
+    rc = L.load().amhip_mosaic_update_dev(mosaic.handle, _f64p(T), C.c_void_p(ptr), row_step, ch)
+    return rc, L.last_error()
+
+
+def _raw_batch_host(mosaic, poses, images, steps, ch):
+    from aerial_mapper_amd import hip_lib as L
+    T = _T_G_C(mosaic, poses)
+    F = T.shape[0]
+    ptrs = (C.c_void_p * F)(*[im.ctypes.data for im in images])
+    rc = L.load().amhip_mosaic_batch(mosaic.handle, _f64p(T), F, ptrs, (C.c_size_t * F)(*steps), ch,
+                                     None, None)
+    return rc, L.last_error()
+
+
+def _padded_device(frames, row_pad=13, frame_pad=29):
+    """the frames in device memory with row_step = row + row_pad and frame_stride = height *
+    row_step + frame_pad, every byte between them 0xA5 -> (buffer, frame_stride, row_step)"""
+    import torch
+    F, H = frames.shape[:2]
+    rows = np.ascontiguousarray(frames).reshape(F, H, -1)
+    row = rows.shape[2]
+    row_step = row + row_pad
+    frame_stride = H * row_step + frame_pad
+    buf = torch.full((F * frame_stride,), 0xA5, dtype=torch.uint8, device="cuda")
+    buf.as_strided((F, H, row), (frame_stride, row_step, 1)).copy_(torch.from_numpy(rows).cuda())
+    torch.cuda.synchronize()
+    return buf, frame_stride, row_step
+
+
+def _wide_host(frames, pad=11):
+    """views of the frames whose rows lie `pad` pixels apart in a buffer of 0xA5"""
+    wide = np.full(frames.shape[:2] + (frames.shape[2] + pad,) + frames.shape[3:], 0xA5, np.uint8)
+    wide[:, :, :frames.shape[2]] = frames
+    views = [w[:, :frames.shape[2]] for w in wide]
+    assert all(v.strides[0] > np.prod(frames.shape[2:]) and not v.flags.c_contiguous for v in views)
+    return views
 
 
 @pytest.mark.parametrize("name", G.names("fwd"))
@@ -146,26 +234,24 @@ def test_incremental_sequence_matches_oracle_every_step():
             _assert_same(mask, fm.mask, "step %d mask" % k)
 
 
-@pytest.mark.parametrize("kind", ["radtan", "equidistant"])
+@pytest.mark.parametrize("kind", sorted(U.CAMERAS))
 def test_distorted_cameras_undistort_then_warp(kind):
+    """The mapped undistorter (k_fwd_undistort) in front of the warp, bit for bit.  radtan calls no
+    libm function and both builds keep fused multiply-adds off; the equidistant model's atan cannot
+    move a coordinate (condition (b)): there is no room for a tolerance.  The pincushion cameras
+    take BORDER_CONSTANT on all four sides, fully and with part of the weight; 257 columns put one
+    live lane into the second workgroup in x."""
     A = _A()
-    if kind == "radtan":
-        cam = S.camera(128, 96, 95.0, O.DIST_RADTAN, (-0.25, 0.06, 3e-4, -2e-4))
-    else:
-        cam = S.camera(128, 96, 95.0, O.DIST_EQUIDISTANT, (-0.02, 0.004, -0.001, 0.0002))
-    desc = O.mosaic_desc(300, 260, 400.0)
-    poses = synth.make_lawnmower_poses(6, 50.0, 500.0, 31, tilt_deg=4.0)
-    frames = synth.make_frames(6, 96, 128, 1, salt=17)
+    cam, desc, poses, frames = _distorted(kind, 6, 1, seed=31, salt=17)
+    _assert_conditions(kind, cam, desc, poses)
     fm = O.ForwardMosaic(cam, desc)
     assert fm.batch(poses, [f for f in frames]) == O.OK
+    assert (fm.mask > 0).mean() > 0.3
     with A.OrthoForwardHomography(_ncam(cam), _settings(desc)) as mosaic:
         mosaic.batch(poses, [f for f in frames])
         res, mask = mosaic.result()
-    # libm (sqrt/atan) of the device vs glibc can move a 1/32-pixel remap
-    # coordinate by one step in rare pixels: allow a handful of 1-LSB cells
-    diff = np.abs(res.astype(np.int32) - fm.result.astype(np.int32))
-    assert (diff > 0).mean() < 1e-3 and diff.max() <= 255
-    assert (mask != fm.mask).mean() < 1e-3
+    _assert_same(res, fm.result, kind + " result")
+    _assert_same(mask, fm.mask, kind + " mask")
 
 
 def test_wide_mosaic_rows_cross_several_wave_chunks():
@@ -267,3 +353,228 @@ def test_forward_random_configurations(seed):
         res, mask = mosaic.result()
     _assert_same(res, fm.result, "result")
     _assert_same(mask, fm.mask, "mask")
+
+
+# ---- shapes that meet a distorted camera (the 300 x 70 pincushion cameras: border rule, two
+# ---- workgroups in x), each bit for bit against the oracle ---------------------------------------
+WIDE = ["radtan_pincushion", "equidistant_pincushion"]
+
+
+@pytest.mark.parametrize("kind", WIDE)
+def test_distorted_colour_frames_from_host_and_device(kind):
+    import torch
+    A = _A()
+    cam, desc, poses, frames = _distorted(kind, 5, 3, seed=43, salt=3)
+    _assert_conditions(kind, cam, desc, poses)
+    fm = O.ForwardMosaic(cam, desc)
+    assert fm.batch(poses, [f for f in frames]) == O.OK
+    assert (fm.mask > 0).mean() > 0.3
+    with A.OrthoForwardHomography(_ncam(cam), _settings(desc)) as mosaic:
+        mosaic.batch(poses, [f for f in frames])
+        res, mask = mosaic.result()
+        _assert_same(res, fm.result, "host frames")
+        _assert_same(mask, fm.mask, "host frames mask")
+        mosaic.reset()
+        mosaic.batch(poses, torch.from_numpy(frames).cuda())
+        res, mask = mosaic.result()
+    _assert_same(res, fm.result, "device frames")
+    _assert_same(mask, fm.mask, "device frames mask")
+
+
+def test_distorted_seventy_frames_take_two_chunks():
+    # 64 + 6 frames: the second chunk is undistorted into the buffer the first one used and reads
+    # its frames at frames + 64 * frame_stride
+    A = _A()
+    kind = "radtan_pincushion"
+    cam, desc, poses, frames = _distorted(kind, 70, 1, seed=47, salt=11)
+    _assert_conditions(kind, cam, desc, poses)
+    for k in range(6):      # the frames a wrong chunk offset would read instead are other frames
+        assert (frames[64 + k] != frames[k]).mean() > 0.9
+        assert np.abs(poses[64 + k, :2] - poses[k, :2]).max() > 1.0
+    fm = O.ForwardMosaic(cam, desc)
+    assert fm.batch(poses, [f for f in frames]) == O.OK
+    first = O.ForwardMosaic(cam, desc)
+    assert first.batch(poses[:64], [f for f in frames[:64]]) == O.OK
+    assert (first.result != fm.result).mean() > 0.2          # the second chunk matters
+    with A.OrthoForwardHomography(_ncam(cam), _settings(desc)) as mosaic:
+        mosaic.batch(poses, [f for f in frames])
+        res, mask = mosaic.result()
+    _assert_same(res, fm.result, "result")
+    _assert_same(mask, fm.mask, "mask")
+
+
+@pytest.mark.parametrize("kind,ch", [("radtan_pincushion", 1), ("equidistant_pincushion", 3)])
+def test_distorted_incremental_sequence_matches_oracle_every_step(kind, ch):
+    # updateOrthomosaic: one frame per call, frame_stride 0
+    import torch
+    A = _A()
+    cam, desc, poses, frames = _distorted(kind, 5, ch, seed=53, salt=7, batch=False)
+    _assert_conditions(kind, cam, desc, poses, quirk=False)
+    fm = O.ForwardMosaic(cam, desc)
+    with A.OrthoForwardHomography(_ncam(cam), _settings(desc)) as mosaic:
+        for k in range(5):
+            assert fm.update(poses[k], frames[k]) == O.OK
+            if k % 2:
+                mosaic.updateOrthomosaic(poses[k], torch.from_numpy(frames[k].copy()).cuda())
+            else:
+                mosaic.updateOrthomosaic(poses[k], frames[k])
+            res, mask = mosaic.result()
+            _assert_same(res, fm.result, "step %d" % k)
+            _assert_same(mask, fm.mask, "step %d mask" % k)
+    assert (fm.mask > 0).mean() > 0.3
+
+
+def test_distorted_frames_that_miss_the_mosaic_and_an_empty_chunk():
+    # three chunks: [0, 64) with frame 3 off the mosaic (no region, but undistorted with its
+    # chunk), [64, 128) with every frame off it (the chunk is skipped), [128, 134) live: it must
+    # still read frames 128 ...
+    A = _A()
+    kind = "equidistant_pincushion"
+    cam, desc, poses, frames = _distorted(kind, 134, 1, seed=59, salt=13)
+    off = [3] + list(range(64, 128))
+    poses[off, 0:2] += 5000.0
+    on = [k for k in range(134) if k not in off]
+    assert not any(U.seen_positions(cam, desc, poses[off]))
+    _assert_conditions(kind, cam, desc, poses[on])
+    fm = O.ForwardMosaic(cam, desc)
+    assert fm.batch(poses, [f for f in frames]) == O.OK
+    without = O.ForwardMosaic(cam, desc)
+    assert without.batch(poses[:128], [f for f in frames[:128]]) == O.OK
+    assert (without.result != fm.result).mean() > 0.2        # the last chunk matters
+    with A.OrthoForwardHomography(_ncam(cam), _settings(desc)) as mosaic:
+        mosaic.batch(poses, [f for f in frames])
+        res, mask = mosaic.result()
+        _assert_same(res, fm.result, "result")
+        _assert_same(mask, fm.mask, "mask")
+        # no frame reaches the mosaic at all: batch() blends nothing
+        mosaic.reset()
+        mosaic.batch(poses[64:128], [f for f in frames[64:128]])
+        res, mask = mosaic.result()
+    assert not res.any() and not mask.any()
+
+
+# ---- layouts: rows and frames that are not dense, with and without distortion ----------------
+def _plain_or_distorted(kind, F, ch, seed, salt, batch=True):
+    if kind != "pinhole":
+        return _distorted(kind, F, ch, seed, salt, batch)
+    cam = S.camera(300, 70, 210.0)
+    desc = U.mosaic_for(cam)
+    poses = U.nadir_poses(cam, F, seed, center=U.batch_center(desc) if batch else (0.0, 0.0))
+    return cam, desc, poses, synth.make_frames(F, 70, 300, ch, salt=salt)
+
+
+@pytest.mark.parametrize("kind,F,ch", [("pinhole", 7, 3), ("radtan_pincushion", 70, 1),
+                                       ("equidistant_pincushion", 7, 3)])
+def test_batch_dev_with_padded_rows_and_frames(kind, F, ch):
+    """amhip_mosaic_batch_dev with row_step = row + 13 and frame_stride = height * row_step + 29
+    (padding 0xA5) equals the dense call and the oracle.  70 frames: the second chunk starts at
+    frames + 64 * frame_stride, and the warp behind the undistorter must go back to the dense
+    strides of the undistorted frames -- both the frame stride and the row step."""
+    import torch
+    from aerial_mapper_amd import hip_lib as L
+    A = _A()
+    cam, desc, poses, frames = _plain_or_distorted(kind, F, ch, seed=61, salt=19)
+    if kind != "pinhole":
+        _assert_conditions(kind, cam, desc, poses)
+    else:
+        assert all(U.seen_whole(cam, desc, poses))
+    fm = O.ForwardMosaic(cam, desc)
+    assert fm.batch(poses, [f for f in frames]) == O.OK
+    buf, frame_stride, row_step = _padded_device(frames)
+    assert row_step == cam.width * ch + 13 and frame_stride == cam.height * row_step + 29
+    with A.OrthoForwardHomography(_ncam(cam), _settings(desc)) as mosaic:
+        mosaic.batch(poses, torch.from_numpy(frames).cuda())
+        dense = mosaic.result()
+        mosaic.reset()
+        rc, text = _raw_batch_dev(mosaic, poses, buf.data_ptr(), frame_stride, row_step, ch)
+        assert rc == L.OK, text
+        res, mask = mosaic.result()
+    _assert_same(res, dense[0], "padded against dense")
+    _assert_same(mask, dense[1], "padded against dense, mask")
+    _assert_same(res, fm.result, "result")
+    _assert_same(mask, fm.mask, "mask")
+
+
+@pytest.mark.parametrize("kind,ch", [("pinhole", 1), ("radtan_pincushion", 3), ("equidistant_pincushion", 1)])
+def test_update_dev_with_padded_rows(kind, ch):
+    from aerial_mapper_amd import hip_lib as L
+    A = _A()
+    cam, desc, poses, frames = _plain_or_distorted(kind, 4, ch, seed=67, salt=21, batch=False)
+    if kind != "pinhole":
+        _assert_conditions(kind, cam, desc, poses, quirk=False)
+    buf, frame_stride, row_step = _padded_device(frames)
+    fm = O.ForwardMosaic(cam, desc)
+    with A.OrthoForwardHomography(_ncam(cam), _settings(desc)) as mosaic:
+        for k in range(4):
+            assert fm.update(poses[k], frames[k]) == O.OK
+            rc, text = _raw_update_dev(mosaic, poses[k], buf.data_ptr() + k * frame_stride, row_step, ch)
+            assert rc == L.OK, text
+            res, mask = mosaic.result()
+            _assert_same(res, fm.result, "step %d" % k)
+            _assert_same(mask, fm.mask, "step %d mask" % k)
+
+
+@pytest.mark.parametrize("kind,ch", [("pinhole", 3), ("radtan_pincushion", 1), ("equidistant_pincushion", 3)])
+def test_host_frames_with_wide_rows(kind, ch):
+    # numpy views whose strides[0] exceeds a row: the staging copy is the two-dimensional one
+    A = _A()
+    cam, desc, poses, frames = _plain_or_distorted(kind, 5, ch, seed=71, salt=23)
+    if kind != "pinhole":
+        _assert_conditions(kind, cam, desc, poses)
+    views = _wide_host(frames)
+    fm = O.ForwardMosaic(cam, desc)
+    assert fm.batch(poses, [f for f in frames]) == O.OK
+    with A.OrthoForwardHomography(_ncam(cam), _settings(desc)) as mosaic:
+        mosaic.batch(poses, views)
+        res, mask = mosaic.result()
+        _assert_same(res, fm.result, "batch")
+        _assert_same(mask, fm.mask, "batch mask")
+        mosaic.reset()
+        fi = O.ForwardMosaic(cam, desc)
+        poses = _plain_or_distorted(kind, 5, ch, seed=71, salt=23, batch=False)[2]
+        for k in range(5):
+            assert fi.update(poses[k], frames[k]) == O.OK
+            mosaic.updateOrthomosaic(poses[k], views[k])
+            res, mask = mosaic.result()
+            _assert_same(res, fi.result, "step %d" % k)
+            _assert_same(mask, fi.mask, "step %d mask" % k)
+    assert (fm.mask > 0).mean() > 0.2 and (fi.mask > 0).mean() > 0.1
+
+
+def test_layouts_that_are_refused_leave_the_mosaic_usable():
+    """AMHIP_ERR_ARG with a text for a row_step one byte short of a row, for two channels, and for
+    a host step smaller than a row; the next good call on the same mosaic matches the oracle."""
+    import torch
+    from aerial_mapper_amd import hip_lib as L
+    A = _A()
+    kind = "radtan_pincushion"
+    cam, desc, poses, frames = _distorted(kind, 4, 1, seed=73, salt=27)
+    _assert_conditions(kind, cam, desc, poses)
+    fm = O.ForwardMosaic(cam, desc)
+    assert fm.batch(poses, [f for f in frames]) == O.OK
+    dev = torch.from_numpy(frames).cuda()
+    torch.cuda.synchronize()
+    row, fb = cam.width, cam.width * cam.height
+    with A.OrthoForwardHomography(_ncam(cam), _settings(desc)) as mosaic:
+        def good(what):
+            mosaic.batch(poses, [f for f in frames])
+            res, mask = mosaic.result()
+            _assert_same(res, fm.result, "after " + what)
+            _assert_same(mask, fm.mask, "after " + what + ", mask")
+            mosaic.reset()
+
+        rc, text = _raw_batch_dev(mosaic, poses, dev.data_ptr(), fb, row - 1, 1)
+        assert rc == L.ERR_ARG and text == "row_step smaller than a row", (rc, text)
+        good("a short row_step in batch_dev")
+        rc, text = _raw_update_dev(mosaic, poses[0], dev.data_ptr(), row - 1, 1)
+        assert rc == L.ERR_ARG and text == "row_step smaller than a row", (rc, text)
+        good("a short row_step in update_dev")
+        rc, text = _raw_batch_dev(mosaic, poses, dev.data_ptr(), fb, 2 * row, 2)
+        assert rc == L.ERR_ARG and text == "channels must be 1 (8UC1) or 3 (8UC3)", (rc, text)
+        rc, text = _raw_batch_host(mosaic, poses, [f for f in frames], [2 * row] * 4, 2)
+        assert rc == L.ERR_ARG and text == "channels must be 1 (8UC1) or 3 (8UC3)", (rc, text)
+        good("two channels")
+        # frame 0 is staged before frame 1 is refused
+        rc, text = _raw_batch_host(mosaic, poses, [f for f in frames], [row, row - 1, row, row], 1)
+        assert rc == L.ERR_ARG and text == "image step smaller than a row", (rc, text)
+        good("a short host step")

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import forward_undistort_cases as UC
 import oracle_ffi as O
 import stereo_front_inputs as FI
 import stereo_front_reference as FR
@@ -232,23 +233,36 @@ def oracle_undistort(cam, frames):
     return out
 
 
-@pytest.mark.parametrize("kind", ["radtan", "equidistant"])
+@pytest.mark.parametrize("kind", ["radtan", "equidistant", "pincushion"])
 def test_undistortion_before_rectification(gmap, kind):
-    """The frames go through the mapped undistorter the forward mosaic uses.  tests/test_gpu_forward.py
-    leaves room for a 1/32-pixel remap coordinate that the device's libm moves by one step; here the
+    """The frames go through the mapped undistorter the forward mosaic uses, and like
+    tests/test_gpu_forward.py this holds it to bit equality: radtan calls no libm function, and the
     map coordinate is rounded to float32 before it is scaled by 32, so a last-bit difference of a
-    double sqrt / atan reaches the float only once in ~2^29 pixels: with 4 x 38400 pixels the frames,
-    and with them the clouds, are held to bit equality."""
+    double atan reaches the float only once in ~2^29 pixels (tests/forward_undistort_cases.py
+    checks that for the cameras it is asked of).  The two barrel lenses pull every coordinate
+    inward; the pincushion one, 272 columns wide, takes BORDER_CONSTANT on all four sides and has
+    live lanes in the second workgroup in x.  (The clouds see a wrong border rule at the top, the
+    bottom and the right; the leftmost columns carry no disparity, so the left side is held by the
+    forward mosaic's tests alone.)"""
+    W, H = 240, 160
     if kind == "radtan":
         distortion, dist = O.DIST_RADTAN, (-0.25, 0.06, 3e-4, -2e-4)
-    else:
+    elif kind == "equidistant":
         distortion, dist = O.DIST_EQUIDISTANT, (-0.02, 0.004, -0.001, 0.0002)
-    seq = SS.Sequence(4, 240, 160, distortion=(distortion, dist))     # rendered through that lens
+    else:
+        distortion, dist, W, H = O.DIST_RADTAN, (0.12, -0.02, -8e-4, 6e-4), 272, 96
+    seq = SS.Sequence(4, W, H, distortion=(distortion, dist))     # rendered through that lens
     cam = O.Camera()
     cam.fu, cam.fv, cam.cu, cam.cv = seq.K[0, 0], seq.K[1, 1], seq.K[0, 2], seq.K[1, 2]
     cam.width, cam.height, cam.distortion = seq.W, seq.H, distortion
     for k in range(4):
         cam.dist[k] = dist[k]
+    if kind == "pincushion":
+        UC.assert_reaches_border(cam, second_workgroup=True)
+    else:
+        assert not UC.border_reach(cam)["outside"].any()
+    if distortion == O.DIST_EQUIDISTANT:
+        UC.assert_atan_robust(cam)
     und = oracle_undistort(cam, seq.frames)
     assert (und != seq.frames).mean() > 0.3          # the step does something
     want_xyz, want_i, _, _ = SS.cpu_chain(seq, SS.pairs_of(4, 1), True, frames=und)
