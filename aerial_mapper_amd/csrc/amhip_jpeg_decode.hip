@@ -1,4 +1,4 @@
-// amhip_jpeg_decode.hip -- baseline JPEG frames, decoded on the GPU: what
+// amhip_jpeg_decode.hip -- baseline and progressive JPEG frames, decoded on the GPU: what
 // io::AerialMapperIO::loadImagesFromFile (aerial-mapper-io.cc:207-227) gets from cv::imread, one
 // file per pose.  The bar is bit identity with libjpeg at its defaults (JDCT_ISLOW, fancy
 // upsampling); tests/jpeg_decode_reference.py restates every rule and is pinned to libjpeg's own
@@ -14,6 +14,9 @@
 //                       and flush every finished block as one 128-byte row of int16 coefficients in
 //                       natural order (lane k writes the coefficient of zigzag position k).  Blocks are stored plane by
 //                       plane, not in scan order.  Parallelism is across the frames of the call.
+//      k_jpegd_entropy_prog  the same for a progressive frame (SOF2): one wave walks the frame's scans in
+//                       file order into its coefficient blocks (see there).  A call may mix both kinds;
+//                       each frame goes to the kernel of its kind, what follows is shared.
 //   2. k_jpegd_idct     jpeg_idct_islow, the mirror of k_jpeg_blocks: eight lanes per block, a lane
 //                       dequantises and transforms a column, the block goes through LDS, the same
 //                       lane transforms a row, adds 128 and clamps.  colored == 0: only Y blocks,
@@ -33,6 +36,7 @@
 // that ends early set the frame's status word and end the walk; bytes between the end of an
 // interval's data and its RSTn, or between the last block and the EOI, are skipped, as libjpeg
 // skips them.
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -285,6 +289,277 @@ __global__ __launch_bounds__(64) void k_jpegd_entropy(const uint8_t* __restrict_
   if (lane == 0) status[fi] = r.err;
 }
 
+// Progressive frames (SOF2; jdphuff.c): one wave per frame walks the frame's scans in file order
+// into its coefficient blocks, which the driver has zeroed.  As in k_jpegd_entropy every value the
+// walk branches on is the same in all lanes.  A block of an AC scan lives in one register per lane,
+// lane k holding the coefficient of zigzag position k (the order the stream speaks in): a
+// refinement block is loaded with one 128-byte read and the lanes it has changed store theirs in
+// one instruction, a first-scan block needs no read (its band is zero: the host has seen that no
+// coefficient is sent first twice) and stores only what it decoded, and a block inside an EOB run
+// of a first scan touches no memory at all.  DC scans touch coefficient 0 alone, from lane 0.
+// Every coefficient of a block is read and written by one and the same lane in every scan.  The
+// scan being walked lies in LDS beside its tables, so that the loops hold only what they change.
+//
+// What bounds each loop: scans by the frame's scan_count; MCUs by the scan's nx * ny and blocks per
+// MCU by ns <= 3 times h * v <= 4, all from the host parser; the table copy by ntab <= 3; Reader's
+// loops as in k_jpegd_entropy, with the scan's own end in place of the EOI.  The band loop of an AC
+// block refills once per round (57 bits and more) and then either decodes one symbol, which ends
+// the block or leads to ++k, or passes at least one coefficient: k <= Se <= 63 bounds it to 63
+// symbols and 63 coefficients.  A coefficient is addressed by k alone (a lane number), checked
+// against Se before it is used; no index comes from the stream.
+__global__ __launch_bounds__(64) void k_jpegd_entropy_prog(const uint8_t* __restrict__ files,
+                                                           const Frame* __restrict__ frames,
+                                                           const uint32_t* __restrict__ list,
+                                                           const uint32_t* __restrict__ script,
+                                                           int16_t* coef, uint32_t* __restrict__ status) {
+  __shared__ HuffTable tbl[3];   // a DC first scan: one per component of the scan; an AC scan: tbl[0]
+  __shared__ uint8_t win[kWindow];
+  __shared__ jpegd::Scan cur;    // the scan being walked: its fields are read where they are used
+  static_assert(sizeof(jpegd::Scan) % 4 == 0, "the scan is copied by words");
+  const int lane = threadIdx.x;
+  const int natural = d_zigzag.at[lane];   // jpeg_natural_order of this lane's zigzag position
+  // What the block loops seldom need lies in LDS, not in registers: the frame's geometry (block
+  // addresses are computed from it in the vector unit), where the script and the frame's status
+  // word are, and how far the walk through the script has come (word offsets of its scans).
+  __shared__ struct {
+    uint64_t coef_base;
+    const uint32_t* script;
+    uint32_t* status;
+    uint32_t comp_base[3], comp_bw[3], comp_h[3], comp_v[3];
+    uint32_t next, last;
+  } geo;
+  constexpr uint32_t kScanWords = (uint32_t)(sizeof(jpegd::Scan) / 4);
+  if (lane == 0) {
+    const uint32_t fi = list[blockIdx.x];
+    const Frame* f = frames + fi;
+    geo.coef_base = f->coef_base;
+    geo.script = script;
+    geo.status = status + fi;
+    geo.next = f->scan_first * kScanWords;
+    geo.last = (f->scan_first + f->scan_count) * kScanWords;
+    for (int c = 0; c < 3; ++c) {
+      geo.comp_base[c] = f->comp_base[c];
+      geo.comp_bw[c] = (uint32_t)f->comp_bw[c];
+      geo.comp_h[c] = (uint32_t)f->comp_h[c];
+      geo.comp_v[c] = (uint32_t)f->comp_v[c];
+    }
+  }
+  Reader r;
+  r.files = files;
+  r.win = win;
+  r.err = 0;
+  for (;;) {   // (the frame's scans: scan_count rounds)
+    __syncthreads();   // (the previous scan and its tables are done with; geo is there)
+    const uint32_t at_scan = uni(geo.next);
+    if (at_scan >= uni(geo.last) || uni(r.err)) break;
+    {
+      // (the lanes behind the scan's last word copy that word again)
+      const uint32_t w = min((uint32_t)lane, kScanWords - 1u);
+      reinterpret_cast<uint32_t*>(&cur)[w] = geo.script[at_scan + w];
+    }
+    if (lane == 0) geo.next = at_scan + kScanWords;
+    __syncthreads();
+    const int ns = (int)uni((uint32_t)cur.ns);
+    const int ss = (int)uni((uint32_t)cur.ss), se = (int)uni((uint32_t)cur.se);
+    const int ah = (int)uni((uint32_t)cur.ah), al = (int)uni((uint32_t)cur.al);
+    const int ntab = ss == 0 ? (ah == 0 ? ns : 0) : 1;
+    for (int t = 0; t < ntab; ++t) {
+      const uint32_t at = uni((uint32_t)(ss == 0 ? cur.dc_tbl[t] : cur.ac_tbl));
+      const uint32_t* src = geo.script + at;   // (a table's first word in the script)
+      uint32_t* dst = reinterpret_cast<uint32_t*>(tbl + t);
+      for (int i = lane; i < (int)(sizeof(HuffTable) / 4); i += 64) dst[i] = src[i];
+    }
+    r.pos = (uint64_t)uni((uint32_t)cur.begin) | ((uint64_t)uni((uint32_t)(cur.begin >> 32)) << 32);
+    r.end = (uint64_t)uni((uint32_t)cur.end) | ((uint64_t)uni((uint32_t)(cur.end >> 32)) << 32);
+    r.acc = 0;
+    r.nbits = 0;
+    r.fake = 0;
+    r.stage(r.pos, lane);   // (its barriers cover the tables too)
+
+    uint32_t pred0 = 0, pred1 = 0, pred2 = 0;   // (wrap instead of overflowing on a corrupt file)
+    uint32_t eobrun = 0;
+    uint32_t todo = uni((uint32_t)cur.restart), next_rst = 0;
+    const int32_t p1 = 1 << al, m1 = -(1 << al);
+    for (uint32_t my = 0; my < uni((uint32_t)cur.ny) && !uni(r.err); ++my) {
+      for (uint32_t mx = 0; mx < uni((uint32_t)cur.nx) && !uni(r.err); ++mx) {
+        if (const uint32_t restart = uni((uint32_t)cur.restart)) {
+          if (todo == 0) {
+            // process_restart / read_restart_marker, the rule of k_jpegd_entropy's MCU loop: the
+            // bits left of the byte are dropped, the next marker (what is no 0xFF and 0xFF 0x00
+            // pairs skipped; then any number of 0xFF and the code) must be the expected RSTn, whose
+            // index starts at 0 in every scan; the predictors and the EOB run go back to 0.  p only
+            // moves forward and never past the scan's end, where the code reads as EOI.
+            r.acc = 0;
+            r.nbits = 0;
+            r.fake = 0;
+            uint64_t p = r.pos, k = r.end;
+            uint32_t code = 0xD9u;
+            while (p < r.end) {   // (bounded by the scan's end)
+              if (r.byte_at(p, lane) != 0xFFu) {
+                ++p;
+                continue;
+              }
+              k = r.behind_ff(p, lane, &code);
+              if (code != 0u) break;
+              p = k + 1;
+            }
+            if (p >= r.end || code != 0xD0u + next_rst) {
+              r.err = jpegd::kBadRestart;
+              break;
+            }
+            r.pos = k + 1;
+            next_rst = (next_rst + 1) & 7u;
+            pred0 = pred1 = pred2 = 0;
+            eobrun = 0;
+            todo = restart;
+          }
+          --todo;
+        }
+        if (ss == 0) {
+          // ---- DC scans: coefficient 0 of every block of the MCU, from lane 0 ---------------------
+#pragma unroll 1
+          for (int j = 0; j < ns && !uni(r.err); ++j) {   // (ns <= 3)
+            const uint32_t c = uni((uint32_t)cur.comp[j]) & 3u;
+            // a scan of one component is not interleaved: one block per MCU (per_scan_setup)
+            const uint32_t ch = ns > 1 ? uni(geo.comp_h[c]) : 1u;
+            const uint32_t cv = ns > 1 ? uni(geo.comp_v[c]) : 1u;
+            const uint32_t nb = ch * cv;   // (1, 2 or 4)
+            uint32_t pred = j == 0 ? pred0 : j == 1 ? pred1 : pred2;
+            for (uint32_t k4 = 0; k4 < nb && !uni(r.err); ++k4) {
+              const uint32_t bx = k4 % ch, by = k4 / ch;
+              int16_t* dc = coef + (geo.coef_base + geo.comp_base[c] + (uint64_t)(my * cv + by) * geo.comp_bw[c] + (mx * ch + bx)) * 64;
+              r.fill(lane);
+              int32_t out;       // (one store for both kinds of DC scan, from lane 0)
+              bool put = true;
+              if (ah == 0) {
+                // decode_mcu_DC_first
+                const uint32_t s = r.symbol(&tbl[j]) & 15u;
+                if (s) pred += (uint32_t)r.receive_extend((int)s);
+                out = (int32_t)(pred << al);
+              } else {
+                // decode_mcu_DC_refine: one bit
+                put = r.peek(1) != 0u;
+                r.drop(1);
+                out = (int32_t)*dc | p1;
+              }
+              if (put && lane == 0) *dc = (int16_t)out;
+            }
+            if (j == 0) pred0 = pred;
+            else if (j == 1) pred1 = pred;
+            else pred2 = pred;
+          }
+          continue;
+        }
+        // ---- AC scans: one component, its real blocks in raster order ------------------------------
+        if (ah == 0 && eobrun > 0) {   // decode_mcu_AC_first inside an EOB run: the block stays as it is
+          --eobrun;
+          continue;
+        }
+        const uint32_t c = uni((uint32_t)cur.comp[0]) & 3u;
+        int16_t* mine = coef + (geo.coef_base + geo.comp_base[c] + (uint64_t)my * geo.comp_bw[c] + mx) * 64 + natural;
+        // this lane's coefficient.  A first scan: zero until the scan sends it.
+        const int32_t was = ah == 0 ? 0 : (int32_t)*mine;
+        int32_t v = was;
+        enum { kSymbol, kAdvance, kTail, kDone };
+        int phase = eobrun > 0 ? kTail : kSymbol;   // (a refinement block inside an EOB run: corrections only)
+        int k = ss, run = 0;
+        int32_t fresh = 0;
+        while (phase != kDone && !uni(r.err)) {
+          r.fill(lane);   // (57 bits and more: a code and its extra bits take at most 31)
+          if (phase == kSymbol) {
+            if (k > se) break;
+            const uint32_t rs = r.symbol(&tbl[0]);
+            run = (int)(rs >> 4);
+            const int size = (int)(rs & 15u);
+            if (size == 0 && run != 15) {
+              // EOBn: the run covers this block too
+              eobrun = 1u << run;
+              if (run) {
+                eobrun += r.peek(run);
+                r.drop(run);
+              }
+              phase = kTail;
+            } else if (ah == 0) {
+              // decode_mcu_AC_first
+              if (size) {
+                k += run;
+                if (k > se) {
+                  r.err = jpegd::kRunPastBand;
+                  break;
+                }
+                const int32_t x = r.receive_extend(size);
+                if (lane == k) v = (int16_t)((uint32_t)x << al);
+                ++k;
+              } else {
+                k += 16;   // ZRL (past Se: the block ends there)
+              }
+              continue;
+            } else {
+              // decode_mcu_AC_refine: a new coefficient of size 1, its sign bit behind the code; or ZRL
+              fresh = 0;
+              if (size) {
+                if (size != 1) {
+                  r.err = jpegd::kBadRefinement;
+                  break;
+                }
+                fresh = r.peek(1) ? p1 : m1;
+                r.drop(1);
+              }
+              phase = kAdvance;
+            }
+          }
+          if (phase == kAdvance) {
+            // pass `run` zero coefficients, correcting the non-zero ones on the way; stop at the
+            // (run + 1)-th zero, or behind Se.  A correction takes one bit; out of bits: refill.
+            bool found = false;
+            while (k <= se && r.nbits > 0) {
+              const int32_t at = __builtin_amdgcn_readlane(v, k);
+              if (at != 0) {
+                const uint32_t bit = r.peek(1);
+                r.drop(1);
+                if (bit && (at & p1) == 0 && lane == k) v = (int16_t)(at + (at >= 0 ? p1 : m1));
+              } else if (--run < 0) {
+                found = true;
+                break;
+              }
+              ++k;
+            }
+            if (!found && k <= se) continue;
+            if (fresh) {
+              if (k > se) {
+                r.err = jpegd::kRunPastBand;
+                break;
+              }
+              if (lane == k) v = (int16_t)fresh;
+            }
+            ++k;
+            phase = kSymbol;
+          } else if (phase == kTail) {
+            // the rest of the band inside an EOB run.  A first scan has nothing to correct.
+            while (ah != 0 && k <= se && r.nbits > 0) {
+              const int32_t at = __builtin_amdgcn_readlane(v, k);
+              if (at != 0) {
+                const uint32_t bit = r.peek(1);
+                r.drop(1);
+                if (bit && (at & p1) == 0 && lane == k) v = (int16_t)(at + (at >= 0 ? p1 : m1));
+              }
+              ++k;
+            }
+            if (ah == 0 || k > se) {
+              --eobrun;
+              phase = kDone;
+            }
+          }
+        }
+        if (v != was) *mine = (int16_t)v;   // (one store of the lanes the block has changed)
+      }
+    }
+    // (what lies between the scan's last block and its end is skipped: the next scan starts at its
+    // own first byte with an empty bit buffer)
+  }
+  if (lane == 0) *geo.status = r.err;
+}
+
 // jpeg_idct_islow's constants (jidctint.c): CONST_BITS = 13, PASS1_BITS = 2
 constexpr int kConstBits = 13, kPass1Bits = 2;
 constexpr int64_t F_0_298 = 2446, F_0_390 = 3196, F_0_541 = 4433, F_0_765 = 6270, F_0_899 = 7373,
@@ -475,11 +750,38 @@ struct JpegStack {
   size_t total = 0;      // bytes of the files so far
   size_t max_idct = 0;   // most blocks k_jpegd_idct transforms in one frame
   DevBuf bytes, coef, planes;
+  // progressive frames (SOF2): their scans and tables, one list each for the call, and per frame of
+  // the call where its coefficients lie in the group's scratch
+  struct Placed {
+    size_t at, bytes;
+    bool progressive;
+  };
+  std::vector<jpegd::Scan> scans;
+  std::vector<HuffTable> tables;
+  std::vector<uint32_t> prog_list;   // the progressive frames' indices, increasing
+  std::vector<Placed> placed;
+  size_t parsed = 0;
+  DevBuf dscript, dlist;   // the script: every scan of the call, then every table
 
   bool parse(const uint8_t* file, size_t len, Frame* f, char* err, size_t errcap) {
-    if (!jpegd::parse(file, len, f, err, errcap)) return false;
+    jpegd::Progressive prog;
+    if (!jpegd::parse(file, len, f, &prog, err, errcap)) return false;
     f->scan_begin += total;
     f->scan_end += total;
+    if (f->progressive) {
+      f->scan_first = (uint32_t)scans.size();
+      for (jpegd::Scan s : prog.scans) {
+        s.begin += total;
+        s.end += total;
+        for (int k = 0; k < 3; ++k)
+          if (s.dc_tbl[k] >= 0) s.dc_tbl[k] += (int32_t)tables.size();
+        if (s.ac_tbl >= 0) s.ac_tbl += (int32_t)tables.size();
+        scans.push_back(s);
+      }
+      tables.insert(tables.end(), prog.tables.begin(), prog.tables.end());
+      prog_list.push_back((uint32_t)parsed);
+    }
+    ++parsed;
     total += len;
     return true;
   }
@@ -488,6 +790,7 @@ struct JpegStack {
     f->coef_base = base_bytes / 128;
     f->plane_base = f->coef_base * 64;
     max_idct = std::max(max_idct, (size_t)(colored ? f->comp_base[f->ncomp] : f->comp_base[1]));
+    placed.push_back({base_bytes, cost_bytes(*f), f->progressive != 0});
   }
   int upload(const uint8_t* const* files, const size_t* lens, size_t F, size_t max_group_bytes, int colored,
              hipStream_t stream) {
@@ -500,11 +803,53 @@ struct JpegStack {
       AMHIP_TRY(hipMemcpyAsync(bytes.as<uint8_t>() + at, files[i], lens[i], hipMemcpyHostToDevice, stream));
       at += lens[i];
     }
+    if (!prog_list.empty()) {
+      // the scans' table numbers become word offsets into the script
+      const size_t scan_bytes = scans.size() * sizeof(jpegd::Scan), table_bytes = tables.size() * sizeof(HuffTable);
+      if ((scan_bytes + table_bytes) / 4 > 0x7FFFFFFFu) {
+        set_last_error(std::string(kDecode) + ": the progressive frames' scans and tables exceed 8 GB");
+        return AMHIP_ERR_ARG;
+      }
+      for (jpegd::Scan& s : scans) {
+        for (int k = 0; k < 3; ++k)
+          if (s.dc_tbl[k] >= 0) s.dc_tbl[k] = (int32_t)((scan_bytes + (size_t)s.dc_tbl[k] * sizeof(HuffTable)) / 4);
+        if (s.ac_tbl >= 0) s.ac_tbl = (int32_t)((scan_bytes + (size_t)s.ac_tbl * sizeof(HuffTable)) / 4);
+      }
+      if ((rc = dscript.alloc(scan_bytes + table_bytes))) return rc;
+      if ((rc = dlist.alloc(prog_list.size() * sizeof(uint32_t)))) return rc;
+      AMHIP_TRY(hipMemcpyAsync(dscript.p, scans.data(), scan_bytes, hipMemcpyHostToDevice, stream));
+      if (table_bytes)
+        AMHIP_TRY(hipMemcpyAsync(dscript.as<uint8_t>() + scan_bytes, tables.data(), table_bytes,
+                                 hipMemcpyHostToDevice, stream));
+      AMHIP_TRY(hipMemcpyAsync(dlist.p, prog_list.data(), prog_list.size() * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, stream));
+    }
     return AMHIP_OK;
   }
+  // Each frame goes to the entropy kernel of its kind: the baseline frames of the group run by run of
+  // consecutive frames (a call without progressive frames: one launch, as ever), the progressive ones
+  // in one launch over their index list, their coefficients zeroed first.
+  void launch_entropy(size_t first, size_t n, const StackLaunch<Frame>& s) {
+    const size_t last = first + n;
+    for (size_t i = first; i < last;) {
+      size_t j = i;
+      while (j < last && placed[j].progressive == placed[i].progressive) ++j;
+      if (placed[i].progressive)
+        (void)hipMemsetAsync(coef.as<uint8_t>() + placed[i].at, 0,
+                             placed[j - 1].at + placed[j - 1].bytes - placed[i].at, s.stream);
+      else
+        hipLaunchKernelGGL(k_jpegd_entropy, dim3((unsigned)(j - i)), dim3(64), 0, s.stream, bytes.as<uint8_t>(),
+                           s.frames, i, coef.as<int16_t>(), s.status);
+      i = j;
+    }
+    const size_t lo = std::lower_bound(prog_list.begin(), prog_list.end(), (uint32_t)first) - prog_list.begin();
+    const size_t hi = std::lower_bound(prog_list.begin(), prog_list.end(), (uint32_t)last) - prog_list.begin();
+    if (hi > lo)
+      hipLaunchKernelGGL(k_jpegd_entropy_prog, dim3((unsigned)(hi - lo)), dim3(64), 0, s.stream, bytes.as<uint8_t>(),
+                         s.frames, dlist.as<uint32_t>() + lo, dscript.as<uint32_t>(), coef.as<int16_t>(), s.status);
+  }
   void launch_group(size_t first, size_t n, const StackLaunch<Frame>& s) {
-    hipLaunchKernelGGL(k_jpegd_entropy, dim3((unsigned)n), dim3(64), 0, s.stream, bytes.as<uint8_t>(), s.frames,
-                       first, coef.as<int16_t>(), s.status);
+    launch_entropy(first, n, s);
     hipLaunchKernelGGL(k_jpegd_idct, dim3((unsigned)((max_idct + kIdctBlocks - 1) / kIdctBlocks), (unsigned)n),
                        dim3(256), 0, s.stream, s.frames, first, coef.as<int16_t>(), planes.as<uint8_t>(), s.out,
                        s.frame_stride, s.row_step, s.colored);

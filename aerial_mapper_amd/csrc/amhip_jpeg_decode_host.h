@@ -8,8 +8,13 @@
 // with Y sampled 1x1, 2x1 or 2x2 and chroma 1x1; 8-bit quantisation tables; Huffman table ids 0
 // and 1; optional DRI; APPn / COM skipped; 0xFF fill bytes in front of any marker, in the header
 // and in the scan (where a run of 0xFF followed by 0x00 is one data byte 0xFF); any bytes between
-// the last block and EOI; bytes behind EOI ignored.  Everything else is refused with a text that
-// names the marker or field.  Every read is checked against the file's length.
+// the last block and EOI; bytes behind EOI ignored.  Also accepted: progressive DCT (SOF2), 8 bit,
+// Huffman, the same components, Huffman table ids 0..3: the whole marker sequence up to EOI becomes
+// a scan list (Progressive), DHT / DQT / DRI / COM / APPn may stand between scans, a component's
+// quantisation table is the one in effect at its first scan.  Its script is held to libjpeg's rules
+// (start_pass_phuff_decoder) and must bring every coefficient to bit 0.  Everything else is refused
+// with a text that names the marker or field, under SOF2 the scan as well.  Every read is checked
+// against the file's length.
 #ifndef AMHIP_JPEG_DECODE_HOST_H_
 #define AMHIP_JPEG_DECODE_HOST_H_
 
@@ -17,6 +22,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "amhip_jpeg_host.h"
 
@@ -51,7 +57,9 @@ struct Frame {
   uint64_t coef_base;       // the frame's first block in the coefficient scratch
   uint64_t plane_base;      // the frame's first byte in the plane scratch
   uint16_t quant[3][64];    // per component, natural order
-  HuffTable dc[2], ac[2];
+  HuffTable dc[2], ac[2];   // SOF0: the tables of the one scan
+  int32_t progressive;      // SOF2: the walk follows the scan list, td / ta / dc / ac / restart unused
+  uint32_t scan_first, scan_count;   // ... its scans in the call's list
 };
 
 // jpeg_make_d_derived_tbl; false when the counts do not describe a prefix code
@@ -128,38 +136,87 @@ inline void layout(Frame* f, const int h[3], const int v[3]) {
   for (int c = f->ncomp; c < 4; ++c) f->comp_base[c] = base;
 }
 
-// The whole header up to the first entropy-coded byte, and the EOI at the file's end.  Returns
-// true and fills *f (scan_begin / scan_end relative to `file`; coef_base / plane_base left 0), or
-// false with a text in err.
-inline bool parse(const uint8_t* file, size_t len, Frame* f, char* err, size_t errcap) {
+// One scan of a progressive file (SOF2), as the entropy kernel walks it.  Offsets are into the buffer
+// that holds the call's files, table indices into the list of the file's tables (the driver turns
+// them into word offsets into the script it uploads: every scan of the call, then every table).
+struct Scan {
+  uint64_t begin;        // first entropy-coded byte
+  uint64_t end;          // the 0xFF of the marker that ends the segment: no byte at or behind it is read
+  int32_t ns;            // components in the scan (1: not interleaved)
+  int32_t comp[3];       // their indices in the frame, increasing
+  int32_t ss, se, ah, al;
+  int32_t restart;       // the scan's MCUs per restart interval as DRI stood at this SOS, 0: none
+  int32_t dc_tbl[3];     // per component of the scan; -1: the scan decodes no DC symbol
+  int32_t ac_tbl;        // -1: a DC scan
+  int32_t nx, ny;        // the scan's MCUs across and down: whole MCUs when interleaved, else the
+                         // component's real blocks (per_scan_setup, jdinput.c)
+};
+
+// what a progressive file adds to its Frame: the scans in file order and every table they use, once
+struct Progressive {
+  std::vector<Scan> scans;
+  std::vector<HuffTable> tables;
+};
+
+// The whole marker sequence.  SOF0: up to the first entropy-coded byte, and the EOI at the file's
+// end.  SOF2: every scan up to EOI into *prog, the script checked as start_pass_phuff_decoder
+// (jdphuff.c) checks it, and stricter: what libjpeg only warns about is refused, and so is a file
+// whose scans leave any coefficient short of bit 0.  Returns true and fills *f (scan_begin /
+// scan_end relative to `file`, of a progressive file those of its last scan; coef_base / plane_base
+// left 0), or false with a text in err.
+inline bool parse(const uint8_t* file, size_t len, Frame* f, Progressive* prog, char* err, size_t errcap) {
   auto fail = [&](const char* fmt, int a, int b) {
     if (err && errcap) std::snprintf(err, errcap, fmt, a, b);
     return false;
   };
   std::memset(f, 0, sizeof(*f));
+  prog->scans.clear();
+  prog->tables.clear();
   if (!file || len < 4 || file[0] != 0xFF || file[1] != 0xD8) return fail("no SOI", 0, 0);
   bool have_q[4] = {false, false, false, false};
-  bool have_h[2][2] = {{false, false}, {false, false}};
+  bool have_h[2][4] = {{false, false, false, false}, {false, false, false, false}};
+  std::vector<HuffTable> cur(8);   // [class * 4 + id], as the DHTs so far define them
+  int pooled[2][4];                // ... and where prog->tables holds that definition, -1: not yet
+  bool high_id = false;            // a DHT with id 2 or 3 was seen: legal under SOF2 only
   uint16_t q[4][64];
   int id[3] = {0, 0, 0}, tq[3] = {0, 0, 0}, h[3] = {1, 1, 1}, v[3] = {1, 1, 1};
-  bool have_sof = false;
+  bool have_sof = false, progressive = false;
+  bool latched[3] = {false, false, false};   // latch_quant_tables (jdinput.c)
+  int bits[3][64];                           // coef_bits: the Al each coefficient has reached, -1: not sent
+  int restart = 0;
   int adobe_transform = -1;
+  for (int c = 0; c < 2; ++c)
+    for (int t = 0; t < 4; ++t) pooled[c][t] = -1;
+  for (int c = 0; c < 3; ++c)
+    for (int k = 0; k < 64; ++k) bits[c][k] = -1;
   size_t p = 2;
   for (;;) {
-    if (p + 4 > len) return fail("no SOS", 0, 0);
+    const bool between = !prog->scans.empty();   // behind a progressive file's first scan
+    if (between) {
+      if (p + 2 > len) return fail("no EOI", 0, 0);
+    } else if (p + 4 > len) {
+      return fail("no SOS", 0, 0);
+    }
     if (file[p] != 0xFF) return fail("marker expected at byte %d", (int)p, 0);
     const int m = file[p + 1];
     if (m == 0xFF) {   // fill byte
       ++p;
       continue;
     }
-    if (m == 0xD9) return fail("no SOS", 0, 0);
+    if (m == 0xD9) {
+      if (between) break;
+      return fail("no SOS", 0, 0);
+    }
+    if (p + 4 > len) return fail("no EOI", 0, 0);
     const size_t L = ((size_t)file[p + 2] << 8) | file[p + 3];
     if (L < 2 || p + 2 + L > len) return fail("segment %02X runs past the file", m, 0);
     const uint8_t* pl = file + p + 4;
     const size_t n = L - 2;
-    if (m == 0xC0) {
-      if (have_sof) return fail("second SOF0", 0, 0);
+    if (between && !(m == 0xC4 || m == 0xDB || m == 0xDD || m == 0xDA || m == 0xFE || (m >= 0xE0 && m <= 0xEF)))
+      return fail("SOF2 (progressive): marker %02X between scans", m, 0);
+    if (m == 0xC0 || m == 0xC2) {
+      // (the texts of both frame types name SOF0 where the rule is SOF0's: one set of words)
+      if (have_sof) return fail(m == 0xC0 ? "second SOF0" : "second SOF2 (progressive)", 0, 0);
       if (n < 6 || n != 6 + 3 * (size_t)pl[5]) return fail("SOF0: bad length", 0, 0);
       if (pl[0] != 8) return fail("SOF0: %d-bit samples", pl[0], 0);
       f->height = (pl[1] << 8) | pl[2];
@@ -180,8 +237,15 @@ inline bool parse(const uint8_t* file, size_t len, Frame* f, char* err, size_t e
         if (!y_ok || h[1] != 1 || v[1] != 1 || h[2] != 1 || v[2] != 1)
           return fail("SOF0: sampling factors other than 4:4:4, 4:2:2, 4:2:0", 0, 0);
         if (id[0] == 'R' && id[1] == 'G' && id[2] == 'B') return fail("SOF0: component ids R G B", 0, 0);
+        if (id[0] == id[1] || id[0] == id[2] || id[1] == id[2]) {
+          if (m == 0xC2) return fail("SOF2 (progressive): a component id twice", 0, 0);
+        }
       }
       have_sof = true;
+      progressive = m == 0xC2;
+      f->progressive = progressive ? 1 : 0;
+      if (!progressive && high_id) return fail("DHT: bad table class, id or length", 0, 0);
+      if (progressive) layout(f, h, v);
     } else if (sof_name(m)) {
       if (err && errcap) std::snprintf(err, errcap, "marker %s", sof_name(m));
       return false;
@@ -198,29 +262,32 @@ inline bool parse(const uint8_t* file, size_t len, Frame* f, char* err, size_t e
     } else if (m == 0xC4) {
       size_t at = 0;
       while (at < n) {
-        if (at + 17 > n || (pl[at] >> 4) > 1 || (pl[at] & 15) > 1)
+        // ids 2 and 3: SOF2 only (T.81 B.2.4.2).  A DHT may precede SOF: then SOF0 refuses them.
+        const int top = have_sof && !progressive ? 1 : 3;
+        if (at + 17 > n || (pl[at] >> 4) > 1 || (pl[at] & 15) > top)
           return fail("DHT: bad table class, id or length", 0, 0);
         const int cls = pl[at] >> 4, th = pl[at] & 15;
+        if (th > 1) high_id = true;
         int nv = 0;
         for (int i = 0; i < 16; ++i) nv += pl[at + 1 + i];
         if (nv > 256 || at + 17 + (size_t)nv > n) return fail("DHT: bad symbol count", 0, 0);
         if (cls == 0)
           for (int i = 0; i < nv; ++i)
             if (pl[at + 17 + i] > 15) return fail("DHT: DC symbol above 15", 0, 0);
-        HuffTable* t = cls ? &f->ac[th] : &f->dc[th];
-        if (!make_table(pl + at + 1, pl + at + 17, nv, t))
+        if (!make_table(pl + at + 1, pl + at + 17, nv, &cur[cls * 4 + th]))
           return fail("DHT: codes do not fit", 0, 0);
         have_h[cls][th] = true;
+        pooled[cls][th] = -1;
         at += 17 + (size_t)nv;
       }
     } else if (m == 0xDD) {
       if (n != 2) return fail("DRI: bad length", 0, 0);
-      f->restart = (pl[0] << 8) | pl[1];
+      restart = (pl[0] << 8) | pl[1];
     } else if (m == 0xEE && n >= 12 && std::memcmp(pl, "Adobe", 5) == 0) {
       adobe_transform = pl[11];
     } else if ((m >= 0xE0 && m <= 0xEF) || m == 0xFE) {
       // APPn, COM: skipped
-    } else if (m == 0xDA) {
+    } else if (m == 0xDA && !progressive) {
       if (!have_sof) return fail("SOS before SOF0", 0, 0);
       if (n < 1 || n != 4 + 2 * (size_t)pl[0]) return fail("SOS: bad length", 0, 0);
       if (pl[0] != f->ncomp) return fail("SOS: several scans (%d of %d components)", pl[0], f->ncomp);
@@ -236,12 +303,124 @@ inline bool parse(const uint8_t* file, size_t len, Frame* f, char* err, size_t e
       if (pl[n - 3] != 0 || pl[n - 2] != 63 || pl[n - 1] != 0)
         return fail("SOS: not a sequential scan (Ss, Se, Ah/Al)", 0, 0);
       if (adobe_transform == 0 && f->ncomp == 3) return fail("Adobe transform 0 (RGB)", 0, 0);
+      f->restart = restart;
+      for (int t = 0; t < 2; ++t) {
+        f->dc[t] = cur[t];
+        f->ac[t] = cur[4 + t];
+      }
       f->scan_begin = p + 2 + L;
       break;
+    } else if (m == 0xDA) {
+      // get_sos (jdmarker.c) and start_pass_phuff_decoder (jdphuff.c); every text names the scan
+      const int si = (int)prog->scans.size();
+      if (n < 1 || n != 4 + 2 * (size_t)pl[0]) return fail("SOF2 (progressive): scan %d: bad SOS length", si, 0);
+      Scan s;
+      std::memset(&s, 0, sizeof(s));
+      s.ns = pl[0];
+      if (s.ns < 1 || s.ns > f->ncomp)
+        return fail("SOF2 (progressive): scan %d: Ns = %d, more components than the frame defines", si, s.ns);
+      s.ss = pl[n - 3];
+      s.se = pl[n - 2];
+      s.ah = pl[n - 1] >> 4;
+      s.al = pl[n - 1] & 15;
+      // (a sequential scan under SOF2, which libjpeg refuses too, keeps the words this file shape
+      // has always been refused with: the baseline restatement's)
+      if (s.ss == 0 && s.se == 63 && pl[n - 1] == 0) return fail("marker SOF2 (progressive)", 0, 0);
+      if (s.ss == 0 && s.se != 0) return fail("SOF2 (progressive): scan %d: Ss = 0 with Se = %d", si, s.se);
+      if (s.ss > 0 && s.ns != 1) return fail("SOF2 (progressive): scan %d: Ss > 0 with Ns = %d", si, s.ns);
+      if (s.se < s.ss || s.se > 63) return fail("SOF2 (progressive): scan %d: Se = %d below Ss or above 63", si, s.se);
+      if (s.al > 13) return fail("SOF2 (progressive): scan %d: Al = %d above 13", si, s.al);
+      if (s.ah != 0 && s.al != s.ah - 1)
+        return fail("SOF2 (progressive): scan %d: Ah = %d with Al other than Ah - 1", si, s.ah);
+      for (int k = 0; k < 3; ++k) s.dc_tbl[k] = -1;
+      s.ac_tbl = -1;
+      for (int k = 0; k < s.ns; ++k) {
+        int c = 0;
+        while (c < f->ncomp && id[c] != pl[1 + 2 * k]) ++c;
+        if (c == f->ncomp)
+          return fail("SOF2 (progressive): scan %d: component id %d the frame does not define", si, pl[1 + 2 * k]);
+        if (k && c <= s.comp[k - 1]) return fail("SOF2 (progressive): scan %d: component order", si, 0);
+        s.comp[k] = c;
+        if (!latched[c]) {
+          if (!have_q[tq[c]]) return fail("SOS: missing quantisation table", 0, 0);
+          std::memcpy(f->quant[c], q[tq[c]], sizeof(q[0]));
+          latched[c] = true;
+        }
+        if (s.ss > 0 && bits[c][0] < 0)
+          return fail("SOF2 (progressive): scan %d: AC scan of component %d before its DC scan", si, c);
+        for (int z = s.ss; z <= s.se; ++z) {
+          if (s.ah == 0 && bits[c][z] >= 0)
+            return fail("SOF2 (progressive): scan %d: coefficient %d sent first twice (Ah = 0)", si, z);
+          if (s.ah != 0 && bits[c][z] < 0)
+            return fail("SOF2 (progressive): scan %d: coefficient %d refined before its first scan (Ah)", si, z);
+          if (s.ah != 0 && bits[c][z] != s.ah)
+            return fail("SOF2 (progressive): scan %d: Ah = %d is not the coefficient's current Al", si, s.ah);
+          bits[c][z] = s.al;
+        }
+        // the tables the scan uses, as they stand: a DC refinement scan decodes no symbol
+        const int cls = s.ss == 0 ? 0 : 1;
+        const int th = cls ? pl[2 + 2 * k] & 15 : pl[2 + 2 * k] >> 4;
+        if (cls == 0 && s.ah != 0) continue;
+        if (th > 3 || !have_h[cls][th])
+          return fail("SOF2 (progressive): scan %d: Huffman table id %d the file does not define", si, th);
+        if (pooled[cls][th] < 0) {
+          size_t t = 0;
+          while (t < prog->tables.size() && std::memcmp(&prog->tables[t], &cur[cls * 4 + th], sizeof(HuffTable))) ++t;
+          if (t == prog->tables.size()) prog->tables.push_back(cur[cls * 4 + th]);
+          pooled[cls][th] = (int)t;
+        }
+        if (cls) s.ac_tbl = pooled[cls][th];
+        else s.dc_tbl[k] = pooled[cls][th];
+      }
+      if (adobe_transform == 0 && f->ncomp == 3) return fail("Adobe transform 0 (RGB)", 0, 0);
+      s.restart = restart;
+      if (s.ns > 1) {
+        s.nx = f->mcux;
+        s.ny = f->mcuy;
+      } else {
+        const int c = s.comp[0];
+        const int ch = f->ncomp == 1 ? 1 : h[c], cv = f->ncomp == 1 ? 1 : v[c];
+        const int hm = f->ncomp == 1 ? 1 : f->hmax, vm = f->ncomp == 1 ? 1 : f->vmax;
+        s.nx = ((f->width * ch + hm - 1) / hm + 7) / 8;
+        s.ny = ((f->height * cv + vm - 1) / vm + 7) / 8;
+      }
+      // the entropy-coded segment ends at the first marker that is neither a stuffed 0xFF 0x00 nor an
+      // RSTn (next_marker); only fill bytes lie between that 0xFF and the marker's code
+      s.begin = p + 2 + L;
+      size_t at = (size_t)s.begin;
+      for (;;) {
+        const uint8_t* ff = at < len ? static_cast<const uint8_t*>(std::memchr(file + at, 0xFF, len - at)) : nullptr;
+        if (!ff) return fail("no EOI", 0, 0);
+        const size_t run = (size_t)(ff - file);
+        size_t k = run + 1;
+        while (k < len && file[k] == 0xFF) ++k;
+        if (k >= len) return fail("no EOI", 0, 0);
+        if (file[k] == 0x00 || (file[k] >= 0xD0 && file[k] <= 0xD7)) {
+          at = k + 1;
+          continue;
+        }
+        s.end = run;
+        break;
+      }
+      prog->scans.push_back(s);
+      p = (size_t)s.end;
+      continue;
     } else {
       return fail("marker %02X", m, 0);
     }
     p += 2 + L;
+  }
+  if (progressive) {
+    // EOI.  libjpeg decodes a file that stops short of full precision, and smooths its blocks
+    // (jdcoefct.c: decompress_smooth_data); that is not reproduced: such a file is refused.
+    for (int c = 0; c < f->ncomp; ++c)
+      for (int z = 0; z < 64; ++z)
+        if (bits[c][z] != 0)
+          return fail("SOF2 (progressive): the file ends before coefficient %d of component %d has reached bit 0", z, c);
+    f->scan_begin = prog->scans.back().begin;
+    f->scan_end = prog->scans.back().end;
+    f->scan_count = (uint32_t)prog->scans.size();
+    return true;
   }
   // The scan ends at the first marker behind it that is neither a stuffed 0xFF 0x00 nor an RSTn: that
   // must be EOI (jdmarker.c: next_marker).  What follows EOI is ignored, as libjpeg ignores it.
@@ -266,6 +445,12 @@ inline bool parse(const uint8_t* file, size_t len, Frame* f, char* err, size_t e
   return true;
 }
 
+// ... for a caller that wants the frame alone (the size of a file, a baseline descriptor)
+inline bool parse(const uint8_t* file, size_t len, Frame* f, char* err, size_t errcap) {
+  Progressive prog;
+  return parse(file, len, f, &prog, err, errcap);
+}
+
 // status words the entropy kernel leaves per frame
 enum Status : uint32_t {
   kOk = 0,
@@ -275,6 +460,8 @@ enum Status : uint32_t {
   kEndsEarly = 4,      // the scan ends before its last block
   // (5 was "bytes left behind the last block": libjpeg skips them, and so does the walk.  Retired,
   // not reused.)
+  kRunPastBand = 6,    // SOF2: a run past the end of the scan's band (Se)
+  kBadRefinement = 7,  // SOF2: a refinement scan's new coefficient of a size other than 1
 };
 
 inline const char* status_text(uint32_t s) {
@@ -284,6 +471,8 @@ inline const char* status_text(uint32_t s) {
     case kRunPast63: return "a run past coefficient 63";
     case kBadRestart: return "a wrong or missing RSTn marker";
     case kEndsEarly: return "the scan ends before its last block";
+    case kRunPastBand: return "a run past the end of the scan's band";
+    case kBadRefinement: return "a refinement coefficient of a size other than 1";
   }
   return "unknown status";
 }

@@ -181,13 +181,16 @@ def _decode_frames(symbol, files, colored, device):
 
 
 def jpeg_info(data):
-    """-> (width, height, channels) of a JPEG file's bytes; raises for a file the decoder refuses."""
+    """-> (width, height, channels) of a JPEG file's bytes, baseline (SOF0) or progressive (SOF2); raises
+    for a file the decoder refuses (of a progressive file the whole scan script is checked)."""
     return _image_info("amhip_jpeg_info", data)
 
 
 def decode_jpeg_frames(files, colored=False, device=0):
-    """files: list of bytes, each one baseline JPEG file of the same width and height -> DeviceFrames
-    (colored=False: 8UC1, of a colour file its Y plane; colored=True: 8UC3 B, G, R)."""
+    """files: list of bytes, each one baseline (SOF0) or progressive (SOF2) JPEG file of the same width
+    and height, mixed in any order -> DeviceFrames (colored=False: 8UC1, of a colour file its Y plane;
+    colored=True: 8UC3 B, G, R).  A progressive file must be complete: one whose scans leave a
+    coefficient short of bit 0 is refused."""
     return _decode_frames("amhip_io_decode_jpeg_frames", files, colored, device)
 
 
@@ -215,7 +218,8 @@ def load_images_named(directory, image_names, colored=False, device=0):
 
 def load_images(filename_base, num_poses, colored=False, device=0):
     """io::AerialMapperIO::loadImagesFromFile: reads <filename_base><i>.jpg, i = 0..num_poses-1, and
-    decodes them on the GPU -> DeviceFrames.  A missing or refused file raises."""
+    decodes them on the GPU -> DeviceFrames; baseline and progressive (SOF2) files alike.  A missing or
+    refused file raises."""
     files = []
     for i in range(int(num_poses)):
         with open("%s%d.jpg" % (filename_base, i), "rb") as f:

@@ -447,18 +447,30 @@ int amhip_io_free(void* dev_ptr);
  * and EXIF orientation is not applied.  Accepted: baseline sequential DCT (SOF0), 8 bit, Huffman, one
  * scan; one component, or Y Cb Cr with Y sampled 1x1, 2x1 or 2x2 and chroma 1x1; 8-bit quantisation
  * tables; Huffman table ids 0 and 1 of any content; optional DRI; APPn / COM skipped; width and
- * height 1..65535.  Everything else (progressive, arithmetic, 12 bit, 4 components, other sampling
- * factors, 16-bit DQT, several scans, Adobe transform 0 or component ids R G B, missing tables, no
+ * height 1..65535.  Also accepted: progressive DCT (SOF2), 8 bit, Huffman, the same components: any
+ * complete scan script (spectral selection, successive approximation, DC scans interleaved or not,
+ * DHT / DQT / DRI / COM / APPn between scans, table ids 0..3), bit for bit libjpeg-turbo's pixels
+ * (tests/golden/jpeg_progressive/).  A call may mix baseline and progressive files.  Refused under
+ * SOF2, each with a text that names the scan and the field: what libjpeg refuses or warns about in a
+ * script (Ss = 0 with Se != 0, Ss > 0 with more than one component, Se < Ss or > 63, Al > 13, Ah with
+ * Al != Ah - 1, a refinement that does not continue where the coefficient stands, a coefficient sent
+ * first twice, an AC scan before the component's DC scan, an undefined component or table), any
+ * other marker between scans, and a file that ends before every coefficient has reached bit 0
+ * (libjpeg would smooth its blocks: not reproduced).  Everything else (arithmetic, 12 bit, 4
+ * components, other sampling
+ * factors, 16-bit DQT, several scans under SOF0, Adobe transform 0 or component ids R G B, missing tables, no
  * SOI / SOS / EOI) is AMHIP_ERR_ARG with a text naming the marker or field, reported before any
- * device is touched.  A scan that does not decode (undefined code, run past coefficient 63, wrong or
- * missing RSTn, early end) is found on the device: AMHIP_ERR_ARG naming the frame, *dev_frames = NULL.
+ * device is touched.  A scan that does not decode (undefined code, run past coefficient 63 or past a
+ * progressive scan's band, wrong or missing RSTn, early end, a refinement coefficient of a size other
+ * than 1) is found on the device: AMHIP_ERR_ARG naming the frame, *dev_frames = NULL.
  * The scan ends at the first EOI behind it; whatever follows that EOI (thumbnails, padding, a second image) is
  * ignored, as libjpeg ignores it.  As in libjpeg, any number of 0xFF fill bytes may stand in front of a marker
  * (a run of 0xFF followed by 0x00 is one data byte 0xFF), and bytes between the end of a restart interval's data
  * and its RSTn, or between the last block and EOI, are skipped.  Stricter than libjpeg, which only warns: a wrong
  * RSTn index and a scan that ends early are errors here.  Scratch is bounded by decoding in groups of frames
  * (tuning key jpegd_coef_budget_mb). */
-/* host only: parses up to SOS, applies every rule above; channels = components in the file (1 or 3) */
+/* host only: parses up to SOS (SOF2: every scan up to EOI), applies every rule above; channels = components in
+ * the file (1 or 3) */
 int amhip_jpeg_info(const uint8_t* file, size_t len, int* width, int* height, int* channels);
 /* F files in host memory -> ONE stack of frames in HBM, frame f at *dev_frames + f * *frame_stride, rows *row_step
  * bytes apart: the layout amhip_ortho_backward_process_dev, amhip_mosaic_batch_dev and amhip_stereo_add_frames_dev

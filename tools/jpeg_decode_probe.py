@@ -13,7 +13,15 @@ The split between the three kernels comes from a kernel trace of a fresh process
 (its *_kernel_stats.csv lists the k_jpegd_* kernels; DESIGN 4.11 quotes it).
 --no-pillow leaves column (c) out: for timing two builds of the library in turn (AMHIP_LIB_PATH names
 the other one), where Pillow's seconds per run buy nothing.
-Usage: python tools/jpeg_decode_probe.py [--reps N] [--frames N] [--distinct N] [--out FILE] [--no-pillow] [--trace-target]"""
+The progressive case (gray_progressive, colour_420_progressive) stands beside the baseline figures of
+the same run: the same frames and pixels, written progressive (SOF2, libjpeg-turbo's default script)
+by Pillow at quality 95 where Pillow is present, recorded in "progressive_writer".  Without Pillow:
+--distinct-progressive N frames (default 1) through the symbol-level ProgressiveWriter of
+tests/jpeg_progressive_inputs.py over tests/jpeg_reference.py's quantised coefficients, in Pillow's
+script; the count is recorded.  --no-progressive leaves the case out (a library from before it
+refuses SOF2).
+Usage: python tools/jpeg_decode_probe.py [--reps N] [--frames N] [--distinct N] [--out FILE] [--no-pillow]
+       [--no-progressive] [--distinct-progressive N] [--trace-target]"""
 import argparse
 import io
 import json
@@ -42,6 +50,51 @@ def timed(fn, reps, warm=3):
     return {"median_ms": float(med), "iqr_ms": float(q3 - q1)}
 
 
+def progressive_files(frames, ch, use_pillow):
+    """the frames' pixels as progressive files at quality 95 (colour: 4:2:0) -> ([bytes], how)"""
+    import numpy as np
+    if use_pillow:
+        from PIL import Image
+        out = []
+        for f in frames:
+            pil = Image.fromarray(f if ch == 1 else np.ascontiguousarray(f[..., ::-1]))
+            buf = io.BytesIO()
+            pil.save(buf, "JPEG", quality=95, progressive=True, **({} if ch == 1 else {"subsampling": 2}))
+            out.append(buf.getvalue())
+        return out, "Pillow"
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import jpeg_progressive_inputs as PI
+    import jpeg_reference as R
+    out = []
+    zz = [int(v) for v in R.ZIGZAG]
+    for f in frames:
+        b = R.blocks_of(f, 95)          # (zigzag order, in the order a baseline scan codes them)
+        nat = np.zeros_like(b.coef)
+        nat[:, zz] = b.coef
+        h, wd = f.shape[:2]
+        if ch == 1:
+            comps, planes = [(1, 1, 1, 0)], [nat.reshape((h + 7) // 8, (wd + 7) // 8, 64)]
+        else:
+            my, mx = (h + 15) // 16, (wd + 15) // 16
+            m = nat.reshape(my, mx, 6, 64)
+            y = m[:, :, :4].reshape(my, mx, 2, 2, 64).transpose(0, 2, 1, 3, 4).reshape(2 * my, 2 * mx, 64)
+            comps, planes = [(1, 2, 2, 0), (2, 1, 1, 1), (3, 1, 1, 1)], [y, m[:, :, 4], m[:, :, 5]]
+        q = R.quant_tables(95)
+        w = PI.ProgressiveWriter(wd, h, comps, {k: q[k] for k in range(1 if ch == 1 else 2)}, planes)
+        n = len(comps)
+        # libjpeg-turbo's default script (jpeg_simple_progression)
+        sc = PI.scan
+        if n == 1:
+            script = [sc([0], 0, 0, 0, 1), sc([0], 1, 5, 0, 2), sc([0], 6, 63, 0, 2), sc([0], 1, 63, 2, 1),
+                      sc([0], 0, 0, 1, 0), sc([0], 1, 63, 1, 0)]
+        else:
+            script = [sc([0, 1, 2], 0, 0, 0, 1, td=[0, 1, 1]), sc([0], 1, 5, 0, 2), sc([2], 1, 63, 0, 1, ta=1),
+                      sc([1], 1, 63, 0, 1, ta=1), sc([0], 6, 63, 0, 2), sc([0], 1, 63, 2, 1), sc([0, 1, 2], 0, 0, 1, 0),
+                      sc([2], 1, 63, 1, 0, ta=1), sc([1], 1, 63, 1, 0, ta=1), sc([0], 1, 63, 1, 0)]
+        out.append(w.write(script))
+    return out, "ProgressiveWriter"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -51,6 +104,9 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-pillow", action="store_true", help="do not time Pillow beside the GPU")
+    ap.add_argument("--no-progressive", action="store_true", help="leave the progressive case out")
+    ap.add_argument("--distinct-progressive", type=int, default=1,
+                    help="distinct progressive frames where Pillow is not there to write them")
     ap.add_argument("--trace-target", action="store_true",
                     help="only decode both stacks twice (the program to run under a kernel trace)")
     args = ap.parse_args()
@@ -61,6 +117,7 @@ def main():
         from PIL import Image
     except ImportError:
         Image = None
+    have_pillow = Image is not None
     if args.no_pillow:
         Image = None
     out = {"build_id": hip_lib.build_id(), "reps": args.reps, "warmup": 3, "frames": args.frames,
@@ -72,8 +129,14 @@ def main():
             frames = synth.make_frames(args.distinct, args.height, args.width, ch, salt=5)
             files = [E.encode_jpeg(m, np.ascontiguousarray(f), 95) for f in frames]
             stacks[name] = [files[k % len(files)] for k in range(args.frames)]
+            if not args.no_progressive:
+                some = frames if have_pillow else frames[:max(1, args.distinct_progressive)]
+                files, how = progressive_files([np.ascontiguousarray(f) for f in some], ch, have_pillow)
+                stacks[name + "_progressive"] = [files[k % len(files)] for k in range(args.frames)]
+                out["progressive_writer"] = how
+                out["distinct_progressive_frames"] = len(files)
     for name, files in stacks.items():
-        colored = name != "gray"
+        colored = not name.startswith("gray")
 
         def decode():
             fr = AIO.decode_jpeg_frames(files, colored=colored)
