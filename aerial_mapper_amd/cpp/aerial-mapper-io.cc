@@ -1,4 +1,4 @@
-// io::AerialMapperIO's text and image loaders over the C ABI
+// io::AerialMapperIO's text and image loaders, format converters and image writers over the C ABI
 // (see include/aerial-mapper-io/aerial-mapper-io.h).
 #include "aerial-mapper-io/aerial-mapper-io.h"
 
@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <iomanip>
 #include <memory>
 #include <string>
 #include <vector>
@@ -224,6 +225,160 @@ void AerialMapperIO::loadPosesFromFileStandard(const std::string& filename, Pose
     if (infile.eof()) break;
   }
   if (T_G_Bs->empty()) amhip_shim::fatal("loadPosesFromFileStandard", "No poses loaded.");
+}
+
+void AerialMapperIO::loadPosesFromFile(const PoseFormat& format, const std::string& filename, Poses* T_G_Bs) {
+  if (!T_G_Bs) amhip_shim::fatal("loadPosesFromFile", "CHECK(T_G_Bs)");
+  if (filename.empty()) amhip_shim::fatal("loadPosesFromFile", "Empty filename");
+  switch (format) {
+    case PoseFormat::Standard:
+      loadPosesFromFileStandard(filename, T_G_Bs);
+      break;
+    case PoseFormat::COLMAP:
+    case PoseFormat::PIX4D:
+      amhip_shim::fatal("loadPosesFromFile", "Not yet implemented!");
+    case PoseFormat::ROS:   // (commented out in the reference's switch as well)
+      break;
+  }
+}
+
+void AerialMapperIO::loadPosesFromFileRos(const std::string& filename, Poses* T_G_Bs,
+                                          std::vector<int64_t>* timestamps_ns) {
+  if (!T_G_Bs) amhip_shim::fatal("loadPosesFromFileRos", "CHECK(T_G_Bs)");
+  if (filename.empty()) amhip_shim::fatal("loadPosesFromFileRos", "Empty filename");
+  if (!timestamps_ns) amhip_shim::fatal("loadPosesFromFileRos", "CHECK(timestamps_ns)");
+  std::fprintf(stderr, "[aerial_mapper_hip] Loading body poses from: %s\n", filename.c_str());
+  std::ifstream infile(filename);
+  double x, y, z, qw, qx, qy, qz;
+  double timestamp_ns;
+  while (infile >> timestamp_ns >> x >> y >> z >> qx >> qy >> qz >> qw) {
+    timestamps_ns->push_back(static_cast<int64_t>(timestamp_ns));
+    T_G_Bs->push_back(Pose(kindr::minimal::RotationQuaternion(qw, qx, qy, qz), Eigen::Vector3d(x, y, z)));
+    if (infile.eof()) break;
+  }
+  if (T_G_Bs->empty()) amhip_shim::fatal("loadPosesFromFileRos", "No poses loaded.");
+  if (T_G_Bs->size() != timestamps_ns->size())
+    amhip_shim::fatal("loadPosesFromFileRos", "CHECK(T_G_Bs->size() == timestamps_ns->size())");
+}
+
+void AerialMapperIO::writeImagesToFileFromDevice(const uint8_t* dev_frames, size_t F, int width, int height,
+                                                 int channels, size_t row_step, size_t frame_stride,
+                                                 const std::vector<std::string>& filenames, int quality) {
+  if (filenames.size() != F) amhip_shim::fatal("writeImagesToFileFromDevice", "CHECK(filenames.size() == F)");
+  std::vector<const char*> names;
+  for (const std::string& name : filenames) names.push_back(name.c_str());
+  amhip_shim::check_status(
+      amhip_io_write_jpeg_frames(device_index(), dev_frames, 1, F, width, height, channels, row_step,
+                                 frame_stride, quality, names.data()),
+      "writeImagesToFileFromDevice");
+}
+
+void AerialMapperIO::convertFromSimulation() {
+  toStandardFormat("/tmp/to_convert/", "vi_imu_poses.csv", "blender_id_time.csv", "/tmp/simulation2/");
+}
+
+void AerialMapperIO::toStandardFormat(const std::string& directory, const std::string& filename_vi_imu_poses,
+                                      const std::string& filename_blender_id_time,
+                                      const std::string& new_directory) {
+  // all body poses with their timestamps
+  Poses T_G_Bs;
+  std::vector<int64_t> timestamps_ns;
+  loadPosesFromFileRos(directory + filename_vi_imu_poses, &T_G_Bs, &timestamps_ns);
+  // the images' names and timestamps
+  std::ifstream infile(directory + filename_blender_id_time);
+  double id, image_name;
+  std::vector<std::string> image_names;
+  std::vector<int64_t> image_timestamps;
+  while (infile >> id >> image_name) {
+    image_names.push_back(std::to_string(static_cast<int64_t>(image_name)));
+    image_timestamps.push_back(static_cast<int64_t>(image_name) - 1);
+    if (infile.eof()) break;
+  }
+  // every image's pose: the last one whose timestamp matches (the reference's loop has no break)
+  Poses T_G_Bs_associated;
+  for (size_t i = 0u; i < image_timestamps.size(); ++i) {
+    bool found_pose_for_image = false;
+    Pose T_G_B;
+    for (size_t j = 0u; j < timestamps_ns.size(); ++j) {
+      if (timestamps_ns[j] == image_timestamps[i]) {
+        found_pose_for_image = true;
+        T_G_B = T_G_Bs[j];
+      }
+    }
+    if (!found_pose_for_image)
+      amhip_shim::fatal("toStandardFormat", ("CHECK(found_pose_for_image): no pose at timestamp " +
+                                             std::to_string(image_timestamps[i]) + " for image " +
+                                             image_names[i] + ".png").c_str());
+    T_G_Bs_associated.push_back(T_G_B);
+  }
+  std::ofstream fs;
+  fs.open((new_directory + "opt_poses.txt").c_str());
+  for (const Pose& T_G_B : T_G_Bs_associated) {
+    double p[7];
+    amhip_shim::pose_to7(T_G_B, p);
+    fs << p[0] << " " << p[1] << " " << p[2] << " " << p[3] << " " << p[4] << " " << p[5] << " " << p[6]
+       << std::endl;
+  }
+  fs.close();
+  // cam0/<name>.png -> one stack in HBM -> image_<i>.jpg, no cv::Mat in between
+  uint8_t* dev = nullptr;
+  int w = 0, h = 0;
+  size_t row_step = 0, frame_stride = 0;
+  loadImagesFromFileToDevice(directory + "cam0/", image_names, false, &dev, &w, &h, &row_step, &frame_stride);
+  std::vector<std::string> filenames;
+  for (size_t i = 0u; i < image_names.size(); ++i)
+    filenames.push_back(new_directory + "image_" + std::to_string(i) + ".jpg");
+  writeImagesToFileFromDevice(dev, image_names.size(), w, h, 1, row_step, frame_stride, filenames);
+  amhip_io_free(dev);
+}
+
+void AerialMapperIO::exportPix4dGeofile(const Poses& T_G_Cs, const Images& images) {
+  exportPix4dGeofile(T_G_Cs, images, "/tmp/pix4d");
+}
+
+void AerialMapperIO::exportPix4dGeofile(const Poses& T_G_Cs, const Images& images,
+                                        const std::string& output_directory) {
+  if (images.size() != T_G_Cs.size())
+    amhip_shim::fatal("exportPix4dGeofile", "CHECK(images.size() == T_G_Cs.size())");
+  if (images.empty()) return;   // (the reference's loop does not run; geofile.txt is left empty)
+  const int w = images[0].cols, h = images[0].rows, ch = images[0].channels();
+  const size_t row = static_cast<size_t>(w) * ch, frame = row * h;
+  // one tight stack, uploaded once
+  std::vector<uint8_t> stack(images.size() * frame);
+  std::vector<std::string> stems, filenames;
+  for (size_t i = 0u; i < images.size(); ++i) {
+    const Image& image = images[i];
+    bool same = image.cols == w && image.rows == h && image.channels() == ch && image.data;
+#if AERIAL_MAPPER_REAL_DEPS
+    same = same && image.depth() == CV_8U;
+#endif
+    if (!same)
+      amhip_shim::fatal("exportPix4dGeofile",
+                        ("image " + std::to_string(i) + " differs from image 0 in size or type (" +
+                         std::to_string(w) + " x " + std::to_string(h) + ", " + std::to_string(ch) +
+                         " channels of 8 bits are expected)").c_str());
+    for (int y = 0; y < h; ++y)
+      std::memcpy(stack.data() + i * frame + static_cast<size_t>(y) * row,
+                  image.data + static_cast<size_t>(y) * image.step, row);
+    char number[32];
+    std::snprintf(number, sizeof(number), "%010zu", i + 1);
+    stems.push_back(std::string("image_") + number + ".jpeg");
+    filenames.push_back(output_directory + "/" + stems.back());
+  }
+  std::vector<const char*> names;
+  for (const std::string& name : filenames) names.push_back(name.c_str());
+  amhip_shim::check_status(
+      amhip_io_write_jpeg_frames(device_index(), stack.data(), 0, images.size(), w, h, ch, row, frame, 95,
+                                 names.data()),
+      "exportPix4dGeofile");
+  std::ofstream fs;
+  fs.open((output_directory + "/geofile.txt").c_str());
+  for (size_t i = 0u; i < images.size(); ++i) {
+    const Eigen::Vector3d& xyz = T_G_Cs[i].getPosition();
+    fs << stems[i] << " " << std::setprecision(15) << xyz(0) << " " << std::setprecision(15) << xyz(1) << " "
+       << std::setprecision(15) << xyz(2) << std::endl;
+  }
+  fs.close();
 }
 
 void AerialMapperIO::subtractOriginFromPoses(const Eigen::Vector3d& origin, Poses* T_G_Bs) {

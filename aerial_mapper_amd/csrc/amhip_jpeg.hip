@@ -23,6 +23,9 @@
 //                       prefix sums, and the copy into the caller's buffer with a 0x00 behind each
 //                       0xFF, behind the header segments (built on the host, amhip_jpeg_host.h) and
 //                       in front of EOI.  Nothing is written when the file would not fit.
+// A stack of frames (amhip_io_encode_jpeg_frames, amhip_io_write_jpeg_frames) takes the
+// same passes once per group of frames: the k_jpegf_* kernels run a pass's body with the frame on
+// grid row y, and k_jpegf_offsets lays the group's files end to end.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -32,6 +35,7 @@
 #include <vector>
 
 #include "amhip_common.h"
+#include "amhip_frame_stack.h"
 #include "amhip_jpeg_host.h"
 
 namespace amhip {
@@ -143,10 +147,11 @@ __device__ __forceinline__ bool y_block_real(const Geom& g, int mx, int my, int 
   return 16 * mx + 8 * (k & 1) < g.width && 16 * my + 8 * (k >> 1) < g.height;
 }
 
+// the body of pass 1, for workgroup `group` of one image's grid (k_jpeg_blocks, k_jpegf_blocks)
 template <int kMode>
-__global__ void __launch_bounds__(256)
-k_jpeg_blocks(const uint8_t* __restrict__ px, size_t step, Geom g, const Blob* __restrict__ blob,
-              int16_t* __restrict__ coef) {
+__device__ __forceinline__ void blocks_body(const uint8_t* __restrict__ px, size_t step, const Geom& g,
+                                            const Blob* __restrict__ blob, int16_t* __restrict__ coef,
+                                            unsigned group) {
   __shared__ int s_pass[kBlocksPerGroup][8][9];
   __shared__ __attribute__((aligned(16))) int16_t s_out[kBlocksPerGroup][64];
   __shared__ uint16_t s_div[2][64];
@@ -155,7 +160,7 @@ k_jpeg_blocks(const uint8_t* __restrict__ px, size_t step, Geom g, const Blob* _
   if (t < 128) s_div[t >> 6][t & 63] = blob->divisor[t >> 6][t & 63];
   else if (t < 192) s_unzig[t - 128] = d_unzig.at[t - 128];
   const int lb = t >> 3, r = t & 7;
-  const unsigned b = blockIdx.x * (unsigned)kBlocksPerGroup + (unsigned)lb;
+  const unsigned b = group * (unsigned)kBlocksPerGroup + (unsigned)lb;
   const bool live = b < g.nb;
   int d[8];
   int table = 0;
@@ -226,6 +231,22 @@ k_jpeg_blocks(const uint8_t* __restrict__ px, size_t step, Geom g, const Blob* _
   if (live)
     reinterpret_cast<uint4*>(coef)[(size_t)b * 8u + (size_t)r] =
         reinterpret_cast<const uint4*>(&s_out[lb][0])[r];
+}
+
+template <int kMode>
+__global__ void __launch_bounds__(256)
+k_jpeg_blocks(const uint8_t* __restrict__ px, size_t step, Geom g, const Blob* __restrict__ blob,
+              int16_t* __restrict__ coef) {
+  blocks_body<kMode>(px, step, g, blob, coef, blockIdx.x);
+}
+
+// frame blockIdx.y of a stack: its pixels at px + f * frame_stride, its coefficients at coef + f * nb * 64
+template <int kMode>
+__global__ void __launch_bounds__(256)
+k_jpegf_blocks(const uint8_t* __restrict__ px, size_t step, size_t frame_stride, Geom g,
+               const Blob* __restrict__ blob, int16_t* __restrict__ coef) {
+  const size_t f = blockIdx.y;
+  blocks_body<kMode>(px + f * frame_stride, step, g, blob, coef + f * (size_t)g.nb * 64u, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -343,13 +364,14 @@ struct CountSink {
   __device__ __forceinline__ void put(uint32_t, uint32_t len) { bits += len; }
 };
 
-__global__ void __launch_bounds__(kTile)
-k_jpeg_lengths(const int16_t* __restrict__ coef, Geom g, uint32_t* __restrict__ bits,
-               unsigned long long* __restrict__ tile_sum) {
+// the body of pass 2 for tile `tile` of one image (coef, bits, tile_sum: that image's)
+__device__ __forceinline__ void lengths_body(const int16_t* __restrict__ coef, const Geom& g,
+                                             uint32_t* __restrict__ bits,
+                                             unsigned long long* __restrict__ tile_sum, unsigned tile) {
   __shared__ EntropyLds s;
   load_tables(&s);
   __syncthreads();
-  const unsigned b = blockIdx.x * (unsigned)kTile + threadIdx.x;
+  const unsigned b = tile * (unsigned)kTile + threadIdx.x;
   CountSink sink = {0};
   if (b < g.nb) {
     walk_block(coef, g, b, &s, sink);
@@ -357,15 +379,21 @@ k_jpeg_lengths(const int16_t* __restrict__ coef, Geom g, uint32_t* __restrict__ 
   }
   uint32_t total;
   (void)block_excl_scan(sink.bits, s.wave_sum, &total);
-  if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+  if (threadIdx.x == 0) tile_sum[tile] = total;
+}
+
+__global__ void __launch_bounds__(kTile)
+k_jpeg_lengths(const int16_t* __restrict__ coef, Geom g, uint32_t* __restrict__ bits,
+               unsigned long long* __restrict__ tile_sum) {
+  lengths_body(coef, g, bits, tile_sum, blockIdx.x);
 }
 
 // a[0..n) -> its exclusive prefix sums, in place; *total = the sum.  One wave.  scan_bits (may be
 // null): the bits of the scan, already on the device -- only the 4096-byte chunks the scan really
 // fills are walked (the launch is sized for the worst case, the entries behind are never read).
-__global__ void __launch_bounds__(64)
-k_jpeg_scan_top(unsigned long long* __restrict__ a, unsigned n, unsigned long long* __restrict__ total,
-                const unsigned long long* __restrict__ scan_bits) {
+__device__ __forceinline__ void scan_top_body(unsigned long long* __restrict__ a, unsigned n,
+                                              unsigned long long* __restrict__ total,
+                                              const unsigned long long* __restrict__ scan_bits) {
   const unsigned lane = threadIdx.x;
   if (scan_bits) {
     const unsigned long long used = (((*scan_bits + 7ull) >> 3) + (kChunk - 1)) / kChunk;
@@ -385,6 +413,12 @@ k_jpeg_scan_top(unsigned long long* __restrict__ a, unsigned n, unsigned long lo
     carry += ((unsigned long long)hi << 32) | lo;
   }
   if (lane == 0) *total = carry;
+}
+
+__global__ void __launch_bounds__(64)
+k_jpeg_scan_top(unsigned long long* __restrict__ a, unsigned n, unsigned long long* __restrict__ total,
+                const unsigned long long* __restrict__ scan_bits) {
+  scan_top_body(a, n, total, scan_bits);
 }
 
 // MSB-first bit writer at bit `off` of a zeroed word array; words are stored byte-swapped so that
@@ -421,18 +455,20 @@ struct BitSink {
   }
 };
 
-__global__ void __launch_bounds__(kTile)
-k_jpeg_pack(const int16_t* __restrict__ coef, Geom g, const uint32_t* __restrict__ bits,
-            const unsigned long long* __restrict__ tile_off, uint32_t* __restrict__ words) {
+// the body of pass 4 for tile `tile` of one image; `words`: that image's zeroed packed words
+__device__ __forceinline__ void pack_body(const int16_t* __restrict__ coef, const Geom& g,
+                                          const uint32_t* __restrict__ bits,
+                                          const unsigned long long* __restrict__ tile_off,
+                                          uint32_t* __restrict__ words, unsigned tile) {
   __shared__ EntropyLds s;
   load_tables(&s);
   __syncthreads();
-  const unsigned b = blockIdx.x * (unsigned)kTile + threadIdx.x;
+  const unsigned b = tile * (unsigned)kTile + threadIdx.x;
   const uint32_t mine = b < g.nb ? bits[b] : 0u;
   uint32_t total;
   const uint32_t excl = block_excl_scan(mine, s.wave_sum, &total);
   if (b >= g.nb) return;
-  const unsigned long long off = tile_off[blockIdx.x] + excl;
+  const unsigned long long off = tile_off[tile] + excl;
   BitSink sink;
   sink.start(words, off);
   walk_block(coef, g, b, &s, sink);
@@ -442,6 +478,12 @@ k_jpeg_pack(const int16_t* __restrict__ coef, Geom g, const uint32_t* __restrict
     if (pad) sink.put((1u << pad) - 1u, pad);
   }
   sink.flush();
+}
+
+__global__ void __launch_bounds__(kTile)
+k_jpeg_pack(const int16_t* __restrict__ coef, Geom g, const uint32_t* __restrict__ bits,
+            const unsigned long long* __restrict__ tile_off, uint32_t* __restrict__ words) {
+  pack_body(coef, g, bits, tile_off, words, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -500,6 +542,131 @@ k_jpeg_stuff(const uint32_t* __restrict__ words, unsigned long long* __restrict_
   const uint32_t before = block_excl_scan(at < nbytes ? count_ff(v) : 0u, s_wave, &total);
   if (at >= nbytes) return;
   uint8_t* dst = out + head + at + chunk_ff[blockIdx.x] + before;
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  const int live = (int)min(16ull, nbytes - at);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    if (i < live) {
+      const uint8_t byte = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+      *dst++ = byte;
+      if (byte == 0xFF) *dst++ = 0;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// a stack of frames (amhip_io_encode_jpeg_frames): the same five passes, frame f of the group on
+// grid row f.  Width, height, channels and quality are the call's, so Geom and Blob are shared; a
+// frame has its own coefficients, bit counts, tile sums, chunk sums and packed words (every region
+// is `n frames x one frame's share`, the packed words a multiple of kChunk per frame: no word and
+// no stuffing chunk is shared between two frames) and one control record.
+// ---------------------------------------------------------------------------
+struct FrameCtrl {
+  unsigned long long bits;     // of the frame's scan
+  unsigned long long ff;       // 0xFF bytes in it
+  unsigned long long size;     // the frame's file
+  unsigned long long offset;   // of the file in the group's output
+};
+
+// what one frame takes of each region
+struct FrameShare {
+  unsigned ntiles, nchunks;
+  size_t pack_words;   // nchunks * kChunk / 4
+};
+
+__global__ void __launch_bounds__(kTile)
+k_jpegf_lengths(const int16_t* __restrict__ coef, Geom g, FrameShare fs, uint32_t* __restrict__ bits,
+                unsigned long long* __restrict__ tile_sum) {
+  const size_t f = blockIdx.y;
+  lengths_body(coef + f * (size_t)g.nb * 64u, g, bits + f * (size_t)g.nb, tile_sum + f * (size_t)fs.ntiles,
+               blockIdx.x);
+}
+
+// one wave per frame.  chunks == 0: the frame's tile sums -> bit offsets, the total -> ctrl.bits;
+// chunks != 0: its chunks' 0xFF counts -> their prefix sums, the total -> ctrl.ff.
+__global__ void __launch_bounds__(64)
+k_jpegf_scan(unsigned long long* __restrict__ a, unsigned per_frame, FrameCtrl* __restrict__ ctrl, int chunks) {
+  const size_t f = blockIdx.x;
+  scan_top_body(a + f * (size_t)per_frame, per_frame, chunks ? &ctrl[f].ff : &ctrl[f].bits,
+                chunks ? &ctrl[f].bits : nullptr);
+}
+
+__global__ void __launch_bounds__(kTile)
+k_jpegf_pack(const int16_t* __restrict__ coef, Geom g, FrameShare fs, const uint32_t* __restrict__ bits,
+             const unsigned long long* __restrict__ tile_off, uint32_t* __restrict__ words) {
+  const size_t f = blockIdx.y;
+  pack_body(coef + f * (size_t)g.nb * 64u, g, bits + f * (size_t)g.nb, tile_off + f * (size_t)fs.ntiles,
+            words + f * fs.pack_words, blockIdx.x);
+}
+
+__global__ void __launch_bounds__(256)
+k_jpegf_ff_count(const uint32_t* __restrict__ words, FrameShare fs, const FrameCtrl* __restrict__ ctrl,
+                 unsigned long long* __restrict__ chunk_ff) {
+  __shared__ uint32_t s_wave[4];
+  const size_t f = blockIdx.y;
+  const unsigned long long nbytes = (ctrl[f].bits + 7ull) >> 3;
+  const unsigned long long at = (unsigned long long)blockIdx.x * kChunk + 16ull * threadIdx.x;
+  uint32_t n = 0;
+  if (at < nbytes) n = count_ff(reinterpret_cast<const uint4*>(words + f * fs.pack_words)[at >> 4]);
+  uint32_t total;
+  (void)block_excl_scan(n, s_wave, &total);
+  if (threadIdx.x == 0) chunk_ff[f * (size_t)fs.nchunks + blockIdx.x] = total;
+}
+
+// one wave: every frame's file size, and where the file starts behind the files before it (64 bit)
+__global__ void __launch_bounds__(64)
+k_jpegf_offsets(FrameCtrl* __restrict__ ctrl, unsigned n, const Blob* __restrict__ blob,
+                unsigned long long* __restrict__ sizes) {
+  const unsigned lane = threadIdx.x;
+  const unsigned long long head = blob->header_bytes;
+  unsigned long long carry = 0;
+  for (unsigned at = 0; at < n; at += 64) {
+    const bool live = at + lane < n;
+    const unsigned long long v = live ? head + ((ctrl[at + lane].bits + 7ull) >> 3) + ctrl[at + lane].ff + 2ull : 0ull;
+    unsigned long long incl = v;
+#pragma unroll
+    for (int dlt = 1; dlt < 64; dlt <<= 1) {
+      const uint32_t lo = __shfl_up((uint32_t)incl, dlt), hi = __shfl_up((uint32_t)(incl >> 32), dlt);
+      if ((int)lane >= dlt) incl += ((unsigned long long)hi << 32) | lo;
+    }
+    if (live) {
+      ctrl[at + lane].size = v;
+      ctrl[at + lane].offset = carry + incl - v;
+      sizes[at + lane] = v;
+    }
+    const uint32_t lo = __shfl((uint32_t)incl, 63), hi = __shfl((uint32_t)(incl >> 32), 63);
+    carry += ((unsigned long long)hi << 32) | lo;
+  }
+}
+
+// header, stuffed scan and EOI of frame blockIdx.y at out + its offset.  `out` holds exactly the
+// group's files (it was sized from `sizes`), so there is no capacity to check.
+__global__ void __launch_bounds__(256)
+k_jpegf_stuff(const uint32_t* __restrict__ words, FrameShare fs, const FrameCtrl* __restrict__ ctrl,
+              const unsigned long long* __restrict__ chunk_ff, const Blob* __restrict__ blob,
+              uint8_t* __restrict__ out) {
+  __shared__ uint32_t s_wave[4];
+  const size_t f = blockIdx.y;
+  const unsigned long long nbytes = (ctrl[f].bits + 7ull) >> 3;
+  const unsigned long long head = blob->header_bytes;
+  const unsigned long long size = ctrl[f].size;
+  out += ctrl[f].offset;
+  if (blockIdx.x == 0) {
+    for (unsigned i = threadIdx.x; i < (unsigned)head; i += blockDim.x) out[i] = blob->header[i];
+    if (threadIdx.x == 0) {
+      out[size - 2] = 0xFF;   // EOI
+      out[size - 1] = 0xD9;
+    }
+  }
+  const unsigned long long chunk_at = (unsigned long long)blockIdx.x * kChunk;
+  if (chunk_at >= nbytes) return;
+  const unsigned long long at = chunk_at + 16ull * threadIdx.x;
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (at < nbytes) v = reinterpret_cast<const uint4*>(words + f * fs.pack_words)[at >> 4];
+  uint32_t total;
+  const uint32_t before = block_excl_scan(at < nbytes ? count_ff(v) : 0u, s_wave, &total);
+  if (at >= nbytes) return;
+  uint8_t* dst = out + head + at + chunk_ff[f * (size_t)fs.nchunks + blockIdx.x] + before;
   const uint32_t w[4] = {v.x, v.y, v.z, v.w};
   const int live = (int)min(16ull, nbytes - at);
 #pragma unroll
@@ -677,12 +844,12 @@ int write_failure(const char* what, const char* filename, int err) {
   return AMHIP_ERR_ARG;
 }
 
-int write_file(const char* what, const char* filename, const std::vector<uint8_t>& file) {
+int write_file(const char* what, const char* filename, const uint8_t* data, size_t size) {
   const int fd = ::open(filename, O_WRONLY | O_CREAT | O_TRUNC, 0644);
   if (fd < 0) return write_failure(what, filename, errno);
   size_t done = 0;
-  while (done < file.size()) {
-    const ssize_t w = ::write(fd, file.data() + done, file.size() - done);
+  while (done < size) {
+    const ssize_t w = ::write(fd, data + done, size - done);
     if (w < 0 && errno == EINTR) continue;
     if (w < 0) {
       const int err = errno;   // (close() below may change it)
@@ -702,8 +869,178 @@ int jpeg_write_run(const char* what, hipStream_t stream, JpegScratch* ws, const 
   std::vector<uint8_t> file;
   const int rc = encode_to_host(stream, ws, src, quality, &file);
   if (rc) return rc;
-  return write_file(what, filename, file);
+  return write_file(what, filename, file.data(), file.size());
 }
+
+// ---------------------------------------------------------------------------
+// host: a stack of frames
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr size_t kMaxGroupFrames = 65535;   // (grid.y of the per-frame launches)
+constexpr size_t kWriteSlice = 8u << 20;    // bytes of files downloaded at a time by the writing call
+
+// One call of amhip_io_encode_jpeg_frames / amhip_io_write_jpeg_frames: the geometry every frame
+// shares, the groups (amhip_frame_plan.h: a frame costs its scratch, the budget is the tuning key
+// jpege_scratch_budget_mb), the scratch of the largest group and the sizes of all files.
+struct FramesEncoder {
+  Geom g;
+  FrameShare fs;
+  int channels = 0, quality = 0;
+  size_t row_step = 0, frame_stride = 0, nb = 0, pack_bytes = 0, F = 0;
+  std::vector<size_t> group_begin;         // the first frame of every group, then F
+  std::vector<unsigned long long> sizes;   // every frame's file, once its group ran
+  DevBuf scratch, blob;
+  hipStream_t stream = nullptr;            // the default stream: the entry points are synchronous
+
+  // where the buffers of a group of n frames lie in the scratch
+  struct Layout {
+    size_t ctrl, sizes, coef, bits, tile, chunk, pack, total;
+  };
+  Layout layout(size_t n) const {
+    Layout l;
+    size_t at = 0;
+    auto carve = [&](size_t bytes) {
+      const size_t a = at;
+      at += round_up(bytes, kChunk);
+      return a;
+    };
+    l.ctrl = carve(n * sizeof(FrameCtrl));
+    l.sizes = carve(n * 8);
+    l.coef = carve(n * nb * 128);
+    l.bits = carve(n * nb * 4);
+    l.tile = carve(n * (size_t)fs.ntiles * 8);
+    l.chunk = carve(n * (size_t)fs.nchunks * 8);
+    l.pack = carve(n * pack_bytes);
+    l.total = at;
+    return l;
+  }
+  size_t groups() const { return group_begin.size() - 1; }
+  size_t group_frames(size_t gi) const { return group_begin[gi + 1] - group_begin[gi]; }
+  unsigned long long group_bytes(size_t gi) const {
+    unsigned long long sum = 0;
+    for (size_t f = group_begin[gi]; f < group_begin[gi + 1]; ++f) sum += sizes[f];
+    return sum;
+  }
+  // the bytes of the stack that group gi's frames span
+  size_t group_span(size_t gi) const {
+    return (group_frames(gi) - 1) * frame_stride + (size_t)g.height * row_step;
+  }
+
+  // host only: geometry and groups
+  void plan(size_t frames, int width, int height, int ch, size_t rstep, size_t fstride, int q) {
+    F = frames;
+    channels = ch;
+    quality = q ? q : 95;
+    row_step = rstep;
+    frame_stride = frames > 1 ? fstride : 0;
+    g.width = width;
+    g.height = height;
+    g.colour = ch == 3;
+    g.bw = g.colour ? (width + 15) / 16 : (width + 7) / 8;
+    nb = jpeg::scan_blocks(width, height, ch);
+    g.nb = (unsigned)nb;
+    pack_bytes = round_up(nb * jpeg::kMaxBlockBytes + 1, kChunk);
+    fs.ntiles = (unsigned)((nb + kTile - 1) / kTile);
+    fs.nchunks = (unsigned)(pack_bytes / kChunk);
+    fs.pack_words = pack_bytes / 4;
+    // a frame's scratch: coefficients, bit counts and packed words of every scan block, its tile
+    // and chunk sums, its control record and its size word
+    const size_t cost = nb * (128 + 4) + pack_bytes + ((size_t)fs.ntiles + fs.nchunks) * 8 + sizeof(FrameCtrl) + 8;
+    std::vector<size_t> costs(F, cost), base(F);
+    size_t max_group_bytes = 0;
+    plan_groups(costs.data(), F, budget_bytes("jpege_scratch_budget_mb", 4096.0), kMaxGroupFrames, &group_begin,
+                base.data(), &max_group_bytes);
+    sizes.assign(F, 0);
+  }
+
+  int open() {
+    size_t most = 0;
+    for (size_t gi = 0; gi < groups(); ++gi) most = group_frames(gi) > most ? group_frames(gi) : most;
+    int rc;
+    if ((rc = scratch.alloc(layout(most).total))) return rc;
+    if ((rc = blob.alloc(sizeof(Blob)))) return rc;
+    Blob hb;
+    std::memset(&hb, 0, sizeof(hb));
+    uint8_t q[2][64];
+    jpeg::quant_tables(quality, q);
+    for (int t = 0; t < 2; ++t)
+      for (int i = 0; i < 64; ++i) hb.divisor[t][i] = (uint16_t)(8 * q[t][i]);
+    hb.header_bytes = (uint32_t)jpeg::write_header(hb.header, sizeof(hb.header), g.width, g.height, channels, quality);
+    AMHIP_TRY(hipMemcpy(blob.p, &hb, sizeof(Blob), hipMemcpyHostToDevice));
+    return AMHIP_OK;
+  }
+
+  // passes 1 - 5 of group gi up to its files' sizes and offsets; `px`: the group's first frame.
+  // Reads back the sizes, nothing else.
+  int front(size_t gi, const uint8_t* px) {
+    const size_t n = group_frames(gi);
+    const Layout l = layout(n);
+    uint8_t* d = scratch.as<uint8_t>();
+    FrameCtrl* ctrl = reinterpret_cast<FrameCtrl*>(d + l.ctrl);
+    unsigned long long* dsizes = reinterpret_cast<unsigned long long*>(d + l.sizes);
+    int16_t* coef = reinterpret_cast<int16_t*>(d + l.coef);
+    uint32_t* bits = reinterpret_cast<uint32_t*>(d + l.bits);
+    unsigned long long* tile = reinterpret_cast<unsigned long long*>(d + l.tile);
+    unsigned long long* chunk = reinterpret_cast<unsigned long long*>(d + l.chunk);
+    uint32_t* words = reinterpret_cast<uint32_t*>(d + l.pack);
+    const Blob* b = blob.as<const Blob>();
+    AMHIP_TRY(hipMemsetAsync(words, 0, n * pack_bytes, stream));
+    const dim3 gb((unsigned)((nb + kBlocksPerGroup - 1) / kBlocksPerGroup), (unsigned)n);
+    if (channels == 1)
+      hipLaunchKernelGGL(k_jpegf_blocks<kGray8>, gb, dim3(256), 0, stream, px, row_step, frame_stride, g, b, coef);
+    else
+      hipLaunchKernelGGL(k_jpegf_blocks<kBgr8>, gb, dim3(256), 0, stream, px, row_step, frame_stride, g, b, coef);
+    const dim3 gt(fs.ntiles, (unsigned)n), gc(fs.nchunks, (unsigned)n);
+    hipLaunchKernelGGL(k_jpegf_lengths, gt, dim3(kTile), 0, stream, coef, g, fs, bits, tile);
+    hipLaunchKernelGGL(k_jpegf_scan, dim3((unsigned)n), dim3(64), 0, stream, tile, fs.ntiles, ctrl, 0);
+    hipLaunchKernelGGL(k_jpegf_pack, gt, dim3(kTile), 0, stream, coef, g, fs, bits, tile, words);
+    hipLaunchKernelGGL(k_jpegf_ff_count, gc, dim3(256), 0, stream, words, fs, ctrl, chunk);
+    hipLaunchKernelGGL(k_jpegf_scan, dim3((unsigned)n), dim3(64), 0, stream, chunk, fs.nchunks, ctrl, 1);
+    hipLaunchKernelGGL(k_jpegf_offsets, dim3(1), dim3(64), 0, stream, ctrl, (unsigned)n, b, dsizes);
+    AMHIP_TRY(hipGetLastError());
+    AMHIP_TRY(hipMemcpyAsync(sizes.data() + group_begin[gi], dsizes, n * 8, hipMemcpyDeviceToHost, stream));
+    AMHIP_TRY(hipStreamSynchronize(stream));
+    return AMHIP_OK;
+  }
+
+  // ... and the copy of group gi's files into `out`, which holds group_bytes(gi) bytes.  front(gi)
+  // ran last.
+  int back(size_t gi, uint8_t* out) {
+    const size_t n = group_frames(gi);
+    const Layout l = layout(n);
+    uint8_t* d = scratch.as<uint8_t>();
+    unsigned long long most = 0;
+    for (size_t f = group_begin[gi]; f < group_begin[gi + 1]; ++f) most = sizes[f] > most ? sizes[f] : most;
+    // (a file is its scan and more: no scan has more chunks than the largest file)
+    const unsigned chunks = (unsigned)((most + kChunk - 1) / kChunk);
+    hipLaunchKernelGGL(k_jpegf_stuff, dim3(chunks < fs.nchunks ? chunks : fs.nchunks, (unsigned)n), dim3(256), 0,
+                       stream, reinterpret_cast<const uint32_t*>(d + l.pack), fs,
+                       reinterpret_cast<const FrameCtrl*>(d + l.ctrl),
+                       reinterpret_cast<const unsigned long long*>(d + l.chunk), blob.as<const Blob>(), out);
+    AMHIP_TRY(hipGetLastError());
+    return AMHIP_OK;
+  }
+};
+
+// the argument rules of both entry points; the text names the export and the field
+int check_frames_args(const char* who, size_t F, int width, int height, int channels, size_t row_step,
+                      size_t frame_stride, int quality) {
+  auto fail = [who](const std::string& msg) {
+    set_last_error(std::string(who) + ": " + msg);
+    return AMHIP_ERR_ARG;
+  };
+  if (F == 0) return fail("no frames (F = 0)");
+  if (width < 1 || width > 65535) return fail("width must be 1..65535");
+  if (height < 1 || height > 65535) return fail("height must be 1..65535");
+  if (channels != 1 && channels != 3) return fail("channels must be 1 (8UC1) or 3 (8UC3, B G R)");
+  if (row_step < (size_t)width * (size_t)channels) return fail("row_step smaller than an image row");
+  if (F > 1 && frame_stride < (size_t)height * row_step) return fail("frame_stride smaller than a frame");
+  if (quality < 0 || quality > 100) return fail("quality must be 1..100 (0: 95)");
+  return AMHIP_OK;
+}
+
+}  // namespace
 
 }  // namespace amhip
 
@@ -768,6 +1105,112 @@ int amhip_layer_write_jpeg(amhip_ctx* h, int layer, int bgr, float lower, float 
   ScopedTimer timer(c, AMHIP_K_MISC);
   const JpegSource src = {dev, row, c->win_cols, c->win_rows, bgr ? kBgr8 : kGray8};
   return jpeg_write_run("amhip_layer_write_jpeg", c->stream, &c->jpeg, src, quality, filename);
+}
+
+int amhip_io_encode_jpeg_frames(int device, const uint8_t* dev_frames, size_t F, int width, int height,
+                                int channels, size_t row_step, size_t frame_stride, int quality,
+                                uint8_t** dev_files, size_t* offsets) {
+  static const char kWho[] = "amhip_io_encode_jpeg_frames";
+  if (dev_files) *dev_files = nullptr;
+  if (!dev_frames || !dev_files || !offsets) {
+    set_last_error(std::string(kWho) + ": null argument");
+    return AMHIP_ERR_ARG;
+  }
+  int rc;
+  if ((rc = check_frames_args(kWho, F, width, height, channels, row_step, frame_stride, quality))) return rc;
+  FramesEncoder enc;
+  enc.plan(F, width, height, channels, row_step, frame_stride, quality);
+  if ((rc = open_device(device, kWho))) return rc;
+  if ((rc = enc.open())) return rc;
+  DevBuf out;
+  const size_t G = enc.groups();
+  if (G == 1) {
+    if ((rc = enc.front(0, dev_frames))) return rc;
+    if ((rc = out.alloc((size_t)enc.group_bytes(0)))) return rc;
+    if ((rc = enc.back(0, out.as<uint8_t>()))) return rc;
+  } else {
+    // The result is one allocation of exactly the files' bytes, so their sizes come first: every
+    // group runs up to its sizes, then again straight into its place in the result.  No second
+    // buffer and no copy; twice the arithmetic, in calls whose scratch exceeds the budget only.
+    unsigned long long total = 0;
+    for (size_t gi = 0; gi < G; ++gi) {
+      if ((rc = enc.front(gi, dev_frames + enc.group_begin[gi] * enc.frame_stride))) return rc;
+      total += enc.group_bytes(gi);
+    }
+    if ((rc = out.alloc((size_t)total))) return rc;
+    unsigned long long at = 0;
+    for (size_t gi = 0; gi < G; ++gi) {
+      if ((rc = enc.front(gi, dev_frames + enc.group_begin[gi] * enc.frame_stride))) return rc;
+      if ((rc = enc.back(gi, out.as<uint8_t>() + at))) return rc;
+      at += enc.group_bytes(gi);
+    }
+  }
+  AMHIP_TRY(hipStreamSynchronize(enc.stream));
+  offsets[0] = 0;
+  for (size_t f = 0; f < F; ++f) offsets[f + 1] = offsets[f] + (size_t)enc.sizes[f];
+  *dev_files = static_cast<uint8_t*>(out.release());
+  return AMHIP_OK;
+}
+
+int amhip_io_write_jpeg_frames(int device, const uint8_t* frames, int on_device, size_t F, int width,
+                               int height, int channels, size_t row_step, size_t frame_stride, int quality,
+                               const char* const* filenames) {
+  static const char kWho[] = "amhip_io_write_jpeg_frames";
+  if (!frames || !filenames) {
+    set_last_error(std::string(kWho) + ": null argument");
+    return AMHIP_ERR_ARG;
+  }
+  int rc;
+  if ((rc = check_frames_args(kWho, F, width, height, channels, row_step, frame_stride, quality))) return rc;
+  for (size_t f = 0; f < F; ++f)
+    if (!filenames[f]) {
+      set_last_error(std::string(kWho) + ": filenames[" + std::to_string(f) + "] is null");
+      return AMHIP_ERR_ARG;
+    }
+  FramesEncoder enc;
+  enc.plan(F, width, height, channels, row_step, frame_stride, quality);
+  if ((rc = open_device(device, kWho))) return rc;
+  if ((rc = enc.open())) return rc;
+  // group by group: encode, download the group's bytes, write its files in order
+  DevBuf staged;   // a group of host frames, uploaded
+  if (!on_device) {
+    size_t most = 0;
+    for (size_t gi = 0; gi < enc.groups(); ++gi) most = enc.group_span(gi) > most ? enc.group_span(gi) : most;
+    if ((rc = staged.alloc(most))) return rc;
+  }
+  std::vector<uint8_t> host;
+  for (size_t gi = 0; gi < enc.groups(); ++gi) {
+    const size_t first = enc.group_begin[gi];
+    const uint8_t* px = frames + first * enc.frame_stride;
+    if (!on_device) {
+      AMHIP_TRY(hipMemcpyAsync(staged.p, px, enc.group_span(gi), hipMemcpyHostToDevice, enc.stream));
+      px = staged.as<const uint8_t>();
+    }
+    if ((rc = enc.front(gi, px))) return rc;
+    const size_t bytes = (size_t)enc.group_bytes(gi);
+    DevBuf out;
+    if ((rc = out.alloc(bytes))) return rc;
+    if ((rc = enc.back(gi, out.as<uint8_t>()))) return rc;
+    // Down in slices of consecutive files, kWriteSlice bytes at the most (one file at the least): the
+    // host buffer is touched once and reused, where one buffer for a group of 200 MB would be fresh
+    // pages, faulted in and zeroed, on every call.
+    const size_t last = enc.group_begin[gi + 1];
+    size_t at = 0;
+    for (size_t f = first; f < last;) {
+      size_t slice = (size_t)enc.sizes[f], end = f + 1;
+      while (end < last && slice + (size_t)enc.sizes[end] <= kWriteSlice) slice += (size_t)enc.sizes[end++];
+      if (host.size() < slice) host.resize(slice);
+      AMHIP_TRY(hipMemcpyAsync(host.data(), out.as<uint8_t>() + at, slice, hipMemcpyDeviceToHost, enc.stream));
+      AMHIP_TRY(hipStreamSynchronize(enc.stream));
+      size_t in_slice = 0;
+      for (; f < end; ++f) {
+        if ((rc = write_file(kWho, filenames[f], host.data() + in_slice, (size_t)enc.sizes[f]))) return rc;
+        in_slice += (size_t)enc.sizes[f];
+      }
+      at += slice;
+    }
+  }
+  return AMHIP_OK;
 }
 
 }  // extern "C"

@@ -72,6 +72,7 @@ EXPORTS = [
     "amhip_session_layer_write_jpeg", "amhip_mosaic_encode_jpeg_dev", "amhip_mosaic_write_jpeg",
     "amhip_jpeg_info", "amhip_io_decode_jpeg_frames", "amhip_io_download_frames",
     "amhip_png_info", "amhip_io_decode_png_frames",
+    "amhip_io_encode_jpeg_frames", "amhip_io_write_jpeg_frames",
 ]
 
 
@@ -310,6 +311,10 @@ def load():
     lib.amhip_io_download_frames.argtypes = [vp, C.c_size_t, vp]
     lib.amhip_png_info.argtypes = lib.amhip_jpeg_info.argtypes
     lib.amhip_io_decode_png_frames.argtypes = lib.amhip_io_decode_jpeg_frames.argtypes
+    lib.amhip_io_encode_jpeg_frames.argtypes = [C.c_int, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t,
+                                                C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    lib.amhip_io_write_jpeg_frames.argtypes = [C.c_int, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                               C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_char_p)]
     del u8p
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:

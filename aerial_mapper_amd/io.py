@@ -8,7 +8,11 @@ OrthoFromPcl.process; `load_poses_text` reads the small pose file on the host;
 `decode_png_frames` their PNG files (`<directory><name>.png`,
 amhip_png_decode.hip) on the GPU; both leave them in HBM as one stack in the
 same layout (DeviceFrames), ready for OrthoBackwardGrid.process,
-OrthoForwardHomography.batch and Stereo.add_frames.
+OrthoForwardHomography.batch and Stereo.add_frames.  The other way,
+`encode_jpeg_frames` / `write_jpeg_frames` turn such a stack into JPEG files
+in one batched encode (amhip_jpeg.hip), and `to_standard_format` /
+`export_pix4d_geofile` / `load_poses_ros` mirror the format converters built
+on it (aerial-mapper-io.cc:58-101,123-205,272-307).
 """
 import ctypes as C
 import mmap
@@ -214,6 +218,140 @@ def load_images_named(directory, image_names, colored=False, device=0):
         with open("%s%s.png" % (directory, name), "rb") as f:
             files.append(f.read())
     return decode_png_frames(files, colored, device)
+
+
+def _refuse(text):
+    raise L.AmhipError(L.ERR_ARG, text)
+
+
+def _frames_arg(frames, device, to_device):
+    """frames -> (pointer, on_device, F, width, height, channels, row_step, frame_stride, keepalive);
+    to_device: a numpy array is uploaded first (the encode call takes device frames only)"""
+    if isinstance(frames, DeviceFrames):
+        return (frames._ptr, 1, frames.num_frames, frames.width, frames.height, frames.channels, frames.row_step,
+                frames.frame_stride, frames)
+    if isinstance(frames, np.ndarray):
+        if frames.dtype != np.uint8 or frames.ndim not in (3, 4) or (frames.ndim == 4 and frames.shape[3] != 3):
+            _refuse("frames: a uint8 array (F, H, W) or (F, H, W, 3) is expected")
+        frames = np.ascontiguousarray(frames)
+        if to_device:
+            import torch
+            return _frames_arg(torch.from_numpy(frames).to("cuda:%d" % device), device, False)
+        n, h, w = frames.shape[:3]
+        ch = 3 if frames.ndim == 4 else 1
+        return frames.ctypes.data, 0, n, w, h, ch, w * ch, h * w * ch, frames
+    import torch
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8):
+        _refuse("frames: a DeviceFrames, a CUDA uint8 tensor or a numpy uint8 array is expected")
+    if frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3):
+        _refuse("frames: a tensor (F, H, W) or (F, H, W, 3) is expected")
+    n, h, w = frames.shape[:3]
+    ch = 3 if frames.dim() == 4 else 1
+    # rows and frames may be padded; within a row the bytes are dense (a dimension of one element has
+    # no stride to speak of)
+    if (w > 1 and frames.stride(2) != ch) or (ch == 3 and frames.stride(3) != 1):
+        _refuse("frames: only rows and frames may be strided, a row's pixels must be dense")
+    row_step = frames.stride(1) if h > 1 else w * ch
+    frame_stride = frames.stride(0) if n > 1 else h * row_step
+    return frames.data_ptr(), 1, n, w, h, ch, row_step, frame_stride, frames
+
+
+def encode_jpeg_frames(frames, quality=95, device=0):
+    """amhip_io_encode_jpeg_frames: every frame of a stack as the baseline JPEG file libjpeg writes at
+    `quality` (8UC1 as one component, 8UC3 B, G, R as Y Cb Cr 4:2:0), all in one batched encode on the
+    GPU -> list of bytes, file f what export.encode_jpeg gives for frame f.  frames: a DeviceFrames, a
+    CUDA uint8 tensor (F, H, W) or (F, H, W, 3) whose rows and frames may be padded, or a numpy array."""
+    lib = L.load()
+    ptr, _, n, w, h, ch, row, stride, keep = _frames_arg(frames, int(device), True)
+    out = C.c_void_p()
+    offsets = (C.c_size_t * (n + 1))()
+    L.check(lib.amhip_io_encode_jpeg_frames(int(device), C.c_void_p(ptr), n, w, h, ch, row, stride, int(quality),
+                                            C.byref(out), offsets))
+    del keep
+    try:
+        host = np.empty(offsets[n], np.uint8)
+        L.check(lib.amhip_io_download_frames(out, host.size, C.c_void_p(host.ctypes.data)))
+    finally:
+        lib.amhip_io_free(out)
+    return [host[offsets[f]:offsets[f + 1]].tobytes() for f in range(n)]
+
+
+def write_jpeg_frames(frames, filenames, quality=95, device=0):
+    """amhip_io_write_jpeg_frames: the files of encode_jpeg_frames, written: frame f to filenames[f].  A
+    file that cannot be written raises and names it; the files before it stay, none behind it is written."""
+    lib = L.load()
+    ptr, on_device, n, w, h, ch, row, stride, keep = _frames_arg(frames, int(device), False)
+    filenames = [os.fsencode(f) for f in filenames]
+    if len(filenames) != n:
+        _refuse("write_jpeg_frames: %d frames, %d filenames" % (n, len(filenames)))
+    names = (C.c_char_p * max(n, 1))(*filenames)
+    L.check(lib.amhip_io_write_jpeg_frames(int(device), C.c_void_p(ptr), on_device, n, w, h, ch, row, stride,
+                                           int(quality), names))
+    del keep
+
+
+def _leading_numbers(filename, per_record):
+    """what a loop of `infile >> a >> b >> ..` reads: whole records of numbers up to the first token that
+    is none"""
+    vals = []
+    with open(filename, "rb") as f:
+        for tok in f.read().split():
+            try:
+                vals.append(float(tok))
+            except ValueError:
+                break
+    n = len(vals) // per_record
+    return np.asarray(vals[:per_record * n], np.float64).reshape(n, per_record)
+
+
+def load_poses_ros(filename):
+    """io::AerialMapperIO::loadPosesFromFileRos: records `time x y z qx qy qz qw` -> (poses (n,7) float64
+    as x y z qw qx qy qz, timestamps (n,) int64: the time read as a double, then truncated)."""
+    if not filename:
+        _refuse("Empty filename")
+    rec = _leading_numbers(filename, 8)
+    if len(rec) == 0:
+        _refuse("No poses loaded.")
+    return np.ascontiguousarray(rec[:, [1, 2, 3, 7, 4, 5, 6]]), rec[:, 0].astype(np.int64)
+
+
+def to_standard_format(directory, poses_csv, id_time_csv, new_directory, device=0):
+    """io::AerialMapperIO::toStandardFormat: a simulated dataset (<directory><poses_csv>,
+    <directory><id_time_csv>, <directory>cam0/<name>.png) -> <new_directory>opt_poses.txt and
+    <new_directory>image_<i>.jpg.  The frames are decoded into HBM and encoded from there; only file
+    bytes cross to the host.  An image without a pose raises.  Returns the associated poses (n,7)."""
+    poses, stamps = load_poses_ros(directory + poses_csv)
+    names, picked = [], []
+    for _, name in _leading_numbers(directory + id_time_csv, 2):
+        names.append(str(int(name)))
+        hits = np.nonzero(stamps == int(name) - 1)[0]
+        if len(hits) == 0:
+            _refuse("toStandardFormat: CHECK(found_pose_for_image): no pose at timestamp %d for image %s.png"
+                    % (int(name) - 1, names[-1]))
+        picked.append(hits[-1])          # (the reference's loop has no break: the last match wins)
+    associated = poses[picked] if picked else np.zeros((0, 7))
+    with open(new_directory + "opt_poses.txt", "w") as f:
+        for p in associated:
+            f.write(" ".join("%g" % v for v in p) + "\n")
+    frames = load_images_named(directory + "cam0/", names, False, device)
+    write_jpeg_frames(frames, ["%simage_%d.jpg" % (new_directory, i) for i in range(len(names))], 95, device)
+    frames.close()
+    return associated
+
+
+def export_pix4d_geofile(poses, frames, output_directory="/tmp/pix4d", device=0):
+    """io::AerialMapperIO::exportPix4dGeofile: <output_directory>/image_%010d.jpeg, numbered from 1, in
+    one batched encode, and <output_directory>/geofile.txt with a line `image_<n>.jpeg x y z` (%.15g) per
+    image.  poses: (n,7) x y z qw qx qy qz; frames: as encode_jpeg_frames.  The directory is not created."""
+    poses = np.asarray(poses, np.float64).reshape(-1, 7)
+    n = _frames_arg(frames, int(device), False)[2]
+    if n != len(poses):
+        _refuse("exportPix4dGeofile: CHECK(images.size() == T_G_Cs.size()): %d images, %d poses" % (n, len(poses)))
+    stems = ["image_%010d.jpeg" % (i + 1) for i in range(n)]
+    write_jpeg_frames(frames, [output_directory + "/" + s for s in stems], 95, device)
+    with open(output_directory + "/geofile.txt", "w") as geofile:
+        for s, p in zip(stems, poses):
+            geofile.write("%s %.15g %.15g %.15g\n" % (s, p[0], p[1], p[2]))
 
 
 def load_images(filename_base, num_poses, colored=False, device=0):

@@ -15,10 +15,17 @@
 //     (amhip_io_decode_png_frames): inflate as zlib defines it, the pixels Pillow gives; 8 bit,
 //     not interlaced; gray from a colour file by libpng's rgb_to_gray rule (adopted, unpinned);
 //     no imshow.
-// The camera-rig loader (aslam YAML) and the format converters stay the reference's.
+//   loadPosesFromFile (:35-56), loadPosesFromFileRos (:58-101) -- read on the host.
+//   toStandardFormat / convertFromSimulation (:123-205) and exportPix4dGeofile (:272-307) -- their
+//     loops of cv::imwrite as ONE batched baseline JPEG encode on the GPU
+//     (amhip_io_write_jpeg_frames): the files libjpeg writes at cv::imwrite's quality 95;
+//     toStandardFormat's frames go from the PNG decoder's stack in HBM straight into the encoder;
+//     no imshow / waitKey.
+// The camera-rig loader (aslam YAML) stays the reference's.
 #ifndef AERIAL_MAPPER_HIP_IO_TYPES_H_
 #define AERIAL_MAPPER_HIP_IO_TYPES_H_
 
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -39,7 +46,31 @@ class AerialMapperIO {
   EIGEN_MAKE_ALIGNED_OPERATOR_NEW
   AerialMapperIO() {}
 
+  // Standard: loadPosesFromFileStandard; COLMAP and PIX4D are fatal ("Not yet implemented!")
+  void loadPosesFromFile(const PoseFormat& format, const std::string& filename, Poses* T_G_Bs);
+
   void loadPosesFromFileStandard(const std::string& filename, Poses* T_G_Bs);
+
+  // records `time x y z qx qy qz qw`; the time is read as a double and stored as int64_t
+  void loadPosesFromFileRos(const std::string& filename, Poses* T_G_Bs,
+                            std::vector<int64_t>* timestamps_ns);
+
+  // toStandardFormat("/tmp/to_convert/", "vi_imu_poses.csv", "blender_id_time.csv", "/tmp/simulation2/")
+  void convertFromSimulation();
+
+  // <directory><filename_vi_imu_poses> (loadPosesFromFileRos) and <directory><filename_blender_id_time>
+  // (`id name` pairs, the image's timestamp is name - 1) -> <new_directory>opt_poses.txt (the pose of
+  // every image, `x y z qw qx qy qz`) and <new_directory>image_<i>.jpg, <directory>cam0/<name>.png
+  // decoded and encoded again on the GPU.  An image without a pose is fatal.
+  void toStandardFormat(const std::string& directory, const std::string& filename_vi_imu_poses,
+                        const std::string& filename_blender_id_time, const std::string& new_directory);
+
+  // /tmp/pix4d/image_%010d.jpeg, numbered from 1, and /tmp/pix4d/geofile.txt (`image_<n>.jpeg x y z`).
+  // The images go to the device once, as one stack, and are encoded in one batch; they must agree in
+  // size and type (fatal, naming the image).  The directory is not created.
+  void exportPix4dGeofile(const Poses& T_G_Cs, const Images& images);
+  // --- extension: the same into another directory
+  void exportPix4dGeofile(const Poses& T_G_Cs, const Images& images, const std::string& output_directory);
 
   void loadPointCloudFromFile(const std::string& filename_point_cloud,
                               AlignedType<std::vector, Eigen::Vector3d>::type* point_cloud_xyz,
@@ -84,6 +115,13 @@ class AerialMapperIO {
                                   const std::vector<std::string>& image_names,
                                   bool load_colored_images, uint8_t** dev_frames, int* width, int* height,
                                   size_t* row_step, size_t* frame_stride);
+
+  // --- extension: the twin of loadImagesFromFileToDevice: F frames of a stack in HBM (8UC1 or 8UC3
+  // B, G, R) -> filenames[f], one batched JPEG encode (amhip_io_write_jpeg_frames).  A file that
+  // cannot be written is fatal and named; the files before it stay.
+  void writeImagesToFileFromDevice(const uint8_t* dev_frames, size_t F, int width, int height, int channels,
+                                   size_t row_step, size_t frame_stride,
+                                   const std::vector<std::string>& filenames, int quality = 95);
 
   // --- extension: the same cloud as a binary file (amhip_io_write_point_cloud_binary) and its
   // loader, staged through pinned buffers straight into HBM.

@@ -557,6 +557,31 @@ int amhip_jpeg_write(amhip_ctx* ctx, const char* filename, const uint8_t* pixels
 int amhip_layer_write_jpeg(amhip_ctx* ctx, int layer, int bgr, float lower, float upper, int quality,
                            const char* filename);
 
+/* ---- a stack of frames -> JPEG files, one batched encode: the cv::imwrite loops of
+ *      io::AerialMapperIO::toStandardFormat (aerial-mapper-io.cc:199-204) and exportPix4dGeofile (:284-305) ----
+ * The frames of a call share width, height, channels and quality, so every pass of the encoder above runs
+ * once per group of frames, not once per frame, and only the files' sizes are read back.  Synchronous calls
+ * on the default stream that take a device, not a context, like the decoders.  Scratch lives for the call
+ * and is bounded by encoding in groups of frames (tuning key jpege_scratch_budget_mb); the result does not
+ * depend on the grouping.  AMHIP_ERR_ARG with a text naming the export and the field, before any device is
+ * touched and with *dev_files = NULL: a null pointer; F = 0; width or height outside 1..65535; channels
+ * other than 1 or 3; row_step < width * channels; F > 1 and frame_stride < height * row_step; quality
+ * outside 0..100; a null filenames[f]. */
+/* F frames of one stack (frame f at dev_frames + f * frame_stride, rows row_step bytes apart: the layout
+ * amhip_io_decode_*_frames leave) -> F baseline JPEG files, tightly concatenated in device memory:
+ * file f is bytes [offsets[f], offsets[f + 1]) of *dev_files, offsets[0] = 0 (offsets: F + 1 host words).
+ * channels 1 (8UC1) or 3 (8UC3 B, G, R -> Y Cb Cr 4:2:0); quality 1..100, 0 = 95.  Each file is byte for
+ * byte what amhip_jpeg_encode_dev writes for that frame.  Release *dev_files with amhip_io_free(). */
+int amhip_io_encode_jpeg_frames(int device, const uint8_t* dev_frames, size_t F, int width, int height,
+                                int channels, size_t row_step, size_t frame_stride, int quality,
+                                uint8_t** dev_files, size_t* offsets);
+/* the same, downloaded and written: file f to filenames[f].  frames: host or device (on_device).  Group by
+ * group: encode, download, write the group's files in order.  A file that cannot be opened or written is
+ * AMHIP_ERR_ARG with its name and errno's text; the files before it stay, none behind it is written. */
+int amhip_io_write_jpeg_frames(int device, const uint8_t* frames, int on_device, size_t F, int width,
+                               int height, int channels, size_t row_step, size_t frame_stride, int quality,
+                               const char* const* filenames);
+
 /* The GeoTiff container io::AerialMapperIO::toGeoTiff / writeDataToDEMGeoTiffColor produce with
  * GDAL (aerial_mapper_io/src/aerial-mapper-io.cc:349-509), without GDAL: classic little-endian
  * TIFF, 8 bits per sample, bands = 1 (BlackIsZero) or 3 (pixel interleaved, as GDAL's GTiff
@@ -968,6 +993,9 @@ int amhip_session_layer_write_jpeg(amhip_session* s, int layer, int bgr, float l
  *   no_distorted_cull, no_distorted_prune, distorted_square_cull   cameras with a distortion model
  *   jpegd_coef_budget_mb (4096)  amhip_io_decode_jpeg_frames: MB of coefficient scratch per group of frames;
  *                             groups run one after another (a small value forces several groups)
+ *   jpege_scratch_budget_mb (4096)  amhip_io_encode_jpeg_frames / amhip_io_write_jpeg_frames: MB of encoder
+ *                             scratch (340 B per scan block) per group of frames; groups run one after
+ *                             another, at least one frame each
  *   pngd_raw_budget_mb (4096)  amhip_io_decode_png_frames: MB of raw scanlines per group of frames; groups run
  *                             one after another, at least one frame each
  *   session_always_copy, session_threads, session_scalar_sums, session_no_partial,
