@@ -13,9 +13,11 @@ from .mapper import (AerialGridMap, Dsm, DsmSettings, GridMapSettings, HostSessi
                      BlockMatchingParameters, compose_T_G_C, compute_disparity_sgbm, compute_disparity_bm, densify, dense_cloud_from_stereo_pair, rectify_stereo_pair,
                      Stereo, StereoSettings)
 from .export import encode_jpeg, write_jpeg, layer_to_jpeg, session_layer_to_jpeg  # noqa: F401
+from .export import encode_png, write_png, layer_to_png, session_layer_to_png  # noqa: F401
 
 __all__ = ["AerialGridMap", "GridMapSettings", "HostSession", "Dsm", "DsmSettings", "OrthoBackwardGrid",
            "OrthoSettings", "OrthoForwardHomography", "OrthoForwardHomographySettings", "OrthoFromPcl", "OrthoFromPclSettings", "NCamera", "compose_T_G_C", "densify", "rectify_stereo_pair", "SgbmParameters", "compute_disparity_sgbm", "BmParameters", "BlockMatchingParameters", "compute_disparity_bm", "dense_cloud_from_stereo_pair", "Stereo", "StereoSettings", "AmhipError", "Camera", "GridDesc",
            "make_grid", "cell_position", "encode_jpeg", "write_jpeg", "layer_to_jpeg", "session_layer_to_jpeg",
+           "encode_png", "write_png", "layer_to_png", "session_layer_to_png",
            "LAYER_NAMES", "DIST_NONE", "DIST_RADTAN",
            "DIST_EQUIDISTANT"]

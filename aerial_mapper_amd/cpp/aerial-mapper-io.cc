@@ -273,6 +273,18 @@ void AerialMapperIO::writeImagesToFileFromDevice(const uint8_t* dev_frames, size
       "writeImagesToFileFromDevice");
 }
 
+void AerialMapperIO::writePngImagesToFileFromDevice(const uint8_t* dev_frames, size_t F, int width, int height,
+                                                    int channels, size_t row_step, size_t frame_stride,
+                                                    const std::vector<std::string>& filenames) {
+  if (filenames.size() != F) amhip_shim::fatal("writePngImagesToFileFromDevice", "CHECK(filenames.size() == F)");
+  std::vector<const char*> names;
+  for (const std::string& name : filenames) names.push_back(name.c_str());
+  amhip_shim::check_status(
+      amhip_io_write_png_frames(device_index(), dev_frames, 1, F, width, height, channels, row_step,
+                                frame_stride, names.data()),
+      "writePngImagesToFileFromDevice");
+}
+
 void AerialMapperIO::convertFromSimulation() {
   toStandardFormat("/tmp/to_convert/", "vi_imu_poses.csv", "blender_id_time.csv", "/tmp/simulation2/");
 }

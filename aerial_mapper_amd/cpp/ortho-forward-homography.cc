@@ -93,13 +93,23 @@ cv::Mat OrthoForwardHomography::result8() const {
   return out;
 }
 
+// does the name end in ".png", compared without case as cv::imwrite's encoder lookup compares it
+static bool names_a_png(const std::string& name) {
+  if (name.size() < 4) return false;
+  const char* e = name.c_str() + name.size() - 4;
+  return e[0] == '.' && (e[1] | 0x20) == 'p' && (e[2] | 0x20) == 'n' && (e[3] | 0x20) == 'g';
+}
+
 void OrthoForwardHomography::writeOutput() const {
   if (settings_.filename_mosaic_output.empty()) return;
   // cv::imwrite(settings_.filename_mosaic_output, result_) (:126-128, :188): the file the
   // settings name, encoded on the GPU from the device-resident result_ (clamped to 0..255 as
-  // result8() clamps it; quality 95, libjpeg's defaults).  Like cv::imwrite, a file that cannot
-  // be written is reported and not fatal.
-  const int rc = amhip_mosaic_write_jpeg(mosaic_, 95, settings_.filename_mosaic_output.c_str());
+  // result8() clamps it).  cv::imwrite picks the encoder by the extension: a name that ends in .png
+  // gets a PNG file, every other name the JPEG of before (quality 95, libjpeg's defaults).  Like
+  // cv::imwrite, a file that cannot be written is reported and not fatal.
+  const char* filename = settings_.filename_mosaic_output.c_str();
+  const int rc = names_a_png(settings_.filename_mosaic_output) ? amhip_mosaic_write_png(mosaic_, filename)
+                                                               : amhip_mosaic_write_jpeg(mosaic_, 95, filename);
   if (rc != AMHIP_OK)
     std::fprintf(stderr, "OrthoForwardHomography: %s not written: %s\n",
                  settings_.filename_mosaic_output.c_str(), amhip_last_error());

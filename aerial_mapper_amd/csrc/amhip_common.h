@@ -215,6 +215,14 @@ int jpeg_encode_run(hipStream_t stream, JpegScratch* ws, const JpegSource& src, 
 // encode, download, write `filename`
 int jpeg_write_run(const char* what, hipStream_t stream, JpegScratch* ws, const JpegSource& src,
                    int quality, const char* filename);
+// the whole of `data` to `filename`; a failure is AMHIP_ERR_ARG with `what`, the name and errno's text
+int write_file(const char* what, const char* filename, const uint8_t* data, size_t size);
+
+// The PNG encoder (amhip_png_encode.hip) on the same sources: the file into dev_out (at most cap
+// bytes, nothing written when it does not fit: AMHIP_ERR_ARG), or downloaded and written.  Its
+// scratch lives for the call.  Arguments checked by the callers (pnge::check_image_args).
+int png_encode_run(hipStream_t stream, const JpegSource& src, uint8_t* dev_out, size_t cap, size_t* bytes);
+int png_write_run(const char* what, hipStream_t stream, const JpegSource& src, const char* filename);
 
 struct TimedRegion {
   hipEvent_t a, b;

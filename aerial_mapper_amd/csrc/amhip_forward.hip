@@ -1087,6 +1087,34 @@ int amhip_mosaic_write_jpeg(amhip_mosaic* h, int quality, const char* filename) 
                         filename);
 }
 
+/* ... and as a PNG file, what cv::imwrite writes when the name ends in .png (amhip_png_encode.hip): the same
+ * clamped B G R, as colour type 2. */
+static int mosaic_png_check(const char* what, const amhip_mosaic* h) {
+  const amhip_mosaic_desc& d = h->impl.desc;
+  if (d.width_mosaic_pixels < 1 || d.height_mosaic_pixels < 1 || d.width_mosaic_pixels > 65535 ||
+      d.height_mosaic_pixels > 65535)
+    return fwd_arg_fail((std::string(what) + ": a PNG file of this encoder holds 1 x 1 to 65535 x 65535 pixels").c_str());
+  return AMHIP_OK;
+}
+
+int amhip_mosaic_encode_png_dev(amhip_mosaic* h, uint8_t* dev_out, size_t cap, size_t* bytes) {
+  if (!h || !dev_out || !bytes) return fwd_arg_fail("amhip_mosaic_encode_png_dev: null argument");
+  int rc = mosaic_png_check("amhip_mosaic_encode_png_dev", h);
+  if (rc) return rc;
+  Mosaic* m = &h->impl;
+  if ((rc = fwd_use(m))) return rc;
+  return png_encode_run(m->stream, mosaic_jpeg_source(m), dev_out, cap, bytes);
+}
+
+int amhip_mosaic_write_png(amhip_mosaic* h, const char* filename) {
+  if (!h || !filename) return fwd_arg_fail("amhip_mosaic_write_png: null argument");
+  int rc = mosaic_png_check("amhip_mosaic_write_png", h);
+  if (rc) return rc;
+  Mosaic* m = &h->impl;
+  if ((rc = fwd_use(m))) return rc;
+  return png_write_run("amhip_mosaic_write_png", m->stream, mosaic_jpeg_source(m), filename);
+}
+
 int amhip_mosaic_device_ptr(amhip_mosaic* h, void** result_16sc3, void** result_mask) {
   if (!h) return fwd_arg_fail("null mosaic");
   if (result_16sc3) *result_16sc3 = h->impl.result16;

@@ -837,9 +837,11 @@ int encode_to_host(hipStream_t stream, JpegScratch* ws, const JpegSource& src, i
   return AMHIP_OK;
 }
 
+}  // namespace
+
 // (the status enum has no I/O code: a file that cannot be written is AMHIP_ERR_ARG, as in the
 // GeoTiff and point-cloud writers, with errno's text)
-int write_failure(const char* what, const char* filename, int err) {
+static int write_failure(const char* what, const char* filename, int err) {
   set_last_error(std::string(what) + ": cannot write " + filename + ": " + std::strerror(err));
   return AMHIP_ERR_ARG;
 }
@@ -861,8 +863,6 @@ int write_file(const char* what, const char* filename, const uint8_t* data, size
   if (::close(fd) != 0) return write_failure(what, filename, errno);
   return AMHIP_OK;
 }
-
-}  // namespace
 
 int jpeg_write_run(const char* what, hipStream_t stream, JpegScratch* ws, const JpegSource& src,
                    int quality, const char* filename) {

@@ -1211,4 +1211,21 @@ int amhip_session_layer_write_jpeg(amhip_session* h, int layer, int bgr, float l
                           bgr ? 3 : 1, quality);
 }
 
+/* ... and amhip_layer_write_png, the same way */
+int amhip_session_layer_write_png(amhip_session* h, int layer, int bgr, float lower, float upper,
+                                  const char* filename) {
+  if (!h || !filename || layer < 0 || layer >= AMHIP_NUM_LAYERS)
+    return arg_failure("amhip_session_layer_write_png: bad argument");
+  if (!bgr && !(upper > lower)) return arg_failure("amhip_session_layer_write_png: upper <= lower");
+  Session& s = h->impl;
+  if (s.grid.rows < 1 || s.grid.cols < 1 || s.grid.rows > 65535 || s.grid.cols > 65535)
+    return arg_failure("amhip_session_layer_write_png: a PNG file of this encoder holds 1 x 1 to 65535 x 65535 pixels");
+  const size_t row = (size_t)s.grid.cols * (bgr ? 3u : 1u);
+  std::vector<uint8_t> image(row * (size_t)s.grid.rows);
+  int rc = amhip_session_layer_to_image(h, layer, bgr, lower, upper, image.data(), row);
+  if (rc) return rc;
+  return amhip_png_write(s.ctx[0], filename, image.data(), /*on_device=*/0, row, s.grid.cols, s.grid.rows,
+                         bgr ? 3 : 1);
+}
+
 }  // extern "C"

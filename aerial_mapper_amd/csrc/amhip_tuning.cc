@@ -32,6 +32,8 @@ const char* const kKeys[] = {
     "pngd_raw_budget_mb",
     // JPEG encoder, stacks of frames
     "jpege_scratch_budget_mb",
+    // PNG encoder
+    "pnge_scratch_budget_mb",
     // lab builds (-DAMHIP_TIMING_PROBES) only
     "gather_tj", "gather_nt", "gather_class_cap0", "gather_class_cap1", "gather_class_cap2", "f32_variant",
     "fx_theta"};

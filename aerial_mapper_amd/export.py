@@ -104,6 +104,59 @@ def session_layer_to_jpeg(session, layer, filename, lower=0.0, upper=255.0, bgr=
                                                     float(upper), int(quality), str(filename).encode()))
 
 
+def encode_png(map_, image, cap=None):
+    """amhip_png_encode_dev on the map's context: the PNG file cv::imwrite(name, image) writes for a
+    name that ends in .png (filter Sub, zlib level 1 with Z_RLE), as bytes.  image and cap: as
+    encode_jpeg's (cap defaults to amhip_png_bound)."""
+    import torch
+    lib = L.load()
+    if not _is_torch(image):
+        image = torch.from_numpy(np.ascontiguousarray(image, np.uint8)).to("cuda:%d" % map_.device)
+    assert image.is_cuda and image.dtype == torch.uint8 and image.dim() in (2, 3)
+    ch = 1 if image.dim() == 2 else int(image.shape[2])
+    assert image.stride(-1) == 1 and (image.dim() == 2 or image.stride(1) == ch)
+    h, w = int(image.shape[0]), int(image.shape[1])
+    bound = lib.amhip_png_bound(w, h, ch)
+    out = torch.empty(max(int(bound if cap is None else cap), 1), dtype=torch.uint8, device=image.device)
+    map_.wait_for_torch(image)
+    n = C.c_size_t()
+    L.check(lib.amhip_png_encode_dev(map_._h, C.c_void_p(image.data_ptr()), int(image.stride(0)), w, h, ch,
+                                     C.c_void_p(out.data_ptr()), int(out.numel() if cap is None else cap),
+                                     C.byref(n)))
+    return out[:n.value].cpu().numpy().tobytes()
+
+
+def write_png(map_, filename, image):
+    """amhip_png_write: encode on the map's device, download, write `filename`."""
+    lib = L.load()
+    if _is_torch(image):
+        assert image.is_cuda and image.element_size() == 1 and image.stride(-1) == 1
+        ch = 1 if image.dim() == 2 else int(image.shape[2])
+        map_.wait_for_torch(image)
+        L.check(lib.amhip_png_write(map_._h, str(filename).encode(), C.c_void_p(image.data_ptr()), 1,
+                                    int(image.stride(0)), int(image.shape[1]), int(image.shape[0]), ch))
+        return
+    image = np.ascontiguousarray(image, np.uint8)
+    ch = 1 if image.ndim == 2 else image.shape[2]
+    L.check(lib.amhip_png_write(map_._h, str(filename).encode(), C.c_void_p(image.ctypes.data), 0,
+                                image.strides[0], image.shape[1], image.shape[0], ch))
+
+
+def layer_to_png(map_, layer, filename, lower=0.0, upper=255.0, bgr=False):
+    """amhip_layer_write_png: layer_to_image on the device, encoded there without loss, written to
+    `filename`."""
+    lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
+    L.check(L.load().amhip_layer_write_png(map_._h, lid, int(bool(bgr)), float(lower), float(upper),
+                                           str(filename).encode()))
+
+
+def session_layer_to_png(session, layer, filename, lower=0.0, upper=255.0, bgr=False):
+    """amhip_session_layer_write_png: the whole map of a HostSession."""
+    lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
+    L.check(L.load().amhip_session_layer_write_png(session._h, lid, int(bool(bgr)), float(lower),
+                                                   float(upper), str(filename).encode()))
+
+
 def write_geotiff(filename, image, geotransform, utm_zone=32, northern=True):
     """amhip_geotiff_write_u8: image (H, W) or (H, W, 3) uint8, bands written in the order given."""
     lib = L.load()

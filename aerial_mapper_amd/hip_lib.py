@@ -73,6 +73,9 @@ EXPORTS = [
     "amhip_jpeg_info", "amhip_io_decode_jpeg_frames", "amhip_io_download_frames",
     "amhip_png_info", "amhip_io_decode_png_frames",
     "amhip_io_encode_jpeg_frames", "amhip_io_write_jpeg_frames",
+    "amhip_png_bound", "amhip_png_encode_dev", "amhip_png_write", "amhip_layer_write_png",
+    "amhip_session_layer_write_png", "amhip_mosaic_encode_png_dev", "amhip_mosaic_write_png",
+    "amhip_io_encode_png_frames", "amhip_io_write_png_frames",
 ]
 
 
@@ -315,6 +318,20 @@ def load():
                                                 C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
     lib.amhip_io_write_jpeg_frames.argtypes = [C.c_int, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                                C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_char_p)]
+    # the PNG encoder: the JPEG calls without `quality`
+    lib.amhip_png_bound.restype = C.c_size_t
+    lib.amhip_png_bound.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.amhip_png_encode_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]
+    lib.amhip_png_write.argtypes = [vp, C.c_char_p, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int]
+    lib.amhip_layer_write_png.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_char_p]
+    lib.amhip_session_layer_write_png.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_char_p]
+    lib.amhip_mosaic_encode_png_dev.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.amhip_mosaic_write_png.argtypes = [vp, C.c_char_p]
+    lib.amhip_io_encode_png_frames.argtypes = [C.c_int, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t,
+                                               C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    lib.amhip_io_write_png_frames.argtypes = [C.c_int, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                              C.c_size_t, C.c_size_t, C.POINTER(C.c_char_p)]
     del u8p
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:

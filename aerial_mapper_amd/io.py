@@ -10,7 +10,8 @@ amhip_png_decode.hip) on the GPU; both leave them in HBM as one stack in the
 same layout (DeviceFrames), ready for OrthoBackwardGrid.process,
 OrthoForwardHomography.batch and Stereo.add_frames.  The other way,
 `encode_jpeg_frames` / `write_jpeg_frames` turn such a stack into JPEG files
-in one batched encode (amhip_jpeg.hip), and `to_standard_format` /
+in one batched encode (amhip_jpeg.hip), `encode_png_frames` / `write_png_frames`
+into PNG files without loss (amhip_png_encode.hip), and `to_standard_format` /
 `export_pix4d_geofile` / `load_poses_ros` mirror the format converters built
 on it (aerial-mapper-io.cc:58-101,123-205,272-307).
 """
@@ -287,6 +288,39 @@ def write_jpeg_frames(frames, filenames, quality=95, device=0):
     names = (C.c_char_p * max(n, 1))(*filenames)
     L.check(lib.amhip_io_write_jpeg_frames(int(device), C.c_void_p(ptr), on_device, n, w, h, ch, row, stride,
                                            int(quality), names))
+    del keep
+
+
+def encode_png_frames(frames, device=0):
+    """amhip_io_encode_png_frames: every frame of a stack as the PNG file cv::imwrite writes (filter Sub,
+    zlib level 1 with Z_RLE; 8UC3 B, G, R stored R, G, B), all in one batched encode on the GPU -> list of
+    bytes, file f what export.encode_png gives for frame f.  frames: as encode_jpeg_frames."""
+    lib = L.load()
+    ptr, _, n, w, h, ch, row, stride, keep = _frames_arg(frames, int(device), True)
+    out = C.c_void_p()
+    offsets = (C.c_size_t * (n + 1))()
+    L.check(lib.amhip_io_encode_png_frames(int(device), C.c_void_p(ptr), n, w, h, ch, row, stride,
+                                           C.byref(out), offsets))
+    del keep
+    try:
+        host = np.empty(offsets[n], np.uint8)
+        L.check(lib.amhip_io_download_frames(out, host.size, C.c_void_p(host.ctypes.data)))
+    finally:
+        lib.amhip_io_free(out)
+    return [host[offsets[f]:offsets[f + 1]].tobytes() for f in range(n)]
+
+
+def write_png_frames(frames, filenames, device=0):
+    """amhip_io_write_png_frames: the files of encode_png_frames, written: frame f to filenames[f].  A
+    file that cannot be written raises and names it; the files before it stay, none behind it is written."""
+    lib = L.load()
+    ptr, on_device, n, w, h, ch, row, stride, keep = _frames_arg(frames, int(device), False)
+    filenames = [os.fsencode(f) for f in filenames]
+    if len(filenames) != n:
+        _refuse("write_png_frames: %d frames, %d filenames" % (n, len(filenames)))
+    names = (C.c_char_p * max(n, 1))(*filenames)
+    L.check(lib.amhip_io_write_png_frames(int(device), C.c_void_p(ptr), on_device, n, w, h, ch, row, stride,
+                                          names))
     del keep
 
 

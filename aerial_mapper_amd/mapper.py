@@ -1151,3 +1151,19 @@ class OrthoForwardHomography(object):
         L.check(lib.amhip_mosaic_encode_jpeg_dev(self.handle, int(quality), C.c_void_p(out.data_ptr()),
                                                  out.numel(), C.byref(n)))
         return out[:n.value].cpu().numpy().tobytes()
+
+    def write_png(self, filename):
+        """what cv::imwrite writes when filename_mosaic_output ends in .png: result_ clamped to 0..255,
+        encoded without loss on the device (amhip_mosaic_write_png)."""
+        L.check(L.load().amhip_mosaic_write_png(self.handle, str(filename).encode()))
+
+    def encode_png(self):
+        """the same file as bytes (amhip_mosaic_encode_png_dev)"""
+        import torch
+        lib = L.load()
+        h, w = self.desc.height_mosaic_pixels, self.desc.width_mosaic_pixels
+        out = torch.empty(lib.amhip_png_bound(w, h, 3), dtype=torch.uint8, device="cuda:%d" % self.device)
+        self._wait_for_torch(out)
+        n = C.c_size_t()
+        L.check(lib.amhip_mosaic_encode_png_dev(self.handle, C.c_void_p(out.data_ptr()), out.numel(), C.byref(n)))
+        return out[:n.value].cpu().numpy().tobytes()

@@ -123,6 +123,13 @@ class AerialMapperIO {
                                    size_t row_step, size_t frame_stride,
                                    const std::vector<std::string>& filenames, int quality = 95);
 
+  // --- extension: its PNG twin (amhip_io_write_png_frames): the files cv::imwrite writes for names
+  // that end in .png, without loss.  A twin and not a dispatch on each name: a call is one batched
+  // encode with one codec, and writeImagesToFileFromDevice keeps writing JPEG whatever the names say.
+  void writePngImagesToFileFromDevice(const uint8_t* dev_frames, size_t F, int width, int height, int channels,
+                                      size_t row_step, size_t frame_stride,
+                                      const std::vector<std::string>& filenames);
+
   // --- extension: the same cloud as a binary file (amhip_io_write_point_cloud_binary) and its
   // loader, staged through pinned buffers straight into HBM.
   void savePointCloudToBinaryFile(const std::string& filename,

@@ -582,6 +582,48 @@ int amhip_io_write_jpeg_frames(int device, const uint8_t* frames, int on_device,
                                int height, int channels, size_t row_step, size_t frame_stride, int quality,
                                const char* const* filenames);
 
+/* ---- PNG, encoded on the GPU -------------------------------------------------------------------
+ * The file libpng and zlib write for cv::imwrite(name, image) when the name ends in .png and no
+ * parameter is given (filename_mosaic_output of the forward mosaic, ortho-forward-homography.cc:
+ * 126-128, 188): signature, IHDR (bit depth 8, colour type 0 for 8UC1, 2 for 8UC3 stored R, G, B),
+ * the zlib stream in IDAT payloads of 8192 bytes, IEND, no other chunk; filter Sub on every row;
+ * zlib at level 1 with strategy Z_RLE, window 15, memLevel 8.  Byte for byte what zlib 1.2.11 writes
+ * for those scanlines (tests/golden/png_encode/); that cv::imwrite chooses these parameters is
+ * adopted, unpinned.  Lossless: amhip_io_decode_png_frames gives the pixels back.
+ * width, height 1..65535; channels 1 or 3.  The calls mirror the JPEG ones without `quality`;
+ * argument errors (AMHIP_ERR_ARG, the text names the export and the field) are reported before any
+ * device is touched, a file that cannot be written is AMHIP_ERR_ARG with errno's text.
+ *   amhip_png_bound        worst-case size of the file (0 for arguments out of range)
+ *   amhip_png_encode_dev   device pixels (rows `step` bytes apart) -> the file in dev_out, at most
+ *                          cap bytes; *bytes = the file's size.  A file larger than cap gives
+ *                          AMHIP_ERR_ARG and nothing is written.  Scratch lives for the call.
+ *   amhip_png_write        encode (host or device pixels), download, write `filename`
+ *   amhip_layer_write_png  amhip_layer_to_image_dev into scratch, then the encoder
+ *   amhip_session_layer_write_png  the whole map of a session, from the assembled image
+ *   amhip_mosaic_encode_png_dev / amhip_mosaic_write_png  the mosaic's device-resident result_
+ *                          (CV_16SC3 clamped to 0..255), as colour type 2 */
+size_t amhip_png_bound(int width, int height, int channels);
+int amhip_png_encode_dev(amhip_ctx* ctx, const uint8_t* dev_pixels, size_t step, int width, int height,
+                         int channels, uint8_t* dev_out, size_t cap, size_t* bytes);
+int amhip_png_write(amhip_ctx* ctx, const char* filename, const uint8_t* pixels, int on_device,
+                    size_t step, int width, int height, int channels);
+int amhip_layer_write_png(amhip_ctx* ctx, int layer, int bgr, float lower, float upper, const char* filename);
+int amhip_mosaic_encode_png_dev(amhip_mosaic* mosaic, uint8_t* dev_out, size_t cap, size_t* bytes);
+int amhip_mosaic_write_png(amhip_mosaic* mosaic, const char* filename);
+/* A stack of frames -> PNG files, one batched encode; the contract of amhip_io_encode_jpeg_frames /
+ * amhip_io_write_jpeg_frames above without `quality`: synchronous, on the default stream, scratch
+ * bounded by encoding in groups of frames (tuning key pnge_scratch_budget_mb), the bytes independent
+ * of the grouping and equal to amhip_png_encode_dev's for each frame.  AMHIP_ERR_ARG before any
+ * device is touched and with *dev_files = NULL: a null pointer; F = 0; width or height outside
+ * 1..65535; channels other than 1 or 3; row_step < width * channels; F > 1 and frame_stride < height
+ * * row_step; a null filenames[f].  Release *dev_files with amhip_io_free(). */
+int amhip_io_encode_png_frames(int device, const uint8_t* dev_frames, size_t F, int width, int height,
+                               int channels, size_t row_step, size_t frame_stride, uint8_t** dev_files,
+                               size_t* offsets);
+int amhip_io_write_png_frames(int device, const uint8_t* frames, int on_device, size_t F, int width,
+                              int height, int channels, size_t row_step, size_t frame_stride,
+                              const char* const* filenames);
+
 /* The GeoTiff container io::AerialMapperIO::toGeoTiff / writeDataToDEMGeoTiffColor produce with
  * GDAL (aerial_mapper_io/src/aerial-mapper-io.cc:349-509), without GDAL: classic little-endian
  * TIFF, 8 bits per sample, bands = 1 (BlackIsZero) or 3 (pixel interleaved, as GDAL's GTiff
@@ -963,6 +1005,9 @@ int amhip_session_layer_to_image(amhip_session* s, int layer, int bgr, float low
 /* amhip_layer_write_jpeg for the whole map of a session, from the assembled image. */
 int amhip_session_layer_write_jpeg(amhip_session* s, int layer, int bgr, float lower, float upper,
                                    int quality, const char* filename);
+/* amhip_layer_write_png for the whole map of a session, the same way. */
+int amhip_session_layer_write_png(amhip_session* s, int layer, int bgr, float lower, float upper,
+                                  const char* filename);
 
 /* ---- tuning knobs: the ONE door for switches that select among correct implementations ----------
  * (tests force every path through them, A-B timing flips them; none is needed in normal use).
@@ -993,6 +1038,8 @@ int amhip_session_layer_write_jpeg(amhip_session* s, int layer, int bgr, float l
  *   no_distorted_cull, no_distorted_prune, distorted_square_cull   cameras with a distortion model
  *   jpegd_coef_budget_mb (4096)  amhip_io_decode_jpeg_frames: MB of coefficient scratch per group of frames;
  *                             groups run one after another (a small value forces several groups)
+ *   pnge_scratch_budget_mb (4096)  amhip_io_encode_png_frames / amhip_io_write_png_frames: MB of encoder
+ *                             scratch per group of frames
  *   jpege_scratch_budget_mb (4096)  amhip_io_encode_jpeg_frames / amhip_io_write_jpeg_frames: MB of encoder
  *                             scratch (340 B per scan block) per group of frames; groups run one after
  *                             another, at least one frame each
