@@ -14,10 +14,14 @@ from .mapper import (AerialGridMap, Dsm, DsmSettings, GridMapSettings, HostSessi
                      Stereo, StereoSettings)
 from .export import encode_jpeg, write_jpeg, layer_to_jpeg, session_layer_to_jpeg  # noqa: F401
 from .export import encode_png, write_png, layer_to_png, session_layer_to_png  # noqa: F401
+from .export import (encode_geotiff, write_geotiff_deflate, layer_to_geotiff, encode_layer_geotiff,  # noqa: F401
+                     session_layer_to_geotiff)
 
 __all__ = ["AerialGridMap", "GridMapSettings", "HostSession", "Dsm", "DsmSettings", "OrthoBackwardGrid",
            "OrthoSettings", "OrthoForwardHomography", "OrthoForwardHomographySettings", "OrthoFromPcl", "OrthoFromPclSettings", "NCamera", "compose_T_G_C", "densify", "rectify_stereo_pair", "SgbmParameters", "compute_disparity_sgbm", "BmParameters", "BlockMatchingParameters", "compute_disparity_bm", "dense_cloud_from_stereo_pair", "Stereo", "StereoSettings", "AmhipError", "Camera", "GridDesc",
            "make_grid", "cell_position", "encode_jpeg", "write_jpeg", "layer_to_jpeg", "session_layer_to_jpeg",
            "encode_png", "write_png", "layer_to_png", "session_layer_to_png",
+           "encode_geotiff", "write_geotiff_deflate", "layer_to_geotiff", "encode_layer_geotiff",
+           "session_layer_to_geotiff",
            "LAYER_NAMES", "DIST_NONE", "DIST_RADTAN",
            "DIST_EQUIDISTANT"]

@@ -440,6 +440,38 @@ void AerialMapperIO::writeDataToDEMGeoTiffColor(const cv::Mat& ortho_image,
       "writeDataToDEMGeoTiffColor");
 }
 
+// extension: see the header.  The session's windows get the map's own matrix first (a session that was
+// made for this call knows nothing of it yet), then the whole map is written from them.
+void AerialMapperIO::writeLayerToGeoTiff(const grid_map::GridMap& map, const std::string& layer,
+                                         const std::string& filename, int utm_zone, bool northern) {
+  static const char* const kLayers[AMHIP_NUM_LAYERS] = {"ortho", "elevation", "elevation_angle", "num_observations",
+                                                        "observation_index", "colored_ortho"};
+  int id = -1;
+  for (int l = 0; l < AMHIP_NUM_LAYERS; ++l)
+    if (layer == kLayers[l]) id = l;
+  if (id < 0 || !map.exists(layer))
+    amhip_shim::fatal("writeLayerToGeoTiff", ("no layer '" + layer + "' the GPU path holds").c_str());
+  const grid_map::Matrix& m = map[layer];
+  const size_t rows = static_cast<size_t>(m.rows());
+  amhip_session* session = amhip_shim::acquire_session(map, nullptr, "writeLayerToGeoTiff");
+  std::vector<float> block;
+  for (int k = 0; k < amhip_session_num_windows(session); ++k) {
+    int32_t w[4];   // i0, j0, rows, cols
+    amhip_shim::check_status(amhip_session_window(session, k, w), "writeLayerToGeoTiff");
+    block.resize(static_cast<size_t>(w[2]) * w[3]);
+    for (int j = 0; j < w[3]; ++j)
+      std::memcpy(block.data() + static_cast<size_t>(j) * w[2], m.data() + w[0] + (static_cast<size_t>(w[1]) + j) * rows,
+                  sizeof(float) * w[2]);
+    amhip_shim::check_status(amhip_layer_upload(amhip_session_context(session, k), id, block.data()),
+                             "writeLayerToGeoTiff");
+  }
+  const int status = amhip_session_layer_write_geotiff(
+      session, id, id == AMHIP_LAYER_COLORED_ORTHO ? AMHIP_GEOTIFF_RGB8 : AMHIP_GEOTIFF_F32, 0.0f, 255.0f, 0,
+      utm_zone, northern ? 1 : 0, filename.c_str());
+  amhip_shim::release_session(session);
+  amhip_shim::check_status(status, "writeLayerToGeoTiff");
+}
+
 void AerialMapperIO::savePointCloudToBinaryFile(
     const std::string& filename,
     const AlignedType<std::vector, Eigen::Vector3d>::type& point_cloud_xyz,

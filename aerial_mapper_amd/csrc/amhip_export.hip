@@ -29,22 +29,15 @@
 #include <vector>
 
 #include "amhip_common.h"
+#include "amhip_layer_image.h"
+#include "amhip_tiff_host.h"
 
 namespace amhip {
 
 // ---------------------------------------------------------------------------
 // layer (column-major f32: (i, j) at i + j * rows) -> image (row-major: row i, column j)
 // ---------------------------------------------------------------------------
-// toImage(): image = zeros(size(0), size(1)); the layer is clamped to [lower, upper]; every cell
-// with a finite value becomes (uchar)(((v - lower) / (upper - lower)) * (float)255) -- float
-// arithmetic, truncating cast; the others stay 0.
-__device__ __forceinline__ uint8_t to_image_u8(float v, float lower, float upper) {
-  if (!isfinite(v)) return 0;
-  v = fminf(fmaxf(v, lower), upper);
-  const float t = ((v - lower) / (upper - lower)) * 255.0f;
-  return (uint8_t)(int)t;
-}
-
+// toImage()'s conversion: to_image_u8 (amhip_layer_image.h)
 // One workgroup = 64 x 64 cells through LDS: lanes run along i on the way in (coalesced 4-byte
 // reads of a layer column) and along j on the way out (coalesced bytes of an image row).
 // kBgr: the layer holds grid_map's packed colours (bits R << 16 | G << 8 | B,
@@ -123,13 +116,11 @@ int layer_to_image_dev(Ctx* c, int layer, int bgr, float lower, float upper, uin
 // ---------------------------------------------------------------------------
 namespace {
 
-struct TiffTag {
-  uint16_t tag, type;
-  uint32_t count;
-  uint32_t value;  // the value, or the file offset of the values
-};
-
-enum { kShort = 3, kLong = 4, kAscii = 2, kDouble = 12 };
+using TiffTag = tiff::Tag;
+using tiff::kAscii;
+using tiff::kDouble;
+using tiff::kLong;
+using tiff::kShort;
 
 template <typename T>
 void put(std::vector<uint8_t>* b, T v) {
@@ -215,25 +206,9 @@ int amhip_geotiff_write_u8(const char* filename, const uint8_t* pixels, int widt
                                              std::max<unsigned long long>(1ull, (64ull << 20) / row));
   const uint32_t nstrips = ((uint32_t)height + rows_per_strip - 1) / rows_per_strip;
 
-  // what SetProjCS(..) + SetWellKnownGeogCS("WGS84") + SetUTM(zone, north) describe
-  // (aerial-mapper-io.cc:390-394, :467-474): EPSG 326zz / 327zz
-  char citation[96];
-  std::snprintf(citation, sizeof(citation), "UTM %d (WGS84) in %s hemisphere.|", utm_zone,
-                northern ? "northern" : "southern");
-  const std::string ascii = std::string(citation) + "WGS 84|";
-  const uint16_t cit_len = (uint16_t)std::strlen(citation);
-  const uint16_t geokeys[] = {
-      1, 1, 0, 7,                                          // version, revision, minor, keys
-      1024, 0, 1, 1,                                       // GTModelType = projected
-      1025, 0, 1, 1,                                       // GTRasterType = PixelIsArea
-      1026, 34737, cit_len, 0,                             // GTCitation
-      2048, 0, 1, 4326,                                    // GeographicType = WGS 84
-      2049, 34737, 7, cit_len,                             // GeogCitation "WGS 84|"
-      3072, 0, 1, (uint16_t)((northern ? 32600 : 32700) + utm_zone),  // ProjectedCSType
-      3076, 0, 1, 9001,                                    // ProjLinearUnits = metre
-  };
-  const double scale[3] = {geotransform[1], -geotransform[5], 0.0};
-  const double tie[6] = {0.0, 0.0, 0.0, geotransform[0], geotransform[3], 0.0};
+  // the geo tags: amhip_tiff_host.h, shared with the tiled Deflate writer
+  const tiff::GeoTags geo = tiff::make_geo_tags(geotransform, utm_zone, northern);
+  const std::string& ascii = geo.ascii;
 
   // ---- layout: header, IFD, out-of-line values, strips ----
   const int ntags = 15;
@@ -250,9 +225,9 @@ int amhip_geotiff_write_u8(const char* filename, const uint8_t* pixels, int widt
   const uint16_t bits3[3] = {8, 8, 8}, fmt3[3] = {1, 1, 1};
   const uint32_t bits_at = bands == 3 ? reserve(bits3, 6) : 0;
   const uint32_t fmt_at = bands == 3 ? reserve(fmt3, 6) : 0;
-  const uint32_t scale_at = reserve(scale, sizeof(scale));
-  const uint32_t tie_at = reserve(tie, sizeof(tie));
-  const uint32_t keys_at = reserve(geokeys, sizeof(geokeys));
+  const uint32_t scale_at = reserve(geo.scale, sizeof(geo.scale));
+  const uint32_t tie_at = reserve(geo.tie, sizeof(geo.tie));
+  const uint32_t keys_at = reserve(geo.keys, sizeof(geo.keys));
   const uint32_t ascii_at = reserve(ascii.c_str(), ascii.size() + 1);
   // strip tables (out of line when there is more than one strip)
   const uint32_t offs_at = nstrips > 1 ? extra_at + (uint32_t)extra.size() : 0;
@@ -285,7 +260,7 @@ int amhip_geotiff_write_u8(const char* filename, const uint8_t* pixels, int widt
       {339, kShort, (uint32_t)bands, bands == 3 ? fmt_at : 1u},
       {33550, kDouble, 3, scale_at},
       {33922, kDouble, 6, tie_at},
-      {34735, kShort, (uint32_t)(sizeof(geokeys) / 2), keys_at},
+      {34735, kShort, (uint32_t)(sizeof(geo.keys) / 2), keys_at},
       {34737, kAscii, (uint32_t)ascii.size() + 1, ascii_at},
   };
   std::vector<uint8_t> head;

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "amhip_common.h"
+#include "amhip_deflate_rle.h"
 #include "amhip_frame_stack.h"
 #include "amhip_png_encode_host.h"
 
@@ -47,40 +48,14 @@ using pnge::Work;
 
 __constant__ Tables d_tables = pnge::make_tables();
 
-constexpr uint32_t kTile = 4096;       // bytes of scanline per workgroup of the byte passes
-constexpr uint32_t kLane = 16;         // ... per lane
+using pnge::Bufs;
+using pnge::FrameCtrl;
+using pnge::kLane;
+using pnge::kNoByte;
+using pnge::kTile;
+using pnge::Share;
+
 constexpr uint32_t kPiece = 128;       // bytes of an IDAT payload per lane of the frame pass
-constexpr uint32_t kNoByte = 0x100;    // stands for a byte outside the data: equal to none inside
-
-// what every frame of a call shares
-struct Share {
-  int width, height, bpp, mode;
-  uint32_t row_bytes;            // 1 + width * bpp
-  uint32_t ntiles, max_blocks;
-  unsigned long long raw_len;    // height * row_bytes
-  unsigned long long zwords;     // 32-bit words of a frame's zlib buffer
-  unsigned long long row_step, frame_stride;
-};
-
-struct FrameCtrl {
-  unsigned long long nsym, zlen, fsize;
-  uint32_t nblocks, adler;
-};
-
-// a group's buffers, frame-major: frame f owns [f * per-frame size, (f + 1) * per-frame size)
-struct Bufs {
-  uint8_t* scan;                     // ntiles * kTile bytes: the scanlines, zero behind raw_len
-  uint16_t* sym;                     // ntiles * kTile symbols: 0..255 literal, 256 + length
-  uint32_t *tile_last, *tile_cnt, *tile_a, *tile_w;   // ntiles each
-  unsigned long long *tile_carry, *tile_base;         // ntiles each
-  unsigned long long* block_pos;     // max_blocks + 1: the byte a block starts at
-  unsigned long long* block_bit;     // max_blocks: the bit it starts at in the zlib stream
-  BlockCode* code;                   // max_blocks
-  uint32_t* z;                       // zwords: the zlib stream
-  FrameCtrl* ctrl;
-  unsigned long long *sizes, *offs;  // one per frame
-  const uint8_t* head;               // kFileHead + kFileTail bytes, shared
-};
 
 template <typename T, bool kMax>
 __device__ __forceinline__ T scan_incl_256(T v, T* sh) {
@@ -569,7 +544,24 @@ __global__ void __launch_bounds__(64) k_pnge_frame(Share s, Bufs b, uint8_t* out
   if (lane < 4) chunk[8 + len + lane] = (uint8_t)(crc >> (24 - 8 * lane));
 }
 
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+}  // namespace
+
+int deflate_rle_middle(hipStream_t stream, const Share& s, const Bufs& b, uint32_t n) {
+  const dim3 tiles(s.ntiles, n), blocks(s.max_blocks, n);
+  hipLaunchKernelGGL(k_pnge_scan_runs, dim3(n), dim3(256), 0, stream, s, b);
+  hipLaunchKernelGGL(k_pnge_tokens<false>, tiles, dim3(256), 0, stream, b.scan, b.tile_carry, b.tile_cnt, b.tile_base,
+                     b.sym, b.block_pos, s.raw_len, s.ntiles, s.max_blocks);
+  hipLaunchKernelGGL(k_pnge_scan_counts, dim3(n), dim3(256), 0, stream, s, b);
+  hipLaunchKernelGGL(k_pnge_tokens<true>, tiles, dim3(256), 0, stream, b.scan, b.tile_carry, b.tile_cnt, b.tile_base,
+                     b.sym, b.block_pos, s.raw_len, s.ntiles, s.max_blocks);
+  hipLaunchKernelGGL(k_pnge_plan, blocks, dim3(64), 0, stream, s, b);
+  hipLaunchKernelGGL(k_pnge_offsets, dim3(n), dim3(64), 0, stream, s, b);
+  hipLaunchKernelGGL(k_pnge_pack, blocks, dim3(256), 0, stream, s, b);
+  AMHIP_TRY(hipGetLastError());
+  return AMHIP_OK;
+}
+
+namespace {
 
 constexpr size_t kMaxGroupFrames = 65535;   // (grid.y of the per-frame launches)
 constexpr size_t kWriteSlice = 8u << 20;    // bytes of files downloaded at a time by the writing call
@@ -585,53 +577,9 @@ struct PngEncoder {
   DevBuf scratch, head;
   hipStream_t stream = nullptr;
 
-  struct Layout {
-    size_t scan, sym, tile32[4], tile64[2], block_pos, block_bit, code, z, ctrl, sizes, offs, total;
-  };
-  Layout layout(size_t n) const {
-    Layout l;
-    size_t at = 0;
-    auto carve = [&](size_t bytes) {
-      const size_t a = at;
-      at += round_up(bytes, 256);
-      return a;
-    };
-    const size_t tiles = n * s.ntiles;
-    l.scan = carve(tiles * kTile);
-    l.sym = carve(tiles * kTile * 2);
-    for (size_t& o : l.tile32) o = carve(tiles * 4);
-    for (size_t& o : l.tile64) o = carve(tiles * 8);
-    l.block_pos = carve(n * ((size_t)s.max_blocks + 1) * 8);
-    l.block_bit = carve(n * (size_t)s.max_blocks * 8);
-    l.code = carve(n * (size_t)s.max_blocks * sizeof(BlockCode));
-    l.z = carve(n * (size_t)s.zwords * 4);
-    l.ctrl = carve(n * sizeof(FrameCtrl));
-    l.sizes = carve(n * 8);
-    l.offs = carve(n * 8);
-    l.total = at;
-    return l;
-  }
-  Bufs bufs(const Layout& l) {
-    uint8_t* d = scratch.as<uint8_t>();
-    Bufs b;
-    b.scan = d + l.scan;
-    b.sym = reinterpret_cast<uint16_t*>(d + l.sym);
-    b.tile_last = reinterpret_cast<uint32_t*>(d + l.tile32[0]);
-    b.tile_cnt = reinterpret_cast<uint32_t*>(d + l.tile32[1]);
-    b.tile_a = reinterpret_cast<uint32_t*>(d + l.tile32[2]);
-    b.tile_w = reinterpret_cast<uint32_t*>(d + l.tile32[3]);
-    b.tile_carry = reinterpret_cast<unsigned long long*>(d + l.tile64[0]);
-    b.tile_base = reinterpret_cast<unsigned long long*>(d + l.tile64[1]);
-    b.block_pos = reinterpret_cast<unsigned long long*>(d + l.block_pos);
-    b.block_bit = reinterpret_cast<unsigned long long*>(d + l.block_bit);
-    b.code = reinterpret_cast<BlockCode*>(d + l.code);
-    b.z = reinterpret_cast<uint32_t*>(d + l.z);
-    b.ctrl = reinterpret_cast<FrameCtrl*>(d + l.ctrl);
-    b.sizes = reinterpret_cast<unsigned long long*>(d + l.sizes);
-    b.offs = reinterpret_cast<unsigned long long*>(d + l.offs);
-    b.head = head.as<const uint8_t>();
-    return b;
-  }
+  using Layout = pnge::Layout;
+  Layout layout(size_t n) const { return pnge::make_layout(s, n); }
+  Bufs bufs(const Layout& l) { return pnge::make_bufs(scratch.as<uint8_t>(), l, head.as<const uint8_t>()); }
   size_t groups() const { return group_begin.size() - 1; }
   size_t group_frames(size_t gi) const { return group_begin[gi + 1] - group_begin[gi]; }
   unsigned long long group_bytes(size_t gi) const {
@@ -651,10 +599,7 @@ struct PngEncoder {
     s.mode = mode;
     s.bpp = mode == kJpegGray8 ? 1 : 3;
     s.row_bytes = 1u + (uint32_t)width * (uint32_t)s.bpp;
-    s.raw_len = pnge::raw_len(width, height, s.bpp);
-    s.ntiles = (uint32_t)((s.raw_len + kTile - 1) / kTile);
-    s.max_blocks = (uint32_t)pnge::max_blocks(s.raw_len);
-    s.zwords = (pnge::zlib_bound(s.raw_len) + 3) / 4 + 2;
+    pnge::share_set_raw(&s, pnge::raw_len(width, height, s.bpp));
     s.row_step = row_step;
     s.frame_stride = frames > 1 ? frame_stride : 0;
     const size_t cost = layout(1).total;
@@ -686,19 +631,12 @@ struct PngEncoder {
     const Layout l = layout(n);
     const Bufs b = bufs(l);
     AMHIP_TRY(hipMemsetAsync(b.z, 0, (size_t)n * (size_t)s.zwords * 4, stream));
-    const dim3 tiles(s.ntiles, n), blocks(s.max_blocks, n);
+    const dim3 tiles(s.ntiles, n);
     if (s.mode == kJpegGray8) hipLaunchKernelGGL(k_pnge_filter<kJpegGray8>, tiles, dim3(256), 0, stream, px, s, b);
     else if (s.mode == kJpegBgr8) hipLaunchKernelGGL(k_pnge_filter<kJpegBgr8>, tiles, dim3(256), 0, stream, px, s, b);
     else hipLaunchKernelGGL(k_pnge_filter<kJpegBgr16s>, tiles, dim3(256), 0, stream, px, s, b);
-    hipLaunchKernelGGL(k_pnge_scan_runs, dim3(n), dim3(256), 0, stream, s, b);
-    hipLaunchKernelGGL(k_pnge_tokens<false>, tiles, dim3(256), 0, stream, b.scan, b.tile_carry, b.tile_cnt, b.tile_base,
-                       b.sym, b.block_pos, s.raw_len, s.ntiles, s.max_blocks);
-    hipLaunchKernelGGL(k_pnge_scan_counts, dim3(n), dim3(256), 0, stream, s, b);
-    hipLaunchKernelGGL(k_pnge_tokens<true>, tiles, dim3(256), 0, stream, b.scan, b.tile_carry, b.tile_cnt, b.tile_base,
-                       b.sym, b.block_pos, s.raw_len, s.ntiles, s.max_blocks);
-    hipLaunchKernelGGL(k_pnge_plan, blocks, dim3(64), 0, stream, s, b);
-    hipLaunchKernelGGL(k_pnge_offsets, dim3(n), dim3(64), 0, stream, s, b);
-    hipLaunchKernelGGL(k_pnge_pack, blocks, dim3(256), 0, stream, s, b);
+    const int rc = deflate_rle_middle(stream, s, b, n);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_pnge_file_offsets, dim3(1), dim3(64), 0, stream, b, n);
     AMHIP_TRY(hipGetLastError());
     AMHIP_TRY(hipMemcpyAsync(sizes.data() + group_begin[gi], b.sizes, (size_t)n * 8, hipMemcpyDeviceToHost, stream));

@@ -1228,4 +1228,63 @@ int amhip_session_layer_write_png(amhip_session* h, int layer, int bgr, float lo
                          bgr ? 3 : 1);
 }
 
+/* amhip_layer_write_geotiff for the whole map of a session: the north-up raster
+ * assembled on the host from every window -- the floats themselves for kind 0, the image of
+ * amhip_session_layer_to_image for kinds 1 and 2 -- and encoded on the first window's device. */
+int amhip_session_layer_write_geotiff(amhip_session* h, int layer, int kind, float lower, float upper, int tile,
+                                      int utm_zone, int northern, const char* filename) {
+  static const char kWho[] = "amhip_session_layer_write_geotiff: ";
+  if (!h || !filename) return arg_failure((std::string(kWho) + "null argument").c_str());
+  if (layer < 0 || layer >= AMHIP_NUM_LAYERS) return arg_failure((std::string(kWho) + "layer: no such layer").c_str());
+  Session& s = h->impl;
+  const size_t rows = (size_t)s.grid.rows, cols = (size_t)s.grid.cols;
+  if (kind < 0 || kind > 2) return arg_failure((std::string(kWho) + "kind must be 0 (f32), 1 (u8) or 2 (rgb8)").c_str());
+  if (rows < 1 || cols < 1 || rows > 65535 || cols > 65535)
+    return arg_failure((std::string(kWho) + "width and height must be 1..65535").c_str());
+  if (tile != 0 && (tile < 16 || tile > 1024 || tile % 16 != 0))
+    return arg_failure((std::string(kWho) + "tile must be a multiple of 16 in 16..1024, or 0 (256)").c_str());
+  if (utm_zone < 1 || utm_zone > 60) return arg_failure((std::string(kWho) + "utm_zone must be 1..60").c_str());
+  if (kind == 1 && !(upper > lower)) return arg_failure((std::string(kWho) + "upper <= lower").c_str());
+  const amhip_grid_desc& g = s.grid;
+  const double gt[6] = {g.pos_x - g.length_x / 2, g.resolution, 0.0, g.pos_y + g.length_y / 2, 0.0, -g.resolution};
+  // raster pixel (r, c) is cell (i, j) = (rows - 1 - c, r): width = rows, height = cols
+  const size_t px = kind == 0 ? 4u : kind == 1 ? 1u : 3u;
+  std::vector<uint8_t> raster(rows * cols * px);
+  int rc;
+  if (kind == 0) {
+    std::vector<float> map(rows * cols);
+    rc = for_windows(s, [&](int k) -> int {
+      Ctx* c = &s.ctx[k]->impl;
+      int r = ctx_use_device(c);
+      if (r) return r;
+      if ((r = ctx_materialize(c, layer))) return r;
+      AMHIP_TRY(copy_window(map_at(map.data(), s, s.win[k]), c->layers[layer], s, s.win[k], true, c->stream));
+      AMHIP_TRY(hipStreamSynchronize(c->stream));
+      return AMHIP_OK;
+    });
+    if (rc) return rc;
+    float* out = reinterpret_cast<float*>(raster.data());
+    for (size_t r = 0; r < cols; ++r)
+      for (size_t c = 0; c < rows; ++c) out[r * rows + c] = map[(rows - 1 - c) + r * rows];
+  } else {
+    const size_t step = cols * px;
+    std::vector<uint8_t> image(rows * step);
+    if ((rc = amhip_session_layer_to_image(h, layer, kind == 2, lower, upper, image.data(), step))) return rc;
+    for (size_t r = 0; r < cols; ++r)
+      for (size_t c = 0; c < rows; ++c) {
+        const uint8_t* p = image.data() + (rows - 1 - c) * step + r * px;
+        uint8_t* q = raster.data() + (r * rows + c) * px;
+        if (kind == 1) {
+          q[0] = p[0];
+        } else {   // the image is B, G, R
+          q[0] = p[2];
+          q[1] = p[1];
+          q[2] = p[0];
+        }
+      }
+  }
+  return amhip_geotiff_write(s.ctx[0], filename, raster.data(), /*on_device=*/0, rows * px, (int)rows, (int)cols, kind,
+                             tile, gt, utm_zone, northern);
+}
+
 }  // extern "C"

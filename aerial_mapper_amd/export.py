@@ -185,6 +185,107 @@ def write_data_to_dem_geotiff_color(ortho_image, xy, filename):
                   (float(xy[0]), 1.0, 0.0, float(xy[1]), 0.0, -1.0))
 
 
+def _geotiff_raster(map_, raster):
+    """-> (torch device tensor or numpy array, kind, height, width, step in bytes)"""
+    if _is_torch(raster):
+        import torch
+        assert raster.is_cuda and raster.dim() in (2, 3) and raster.stride(-1) == 1
+        if raster.dim() == 3:
+            assert raster.dtype == torch.uint8 and raster.shape[2] == 3 and raster.stride(1) == 3
+            kind = "rgb8"
+        else:
+            assert raster.dtype in (torch.float32, torch.uint8)
+            kind = "f32" if raster.dtype == torch.float32 else "u8"
+        step = int(raster.stride(0)) * raster.element_size()
+    else:
+        raster = np.asarray(raster)
+        assert raster.ndim in (2, 3) and raster.dtype in (np.float32, np.uint8)
+        if raster.ndim == 3:
+            assert raster.dtype == np.uint8 and raster.shape[2] == 3
+        raster = np.ascontiguousarray(raster)
+        kind = "rgb8" if raster.ndim == 3 else "f32" if raster.dtype == np.float32 else "u8"
+        step = raster.strides[0]
+    return raster, L.GEOTIFF_KINDS[kind], int(raster.shape[0]), int(raster.shape[1]), int(step)
+
+
+def encode_geotiff(map_, raster, geotransform, utm_zone=32, northern=True, tile=256, cap=None):
+    """amhip_geotiff_encode_dev on the map's context: the tiled Deflate GeoTIFF of a north-up raster,
+    as bytes.  raster: (H, W) float32 or uint8, or (H, W, 3) uint8 (bands in the order given) -- a
+    numpy array, or a torch device tensor (rows may be padded: stride(0) is the step).  cap: bytes
+    of the device buffer the file is encoded into (default amhip_geotiff_bound); a file that does
+    not fit raises AMHIP_ERR_ARG."""
+    import torch
+    lib = L.load()
+    raster, kind, h, w, step = _geotiff_raster(map_, raster)
+    if not _is_torch(raster):
+        raster = torch.from_numpy(raster).to("cuda:%d" % map_.device)
+    bound = lib.amhip_geotiff_bound(w, h, kind, int(tile))
+    out = torch.empty(max(int(bound if cap is None else cap), 1), dtype=torch.uint8, device=raster.device)
+    map_.wait_for_torch(raster)
+    gt = (C.c_double * 6)(*[float(v) for v in geotransform])
+    n = C.c_size_t()
+    L.check(lib.amhip_geotiff_encode_dev(map_._h, C.c_void_p(raster.data_ptr()), step, w, h, kind, int(tile), gt,
+                                         int(utm_zone), int(bool(northern)), C.c_void_p(out.data_ptr()),
+                                         int(out.numel() if cap is None else cap), C.byref(n)))
+    return out[:n.value].cpu().numpy().tobytes()
+
+
+def write_geotiff_deflate(map_, filename, raster, geotransform, utm_zone=32, northern=True, tile=256):
+    """amhip_geotiff_write: encode on the map's device, download, write `filename`."""
+    lib = L.load()
+    raster, kind, h, w, step = _geotiff_raster(map_, raster)
+    gt = (C.c_double * 6)(*[float(v) for v in geotransform])
+    if _is_torch(raster):
+        map_.wait_for_torch(raster)
+        ptr, on_device = raster.data_ptr(), 1
+    else:
+        ptr, on_device = raster.ctypes.data, 0
+    L.check(lib.amhip_geotiff_write(map_._h, str(filename).encode(), C.c_void_p(ptr), on_device, step, w, h, kind,
+                                    int(tile), gt, int(utm_zone), int(bool(northern))))
+
+
+def _geotiff_kind(kind):
+    return L.GEOTIFF_KINDS[kind] if isinstance(kind, str) else int(kind)
+
+
+def layer_to_geotiff(map_, layer, filename, kind="f32", lower=0.0, upper=255.0, utm_zone=32, northern=True,
+                     tile=256):
+    """amhip_layer_write_geotiff: the map's window of a layer as its north-up raster (x easting, y
+    northing), georeferenced from the map's own geometry, tiled and Deflate-compressed on the device.
+    kind: "f32" (the layer's floats, nodata NaN), "u8" (layer_to_image's rescale) or "rgb8" (the
+    packed colour layer as R, G, B)."""
+    lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
+    L.check(L.load().amhip_layer_write_geotiff(map_._h, lid, _geotiff_kind(kind), float(lower), float(upper),
+                                               int(tile), int(utm_zone), int(bool(northern)),
+                                               str(filename).encode()))
+
+
+def encode_layer_geotiff(map_, layer, kind="f32", lower=0.0, upper=255.0, utm_zone=32, northern=True, tile=256,
+                         cap=None):
+    """amhip_layer_encode_geotiff_dev: layer_to_geotiff's file, as bytes."""
+    import torch
+    lib = L.load()
+    lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
+    k = _geotiff_kind(kind)
+    bound = lib.amhip_geotiff_bound(int(map_.window[2]), int(map_.window[3]), k, int(tile))
+    out = torch.empty(max(int(bound if cap is None else cap), 1), dtype=torch.uint8,
+                      device="cuda:%d" % map_.device)
+    n = C.c_size_t()
+    L.check(lib.amhip_layer_encode_geotiff_dev(map_._h, lid, k, float(lower), float(upper), int(tile),
+                                               int(utm_zone), int(bool(northern)), C.c_void_p(out.data_ptr()),
+                                               int(out.numel() if cap is None else cap), C.byref(n)))
+    return out[:n.value].cpu().numpy().tobytes()
+
+
+def session_layer_to_geotiff(session, layer, filename, kind="f32", lower=0.0, upper=255.0, utm_zone=32,
+                             northern=True, tile=256):
+    """amhip_session_layer_write_geotiff: the whole map of a HostSession."""
+    lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
+    L.check(L.load().amhip_session_layer_write_geotiff(session._h, lid, _geotiff_kind(kind), float(lower),
+                                                       float(upper), int(tile), int(utm_zone),
+                                                       int(bool(northern)), str(filename).encode()))
+
+
 def grid_map_msg_layout(grid, stamp_ns, frame_id="world", layers=GRID_MAP_LAYERS):
     """(buffer, payload offsets): the message with empty payloads (host only)."""
     lib = L.load()

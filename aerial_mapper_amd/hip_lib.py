@@ -76,7 +76,12 @@ EXPORTS = [
     "amhip_png_bound", "amhip_png_encode_dev", "amhip_png_write", "amhip_layer_write_png",
     "amhip_session_layer_write_png", "amhip_mosaic_encode_png_dev", "amhip_mosaic_write_png",
     "amhip_io_encode_png_frames", "amhip_io_write_png_frames",
+    "amhip_geotiff_bound", "amhip_geotiff_encode_dev", "amhip_geotiff_write", "amhip_layer_encode_geotiff_dev",
+    "amhip_layer_write_geotiff", "amhip_session_layer_write_geotiff",
 ]
+
+# amhip_geotiff_*: the raster kinds
+GEOTIFF_KINDS = {"f32": 0, "u8": 1, "rgb8": 2}
 
 
 class GridDesc(C.Structure):
@@ -332,6 +337,18 @@ def load():
                                                C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     lib.amhip_io_write_png_frames.argtypes = [C.c_int, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                               C.c_size_t, C.c_size_t, C.POINTER(C.c_char_p)]
+    # the tiled Deflate GeoTIFF writer
+    lib.amhip_geotiff_bound.restype = C.c_size_t
+    lib.amhip_geotiff_bound.argtypes = [C.c_int] * 4
+    lib.amhip_geotiff_encode_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int,
+                                             C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.amhip_geotiff_write.argtypes = [vp, C.c_char_p, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        f64p, C.c_int, C.c_int]
+    lib.amhip_layer_encode_geotiff_dev.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                                   C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.amhip_layer_write_geotiff.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
+                                              C.c_char_p]
+    lib.amhip_session_layer_write_geotiff.argtypes = lib.amhip_layer_write_geotiff.argtypes
     del u8p
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:

@@ -130,6 +130,17 @@ class AerialMapperIO {
                                       size_t row_step, size_t frame_stride,
                                       const std::vector<std::string>& filenames);
 
+  // --- extension: a layer of the map as a GeoTIFF GIS tools read as it is: north-up (x easting, y
+  // northing), georeferenced from the map's own geometry in UTM zone `utm_zone`, tiled and
+  // Deflate-compressed on the GPU (amhip_session_layer_write_geotiff).  "colored_ortho" goes as
+  // three byte bands R, G, B; every other layer of the GPU path ("elevation", "ortho",
+  // "elevation_angle", "num_observations", "observation_index") as 32-bit floats with nodata NaN.
+  // The map's matrices are what is written: they are uploaded to the map's session first.  The
+  // reference has no such writer (its two GDAL calls write uncompressed bytes); any other layer name
+  // and a file that cannot be written are fatal.
+  void writeLayerToGeoTiff(const grid_map::GridMap& map, const std::string& layer, const std::string& filename,
+                           int utm_zone, bool northern);
+
   // --- extension: the same cloud as a binary file (amhip_io_write_point_cloud_binary) and its
   // loader, staged through pinned buffers straight into HBM.
   void savePointCloudToBinaryFile(const std::string& filename,

@@ -635,6 +635,53 @@ int amhip_geotiff_write_u8(const char* filename, const uint8_t* pixels, int widt
                            size_t step, int bands, const double* geotransform, int utm_zone,
                            int northern);
 
+/* ---- tiled Deflate GeoTIFF, compressed on the GPU (an extension: the reference's two GDAL calls
+ * write uncompressed bytes) -------------------------------------------------------------------------
+ * A classic little-endian TIFF with one IFD, square tiles of `tile` pixels a side (a multiple of 16
+ * in 16..1024; 0: 256) in row-major tile order, every tile full size (zero bytes outside the
+ * raster), Compression 8 (Adobe Deflate), PlanarConfiguration 1, and the geo tags
+ * amhip_geotiff_write_u8 writes for the same geotransform, zone and hemisphere.  kind:
+ *   AMHIP_GEOTIFF_F32 (0)   one band of 32-bit floats, Predictor 3, SampleFormat 3, GDAL_NODATA "nan"
+ *   AMHIP_GEOTIFF_U8 (1)    one band of bytes, Predictor 2, BlackIsZero
+ *   AMHIP_GEOTIFF_RGB8 (2)  three bands of bytes, pixel interleaved in the order given, Predictor 2
+ * Every tile is one zlib stream: byte for byte what zlib 1.2.11 writes for the tile's predictor
+ * bytes at level 1 with strategy Z_RLE, window 15, memLevel 8 (tests/golden/geotiff/).
+ * Any TIFF reader accepts the file; identity with a file GDAL would write is not claimed.  A file
+ * of more than 2^32 - 1 bytes is refused (no BigTIFF).  Scratch lives for the call and is bounded by
+ * encoding in groups of tiles (tuning key tiffe_scratch_budget_mb); the bytes do not depend on the
+ * grouping.  Argument errors (AMHIP_ERR_ARG, the text names the export and the field) are reported
+ * before any device is touched: a null pointer; width or height outside 1..65535; a bad kind or
+ * tile; a step smaller than a row; a geotransform that is not north-up; a zone outside 1..60;
+ * upper <= lower for AMHIP_GEOTIFF_U8 of a layer.  A file that cannot be written is AMHIP_ERR_ARG
+ * with errno's text.
+ *   amhip_geotiff_bound       worst-case size of the file (0 for arguments out of range)
+ *   amhip_geotiff_encode_dev  a row-major device raster (rows `step` bytes apart) -> the file in
+ *                             dev_out, at most cap bytes; *bytes = the file's size.  A file larger
+ *                             than cap gives AMHIP_ERR_ARG and nothing is written.
+ *   amhip_geotiff_write       encode (host or device raster), download, write `filename`
+ *   amhip_layer_encode_geotiff_dev / amhip_layer_write_geotiff   the context's window of a layer as
+ *                             its north-up raster, reoriented and converted inside the encoder:
+ *                             x is easting, y northing, so the raster is win_rows wide and win_cols
+ *                             high, pixel (r, c) is cell (win_rows - 1 - c, r) of the window, and the
+ *                             geotransform is {x0, res, 0, y0, 0, -res} with x0 = pos_x - length_x / 2
+ *                             + res * (rows - win_i0 - win_rows), y0 = pos_y + length_y / 2 - res *
+ *                             win_j0.  Kind 0: the layer's bits (NaN stays NaN); kind 1:
+ *                             amhip_layer_to_image's conversion with lower / upper; kind 2: the
+ *                             packed colour layer as R, G, B (NaN: 0, 0, 0).
+ *   amhip_session_layer_write_geotiff   (below) the whole map of a session */
+enum { AMHIP_GEOTIFF_F32 = 0, AMHIP_GEOTIFF_U8 = 1, AMHIP_GEOTIFF_RGB8 = 2 };
+size_t amhip_geotiff_bound(int width, int height, int kind, int tile);
+int amhip_geotiff_encode_dev(amhip_ctx* ctx, const void* dev_raster, size_t step, int width, int height,
+                             int kind, int tile, const double* geotransform, int utm_zone, int northern,
+                             uint8_t* dev_out, size_t cap, size_t* bytes);
+int amhip_geotiff_write(amhip_ctx* ctx, const char* filename, const void* raster, int on_device,
+                        size_t step, int width, int height, int kind, int tile,
+                        const double* geotransform, int utm_zone, int northern);
+int amhip_layer_encode_geotiff_dev(amhip_ctx* ctx, int layer, int kind, float lower, float upper, int tile,
+                                   int utm_zone, int northern, uint8_t* dev_out, size_t cap, size_t* bytes);
+int amhip_layer_write_geotiff(amhip_ctx* ctx, int layer, int kind, float lower, float upper, int tile,
+                              int utm_zone, int northern, const char* filename);
+
 /* grid_map_msgs/GridMap in ROS 1 wire format, as GridMapRosConverter::toMessage fills it for
  * AerialGridMap::publishOnce / publishUntilShutdown (aerial-mapper-grid-map.cc:51-72).
  * _bytes: size of the message; _layout: writes everything except the layers' float payloads and
@@ -1008,6 +1055,10 @@ int amhip_session_layer_write_jpeg(amhip_session* s, int layer, int bgr, float l
 /* amhip_layer_write_png for the whole map of a session, the same way. */
 int amhip_session_layer_write_png(amhip_session* s, int layer, int bgr, float lower, float upper,
                                   const char* filename);
+/* amhip_layer_write_geotiff for the whole map of a session: the north-up raster assembled through
+ * the host, encoded on the first window's device; the bytes of a single context's file. */
+int amhip_session_layer_write_geotiff(amhip_session* s, int layer, int kind, float lower, float upper, int tile,
+                                      int utm_zone, int northern, const char* filename);
 
 /* ---- tuning knobs: the ONE door for switches that select among correct implementations ----------
  * (tests force every path through them, A-B timing flips them; none is needed in normal use).
@@ -1040,6 +1091,8 @@ int amhip_session_layer_write_png(amhip_session* s, int layer, int bgr, float lo
  *                             groups run one after another (a small value forces several groups)
  *   pnge_scratch_budget_mb (4096)  amhip_io_encode_png_frames / amhip_io_write_png_frames: MB of encoder
  *                             scratch per group of frames
+ *   tiffe_scratch_budget_mb (4096)  amhip_geotiff_encode_dev and its kin: MB of encoder scratch per group of
+ *                             tiles; groups run one after another, at least one tile each
  *   jpege_scratch_budget_mb (4096)  amhip_io_encode_jpeg_frames / amhip_io_write_jpeg_frames: MB of encoder
  *                             scratch (340 B per scan block) per group of frames; groups run one after
  *                             another, at least one frame each
