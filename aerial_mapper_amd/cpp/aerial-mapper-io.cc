@@ -472,6 +472,24 @@ void AerialMapperIO::writeLayerToGeoTiff(const grid_map::GridMap& map, const std
   amhip_shim::check_status(status, "writeLayerToGeoTiff");
 }
 
+// extension: see the header.  The session takes the map's own matrix in as the layer's state (cells the
+// file does not reach keep it), places the file's pixels on the GPU and hands the matrix back.
+void AerialMapperIO::loadLayerFromGeoTiff(grid_map::GridMap* map, const std::string& layer,
+                                          const std::string& filename) {
+  static const char* const kLayers[AMHIP_NUM_LAYERS] = {"ortho", "elevation", "elevation_angle", "num_observations",
+                                                        "observation_index", "colored_ortho"};
+  int id = -1;
+  for (int l = 0; l < AMHIP_NUM_LAYERS; ++l)
+    if (layer == kLayers[l]) id = l;
+  if (!map || id < 0 || !map->exists(layer))
+    amhip_shim::fatal("loadLayerFromGeoTiff", ("no layer '" + layer + "' the GPU path holds").c_str());
+  grid_map::Matrix& m = (*map)[layer];
+  amhip_session* session = amhip_shim::acquire_session(*map, nullptr, "loadLayerFromGeoTiff");
+  const int status = amhip_session_layer_read_geotiff(session, id, filename.c_str(), m.data());
+  amhip_shim::release_session(session);
+  amhip_shim::check_status(status, "loadLayerFromGeoTiff");
+}
+
 void AerialMapperIO::savePointCloudToBinaryFile(
     const std::string& filename,
     const AlignedType<std::vector, Eigen::Vector3d>::type& point_cloud_xyz,

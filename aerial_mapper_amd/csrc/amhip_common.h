@@ -224,6 +224,18 @@ int write_file(const char* what, const char* filename, const uint8_t* data, size
 int png_encode_run(hipStream_t stream, const JpegSource& src, uint8_t* dev_out, size_t cap, size_t* bytes);
 int png_write_run(const char* what, hipStream_t stream, const JpegSource& src, const char* filename);
 
+// The GeoTIFF reader (amhip_tiff_decode.hip) under a layer, in two halves, so that a session can run the
+// first on every window before the second on any: prepare parses the file and decodes the pixels under
+// the context's window into a raster of its own (no layer is touched; an error leaves nothing behind),
+// place writes the layer.  The job is freed by the caller, after either.
+struct TiffLayerJob;
+struct Ctx;
+int tiff_layer_prepare(Ctx* c, const char* who, int layer, const uint8_t* file, size_t len, TiffLayerJob** job);
+int tiff_layer_place(Ctx* c, TiffLayerJob* job);
+void tiff_layer_job_free(TiffLayerJob* job);
+// the whole of `filename`; a failure is AMHIP_ERR_ARG with `what`, the name and errno's text
+int read_file(const char* what, const char* filename, std::vector<uint8_t>* out);
+
 struct TimedRegion {
   hipEvent_t a, b;
   int slot;

@@ -36,6 +36,7 @@
 #include "amhip_device.h"
 #include "amhip_frame_stack.h"
 #include "amhip_png_decode_host.h"
+#include "amhip_png_inflate.h"
 
 namespace amhip {
 
@@ -635,6 +636,16 @@ size_t round16(size_t n) {
   return (n + 15) & ~(size_t)15;
 }
 
+}  // namespace
+
+// (amhip_png_inflate.h: the GeoTIFF reader's chunks are such streams too)
+void pngd::launch_inflate(hipStream_t stream, const uint8_t* bytes, const pngd::Frame* frames, size_t first, size_t n,
+                          uint8_t* raw, uint32_t* status) {
+  hipLaunchKernelGGL(k_pngd_inflate, dim3((unsigned)n), dim3(64), 0, stream, bytes, frames, first, raw, status);
+}
+
+namespace {
+
 // The codec description of decode_frame_stack (amhip_frame_stack.h): every frame's IDAT payloads are
 // joined into one zlib stream at a multiple of 16; a frame costs its raw scanlines, rounded up to 16.
 struct PngStack {
@@ -684,8 +695,7 @@ struct PngStack {
     return AMHIP_OK;
   }
   void launch_group(size_t first, size_t n, const StackLaunch<Frame>& s) {
-    hipLaunchKernelGGL(k_pngd_inflate, dim3((unsigned)n), dim3(64), 0, s.stream, bytes.as<uint8_t>(), s.frames,
-                       first, raw.as<uint8_t>(), s.status);
+    pngd::launch_inflate(s.stream, bytes.as<uint8_t>(), s.frames, first, n, raw.as<uint8_t>(), s.status);
     hipLaunchKernelGGL(k_pngd_unfilter, dim3((unsigned)n), dim3(64), 0, s.stream, s.frames, first,
                        raw.as<uint8_t>(), s.status);
     hipLaunchKernelGGL(k_pngd_pixels, dim3((unsigned)((s.width + 255) / 256), (unsigned)s.height, (unsigned)n),

@@ -1287,4 +1287,43 @@ int amhip_session_layer_write_geotiff(amhip_session* h, int layer, int kind, flo
                              tile, gt, utm_zone, northern);
 }
 
+/* amhip_layer_read_geotiff for every window of a session, then the layer into the GridMap's host
+ * matrix.  Two passes over the windows: every window decodes the chunks under its own cells first
+ * (tiff_layer_prepare: no layer, no matrix touched), and only when all of them have succeeded does
+ * any of them take the host matrix in (sync_in, as a DSM call does), place the pixels and hand the
+ * result back (sync_out), which leaves the content sums agreeing with the matrix. */
+int amhip_session_layer_read_geotiff(amhip_session* h, int layer, const char* filename, float* matrix) {
+  static const char kWho[] = "amhip_session_layer_read_geotiff";
+  if (!h || !filename || !matrix) return arg_failure((std::string(kWho) + ": null argument").c_str());
+  if (layer < 0 || layer >= AMHIP_NUM_LAYERS) return arg_failure((std::string(kWho) + ": layer: no such layer").c_str());
+  Session& s = h->impl;
+  std::vector<uint8_t> file;
+  int rc = read_file(kWho, filename, &file);
+  if (rc) return rc;
+  std::vector<TiffLayerJob*> jobs(s.W(), nullptr);
+  rc = for_windows(s, [&](int k) -> int {
+    return tiff_layer_prepare(&s.ctx[k]->impl, kWho, layer, file.data(), file.size(), &jobs[k]);
+  });
+  if (rc == AMHIP_OK) {
+    std::vector<Hash128> hh;
+    const float* mats[1] = {matrix};
+    if (!s.always_copy) host_hashes(s, mats, 1, &hh);
+    else hh.assign(s.W(), Hash128());
+    rc = for_windows(s, [&](int k) -> int {
+      Ctx* c = &s.ctx[k]->impl;
+      int r = ctx_use_device(c);
+      if (r) return r;
+      if ((r = sync_in(s, k, layer, matrix, hh[k], true))) return r;
+      AMHIP_TRY(hipEventRecord(s.ev_k0[k], c->stream));
+      if ((r = tiff_layer_place(c, jobs[k]))) return r;
+      const int lay[1] = {layer};
+      float* outs[1] = {matrix};
+      if ((r = sync_out(s, k, lay, outs, 1))) return r;
+      return ctx_fetch_status(c);
+    });
+  }
+  for (TiffLayerJob* j : jobs) tiff_layer_job_free(j);
+  return rc;
+}
+
 }  // extern "C"

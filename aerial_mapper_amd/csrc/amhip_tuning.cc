@@ -36,6 +36,8 @@ const char* const kKeys[] = {
     "pnge_scratch_budget_mb",
     // GeoTIFF encoder
     "tiffe_scratch_budget_mb",
+    // GeoTIFF reader
+    "tiffd_scratch_budget_mb",
     // lab builds (-DAMHIP_TIMING_PROBES) only
     "gather_tj", "gather_nt", "gather_class_cap0", "gather_class_cap1", "gather_class_cap2", "f32_variant",
     "fx_theta"};

@@ -78,10 +78,20 @@ EXPORTS = [
     "amhip_io_encode_png_frames", "amhip_io_write_png_frames",
     "amhip_geotiff_bound", "amhip_geotiff_encode_dev", "amhip_geotiff_write", "amhip_layer_encode_geotiff_dev",
     "amhip_layer_write_geotiff", "amhip_session_layer_write_geotiff",
+    "amhip_geotiff_info", "amhip_geotiff_decode_dev", "amhip_layer_decode_geotiff", "amhip_layer_read_geotiff",
+    "amhip_session_layer_read_geotiff",
 ]
 
-# amhip_geotiff_*: the raster kinds
-GEOTIFF_KINDS = {"f32": 0, "u8": 1, "rgb8": 2}
+# amhip_geotiff_*: the raster kinds (the writer takes the first three)
+GEOTIFF_KINDS = {"f32": 0, "u8": 1, "rgb8": 2, "u16": 3, "i16": 4}
+
+
+class GeotiffDesc(C.Structure):
+    """amhip_geotiff_desc"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "width", "height", "bands", "kind", "tiled", "tile_width", "tile_height", "rows_per_strip",
+        "compression", "predictor", "has_geo", "epsg", "raster_type", "has_nodata")] + \
+        [("geotransform", C.c_double * 6), ("nodata", C.c_double)]
 
 
 class GridDesc(C.Structure):
@@ -349,6 +359,13 @@ def load():
     lib.amhip_layer_write_geotiff.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                               C.c_char_p]
     lib.amhip_session_layer_write_geotiff.argtypes = lib.amhip_layer_write_geotiff.argtypes
+    # ... and the reader
+    lib.amhip_geotiff_info.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(GeotiffDesc)]
+    lib.amhip_geotiff_decode_dev.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                             C.c_size_t]
+    lib.amhip_layer_decode_geotiff.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t]
+    lib.amhip_layer_read_geotiff.argtypes = [vp, C.c_int, C.c_char_p]
+    lib.amhip_session_layer_read_geotiff.argtypes = [vp, C.c_int, C.c_char_p, vp]
     del u8p
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:

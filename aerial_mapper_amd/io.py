@@ -13,7 +13,10 @@ OrthoForwardHomography.batch and Stereo.add_frames.  The other way,
 in one batched encode (amhip_jpeg.hip), `encode_png_frames` / `write_png_frames`
 into PNG files without loss (amhip_png_encode.hip), and `to_standard_format` /
 `export_pix4d_geofile` / `load_poses_ros` mirror the format converters built
-on it (aerial-mapper-io.cc:58-101,123-205,272-307).
+on it (aerial-mapper-io.cc:58-101,123-205,272-307).  `geotiff_info` /
+`decode_geotiff` / `layer_from_geotiff` / `session_layer_from_geotiff` read a
+Deflate GeoTIFF -- a DEM, or what `layer_to_geotiff` wrote -- into a device
+raster or under a map layer (amhip_tiff_decode.hip).
 """
 import ctypes as C
 import mmap
@@ -219,6 +222,82 @@ def load_images_named(directory, image_names, colored=False, device=0):
         with open("%s%s.png" % (directory, name), "rb") as f:
             files.append(f.read())
     return decode_png_frames(files, colored, device)
+
+
+_GEOTIFF_KIND_NAMES = {v: k for k, v in L.GEOTIFF_KINDS.items()}
+_GEOTIFF_TYPESTR = {"f32": "<f4", "u8": "|u1", "rgb8": "|u1", "u16": "<u2", "i16": "<i2"}
+
+
+def _file_bytes(data_or_path):
+    if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+        return bytes(data_or_path)
+    with open(os.fspath(data_or_path), "rb") as f:
+        return f.read()
+
+
+def geotiff_info(data_or_path):
+    """amhip_geotiff_info (host only): a dict of the file's width, height, bands, kind ("f32", "u8",
+    "rgb8", "u16", "i16"), tiled, tile_width, tile_height, rows_per_strip, compression, predictor, has_geo,
+    geotransform (GDAL's six numbers, of pixel areas), epsg, raster_type and nodata (None: no tag).  Raises
+    for a file the reader refuses; the text names the tag."""
+    data = _file_bytes(data_or_path)
+    d = L.GeotiffDesc()
+    L.check(L.load().amhip_geotiff_info(data, len(data), C.byref(d)))
+    out = {n: int(getattr(d, n)) for n in ("width", "height", "bands", "tiled", "tile_width", "tile_height",
+                                           "rows_per_strip", "compression", "predictor", "epsg", "raster_type")}
+    out["kind"] = _GEOTIFF_KIND_NAMES[int(d.kind)]
+    out["has_geo"] = bool(d.has_geo)
+    out["geotransform"] = tuple(float(v) for v in d.geotransform)
+    out["nodata"] = float(d.nodata) if d.has_nodata else None
+    return out
+
+
+def decode_geotiff(map_, data_or_path, window=None, step=None):
+    """amhip_geotiff_decode_dev on the map's context: the pixel window (x0, y0, w, h) of the file (default:
+    all of it) as a torch device tensor (h, w) of the file's dtype -- (h, w, 3) uint8 for three bands --
+    and the info.  step: bytes between the tensor's rows (default: packed)."""
+    import torch
+    data = _file_bytes(data_or_path)
+    info = geotiff_info(data)
+    x0, y0, w, h = (0, 0, info["width"], info["height"]) if window is None else [int(v) for v in window]
+    kind = info["kind"]
+    dtype = {"f32": torch.float32, "u8": torch.uint8, "rgb8": torch.uint8, "u16": torch.uint16,
+             "i16": torch.int16}[kind]
+    item = np.dtype(_GEOTIFF_TYPESTR[kind]).itemsize
+    row = max(w, 0) * (3 if kind == "rgb8" else 1)          # samples per row
+    step = row * item if step is None else int(step)
+    buf = torch.zeros((max(h, 1), max(step, item)), dtype=torch.uint8, device="cuda:%d" % map_.device)
+    map_.wait_for_torch(buf)
+    L.check(L.load().amhip_geotiff_decode_dev(map_._h, data, len(data), x0, y0, w, h, C.c_void_p(buf.data_ptr()),
+                                              step))
+    out = buf[:, :step - step % item].view(dtype)[:h, :row]
+    return (out.unflatten(1, (w, 3)) if kind == "rgb8" else out), info
+
+
+def layer_from_geotiff(map_, layer, data_or_path):
+    """amhip_layer_decode_geotiff / amhip_layer_read_geotiff: the file under the map's window of `layer`.
+    A cell takes the pixel its centre lies in (no resampling, no reprojection); cells outside the raster,
+    on a nodata pixel or on a NaN keep what they hold.  On any error the layer is as it was."""
+    lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
+    lib = L.load()
+    map_._touched(L.LAYER_NAMES[lid] if 0 <= lid < len(L.LAYER_NAMES) else layer)
+    if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+        data = bytes(data_or_path)
+        L.check(lib.amhip_layer_decode_geotiff(map_._h, lid, data, len(data)))
+    else:
+        L.check(lib.amhip_layer_read_geotiff(map_._h, lid, os.fsencode(data_or_path)))
+
+
+def session_layer_from_geotiff(session, layer, path, matrix):
+    """amhip_session_layer_read_geotiff: the file under every window of a HostSession, then into `matrix`,
+    the layer's host matrix as AerialGridMap.get() shapes it -- float32, shape (cols, rows), C-contiguous --,
+    updated in place.  The next session call that is handed the same matrix uploads none of it."""
+    lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
+    if not (isinstance(matrix, np.ndarray) and matrix.dtype == np.float32 and matrix.flags.c_contiguous and
+            matrix.size == session.grid.rows * session.grid.cols):
+        _refuse("session_layer_from_geotiff: matrix: a C-contiguous float32 array of rows * cols cells is expected")
+    L.check(L.load().amhip_session_layer_read_geotiff(session._h, lid, os.fsencode(path),
+                                                      C.c_void_p(matrix.ctypes.data)))
 
 
 def _refuse(text):

@@ -141,6 +141,15 @@ class AerialMapperIO {
   void writeLayerToGeoTiff(const grid_map::GridMap& map, const std::string& layer, const std::string& filename,
                            int utm_zone, bool northern);
 
+  // --- extension: the other way.  A Deflate GeoTIFF -- what writeLayerToGeoTiff wrote, or a terrain model
+  // from elsewhere -- under a layer of the map, decoded on the GPU (amhip_session_layer_read_geotiff): a
+  // cell takes the pixel its centre lies in; a cell outside the raster, on a nodata pixel or on a NaN keeps
+  // the map's value.  Nothing is resampled or reprojected: the file has to be in the map's coordinates.
+  // One band goes to any layer of the GPU path, three bands of bytes to "colored_ortho" only.  A file
+  // the reader refuses, or one that fails to decode, is fatal with the library's text; the map is then
+  // as it was.
+  void loadLayerFromGeoTiff(grid_map::GridMap* map, const std::string& layer, const std::string& filename);
+
   // --- extension: the same cloud as a binary file (amhip_io_write_point_cloud_binary) and its
   // loader, staged through pinned buffers straight into HBM.
   void savePointCloudToBinaryFile(const std::string& filename,

@@ -682,6 +682,58 @@ int amhip_layer_encode_geotiff_dev(amhip_ctx* ctx, int layer, int kind, float lo
 int amhip_layer_write_geotiff(amhip_ctx* ctx, int layer, int kind, float lower, float upper, int tile,
                               int utm_zone, int northern, const char* filename);
 
+/* ---- GeoTIFF in: a DEM (or any raster of the accepted set) from a Deflate GeoTIFF into a layer, decoded
+ * on the GPU (amhip_tiff_decode.hip).  Read: a classic little-endian TIFF, its first IFD
+ * only; tiles (width and length multiples of 16) or strips; Compression 1, 8 or 32946; one band of
+ * 32-bit floats, of 8- or 16-bit unsigned or of 16-bit signed integers, or three bands of 8 bit, pixel
+ * interleaved; Predictor 1, 2, or 3 (floats only; with Compression 1 the tag is not acted on, as in
+ * libtiff); FillOrder and Orientation 1; width and height up to 2^20.  Geo tags: ModelPixelScale + one ModelTiepoint, or a ModelTransformation without rotation,
+ * north-up only; a PixelIsPoint file's origin is moved by half a pixel, so `geotransform` always
+ * describes pixel areas (GDAL's convention); GeoKey 3072 is reported as `epsg`, nothing is
+ * reprojected.  GDAL_NODATA is read as strtod reads it.  Anything else -- big-endian, BigTIFF, LZW,
+ * PackBits, JPEG, ZSTD, LERC, 64-, 1- or 4-bit samples, 2 or 4 bands, a palette, ExtraSamples, a
+ * count or an offset that leaves the file -- is AMHIP_ERR_ARG before any device is touched, with a
+ * text that names the tag and the value.
+ *   amhip_geotiff_info        host only: the file's description
+ *   amhip_geotiff_decode_dev  the pixel window (x0, y0, w, h) of the file, in the file's sample type,
+ *                             row-major into dev_out, rows `step` bytes apart (dev_out and step
+ *                             multiples of the sample's size).  Only the chunks that meet the window
+ *                             are uploaded and inflated (one wave per chunk), in groups bounded by
+ *                             the tuning key tiffd_scratch_budget_mb; the result does not depend on
+ *                             the grouping.  A chunk the walk refuses is an error that names the
+ *                             chunk and the inflate status; dev_out is then undefined.
+ *   amhip_layer_decode_geotiff / amhip_layer_read_geotiff   the file under the context's window of
+ *                             a layer: a cell takes the pixel its centre (getPosition) lies in,
+ *                             col = floor((x - GT0) / GT1), row = floor((y - GT3) / GT5) in IEEE double;
+ *                             a float keeps its bits, integers are converted to float, rgb8 becomes
+ *                             the packed colour value (R << 16 | G << 8 | B as a float's bits) and
+ *                             goes to colored_ortho only.  A cell whose centre lies outside the
+ *                             raster, whose pixel equals the nodata value or is a NaN is left as it
+ *                             is (on a reset map: the layer's initial value).  No resampling.  The
+ *                             layer is written only after every chunk has decoded: on any error it
+ *                             is as it was.  A file without geo tags is refused here.
+ *   amhip_session_layer_read_geotiff   (below) every window of a session, and the host matrix */
+enum { AMHIP_GEOTIFF_U16 = 3, AMHIP_GEOTIFF_I16 = 4 };   /* kinds only a file that is read can have */
+typedef struct amhip_geotiff_desc {
+  int32_t width, height, bands;
+  int32_t kind;             /* AMHIP_GEOTIFF_* */
+  int32_t tiled;            /* 1: tiles of tile_width x tile_height; 0: strips of rows_per_strip rows */
+  int32_t tile_width, tile_height, rows_per_strip;
+  int32_t compression;      /* 1, 8 or 32946 */
+  int32_t predictor;        /* 1, 2 or 3 */
+  int32_t has_geo;          /* 0: no geo tags (geotransform = 0, 1, 0, 0, 0, 1) */
+  int32_t epsg;             /* GeoKey 3072, 0: none */
+  int32_t raster_type;      /* GeoKey 1025: 1 PixelIsArea (or absent), 2 PixelIsPoint */
+  int32_t has_nodata;
+  double geotransform[6];   /* GDAL's: x = GT0 + col * GT1, y = GT3 + row * GT5, of pixel areas */
+  double nodata;
+} amhip_geotiff_desc;
+int amhip_geotiff_info(const uint8_t* file, size_t len, amhip_geotiff_desc* desc);
+int amhip_geotiff_decode_dev(amhip_ctx* ctx, const uint8_t* file, size_t len, int x0, int y0, int w, int h,
+                             void* dev_out, size_t step);
+int amhip_layer_decode_geotiff(amhip_ctx* ctx, int layer, const uint8_t* file, size_t len);
+int amhip_layer_read_geotiff(amhip_ctx* ctx, int layer, const char* filename);
+
 /* grid_map_msgs/GridMap in ROS 1 wire format, as GridMapRosConverter::toMessage fills it for
  * AerialGridMap::publishOnce / publishUntilShutdown (aerial-mapper-grid-map.cc:51-72).
  * _bytes: size of the message; _layout: writes everything except the layers' float payloads and
@@ -1060,6 +1112,13 @@ int amhip_session_layer_write_png(amhip_session* s, int layer, int bgr, float lo
 int amhip_session_layer_write_geotiff(amhip_session* s, int layer, int kind, float lower, float upper, int tile,
                                       int utm_zone, int northern, const char* filename);
 
+/* amhip_layer_read_geotiff for every window of a session (each decodes the chunks under its own cells),
+ * then into `matrix`, the GridMap's host matrix of the layer (rows x cols, column-major): cells the file
+ * does not reach keep the matrix's values.  The session's content sums agree with the matrix
+ * afterwards: the next call that is handed the same matrix uploads no byte of it.  On any error no
+ * window's layer and no cell of the matrix has changed. */
+int amhip_session_layer_read_geotiff(amhip_session* s, int layer, const char* filename, float* matrix);
+
 /* ---- tuning knobs: the ONE door for switches that select among correct implementations ----------
  * (tests force every path through them, A-B timing flips them; none is needed in normal use).
  * amhip_set_tuning(key, value) -- value NaN clears the key -- or, for hosts that cannot be
@@ -1093,6 +1152,8 @@ int amhip_session_layer_write_geotiff(amhip_session* s, int layer, int kind, flo
  *                             scratch per group of frames
  *   tiffe_scratch_budget_mb (4096)  amhip_geotiff_encode_dev and its kin: MB of encoder scratch per group of
  *                             tiles; groups run one after another, at least one tile each
+ *   tiffd_scratch_budget_mb (4096)  amhip_geotiff_decode_dev and its kin: MB of inflated chunks per group of
+ *                             chunks; groups run one after another, at least one chunk each
  *   jpege_scratch_budget_mb (4096)  amhip_io_encode_jpeg_frames / amhip_io_write_jpeg_frames: MB of encoder
  *                             scratch (340 B per scan block) per group of frames; groups run one after
  *                             another, at least one frame each
