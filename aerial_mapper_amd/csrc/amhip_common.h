@@ -207,6 +207,8 @@ struct JpegSource {
 };
 void jpeg_scratch_free(JpegScratch* ws);
 int jpeg_scratch_image(JpegScratch* ws, size_t bytes, uint8_t** out);
+// true: rows x cols pixels are what a JPEG file, or a PNG file of this encoder, holds
+inline bool image_size_ok(int rows, int cols) { return rows >= 1 && cols >= 1 && rows <= 65535 && cols <= 65535; }
 // the whole file into dev_out (at most cap bytes, nothing written when it does not fit:
 // AMHIP_ERR_ARG); asynchronous on `stream` up to the read-back of *bytes.  Arguments checked by
 // the callers (jpeg::check_image_args); quality 0 = 95.
@@ -223,6 +225,14 @@ int write_file(const char* what, const char* filename, const uint8_t* data, size
 // scratch lives for the call.  Arguments checked by the callers (pnge::check_image_args).
 int png_encode_run(hipStream_t stream, const JpegSource& src, uint8_t* dev_out, size_t cap, size_t* bytes);
 int png_write_run(const char* what, hipStream_t stream, const JpegSource& src, const char* filename);
+
+// What the JPEG and the PNG entry points share (amhip_jpeg.hip).  stage_host_image: a host image (*src)
+// -> the context's image scratch, rows packed; *src then names the copy.  layer_image_source: the
+// context's window of `layer` as an image in that scratch -> *src; `limit`: the whole refusal of a
+// window no file of the format holds.
+struct Ctx;
+int stage_host_image(Ctx* c, int channels, JpegSource* src);
+int layer_image_source(amhip_ctx* h, const char* limit, int layer, int bgr, float lower, float upper, JpegSource* src);
 
 // The GeoTIFF reader (amhip_tiff_decode.hip) under a layer, in two halves, so that a session can run the
 // first on every window before the second on any: prepare parses the file and decodes the pixels under

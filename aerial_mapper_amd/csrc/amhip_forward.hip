@@ -1058,14 +1058,21 @@ static JpegSource mosaic_jpeg_source(const Mosaic* m) {
   return src;
 }
 
+static const char kJpegLimit[] = ": a JPEG file holds 1 x 1 to 65535 x 65535 pixels";
+static const char kPngLimit[] = ": a PNG file of this encoder holds 1 x 1 to 65535 x 65535 pixels";
+
+// the mosaic must be what a file of the format holds; `limit`: the format's text
+static int mosaic_size_check(const char* what, const amhip_mosaic* h, const char* limit) {
+  const amhip_mosaic_desc& d = h->impl.desc;
+  if (!image_size_ok(d.height_mosaic_pixels, d.width_mosaic_pixels))
+    return fwd_arg_fail((std::string(what) + limit).c_str());
+  return AMHIP_OK;
+}
+
 static int mosaic_jpeg_check(const char* what, const amhip_mosaic* h, int quality) {
   if (quality < 0 || quality > 100)
     return fwd_arg_fail((std::string(what) + ": quality must be 1..100 (0: 95)").c_str());
-  const amhip_mosaic_desc& d = h->impl.desc;
-  if (d.width_mosaic_pixels < 1 || d.height_mosaic_pixels < 1 || d.width_mosaic_pixels > 65535 ||
-      d.height_mosaic_pixels > 65535)
-    return fwd_arg_fail((std::string(what) + ": a JPEG file holds 1 x 1 to 65535 x 65535 pixels").c_str());
-  return AMHIP_OK;
+  return mosaic_size_check(what, h, kJpegLimit);
 }
 
 int amhip_mosaic_encode_jpeg_dev(amhip_mosaic* h, int quality, uint8_t* dev_out, size_t cap, size_t* bytes) {
@@ -1089,17 +1096,9 @@ int amhip_mosaic_write_jpeg(amhip_mosaic* h, int quality, const char* filename) 
 
 /* ... and as a PNG file, what cv::imwrite writes when the name ends in .png (amhip_png_encode.hip): the same
  * clamped B G R, as colour type 2. */
-static int mosaic_png_check(const char* what, const amhip_mosaic* h) {
-  const amhip_mosaic_desc& d = h->impl.desc;
-  if (d.width_mosaic_pixels < 1 || d.height_mosaic_pixels < 1 || d.width_mosaic_pixels > 65535 ||
-      d.height_mosaic_pixels > 65535)
-    return fwd_arg_fail((std::string(what) + ": a PNG file of this encoder holds 1 x 1 to 65535 x 65535 pixels").c_str());
-  return AMHIP_OK;
-}
-
 int amhip_mosaic_encode_png_dev(amhip_mosaic* h, uint8_t* dev_out, size_t cap, size_t* bytes) {
   if (!h || !dev_out || !bytes) return fwd_arg_fail("amhip_mosaic_encode_png_dev: null argument");
-  int rc = mosaic_png_check("amhip_mosaic_encode_png_dev", h);
+  int rc = mosaic_size_check("amhip_mosaic_encode_png_dev", h, kPngLimit);
   if (rc) return rc;
   Mosaic* m = &h->impl;
   if ((rc = fwd_use(m))) return rc;
@@ -1108,7 +1107,7 @@ int amhip_mosaic_encode_png_dev(amhip_mosaic* h, uint8_t* dev_out, size_t cap, s
 
 int amhip_mosaic_write_png(amhip_mosaic* h, const char* filename) {
   if (!h || !filename) return fwd_arg_fail("amhip_mosaic_write_png: null argument");
-  int rc = mosaic_png_check("amhip_mosaic_write_png", h);
+  int rc = mosaic_size_check("amhip_mosaic_write_png", h, kPngLimit);
   if (rc) return rc;
   Mosaic* m = &h->impl;
   if ((rc = fwd_use(m))) return rc;

@@ -1,6 +1,6 @@
-// amhip_frame_plan.h -- how the image decoders (amhip_frame_stack.h) cut a call's frames into groups
-// that share one scratch buffer.  No HIP in here: tests/cpp/frame_stack_host_main.cc compiles it
-// alone under the sanitizers.
+// amhip_frame_plan.h -- how the image decoders and encoders (amhip_frame_stack.h) cut a call's frames
+// into groups that share one scratch buffer, and a group's files into download slices.  No HIP in
+// here: tests/cpp/frame_stack_host_main.cc compiles it alone under the sanitizers.
 #ifndef AMHIP_FRAME_PLAN_H_
 #define AMHIP_FRAME_PLAN_H_
 
@@ -31,6 +31,24 @@ inline void plan_groups(const size_t* cost_bytes, size_t F, size_t budget, size_
     if (running > *max_group_bytes) *max_group_bytes = running;
   }
   group_begin->push_back(F);
+}
+
+// The cut of files [first, last) of consecutive `sizes` into download slices.  A slice starts at a
+// file and takes the following files while the sum stays <= `limit`; so it holds at least one file,
+// whatever that file's size.  -> the file behind the slice that starts at `first`; *bytes: its sum.
+template <typename Size>
+inline size_t slice_end(const Size* sizes, size_t first, size_t last, size_t limit, size_t* bytes) {
+  size_t sum = (size_t)sizes[first], end = first + 1;
+  while (end < last && sum + (size_t)sizes[end] <= limit) sum += (size_t)sizes[end++];
+  *bytes = sum;
+  return end;
+}
+
+// offsets[f]: the bytes in front of file f, offsets[F]: all of them (the exclusive prefix sums)
+template <typename Size>
+inline void prefix_offsets(const Size* sizes, size_t F, size_t* offsets) {
+  offsets[0] = 0;
+  for (size_t f = 0; f < F; ++f) offsets[f + 1] = offsets[f] + (size_t)sizes[f];
 }
 
 }  // namespace amhip

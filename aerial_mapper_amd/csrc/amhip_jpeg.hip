@@ -26,10 +26,6 @@
 // A stack of frames (amhip_io_encode_jpeg_frames, amhip_io_write_jpeg_frames) takes the
 // same passes once per group of frames: the k_jpegf_* kernels run a pass's body with the frame on
 // grid row y, and k_jpegf_offsets lays the group's files end to end.
-#include <fcntl.h>
-#include <unistd.h>
-
-#include <cerrno>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -793,12 +789,7 @@ int encode_back(hipStream_t stream, const Plan& plan, size_t chunks, uint8_t* de
   AMHIP_TRY(hipMemcpyAsync(plan.hres, plan.ctrl + 2, 16, hipMemcpyDeviceToHost, stream));
   AMHIP_TRY(hipStreamSynchronize(stream));
   if (bytes) *bytes = (size_t)plan.hres[0];
-  if (plan.hres[1]) {
-    char msg[160];
-    std::snprintf(msg, sizeof(msg), "jpeg: the file takes %llu bytes, the buffer holds %llu (nothing written)",
-                  plan.hres[0], (unsigned long long)cap);
-    return arg_failure(msg);
-  }
+  if (plan.hres[1]) return capacity_failure("jpeg", plan.hres[0], cap);
   return AMHIP_OK;
 }
 
@@ -839,31 +830,6 @@ int encode_to_host(hipStream_t stream, JpegScratch* ws, const JpegSource& src, i
 
 }  // namespace
 
-// (the status enum has no I/O code: a file that cannot be written is AMHIP_ERR_ARG, as in the
-// GeoTiff and point-cloud writers, with errno's text)
-static int write_failure(const char* what, const char* filename, int err) {
-  set_last_error(std::string(what) + ": cannot write " + filename + ": " + std::strerror(err));
-  return AMHIP_ERR_ARG;
-}
-
-int write_file(const char* what, const char* filename, const uint8_t* data, size_t size) {
-  const int fd = ::open(filename, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (fd < 0) return write_failure(what, filename, errno);
-  size_t done = 0;
-  while (done < size) {
-    const ssize_t w = ::write(fd, data + done, size - done);
-    if (w < 0 && errno == EINTR) continue;
-    if (w < 0) {
-      const int err = errno;   // (close() below may change it)
-      (void)::close(fd);
-      return write_failure(what, filename, err);
-    }
-    done += (size_t)w;
-  }
-  if (::close(fd) != 0) return write_failure(what, filename, errno);
-  return AMHIP_OK;
-}
-
 int jpeg_write_run(const char* what, hipStream_t stream, JpegScratch* ws, const JpegSource& src,
                    int quality, const char* filename) {
   std::vector<uint8_t> file;
@@ -877,21 +843,15 @@ int jpeg_write_run(const char* what, hipStream_t stream, JpegScratch* ws, const 
 // ---------------------------------------------------------------------------
 namespace {
 
-constexpr size_t kMaxGroupFrames = 65535;   // (grid.y of the per-frame launches)
-constexpr size_t kWriteSlice = 8u << 20;    // bytes of files downloaded at a time by the writing call
-
 // One call of amhip_io_encode_jpeg_frames / amhip_io_write_jpeg_frames: the geometry every frame
 // shares, the groups (amhip_frame_plan.h: a frame costs its scratch, the budget is the tuning key
 // jpege_scratch_budget_mb), the scratch of the largest group and the sizes of all files.
-struct FramesEncoder {
+struct FramesEncoder : EncodeGroups {
   Geom g;
   FrameShare fs;
   int channels = 0, quality = 0;
-  size_t row_step = 0, frame_stride = 0, nb = 0, pack_bytes = 0, F = 0;
-  std::vector<size_t> group_begin;         // the first frame of every group, then F
-  std::vector<unsigned long long> sizes;   // every frame's file, once its group ran
-  DevBuf scratch, blob;
-  hipStream_t stream = nullptr;            // the default stream: the entry points are synchronous
+  size_t row_step = 0, fstride = 0, nb = 0, pack_bytes = 0;
+  DevBuf blob;
 
   // where the buffers of a group of n frames lie in the scratch
   struct Layout {
@@ -915,25 +875,16 @@ struct FramesEncoder {
     l.total = at;
     return l;
   }
-  size_t groups() const { return group_begin.size() - 1; }
-  size_t group_frames(size_t gi) const { return group_begin[gi + 1] - group_begin[gi]; }
-  unsigned long long group_bytes(size_t gi) const {
-    unsigned long long sum = 0;
-    for (size_t f = group_begin[gi]; f < group_begin[gi + 1]; ++f) sum += sizes[f];
-    return sum;
-  }
+  size_t frame_stride() const { return fstride; }
   // the bytes of the stack that group gi's frames span
-  size_t group_span(size_t gi) const {
-    return (group_frames(gi) - 1) * frame_stride + (size_t)g.height * row_step;
-  }
+  size_t group_span(size_t gi) const { return (group_frames(gi) - 1) * fstride + (size_t)g.height * row_step; }
 
   // host only: geometry and groups
-  void plan(size_t frames, int width, int height, int ch, size_t rstep, size_t fstride, int q) {
-    F = frames;
+  void plan(size_t frames, int width, int height, int ch, size_t rstep, size_t stride, int q) {
     channels = ch;
     quality = q ? q : 95;
     row_step = rstep;
-    frame_stride = frames > 1 ? fstride : 0;
+    fstride = frames > 1 ? stride : 0;
     g.width = width;
     g.height = height;
     g.colour = ch == 3;
@@ -947,18 +898,12 @@ struct FramesEncoder {
     // a frame's scratch: coefficients, bit counts and packed words of every scan block, its tile
     // and chunk sums, its control record and its size word
     const size_t cost = nb * (128 + 4) + pack_bytes + ((size_t)fs.ntiles + fs.nchunks) * 8 + sizeof(FrameCtrl) + 8;
-    std::vector<size_t> costs(F, cost), base(F);
-    size_t max_group_bytes = 0;
-    plan_groups(costs.data(), F, budget_bytes("jpege_scratch_budget_mb", 4096.0), kMaxGroupFrames, &group_begin,
-                base.data(), &max_group_bytes);
-    sizes.assign(F, 0);
+    plan_uniform(frames, cost, "jpege_scratch_budget_mb", 4096.0, kMaxGroupFrames);
   }
 
   int open() {
-    size_t most = 0;
-    for (size_t gi = 0; gi < groups(); ++gi) most = group_frames(gi) > most ? group_frames(gi) : most;
     int rc;
-    if ((rc = scratch.alloc(layout(most).total))) return rc;
+    if ((rc = scratch.alloc(layout(most_group_frames()).total))) return rc;
     if ((rc = blob.alloc(sizeof(Blob)))) return rc;
     Blob hb;
     std::memset(&hb, 0, sizeof(hb));
@@ -988,9 +933,9 @@ struct FramesEncoder {
     AMHIP_TRY(hipMemsetAsync(words, 0, n * pack_bytes, stream));
     const dim3 gb((unsigned)((nb + kBlocksPerGroup - 1) / kBlocksPerGroup), (unsigned)n);
     if (channels == 1)
-      hipLaunchKernelGGL(k_jpegf_blocks<kGray8>, gb, dim3(256), 0, stream, px, row_step, frame_stride, g, b, coef);
+      hipLaunchKernelGGL(k_jpegf_blocks<kGray8>, gb, dim3(256), 0, stream, px, row_step, fstride, g, b, coef);
     else
-      hipLaunchKernelGGL(k_jpegf_blocks<kBgr8>, gb, dim3(256), 0, stream, px, row_step, frame_stride, g, b, coef);
+      hipLaunchKernelGGL(k_jpegf_blocks<kBgr8>, gb, dim3(256), 0, stream, px, row_step, fstride, g, b, coef);
     const dim3 gt(fs.ntiles, (unsigned)n), gc(fs.nchunks, (unsigned)n);
     hipLaunchKernelGGL(k_jpegf_lengths, gt, dim3(kTile), 0, stream, coef, g, fs, bits, tile);
     hipLaunchKernelGGL(k_jpegf_scan, dim3((unsigned)n), dim3(64), 0, stream, tile, fs.ntiles, ctrl, 0);
@@ -1004,28 +949,26 @@ struct FramesEncoder {
     return AMHIP_OK;
   }
 
-  // ... and the copy of group gi's files into `out`, which holds group_bytes(gi) bytes.  front(gi)
+  // ... and the copy of group gi's files to out + at, which holds group_bytes(gi) bytes.  front(gi)
   // ran last.
-  int back(size_t gi, uint8_t* out) {
+  int back(size_t gi, uint8_t* out, uint64_t at) {
     const size_t n = group_frames(gi);
     const Layout l = layout(n);
     uint8_t* d = scratch.as<uint8_t>();
-    unsigned long long most = 0;
-    for (size_t f = group_begin[gi]; f < group_begin[gi + 1]; ++f) most = sizes[f] > most ? sizes[f] : most;
     // (a file is its scan and more: no scan has more chunks than the largest file)
-    const unsigned chunks = (unsigned)((most + kChunk - 1) / kChunk);
+    const unsigned chunks = (unsigned)((largest_file(gi) + kChunk - 1) / kChunk);
     hipLaunchKernelGGL(k_jpegf_stuff, dim3(chunks < fs.nchunks ? chunks : fs.nchunks, (unsigned)n), dim3(256), 0,
                        stream, reinterpret_cast<const uint32_t*>(d + l.pack), fs,
                        reinterpret_cast<const FrameCtrl*>(d + l.ctrl),
-                       reinterpret_cast<const unsigned long long*>(d + l.chunk), blob.as<const Blob>(), out);
+                       reinterpret_cast<const unsigned long long*>(d + l.chunk), blob.as<const Blob>(), out + at);
     AMHIP_TRY(hipGetLastError());
     return AMHIP_OK;
   }
 };
 
-// the argument rules of both entry points; the text names the export and the field
-int check_frames_args(const char* who, size_t F, int width, int height, int channels, size_t row_step,
-                      size_t frame_stride, int quality) {
+// the argument rules of both entry points (the text names the export and the field), then the plan
+int plan_frames(const char* who, FramesEncoder* enc, size_t F, int width, int height, int channels, size_t row_step,
+                size_t frame_stride, int quality) {
   auto fail = [who](const std::string& msg) {
     set_last_error(std::string(who) + ": " + msg);
     return AMHIP_ERR_ARG;
@@ -1037,10 +980,39 @@ int check_frames_args(const char* who, size_t F, int width, int height, int chan
   if (row_step < (size_t)width * (size_t)channels) return fail("row_step smaller than an image row");
   if (F > 1 && frame_stride < (size_t)height * row_step) return fail("frame_stride smaller than a frame");
   if (quality < 0 || quality > 100) return fail("quality must be 1..100 (0: 95)");
+  enc->plan(F, width, height, channels, row_step, frame_stride, quality);
   return AMHIP_OK;
 }
 
 }  // namespace
+
+// a host image -> the context's image scratch, rows packed; *src then names the copy
+int stage_host_image(Ctx* c, int channels, JpegSource* src) {
+  const size_t row = (size_t)src->width * (size_t)channels;
+  uint8_t* dev = nullptr;
+  const int rc = jpeg_scratch_image(&c->jpeg, row * (size_t)src->height, &dev);
+  if (rc) return rc;
+  AMHIP_TRY(hipMemcpy2DAsync(dev, row, src->dev, src->step, row, (size_t)src->height, hipMemcpyHostToDevice,
+                             c->stream));
+  src->dev = dev;
+  src->step = row;
+  return AMHIP_OK;
+}
+
+// the context's window of `layer` as an image in its image scratch (amhip_layer_to_image_dev) -> *src;
+// limit: the format's refusal of a window no file of it holds
+int layer_image_source(amhip_ctx* h, const char* limit, int layer, int bgr, float lower, float upper, JpegSource* src) {
+  Ctx* c = &h->impl;
+  if (!image_size_ok(c->win_rows, c->win_cols)) return arg_failure(limit);
+  int rc = ctx_use_device(c);
+  if (rc) return rc;
+  const size_t row = (size_t)c->win_cols * (bgr ? 3u : 1u);
+  uint8_t* dev = nullptr;
+  if ((rc = jpeg_scratch_image(&c->jpeg, row * (size_t)c->win_rows, &dev))) return rc;
+  if ((rc = amhip_layer_to_image_dev(h, layer, bgr, lower, upper, dev, row))) return rc;
+  *src = JpegSource{dev, row, c->win_cols, c->win_rows, bgr ? kJpegBgr8 : kJpegGray8};
+  return AMHIP_OK;
+}
 
 }  // namespace amhip
 
@@ -1075,14 +1047,7 @@ int amhip_jpeg_write(amhip_ctx* h, const char* filename, const uint8_t* pixels, 
   int rc = ctx_use_device(c);
   if (rc) return rc;
   JpegSource src = {pixels, step, width, height, channels == 1 ? kGray8 : kBgr8};
-  if (!on_device) {
-    const size_t row = (size_t)width * (size_t)channels;
-    uint8_t* dev = nullptr;
-    if ((rc = jpeg_scratch_image(&c->jpeg, row * (size_t)height, &dev))) return rc;
-    AMHIP_TRY(hipMemcpy2DAsync(dev, row, pixels, step, row, (size_t)height, hipMemcpyHostToDevice, c->stream));
-    src.dev = dev;
-    src.step = row;
-  }
+  if (!on_device && (rc = stage_host_image(c, channels, &src))) return rc;
   ScopedTimer timer(c, AMHIP_K_MISC);
   return jpeg_write_run("amhip_jpeg_write", c->stream, &c->jpeg, src, quality, filename);
 }
@@ -1093,17 +1058,12 @@ int amhip_layer_write_jpeg(amhip_ctx* h, int layer, int bgr, float lower, float 
     return arg_failure("amhip_layer_write_jpeg: bad argument");
   if (quality < 0 || quality > 100) return arg_failure("amhip_layer_write_jpeg: quality must be 1..100 (0: 95)");
   if (!bgr && !(upper > lower)) return arg_failure("amhip_layer_write_jpeg: upper <= lower");
-  Ctx* c = &h->impl;
-  if (c->win_rows < 1 || c->win_cols < 1 || c->win_rows > 65535 || c->win_cols > 65535)
-    return arg_failure("amhip_layer_write_jpeg: a JPEG file holds 1 x 1 to 65535 x 65535 pixels");
-  int rc = ctx_use_device(c);
+  JpegSource src;
+  const int rc = layer_image_source(h, "amhip_layer_write_jpeg: a JPEG file holds 1 x 1 to 65535 x 65535 pixels", layer,
+                                    bgr, lower, upper, &src);
   if (rc) return rc;
-  const size_t row = (size_t)c->win_cols * (bgr ? 3u : 1u);
-  uint8_t* dev = nullptr;
-  if ((rc = jpeg_scratch_image(&c->jpeg, row * (size_t)c->win_rows, &dev))) return rc;
-  if ((rc = amhip_layer_to_image_dev(h, layer, bgr, lower, upper, dev, row))) return rc;
+  Ctx* c = &h->impl;
   ScopedTimer timer(c, AMHIP_K_MISC);
-  const JpegSource src = {dev, row, c->win_cols, c->win_rows, bgr ? kBgr8 : kGray8};
   return jpeg_write_run("amhip_layer_write_jpeg", c->stream, &c->jpeg, src, quality, filename);
 }
 
@@ -1111,106 +1071,18 @@ int amhip_io_encode_jpeg_frames(int device, const uint8_t* dev_frames, size_t F,
                                 int channels, size_t row_step, size_t frame_stride, int quality,
                                 uint8_t** dev_files, size_t* offsets) {
   static const char kWho[] = "amhip_io_encode_jpeg_frames";
-  if (dev_files) *dev_files = nullptr;
-  if (!dev_frames || !dev_files || !offsets) {
-    set_last_error(std::string(kWho) + ": null argument");
-    return AMHIP_ERR_ARG;
-  }
-  int rc;
-  if ((rc = check_frames_args(kWho, F, width, height, channels, row_step, frame_stride, quality))) return rc;
-  FramesEncoder enc;
-  enc.plan(F, width, height, channels, row_step, frame_stride, quality);
-  if ((rc = open_device(device, kWho))) return rc;
-  if ((rc = enc.open())) return rc;
-  DevBuf out;
-  const size_t G = enc.groups();
-  if (G == 1) {
-    if ((rc = enc.front(0, dev_frames))) return rc;
-    if ((rc = out.alloc((size_t)enc.group_bytes(0)))) return rc;
-    if ((rc = enc.back(0, out.as<uint8_t>()))) return rc;
-  } else {
-    // The result is one allocation of exactly the files' bytes, so their sizes come first: every
-    // group runs up to its sizes, then again straight into its place in the result.  No second
-    // buffer and no copy; twice the arithmetic, in calls whose scratch exceeds the budget only.
-    unsigned long long total = 0;
-    for (size_t gi = 0; gi < G; ++gi) {
-      if ((rc = enc.front(gi, dev_frames + enc.group_begin[gi] * enc.frame_stride))) return rc;
-      total += enc.group_bytes(gi);
-    }
-    if ((rc = out.alloc((size_t)total))) return rc;
-    unsigned long long at = 0;
-    for (size_t gi = 0; gi < G; ++gi) {
-      if ((rc = enc.front(gi, dev_frames + enc.group_begin[gi] * enc.frame_stride))) return rc;
-      if ((rc = enc.back(gi, out.as<uint8_t>() + at))) return rc;
-      at += enc.group_bytes(gi);
-    }
-  }
-  AMHIP_TRY(hipStreamSynchronize(enc.stream));
-  offsets[0] = 0;
-  for (size_t f = 0; f < F; ++f) offsets[f + 1] = offsets[f] + (size_t)enc.sizes[f];
-  *dev_files = static_cast<uint8_t*>(out.release());
-  return AMHIP_OK;
+  return encode_frame_stack<FramesEncoder>(kWho, device, dev_frames, dev_files, offsets, [&](FramesEncoder* enc) {
+    return plan_frames(kWho, enc, F, width, height, channels, row_step, frame_stride, quality);
+  });
 }
 
 int amhip_io_write_jpeg_frames(int device, const uint8_t* frames, int on_device, size_t F, int width,
                                int height, int channels, size_t row_step, size_t frame_stride, int quality,
                                const char* const* filenames) {
   static const char kWho[] = "amhip_io_write_jpeg_frames";
-  if (!frames || !filenames) {
-    set_last_error(std::string(kWho) + ": null argument");
-    return AMHIP_ERR_ARG;
-  }
-  int rc;
-  if ((rc = check_frames_args(kWho, F, width, height, channels, row_step, frame_stride, quality))) return rc;
-  for (size_t f = 0; f < F; ++f)
-    if (!filenames[f]) {
-      set_last_error(std::string(kWho) + ": filenames[" + std::to_string(f) + "] is null");
-      return AMHIP_ERR_ARG;
-    }
-  FramesEncoder enc;
-  enc.plan(F, width, height, channels, row_step, frame_stride, quality);
-  if ((rc = open_device(device, kWho))) return rc;
-  if ((rc = enc.open())) return rc;
-  // group by group: encode, download the group's bytes, write its files in order
-  DevBuf staged;   // a group of host frames, uploaded
-  if (!on_device) {
-    size_t most = 0;
-    for (size_t gi = 0; gi < enc.groups(); ++gi) most = enc.group_span(gi) > most ? enc.group_span(gi) : most;
-    if ((rc = staged.alloc(most))) return rc;
-  }
-  std::vector<uint8_t> host;
-  for (size_t gi = 0; gi < enc.groups(); ++gi) {
-    const size_t first = enc.group_begin[gi];
-    const uint8_t* px = frames + first * enc.frame_stride;
-    if (!on_device) {
-      AMHIP_TRY(hipMemcpyAsync(staged.p, px, enc.group_span(gi), hipMemcpyHostToDevice, enc.stream));
-      px = staged.as<const uint8_t>();
-    }
-    if ((rc = enc.front(gi, px))) return rc;
-    const size_t bytes = (size_t)enc.group_bytes(gi);
-    DevBuf out;
-    if ((rc = out.alloc(bytes))) return rc;
-    if ((rc = enc.back(gi, out.as<uint8_t>()))) return rc;
-    // Down in slices of consecutive files, kWriteSlice bytes at the most (one file at the least): the
-    // host buffer is touched once and reused, where one buffer for a group of 200 MB would be fresh
-    // pages, faulted in and zeroed, on every call.
-    const size_t last = enc.group_begin[gi + 1];
-    size_t at = 0;
-    for (size_t f = first; f < last;) {
-      size_t slice = (size_t)enc.sizes[f], end = f + 1;
-      while (end < last && slice + (size_t)enc.sizes[end] <= kWriteSlice) slice += (size_t)enc.sizes[end++];
-      if (host.size() < slice) host.resize(slice);
-      AMHIP_TRY(hipMemcpyAsync(host.data(), out.as<uint8_t>() + at, slice, hipMemcpyDeviceToHost, enc.stream));
-      AMHIP_TRY(hipStreamSynchronize(enc.stream));
-      size_t in_slice = 0;
-      for (; f < end; ++f) {
-        if ((rc = write_file(kWho, filenames[f], host.data() + in_slice, (size_t)enc.sizes[f]))) return rc;
-        in_slice += (size_t)enc.sizes[f];
-      }
-      at += slice;
-    }
-  }
-  return AMHIP_OK;
+  return write_frame_stack<FramesEncoder>(kWho, device, frames, on_device, filenames, [&](FramesEncoder* enc) {
+    return plan_frames(kWho, enc, F, width, height, channels, row_step, frame_stride, quality);
+  });
 }
 
 }  // extern "C"

@@ -25,10 +25,6 @@
 //   k_pnge_frame        a wave per IDAT payload: length, type, 8192 bytes, CRC-32 (a lane per 128
 //                       bytes, combined by x^(8n) mod P); signature, IHDR and IEND around them
 // Every pass is bounded by its buffer: see the comments at each store.
-#include <fcntl.h>
-#include <unistd.h>
-
-#include <cerrno>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -563,37 +559,24 @@ int deflate_rle_middle(hipStream_t stream, const Share& s, const Bufs& b, uint32
 
 namespace {
 
-constexpr size_t kMaxGroupFrames = 65535;   // (grid.y of the per-frame launches)
-constexpr size_t kWriteSlice = 8u << 20;    // bytes of files downloaded at a time by the writing call
-
 // One call: the geometry every frame shares, the groups (amhip_frame_plan.h: a frame costs its
 // scratch, the budget is the tuning key pnge_scratch_budget_mb), the scratch of the largest group
 // and the sizes of all files.  The scratch lives for the call.
-struct PngEncoder {
+struct PngEncoder : EncodeGroups {
   Share s;
-  size_t F = 0;
-  std::vector<size_t> group_begin;
-  std::vector<unsigned long long> sizes;
-  DevBuf scratch, head;
-  hipStream_t stream = nullptr;
+  DevBuf head;
 
   using Layout = pnge::Layout;
   Layout layout(size_t n) const { return pnge::make_layout(s, n); }
   Bufs bufs(const Layout& l) { return pnge::make_bufs(scratch.as<uint8_t>(), l, head.as<const uint8_t>()); }
-  size_t groups() const { return group_begin.size() - 1; }
-  size_t group_frames(size_t gi) const { return group_begin[gi + 1] - group_begin[gi]; }
-  unsigned long long group_bytes(size_t gi) const {
-    unsigned long long sum = 0;
-    for (size_t f = group_begin[gi]; f < group_begin[gi + 1]; ++f) sum += sizes[f];
-    return sum;
-  }
+  size_t frame_stride() const { return (size_t)s.frame_stride; }
+  // the bytes of the stack that group gi's frames span
   size_t group_span(size_t gi) const {
     return (group_frames(gi) - 1) * (size_t)s.frame_stride + (size_t)s.height * (size_t)s.row_step;
   }
 
   // host only: geometry and groups
   void plan(size_t frames, int width, int height, int mode, size_t row_step, size_t frame_stride) {
-    F = frames;
     s.width = width;
     s.height = height;
     s.mode = mode;
@@ -602,19 +585,12 @@ struct PngEncoder {
     pnge::share_set_raw(&s, pnge::raw_len(width, height, s.bpp));
     s.row_step = row_step;
     s.frame_stride = frames > 1 ? frame_stride : 0;
-    const size_t cost = layout(1).total;
-    std::vector<size_t> costs(F, cost), base(F);
-    size_t max_group_bytes = 0;
-    plan_groups(costs.data(), F, budget_bytes("pnge_scratch_budget_mb", 4096.0), kMaxGroupFrames, &group_begin,
-                base.data(), &max_group_bytes);
-    sizes.assign(F, 0);
+    plan_uniform(frames, layout(1).total, "pnge_scratch_budget_mb", 4096.0, kMaxGroupFrames);
   }
 
   int open() {
-    size_t most = 0;
-    for (size_t gi = 0; gi < groups(); ++gi) most = group_frames(gi) > most ? group_frames(gi) : most;
     int rc;
-    if ((rc = scratch.alloc(layout(most).total))) return rc;
+    if ((rc = scratch.alloc(layout(most_group_frames()).total))) return rc;
     if ((rc = head.alloc(pnge::kFileHead + pnge::kFileTail))) return rc;
     static const Tables kTables = pnge::make_tables();
     uint8_t h[pnge::kFileHead + pnge::kFileTail];
@@ -644,66 +620,67 @@ struct PngEncoder {
     return AMHIP_OK;
   }
 
-  // ... and group gi's files into `out`, which holds group_bytes(gi) bytes.  front(gi) ran last.
-  int back(size_t gi, uint8_t* out) {
+  // ... and group gi's files to out + at, which holds group_bytes(gi) bytes.  front(gi) ran last.
+  int back(size_t gi, uint8_t* out, uint64_t at) {
     const uint32_t n = (uint32_t)group_frames(gi);
     const Bufs b = bufs(layout(n));
-    unsigned long long most = 0;
-    for (size_t f = group_begin[gi]; f < group_begin[gi + 1]; ++f) most = sizes[f] > most ? sizes[f] : most;
-    // (a file is its zlib stream and more: no stream has more payloads than this)
-    const unsigned idats = (unsigned)((most + pnge::kIdatBytes - 1) / pnge::kIdatBytes);
-    hipLaunchKernelGGL(k_pnge_frame, dim3(idats, n), dim3(64), 0, stream, s, b, out);
+    // (a file is its zlib stream and more: no stream has more payloads than the largest file)
+    const unsigned idats = (unsigned)((largest_file(gi) + pnge::kIdatBytes - 1) / pnge::kIdatBytes);
+    hipLaunchKernelGGL(k_pnge_frame, dim3(idats, n), dim3(64), 0, stream, s, b, out + at);
     AMHIP_TRY(hipGetLastError());
     return AMHIP_OK;
   }
 };
 
-int fail(const char* who, const std::string& msg) {
-  set_last_error(std::string(who) + ": " + msg);
-  return AMHIP_ERR_ARG;
+// the argument rules of both stack entry points, then the plan
+int plan_frames(const char* who, PngEncoder* enc, size_t F, int width, int height, int channels, size_t row_step,
+                size_t frame_stride) {
+  if (const char* why = pnge::check_frames_args(F, width, height, channels, row_step, frame_stride)) {
+    set_last_error(std::string(who) + ": " + why);
+    return AMHIP_ERR_ARG;
+  }
+  enc->plan(F, width, height, channels == 1 ? kJpegGray8 : kJpegBgr8, row_step, frame_stride);
+  return AMHIP_OK;
 }
 
-// one image -> host memory
-int encode_to_host(hipStream_t stream, const JpegSource& src, std::vector<uint8_t>* file) {
+// One image, a stack of one.  dev_out != null: into it, at most cap bytes, nothing written when it
+// does not fit.  Otherwise into *host.  *bytes: the file's size.
+int png_encode(hipStream_t stream, const JpegSource& src, uint8_t* dev_out, size_t cap, std::vector<uint8_t>* host,
+               size_t* bytes) {
   PngEncoder enc;
   enc.stream = stream;
   enc.plan(1, src.width, src.height, src.mode, src.step, 0);
   int rc;
   if ((rc = enc.open())) return rc;
-  if ((rc = enc.front(0, static_cast<const uint8_t*>(src.dev)))) return rc;
-  DevBuf out;
-  if ((rc = out.alloc((size_t)enc.sizes[0]))) return rc;
-  if ((rc = enc.back(0, out.as<uint8_t>()))) return rc;
-  file->resize((size_t)enc.sizes[0]);
-  AMHIP_TRY(hipMemcpyAsync(file->data(), out.p, file->size(), hipMemcpyDeviceToHost, stream));
-  AMHIP_TRY(hipStreamSynchronize(stream));
+  DevBuf owned;
+  rc = encode_groups(
+      enc, [&](size_t gi) { return enc.front(gi, static_cast<const uint8_t*>(src.dev)); },
+      [&](uint8_t** to, uint64_t*) {
+        if (bytes) *bytes = (size_t)enc.sizes[0];
+        *to = dev_out;
+        if (dev_out) return enc.sizes[0] > cap ? capacity_failure("png", enc.sizes[0], cap) : (int)AMHIP_OK;
+        const int r = owned.alloc((size_t)enc.sizes[0]);
+        *to = owned.as<uint8_t>();
+        return r;
+      });
+  if (rc) return rc;
+  if (!dev_out) {
+    host->resize((size_t)enc.sizes[0]);
+    AMHIP_TRY(hipMemcpyAsync(host->data(), owned.p, host->size(), hipMemcpyDeviceToHost, stream));
+  }
+  AMHIP_TRY(hipStreamSynchronize(stream));   // (the scratch goes with this call)
   return AMHIP_OK;
 }
 
 }  // namespace
 
 int png_encode_run(hipStream_t stream, const JpegSource& src, uint8_t* dev_out, size_t cap, size_t* bytes) {
-  PngEncoder enc;
-  enc.stream = stream;
-  enc.plan(1, src.width, src.height, src.mode, src.step, 0);
-  int rc;
-  if ((rc = enc.open())) return rc;
-  if ((rc = enc.front(0, static_cast<const uint8_t*>(src.dev)))) return rc;
-  if (bytes) *bytes = (size_t)enc.sizes[0];
-  if (enc.sizes[0] > cap) {
-    char msg[160];
-    std::snprintf(msg, sizeof(msg), "png: the file takes %llu bytes, the buffer holds %llu (nothing written)",
-                  enc.sizes[0], (unsigned long long)cap);
-    return arg_failure(msg);
-  }
-  if ((rc = enc.back(0, dev_out))) return rc;
-  AMHIP_TRY(hipStreamSynchronize(stream));   // (the scratch goes with this call)
-  return AMHIP_OK;
+  return png_encode(stream, src, dev_out, cap, nullptr, bytes);
 }
 
 int png_write_run(const char* what, hipStream_t stream, const JpegSource& src, const char* filename) {
   std::vector<uint8_t> file;
-  const int rc = encode_to_host(stream, src, &file);
+  const int rc = png_encode(stream, src, nullptr, 0, &file, nullptr);
   if (rc) return rc;
   return write_file(what, filename, file.data(), file.size());
 }
@@ -741,14 +718,7 @@ int amhip_png_write(amhip_ctx* h, const char* filename, const uint8_t* pixels, i
   int rc = ctx_use_device(c);
   if (rc) return rc;
   JpegSource src = {pixels, step, width, height, channels == 1 ? kJpegGray8 : kJpegBgr8};
-  if (!on_device) {
-    const size_t row = (size_t)width * (size_t)channels;
-    uint8_t* dev = nullptr;
-    if ((rc = jpeg_scratch_image(&c->jpeg, row * (size_t)height, &dev))) return rc;
-    AMHIP_TRY(hipMemcpy2DAsync(dev, row, pixels, step, row, (size_t)height, hipMemcpyHostToDevice, c->stream));
-    src.dev = dev;
-    src.step = row;
-  }
+  if (!on_device && (rc = stage_host_image(c, channels, &src))) return rc;
   ScopedTimer timer(c, AMHIP_K_MISC);
   return png_write_run("amhip_png_write", c->stream, src, filename);
 }
@@ -757,17 +727,12 @@ int amhip_layer_write_png(amhip_ctx* h, int layer, int bgr, float lower, float u
   if (!h || !filename || layer < 0 || layer >= AMHIP_NUM_LAYERS)
     return arg_failure("amhip_layer_write_png: bad argument");
   if (!bgr && !(upper > lower)) return arg_failure("amhip_layer_write_png: upper <= lower");
-  Ctx* c = &h->impl;
-  if (c->win_rows < 1 || c->win_cols < 1 || c->win_rows > 65535 || c->win_cols > 65535)
-    return arg_failure("amhip_layer_write_png: a PNG file of this encoder holds 1 x 1 to 65535 x 65535 pixels");
-  int rc = ctx_use_device(c);
+  JpegSource src;
+  const int rc = layer_image_source(h, "amhip_layer_write_png: a PNG file of this encoder holds 1 x 1 to 65535 x 65535 pixels",
+                                    layer, bgr, lower, upper, &src);
   if (rc) return rc;
-  const size_t row = (size_t)c->win_cols * (bgr ? 3u : 1u);
-  uint8_t* dev = nullptr;
-  if ((rc = jpeg_scratch_image(&c->jpeg, row * (size_t)c->win_rows, &dev))) return rc;
-  if ((rc = amhip_layer_to_image_dev(h, layer, bgr, lower, upper, dev, row))) return rc;
+  Ctx* c = &h->impl;
   ScopedTimer timer(c, AMHIP_K_MISC);
-  const JpegSource src = {dev, row, c->win_cols, c->win_rows, bgr ? kJpegBgr8 : kJpegGray8};
   return png_write_run("amhip_layer_write_png", c->stream, src, filename);
 }
 
@@ -775,93 +740,17 @@ int amhip_io_encode_png_frames(int device, const uint8_t* dev_frames, size_t F, 
                                int channels, size_t row_step, size_t frame_stride, uint8_t** dev_files,
                                size_t* offsets) {
   static const char kWho[] = "amhip_io_encode_png_frames";
-  if (dev_files) *dev_files = nullptr;
-  if (!dev_frames || !dev_files || !offsets) return fail(kWho, "null argument");
-  if (const char* why = pnge::check_frames_args(F, width, height, channels, row_step, frame_stride))
-    return fail(kWho, why);
-  PngEncoder enc;
-  enc.plan(F, width, height, channels == 1 ? kJpegGray8 : kJpegBgr8, row_step, frame_stride);
-  int rc;
-  if ((rc = open_device(device, kWho))) return rc;
-  if ((rc = enc.open())) return rc;
-  DevBuf out;
-  const size_t G = enc.groups();
-  if (G == 1) {
-    if ((rc = enc.front(0, dev_frames))) return rc;
-    if ((rc = out.alloc((size_t)enc.group_bytes(0)))) return rc;
-    if ((rc = enc.back(0, out.as<uint8_t>()))) return rc;
-  } else {
-    // The result is one allocation of exactly the files' bytes, so their sizes come first: every
-    // group runs up to its sizes, then again straight into its place in the result, as the JPEG
-    // stack encoder does.
-    unsigned long long total = 0;
-    for (size_t gi = 0; gi < G; ++gi) {
-      if ((rc = enc.front(gi, dev_frames + enc.group_begin[gi] * (size_t)enc.s.frame_stride))) return rc;
-      total += enc.group_bytes(gi);
-    }
-    if ((rc = out.alloc((size_t)total))) return rc;
-    unsigned long long at = 0;
-    for (size_t gi = 0; gi < G; ++gi) {
-      if ((rc = enc.front(gi, dev_frames + enc.group_begin[gi] * (size_t)enc.s.frame_stride))) return rc;
-      if ((rc = enc.back(gi, out.as<uint8_t>() + at))) return rc;
-      at += enc.group_bytes(gi);
-    }
-  }
-  AMHIP_TRY(hipStreamSynchronize(enc.stream));
-  offsets[0] = 0;
-  for (size_t f = 0; f < F; ++f) offsets[f + 1] = offsets[f] + (size_t)enc.sizes[f];
-  *dev_files = static_cast<uint8_t*>(out.release());
-  return AMHIP_OK;
+  return encode_frame_stack<PngEncoder>(kWho, device, dev_frames, dev_files, offsets, [&](PngEncoder* enc) {
+    return plan_frames(kWho, enc, F, width, height, channels, row_step, frame_stride);
+  });
 }
 
 int amhip_io_write_png_frames(int device, const uint8_t* frames, int on_device, size_t F, int width, int height,
                               int channels, size_t row_step, size_t frame_stride, const char* const* filenames) {
   static const char kWho[] = "amhip_io_write_png_frames";
-  if (!frames || !filenames) return fail(kWho, "null argument");
-  if (const char* why = pnge::check_frames_args(F, width, height, channels, row_step, frame_stride))
-    return fail(kWho, why);
-  for (size_t f = 0; f < F; ++f)
-    if (!filenames[f]) return fail(kWho, "filenames[" + std::to_string(f) + "] is null");
-  PngEncoder enc;
-  enc.plan(F, width, height, channels == 1 ? kJpegGray8 : kJpegBgr8, row_step, frame_stride);
-  int rc;
-  if ((rc = open_device(device, kWho))) return rc;
-  if ((rc = enc.open())) return rc;
-  // group by group: encode, download the group's bytes in slices of whole files, write them in order
-  DevBuf staged;   // a group of host frames, uploaded
-  if (!on_device) {
-    size_t most = 0;
-    for (size_t gi = 0; gi < enc.groups(); ++gi) most = enc.group_span(gi) > most ? enc.group_span(gi) : most;
-    if ((rc = staged.alloc(most))) return rc;
-  }
-  std::vector<uint8_t> host;
-  for (size_t gi = 0; gi < enc.groups(); ++gi) {
-    const size_t first = enc.group_begin[gi], last = enc.group_begin[gi + 1];
-    const uint8_t* px = frames + first * (size_t)enc.s.frame_stride;
-    if (!on_device) {
-      AMHIP_TRY(hipMemcpyAsync(staged.p, px, enc.group_span(gi), hipMemcpyHostToDevice, enc.stream));
-      px = staged.as<const uint8_t>();
-    }
-    if ((rc = enc.front(gi, px))) return rc;
-    DevBuf out;
-    if ((rc = out.alloc((size_t)enc.group_bytes(gi)))) return rc;
-    if ((rc = enc.back(gi, out.as<uint8_t>()))) return rc;
-    size_t at = 0;
-    for (size_t f = first; f < last;) {
-      size_t slice = (size_t)enc.sizes[f], end = f + 1;
-      while (end < last && slice + (size_t)enc.sizes[end] <= kWriteSlice) slice += (size_t)enc.sizes[end++];
-      if (host.size() < slice) host.resize(slice);
-      AMHIP_TRY(hipMemcpyAsync(host.data(), out.as<uint8_t>() + at, slice, hipMemcpyDeviceToHost, enc.stream));
-      AMHIP_TRY(hipStreamSynchronize(enc.stream));
-      size_t in_slice = 0;
-      for (; f < end; ++f) {
-        if ((rc = write_file(kWho, filenames[f], host.data() + in_slice, (size_t)enc.sizes[f]))) return rc;
-        in_slice += (size_t)enc.sizes[f];
-      }
-      at += slice;
-    }
-  }
-  return AMHIP_OK;
+  return write_frame_stack<PngEncoder>(kWho, device, frames, on_device, filenames, [&](PngEncoder* enc) {
+    return plan_frames(kWho, enc, F, width, height, channels, row_step, frame_stride);
+  });
 }
 
 }  // extern "C"

@@ -37,6 +37,7 @@
 
 #include "amhip_common.h"
 #include "amhip_content_sum.h"
+#include "amhip_tiff_host.h"
 
 namespace amhip {
 
@@ -1191,8 +1192,18 @@ int amhip_session_layer_to_image(amhip_session* h, int layer, int bgr, float low
   });
 }
 
-/* amhip_layer_write_jpeg for the whole map of a session: the image assembled from every window
- * (amhip_session_layer_to_image), encoded on the first window's device. */
+/* The whole map's layer for a JPEG or PNG writer: the image assembled on the host from every window
+ * (amhip_session_layer_to_image), rows packed.  limit: the format's refusal of a map no file of it holds. */
+static int session_layer_image(amhip_session* h, const char* limit, int layer, int bgr, float lower, float upper,
+                               std::vector<uint8_t>* image, size_t* row) {
+  const amhip_grid_desc& g = h->impl.grid;
+  if (!image_size_ok(g.rows, g.cols)) return arg_failure(limit);
+  *row = (size_t)g.cols * (bgr ? 3u : 1u);
+  image->resize(*row * (size_t)g.rows);
+  return amhip_session_layer_to_image(h, layer, bgr, lower, upper, image->data(), *row);
+}
+
+/* amhip_layer_write_jpeg for the whole map of a session, encoded on the first window's device. */
 int amhip_session_layer_write_jpeg(amhip_session* h, int layer, int bgr, float lower, float upper,
                                    int quality, const char* filename) {
   if (!h || !filename || layer < 0 || layer >= AMHIP_NUM_LAYERS)
@@ -1201,11 +1212,10 @@ int amhip_session_layer_write_jpeg(amhip_session* h, int layer, int bgr, float l
     return arg_failure("amhip_session_layer_write_jpeg: quality must be 1..100 (0: 95)");
   if (!bgr && !(upper > lower)) return arg_failure("amhip_session_layer_write_jpeg: upper <= lower");
   Session& s = h->impl;
-  if (s.grid.rows < 1 || s.grid.cols < 1 || s.grid.rows > 65535 || s.grid.cols > 65535)
-    return arg_failure("amhip_session_layer_write_jpeg: a JPEG file holds 1 x 1 to 65535 x 65535 pixels");
-  const size_t row = (size_t)s.grid.cols * (bgr ? 3u : 1u);
-  std::vector<uint8_t> image(row * (size_t)s.grid.rows);
-  int rc = amhip_session_layer_to_image(h, layer, bgr, lower, upper, image.data(), row);
+  std::vector<uint8_t> image;
+  size_t row = 0;
+  const int rc = session_layer_image(h, "amhip_session_layer_write_jpeg: a JPEG file holds 1 x 1 to 65535 x 65535 pixels",
+                                     layer, bgr, lower, upper, &image, &row);
   if (rc) return rc;
   return amhip_jpeg_write(s.ctx[0], filename, image.data(), /*on_device=*/0, row, s.grid.cols, s.grid.rows,
                           bgr ? 3 : 1, quality);
@@ -1218,11 +1228,11 @@ int amhip_session_layer_write_png(amhip_session* h, int layer, int bgr, float lo
     return arg_failure("amhip_session_layer_write_png: bad argument");
   if (!bgr && !(upper > lower)) return arg_failure("amhip_session_layer_write_png: upper <= lower");
   Session& s = h->impl;
-  if (s.grid.rows < 1 || s.grid.cols < 1 || s.grid.rows > 65535 || s.grid.cols > 65535)
-    return arg_failure("amhip_session_layer_write_png: a PNG file of this encoder holds 1 x 1 to 65535 x 65535 pixels");
-  const size_t row = (size_t)s.grid.cols * (bgr ? 3u : 1u);
-  std::vector<uint8_t> image(row * (size_t)s.grid.rows);
-  int rc = amhip_session_layer_to_image(h, layer, bgr, lower, upper, image.data(), row);
+  std::vector<uint8_t> image;
+  size_t row = 0;
+  const int rc = session_layer_image(
+      h, "amhip_session_layer_write_png: a PNG file of this encoder holds 1 x 1 to 65535 x 65535 pixels", layer, bgr,
+      lower, upper, &image, &row);
   if (rc) return rc;
   return amhip_png_write(s.ctx[0], filename, image.data(), /*on_device=*/0, row, s.grid.cols, s.grid.rows,
                          bgr ? 3 : 1);
@@ -1238,11 +1248,11 @@ int amhip_session_layer_write_geotiff(amhip_session* h, int layer, int kind, flo
   if (layer < 0 || layer >= AMHIP_NUM_LAYERS) return arg_failure((std::string(kWho) + "layer: no such layer").c_str());
   Session& s = h->impl;
   const size_t rows = (size_t)s.grid.rows, cols = (size_t)s.grid.cols;
-  if (kind < 0 || kind > 2) return arg_failure((std::string(kWho) + "kind must be 0 (f32), 1 (u8) or 2 (rgb8)").c_str());
+  // (the kind and tile rules and their texts are the raster writer's; the size has a text of its own here)
+  if (const char* why = tiff::check_kind(kind)) return arg_failure((std::string(kWho) + why).c_str());
   if (rows < 1 || cols < 1 || rows > 65535 || cols > 65535)
     return arg_failure((std::string(kWho) + "width and height must be 1..65535").c_str());
-  if (tile != 0 && (tile < 16 || tile > 1024 || tile % 16 != 0))
-    return arg_failure((std::string(kWho) + "tile must be a multiple of 16 in 16..1024, or 0 (256)").c_str());
+  if (const char* why = tiff::check_tile(tile)) return arg_failure((std::string(kWho) + why).c_str());
   if (utm_zone < 1 || utm_zone > 60) return arg_failure((std::string(kWho) + "utm_zone must be 1..60").c_str());
   if (kind == 1 && !(upper > lower)) return arg_failure((std::string(kWho) + "upper <= lower").c_str());
   const amhip_grid_desc& g = s.grid;

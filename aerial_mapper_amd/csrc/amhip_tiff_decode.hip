@@ -336,19 +336,6 @@ bool parse_or_text(const char* who, const uint8_t* file, size_t len, Parsed* P) 
 
 }  // namespace
 
-int read_file(const char* what, const char* filename, std::vector<uint8_t>* out) {
-  FILE* f = std::fopen(filename, "rb");
-  if (!f) return bad(what, std::string("cannot open ") + filename + ": " + std::strerror(errno));
-  out->clear();
-  uint8_t block[1 << 16];
-  size_t got;
-  while ((got = std::fread(block, 1, sizeof(block), f)) > 0) out->insert(out->end(), block, block + got);
-  const bool failed = std::ferror(f) != 0;
-  std::fclose(f);
-  if (failed) return bad(what, std::string("cannot read ") + filename);
-  return AMHIP_OK;
-}
-
 // One layer call in its two halves (the session runs the first half on every window before the
 // second on any): what has been decoded for the context's window, and where it lies in the file.
 struct TiffLayerJob {

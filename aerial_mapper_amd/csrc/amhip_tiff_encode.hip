@@ -227,31 +227,17 @@ __global__ void __launch_bounds__(256) k_tiff_gather(Share s, Bufs b, uint8_t* o
   for (unsigned long long k = lo; k < hi; ++k) dst[k] = src[k];
 }
 
-constexpr size_t kMaxGroupTiles = 65535;   // (grid.y of the per-tile launches)
-
-// One call: the tiles' geometry, the groups (a tile costs its scratch, the budget is the tuning key
-// tiffe_scratch_budget_mb), the scratch of the largest group and the lengths of all streams.  The
-// scratch lives for the call.
-struct TiffEncoder {
+// One call: the tiles' geometry, the groups (a tile is a frame: it costs its scratch, the budget is the
+// tuning key tiffe_scratch_budget_mb), the scratch of the largest group and, in `sizes`, the lengths of
+// all streams.
+struct TiffEncoder : EncodeGroups {
   Share s = {};
   TileSrc src = {};
   int kind = 0;
   bool layer = false;
-  size_t T = 0;
-  std::vector<size_t> group_begin;
-  std::vector<uint64_t> counts;
-  DevBuf scratch;
-  hipStream_t stream = nullptr;
 
   pnge::Layout layout(size_t n) const { return pnge::make_layout(s, n); }
   Bufs bufs(size_t n) { return pnge::make_bufs(scratch.as<uint8_t>(), layout(n), nullptr); }
-  size_t groups() const { return group_begin.size() - 1; }
-  size_t group_tiles(size_t gi) const { return group_begin[gi + 1] - group_begin[gi]; }
-  uint64_t group_bytes(size_t gi) const {
-    uint64_t sum = 0;
-    for (size_t t = group_begin[gi]; t < group_begin[gi + 1]; ++t) sum += counts[t];
-    return sum;
-  }
 
   // host only: geometry and groups.  false: a piece could touch more rows than the LDS stage holds
   // (no tile side this writer accepts does).
@@ -281,21 +267,12 @@ struct TiffEncoder {
     s.row_step = 0;
     s.frame_stride = 0;
     pnge::share_set_raw(&s, tiff::tile_raw(kind, tile));
-    T = (size_t)tiff::tile_count(width, height, tile);
-    const size_t cost = layout(1).total;
-    std::vector<size_t> costs(T, cost), at(T);
-    size_t max_group_bytes = 0;
-    plan_groups(costs.data(), T, budget_bytes("tiffe_scratch_budget_mb", 4096.0), kMaxGroupTiles, &group_begin,
-                at.data(), &max_group_bytes);
-    counts.assign(T, 0);
+    plan_uniform((size_t)tiff::tile_count(width, height, tile), layout(1).total, "tiffe_scratch_budget_mb", 4096.0,
+                 kMaxGroupFrames);
     return true;
   }
 
-  int open() {
-    size_t most = 0;
-    for (size_t gi = 0; gi < groups(); ++gi) most = group_tiles(gi) > most ? group_tiles(gi) : most;
-    return scratch.alloc(layout(most).total);
-  }
+  int open() { return scratch.alloc(layout(most_group_frames()).total); }
 
   template <int kKind>
   void launch_tiles(const dim3& grid, const TileSrc& ts, const Bufs& b) {
@@ -305,7 +282,7 @@ struct TiffEncoder {
 
   // every pass of group gi up to the streams and their lengths, which are read back
   int front(size_t gi) {
-    const uint32_t n = (uint32_t)group_tiles(gi);
+    const uint32_t n = (uint32_t)group_frames(gi);
     const Bufs b = bufs(n);
     AMHIP_TRY(hipMemsetAsync(b.z, 0, (size_t)n * (size_t)s.zwords * 4, stream));
     TileSrc ts = src;
@@ -320,19 +297,17 @@ struct TiffEncoder {
     hipLaunchKernelGGL(k_tiff_offsets, dim3(1), dim3(64), 0, stream, b, n);
     AMHIP_TRY(hipGetLastError());
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the lengths are copied as they lie");
-    AMHIP_TRY(hipMemcpyAsync(counts.data() + group_begin[gi], b.sizes, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
+    AMHIP_TRY(hipMemcpyAsync(sizes.data() + group_begin[gi], b.sizes, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
     AMHIP_TRY(hipStreamSynchronize(stream));
     return AMHIP_OK;
   }
 
   // ... and group gi's streams into the file at `file`, from byte `base` on.  front(gi) ran last.
   int back(size_t gi, uint8_t* file, uint64_t base) {
-    const uint32_t n = (uint32_t)group_tiles(gi);
+    const uint32_t n = (uint32_t)group_frames(gi);
     const Bufs b = bufs(n);
-    uint64_t most = 0;
-    for (size_t t = group_begin[gi]; t < group_begin[gi + 1]; ++t) most = counts[t] > most ? counts[t] : most;
     // (a stream of z bytes behind a lead of at most 15 touches at most (z + 15 + 15) / 16 blocks)
-    const unsigned blocks = (unsigned)(((most + 30) / 16 + 255) / 256);
+    const unsigned blocks = (unsigned)(((largest_file(gi) + 30) / 16 + 255) / 256);
     hipLaunchKernelGGL(k_tiff_gather, dim3(blocks, n), dim3(256), 0, stream, s, b, file, (unsigned long long)base);
     AMHIP_TRY(hipGetLastError());
     return AMHIP_OK;
@@ -360,36 +335,30 @@ int tiff_encode(const char* who, hipStream_t stream, const TiffJob& job, uint8_t
     return arg_failure((std::string(who) + ": tile: a piece of the tile would not fit the producer's stage").c_str());
   int rc;
   if ((rc = enc.open())) return rc;
-  const size_t G = enc.groups();
-  // The tile tables stand in front of the tiles, and nothing may be written to a buffer the file does
-  // not fit: so the lengths come first.  With more than one group every group runs up to its
-  // lengths, then again straight into its place, as the PNG stack encoder does.
-  for (size_t gi = 0; gi < G; ++gi)
-    if ((rc = enc.front(gi))) return rc;
-  const tiff::GeoTags geo = tiff::make_geo_tags(job.geotransform, job.utm_zone, job.northern);
+  // The tile tables stand in front of the tiles, so the head is built from the streams' lengths and
+  // copied in before the first stream follows it.
   tiff::Container file;
-  if (!tiff::build_container(job.width, job.height, job.kind, job.tile, geo, enc.counts.data(), enc.T, &file))
-    return arg_failure((std::string(who) + ": the file would exceed 4 GB - 1 (BigTIFF is not written; nothing written)").c_str());
-  if (bytes) *bytes = (size_t)file.file_bytes;
-  uint8_t* out = dev_out;
-  if (dev_out) {
-    if (file.file_bytes > cap) {
-      char msg[200];
-      std::snprintf(msg, sizeof(msg), "%s: the file takes %llu bytes, the buffer holds %llu (nothing written)", who,
-                    (unsigned long long)file.file_bytes, (unsigned long long)cap);
-      return arg_failure(msg);
-    }
-  } else {
-    if ((rc = owned->alloc((size_t)file.file_bytes))) return rc;
-    out = owned->as<uint8_t>();
-  }
-  AMHIP_TRY(hipMemcpyAsync(out, file.head.data(), file.head.size(), hipMemcpyHostToDevice, stream));
-  uint64_t at = file.head.size();
-  for (size_t gi = 0; gi < G; ++gi) {
-    if (G > 1 && (rc = enc.front(gi))) return rc;
-    if ((rc = enc.back(gi, out, at))) return rc;
-    at += enc.group_bytes(gi);
-  }
+  rc = encode_groups(
+      enc, [&](size_t gi) { return enc.front(gi); },
+      [&](uint8_t** to, uint64_t* at) {
+        const tiff::GeoTags geo = tiff::make_geo_tags(job.geotransform, job.utm_zone, job.northern);
+        if (!tiff::build_container(job.width, job.height, job.kind, job.tile, geo, enc.sizes.data(), enc.F, &file))
+          return arg_failure(
+              (std::string(who) + ": the file would exceed 4 GB - 1 (BigTIFF is not written; nothing written)").c_str());
+        if (bytes) *bytes = (size_t)file.file_bytes;
+        *to = dev_out;
+        if (dev_out) {
+          if (file.file_bytes > cap) return capacity_failure(who, file.file_bytes, cap);
+        } else {
+          const int r = owned->alloc((size_t)file.file_bytes);
+          if (r) return r;
+          *to = owned->as<uint8_t>();
+        }
+        AMHIP_TRY(hipMemcpyAsync(*to, file.head.data(), file.head.size(), hipMemcpyHostToDevice, stream));
+        *at = file.head.size();
+        return (int)AMHIP_OK;
+      });
+  if (rc) return rc;
   AMHIP_TRY(hipStreamSynchronize(stream));   // (the scratch and the head go with this call)
   return AMHIP_OK;
 }

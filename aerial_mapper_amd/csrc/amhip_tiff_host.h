@@ -81,12 +81,17 @@ inline uint64_t tile_raw(int kind, int tile) {
 }
 
 // null: fine; else which field is wrong
+inline const char* check_kind(int kind) {
+  return kind != kF32 && kind != kU8 && kind != kRgb8 ? "kind must be 0 (f32), 1 (u8) or 2 (rgb8)" : nullptr;
+}
+inline const char* check_tile(int tile) {
+  return tile_ok(tile) ? nullptr : "tile must be a multiple of 16 in 16..1024, or 0 (256)";
+}
 inline const char* check_raster(int width, int height, int kind, int tile) {
   if (width < 1 || width > 65535) return "width must be 1..65535";
   if (height < 1 || height > 65535) return "height must be 1..65535";
-  if (kind != kF32 && kind != kU8 && kind != kRgb8) return "kind must be 0 (f32), 1 (u8) or 2 (rgb8)";
-  if (!tile_ok(tile)) return "tile must be a multiple of 16 in 16..1024, or 0 (256)";
-  return nullptr;
+  if (const char* why = check_kind(kind)) return why;
+  return check_tile(tile);
 }
 inline const char* check_geo(const double* geotransform, int utm_zone) {
   if (!north_up(geotransform))

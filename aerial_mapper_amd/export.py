@@ -49,12 +49,9 @@ def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch"
 
 
-def encode_jpeg(map_, image, quality=95, cap=None):
-    """amhip_jpeg_encode_dev on the map's context: the baseline JPEG file libjpeg writes for
-    cv::imwrite(name, image) at this quality (colour: 4:2:0), as bytes.  image: (H, W) or (H, W, 3)
-    uint8 in B, G, R -- a numpy array, or a torch device tensor (rows may be padded: stride(0) is
-    the step).  cap: bytes of the device buffer the file is encoded into (default
-    amhip_jpeg_bound); a file that does not fit raises AMHIP_ERR_ARG."""
+def _encode_image(map_, image, cap, bound_symbol, encode_symbol, *extra):
+    """image -> device tensor, the format's bound, one amhip_*_encode_dev call (extra: the format's own
+    arguments, behind channels) -> the file's bytes"""
     import torch
     lib = L.load()
     if not _is_torch(image):
@@ -63,31 +60,44 @@ def encode_jpeg(map_, image, quality=95, cap=None):
     ch = 1 if image.dim() == 2 else int(image.shape[2])
     assert image.stride(-1) == 1 and (image.dim() == 2 or image.stride(1) == ch)
     h, w = int(image.shape[0]), int(image.shape[1])
-    bound = lib.amhip_jpeg_bound(w, h, ch)
+    bound = getattr(lib, bound_symbol)(w, h, ch)
     out = torch.empty(max(int(bound if cap is None else cap), 1), dtype=torch.uint8, device=image.device)
     map_.wait_for_torch(image)
     n = C.c_size_t()
-    L.check(lib.amhip_jpeg_encode_dev(map_._h, C.c_void_p(image.data_ptr()), int(image.stride(0)), w, h,
-                                      ch, int(quality), C.c_void_p(out.data_ptr()),
-                                      int(out.numel() if cap is None else cap), C.byref(n)))
+    L.check(getattr(lib, encode_symbol)(map_._h, C.c_void_p(image.data_ptr()), int(image.stride(0)), w, h, ch,
+                                        *(extra + (C.c_void_p(out.data_ptr()),
+                                                   int(out.numel() if cap is None else cap), C.byref(n)))))
     return out[:n.value].cpu().numpy().tobytes()
 
 
-def write_jpeg(map_, filename, image, quality=95):
-    """amhip_jpeg_write: encode on the map's device, download, write `filename`."""
-    lib = L.load()
+def _write_image(map_, filename, image, symbol, *extra):
+    """one amhip_*_write call from a torch device tensor or a numpy array (extra: behind channels)"""
+    fn = getattr(L.load(), symbol)
     if _is_torch(image):
         assert image.is_cuda and image.element_size() == 1 and image.stride(-1) == 1
         ch = 1 if image.dim() == 2 else int(image.shape[2])
         map_.wait_for_torch(image)
-        L.check(lib.amhip_jpeg_write(map_._h, str(filename).encode(), C.c_void_p(image.data_ptr()), 1,
-                                     int(image.stride(0)), int(image.shape[1]), int(image.shape[0]), ch,
-                                     int(quality)))
+        L.check(fn(map_._h, str(filename).encode(), C.c_void_p(image.data_ptr()), 1, int(image.stride(0)),
+                   int(image.shape[1]), int(image.shape[0]), ch, *extra))
         return
     image = np.ascontiguousarray(image, np.uint8)
     ch = 1 if image.ndim == 2 else image.shape[2]
-    L.check(lib.amhip_jpeg_write(map_._h, str(filename).encode(), C.c_void_p(image.ctypes.data), 0,
-                                 image.strides[0], image.shape[1], image.shape[0], ch, int(quality)))
+    L.check(fn(map_._h, str(filename).encode(), C.c_void_p(image.ctypes.data), 0, image.strides[0],
+               image.shape[1], image.shape[0], ch, *extra))
+
+
+def encode_jpeg(map_, image, quality=95, cap=None):
+    """amhip_jpeg_encode_dev on the map's context: the baseline JPEG file libjpeg writes for
+    cv::imwrite(name, image) at this quality (colour: 4:2:0), as bytes.  image: (H, W) or (H, W, 3)
+    uint8 in B, G, R -- a numpy array, or a torch device tensor (rows may be padded: stride(0) is
+    the step).  cap: bytes of the device buffer the file is encoded into (default
+    amhip_jpeg_bound); a file that does not fit raises AMHIP_ERR_ARG."""
+    return _encode_image(map_, image, cap, "amhip_jpeg_bound", "amhip_jpeg_encode_dev", int(quality))
+
+
+def write_jpeg(map_, filename, image, quality=95):
+    """amhip_jpeg_write: encode on the map's device, download, write `filename`."""
+    _write_image(map_, filename, image, "amhip_jpeg_write", int(quality))
 
 
 def layer_to_jpeg(map_, layer, filename, lower=0.0, upper=255.0, bgr=False, quality=95):
@@ -108,38 +118,12 @@ def encode_png(map_, image, cap=None):
     """amhip_png_encode_dev on the map's context: the PNG file cv::imwrite(name, image) writes for a
     name that ends in .png (filter Sub, zlib level 1 with Z_RLE), as bytes.  image and cap: as
     encode_jpeg's (cap defaults to amhip_png_bound)."""
-    import torch
-    lib = L.load()
-    if not _is_torch(image):
-        image = torch.from_numpy(np.ascontiguousarray(image, np.uint8)).to("cuda:%d" % map_.device)
-    assert image.is_cuda and image.dtype == torch.uint8 and image.dim() in (2, 3)
-    ch = 1 if image.dim() == 2 else int(image.shape[2])
-    assert image.stride(-1) == 1 and (image.dim() == 2 or image.stride(1) == ch)
-    h, w = int(image.shape[0]), int(image.shape[1])
-    bound = lib.amhip_png_bound(w, h, ch)
-    out = torch.empty(max(int(bound if cap is None else cap), 1), dtype=torch.uint8, device=image.device)
-    map_.wait_for_torch(image)
-    n = C.c_size_t()
-    L.check(lib.amhip_png_encode_dev(map_._h, C.c_void_p(image.data_ptr()), int(image.stride(0)), w, h, ch,
-                                     C.c_void_p(out.data_ptr()), int(out.numel() if cap is None else cap),
-                                     C.byref(n)))
-    return out[:n.value].cpu().numpy().tobytes()
+    return _encode_image(map_, image, cap, "amhip_png_bound", "amhip_png_encode_dev")
 
 
 def write_png(map_, filename, image):
     """amhip_png_write: encode on the map's device, download, write `filename`."""
-    lib = L.load()
-    if _is_torch(image):
-        assert image.is_cuda and image.element_size() == 1 and image.stride(-1) == 1
-        ch = 1 if image.dim() == 2 else int(image.shape[2])
-        map_.wait_for_torch(image)
-        L.check(lib.amhip_png_write(map_._h, str(filename).encode(), C.c_void_p(image.data_ptr()), 1,
-                                    int(image.stride(0)), int(image.shape[1]), int(image.shape[0]), ch))
-        return
-    image = np.ascontiguousarray(image, np.uint8)
-    ch = 1 if image.ndim == 2 else image.shape[2]
-    L.check(lib.amhip_png_write(map_._h, str(filename).encode(), C.c_void_p(image.ctypes.data), 0,
-                                image.strides[0], image.shape[1], image.shape[0], ch))
+    _write_image(map_, filename, image, "amhip_png_write")
 
 
 def layer_to_png(map_, layer, filename, lower=0.0, upper=255.0, bgr=False):

@@ -336,17 +336,14 @@ def _frames_arg(frames, device, to_device):
     return frames.data_ptr(), 1, n, w, h, ch, row_step, frame_stride, frames
 
 
-def encode_jpeg_frames(frames, quality=95, device=0):
-    """amhip_io_encode_jpeg_frames: every frame of a stack as the baseline JPEG file libjpeg writes at
-    `quality` (8UC1 as one component, 8UC3 B, G, R as Y Cb Cr 4:2:0), all in one batched encode on the
-    GPU -> list of bytes, file f what export.encode_jpeg gives for frame f.  frames: a DeviceFrames, a
-    CUDA uint8 tensor (F, H, W) or (F, H, W, 3) whose rows and frames may be padded, or a numpy array."""
+def _encode_frames(symbol, frames, device, *extra):
+    """one amhip_io_encode_*_frames call (extra: the format's own arguments, behind frame_stride) -> the
+    files, downloaded"""
     lib = L.load()
     ptr, _, n, w, h, ch, row, stride, keep = _frames_arg(frames, int(device), True)
     out = C.c_void_p()
     offsets = (C.c_size_t * (n + 1))()
-    L.check(lib.amhip_io_encode_jpeg_frames(int(device), C.c_void_p(ptr), n, w, h, ch, row, stride, int(quality),
-                                            C.byref(out), offsets))
+    L.check(getattr(lib, symbol)(int(device), C.c_void_p(ptr), n, w, h, ch, row, stride, *(extra + (C.byref(out), offsets))))
     del keep
     try:
         host = np.empty(offsets[n], np.uint8)
@@ -356,51 +353,43 @@ def encode_jpeg_frames(frames, quality=95, device=0):
     return [host[offsets[f]:offsets[f + 1]].tobytes() for f in range(n)]
 
 
-def write_jpeg_frames(frames, filenames, quality=95, device=0):
-    """amhip_io_write_jpeg_frames: the files of encode_jpeg_frames, written: frame f to filenames[f].  A
-    file that cannot be written raises and names it; the files before it stay, none behind it is written."""
+def _write_frames(symbol, who, frames, filenames, device, *extra):
+    """one amhip_io_write_*_frames call; who: the public function's name, for the refusal"""
     lib = L.load()
     ptr, on_device, n, w, h, ch, row, stride, keep = _frames_arg(frames, int(device), False)
     filenames = [os.fsencode(f) for f in filenames]
     if len(filenames) != n:
-        _refuse("write_jpeg_frames: %d frames, %d filenames" % (n, len(filenames)))
+        _refuse("%s: %d frames, %d filenames" % (who, n, len(filenames)))
     names = (C.c_char_p * max(n, 1))(*filenames)
-    L.check(lib.amhip_io_write_jpeg_frames(int(device), C.c_void_p(ptr), on_device, n, w, h, ch, row, stride,
-                                           int(quality), names))
+    L.check(getattr(lib, symbol)(int(device), C.c_void_p(ptr), on_device, n, w, h, ch, row, stride, *(extra + (names,))))
     del keep
+
+
+def encode_jpeg_frames(frames, quality=95, device=0):
+    """amhip_io_encode_jpeg_frames: every frame of a stack as the baseline JPEG file libjpeg writes at
+    `quality` (8UC1 as one component, 8UC3 B, G, R as Y Cb Cr 4:2:0), all in one batched encode on the
+    GPU -> list of bytes, file f what export.encode_jpeg gives for frame f.  frames: a DeviceFrames, a
+    CUDA uint8 tensor (F, H, W) or (F, H, W, 3) whose rows and frames may be padded, or a numpy array."""
+    return _encode_frames("amhip_io_encode_jpeg_frames", frames, device, int(quality))
+
+
+def write_jpeg_frames(frames, filenames, quality=95, device=0):
+    """amhip_io_write_jpeg_frames: the files of encode_jpeg_frames, written: frame f to filenames[f].  A
+    file that cannot be written raises and names it; the files before it stay, none behind it is written."""
+    _write_frames("amhip_io_write_jpeg_frames", "write_jpeg_frames", frames, filenames, device, int(quality))
 
 
 def encode_png_frames(frames, device=0):
     """amhip_io_encode_png_frames: every frame of a stack as the PNG file cv::imwrite writes (filter Sub,
     zlib level 1 with Z_RLE; 8UC3 B, G, R stored R, G, B), all in one batched encode on the GPU -> list of
     bytes, file f what export.encode_png gives for frame f.  frames: as encode_jpeg_frames."""
-    lib = L.load()
-    ptr, _, n, w, h, ch, row, stride, keep = _frames_arg(frames, int(device), True)
-    out = C.c_void_p()
-    offsets = (C.c_size_t * (n + 1))()
-    L.check(lib.amhip_io_encode_png_frames(int(device), C.c_void_p(ptr), n, w, h, ch, row, stride,
-                                           C.byref(out), offsets))
-    del keep
-    try:
-        host = np.empty(offsets[n], np.uint8)
-        L.check(lib.amhip_io_download_frames(out, host.size, C.c_void_p(host.ctypes.data)))
-    finally:
-        lib.amhip_io_free(out)
-    return [host[offsets[f]:offsets[f + 1]].tobytes() for f in range(n)]
+    return _encode_frames("amhip_io_encode_png_frames", frames, device)
 
 
 def write_png_frames(frames, filenames, device=0):
     """amhip_io_write_png_frames: the files of encode_png_frames, written: frame f to filenames[f].  A
     file that cannot be written raises and names it; the files before it stay, none behind it is written."""
-    lib = L.load()
-    ptr, on_device, n, w, h, ch, row, stride, keep = _frames_arg(frames, int(device), False)
-    filenames = [os.fsencode(f) for f in filenames]
-    if len(filenames) != n:
-        _refuse("write_png_frames: %d frames, %d filenames" % (n, len(filenames)))
-    names = (C.c_char_p * max(n, 1))(*filenames)
-    L.check(lib.amhip_io_write_png_frames(int(device), C.c_void_p(ptr), on_device, n, w, h, ch, row, stride,
-                                          names))
-    del keep
+    _write_frames("amhip_io_write_png_frames", "write_png_frames", frames, filenames, device)
 
 
 def _leading_numbers(filename, per_record):

@@ -1,5 +1,6 @@
-"""The group planner of the image decoders (amhip_frame_plan.h: which frames of a call share one
-scratch buffer) as a stand-alone program (tests/cpp/frame_stack_host_main.cc) under the address and
+"""The group planner of the image decoders and encoders (amhip_frame_plan.h: which frames of a call share
+one scratch buffer), the cut of a group's files into download slices and the files' offsets, as a
+stand-alone program (tests/cpp/frame_stack_host_main.cc) under the address and
 undefined-behaviour sanitizers, compared with a restatement of the rule.  No GPU, nothing loaded into
 python.  The decoders' count cap (32768 frames per group) is reached by no GPU test: here the cap is
 a parameter."""
@@ -112,3 +113,85 @@ def test_seeded_random_cases_equal_the_rule(exe):
     # both reasons for a new group, and groups of several frames, occur
     assert any(len(g[0]) == 2 for g in got) and any(len(g[0]) > 4 for g in got)
     assert any(max(b - a for a, b in zip(g[0], g[0][1:])) == c[2] for c, g in zip(cases, got))
+
+
+# ---- the writers' download slices and the encoders' offsets ------------------------------------------
+LIMIT = 1000
+
+
+def _run_slices(exe, cases):
+    """cases: (sizes, limit) -> per case (ends, bytes, offsets)"""
+    args = ["%d:%s" % (limit, ",".join(str(c) for c in sizes)) for sizes, limit in cases]
+    r = subprocess.run([exe, "slices"] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       universal_newlines=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-500:], r.stderr[-2000:])
+    lines = r.stdout.strip().split("\n")
+    assert len(lines) == 3 * len(cases)
+    out = []
+    for k in range(len(cases)):
+        e, b, o = (line.split() for line in lines[3 * k:3 * k + 3])
+        assert (e[0], b[0], o[0]) == ("ends", "bytes", "offsets")
+        out.append(([int(x) for x in e[1:]], [int(x) for x in b[1:]], [int(x) for x in o[1:]]))
+    return out
+
+
+def _slice_rule(sizes, limit):
+    """A slice starts at a file and takes the following files while the sum stays <= limit; offsets are
+    the exclusive prefix sums."""
+    ends, sums, f = [], [], 0
+    while f < len(sizes):
+        total, end = sizes[f], f + 1
+        while end < len(sizes) and total + sizes[end] <= limit:
+            total += sizes[end]
+            end += 1
+        ends.append(end)
+        sums.append(total)
+        f = end
+    return ends, sums, [sum(sizes[:i]) for i in range(len(sizes) + 1)]
+
+
+def _slice_properties(case, got):
+    sizes, limit = case
+    ends, sums, offsets = got
+    # contiguous, every file in exactly one slice, none empty
+    starts = [0] + ends[:-1]
+    assert ends[-1] == len(sizes) and all(a < b for a, b in zip(starts, ends)), (case, got)
+    for a, b, total in zip(starts, ends, sums):
+        assert total == sum(sizes[a:b]), (case, got)
+        assert total <= limit or b - a == 1, (case, got)
+    assert offsets == [sum(sizes[:i]) for i in range(len(sizes) + 1)], (case, got)
+
+
+# (what, sizes, ends, bytes)
+NAMED_SLICES = [
+    ("one file exactly at the limit", [LIMIT], [1], [LIMIT]),
+    ("one file over the limit, alone", [LIMIT + 1], [1], [LIMIT + 1]),
+    ("[1, limit]: the second file does not fit behind the first", [1, LIMIT], [1, 2], [1, LIMIT]),
+    ("[limit/2, limit/2, 1]: two fill the slice exactly", [LIMIT // 2, LIMIT // 2, 1], [2, 3], [LIMIT, 1]),
+    ("a zero-length file rides along", [LIMIT, 0, 5], [2, 3], [LIMIT, 5]),
+    ("a zero-length file first and alone", [0], [1], [0]),
+    ("an oversized file in the middle", [3, 5 * LIMIT, 4], [1, 2, 3], [3, 5 * LIMIT, 4]),
+]
+
+
+def test_named_slice_cases(exe):
+    cases = [(s, LIMIT) for _, s, _, _ in NAMED_SLICES]
+    for (what, sizes, ends, sums), got in zip(NAMED_SLICES, _run_slices(exe, cases)):
+        assert got[:2] == (ends, sums), what
+        assert got == _slice_rule(sizes, LIMIT), what
+        _slice_properties((sizes, LIMIT), got)
+
+
+def test_seeded_random_slice_cases_equal_the_rule(exe):
+    rng = random.Random(20261020)
+    cases = []
+    for _ in range(200):
+        F = rng.randint(1, 14)
+        cases.append(([rng.choice([0, 1, LIMIT // 2, LIMIT, LIMIT + 1, rng.randint(0, 1500)]) for _ in range(F)], LIMIT))
+    got = _run_slices(exe, cases)
+    for case, g in zip(cases, got):
+        assert g == _slice_rule(*case), case
+        _slice_properties(case, g)
+    # slices of one oversized file and slices of several files both occur
+    assert any(b > LIMIT for g in got for b in g[1])
+    assert any(e - s > 2 for g in got for s, e in zip([0] + g[0][:-1], g[0]))

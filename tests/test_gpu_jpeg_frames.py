@@ -198,18 +198,24 @@ def _frame_cost(w, h, ch):
     return nb * 132 + pack + 8 * (-(-nb // 256) + pack // 4096) + 32 + 8
 
 
-@pytest.mark.parametrize("budget_mb,groups", [(0.125, "2, 2, 1"), (0.01, "1 each"), (0.0, "1 each")])
-def test_groups_of_frames_equal_one_group(budget_mb, groups, tuning, tmp_path):
+# (the device cases keep the ids they had before the writer's source became a parameter)
+@pytest.mark.parametrize("budget_mb,groups,source", [
+    pytest.param(b, g, s, id="%s-%s%s" % (b, g, "" if s == "device" else "-host"))
+    for s in ("device", "host") for b, g in [(0.125, "2, 2, 1"), (0.01, "1 each"), (0.0, "1 each")]])
+def test_groups_of_frames_equal_one_group(budget_mb, groups, source, tuning, tmp_path):
+    """source "host": the writer uploads the host stack group by group, group_span bytes from each
+    group's first frame"""
     cost = _frame_cost(129, 47, 3)
     budget = int(budget_mb * 1048576)
     assert (2 * cost <= budget < 3 * cost) if groups == "2, 2, 1" else budget < cost
     cases = [I.Case(c, 129, 47, 3) for c in ("noise", "stuffed", "zero", "checker", "ramp")]
-    dev = padded_device(stack_of(cases))
+    stack = stack_of(cases)
+    dev = padded_device(stack)
     whole, whole_offsets = _raw_encode(dev, 100)
     names = [str(tmp_path / ("g_%d.jpg" % f)) for f in range(5)]
     tuning(jpege_scratch_budget_mb=budget_mb)
     got, offsets = _raw_encode(dev, 100)
-    _io().write_jpeg_frames(dev, names, 100)
+    _io().write_jpeg_frames(dev if source == "device" else stack, names, 100)
     tuning(jpege_scratch_budget_mb=None)
     assert offsets == whole_offsets and got == whole
     ref = [want(c, 100) for c in cases]

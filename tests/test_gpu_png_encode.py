@@ -134,18 +134,24 @@ def _frame_cost(w, h, ch):
     return sum(-(-p // 256) * 256 for p in parts)
 
 
-@pytest.mark.parametrize("budget_mb,groups", [(0.15, "2, 2, 1"), (0.01, "1 each")])
-def test_groups_of_frames_equal_one_group(budget_mb, groups, tuning, tmp_path):
+# (the device cases keep the ids they had before the writer's source became a parameter)
+@pytest.mark.parametrize("budget_mb,groups,source", [
+    pytest.param(b, g, s, id="%s-%s%s" % (b, g, "" if s == "device" else "-host"))
+    for s in ("device", "host") for b, g in [(0.15, "2, 2, 1"), (0.01, "1 each")]])
+def test_groups_of_frames_equal_one_group(budget_mb, groups, source, tuning, tmp_path):
+    """source "host": the writer uploads the host stack group by group, group_span bytes from each
+    group's first frame"""
     frames = [f for f in I.random_frames(20) if f.ndim == 3][:5]
     cost = _frame_cost(83, 61, 3)
     budget = int(budget_mb * 1048576)
     assert (2 * cost <= budget < 3 * cost) if groups == "2, 2, 1" else budget < cost, (cost, budget)
-    dev = padded_device(np.stack(frames))
+    stack = np.stack(frames)
+    dev = padded_device(stack)
     whole = _io().encode_png_frames(dev)
     names = [str(tmp_path / ("g_%d.png" % f)) for f in range(5)]
     tuning(pnge_scratch_budget_mb=budget_mb)
     got = _io().encode_png_frames(dev)
-    _io().write_png_frames(dev, names)
+    _io().write_png_frames(dev if source == "device" else stack, names)
     tuning(pnge_scratch_budget_mb=None)
     ref = [want(f) for f in frames]
     assert got == whole == ref
