@@ -16,7 +16,7 @@ from .export import encode_jpeg, write_jpeg, layer_to_jpeg, session_layer_to_jpe
 from .export import encode_png, write_png, layer_to_png, session_layer_to_png  # noqa: F401
 from .export import (encode_geotiff, write_geotiff_deflate, layer_to_geotiff, encode_layer_geotiff,  # noqa: F401
                      session_layer_to_geotiff)
-from .io import geotiff_info, decode_geotiff, layer_from_geotiff, session_layer_from_geotiff  # noqa: F401
+from .io import geotiff_info, geotiff_levels, decode_geotiff, layer_from_geotiff, session_layer_from_geotiff  # noqa: F401
 
 __all__ = ["AerialGridMap", "GridMapSettings", "HostSession", "Dsm", "DsmSettings", "OrthoBackwardGrid",
            "OrthoSettings", "OrthoForwardHomography", "OrthoForwardHomographySettings", "OrthoFromPcl", "OrthoFromPclSettings", "NCamera", "compose_T_G_C", "densify", "rectify_stereo_pair", "SgbmParameters", "compute_disparity_sgbm", "BmParameters", "BlockMatchingParameters", "compute_disparity_bm", "dense_cloud_from_stereo_pair", "Stereo", "StereoSettings", "AmhipError", "Camera", "GridDesc",
@@ -24,6 +24,6 @@ __all__ = ["AerialGridMap", "GridMapSettings", "HostSession", "Dsm", "DsmSetting
            "encode_png", "write_png", "layer_to_png", "session_layer_to_png",
            "encode_geotiff", "write_geotiff_deflate", "layer_to_geotiff", "encode_layer_geotiff",
            "session_layer_to_geotiff",
-           "geotiff_info", "decode_geotiff", "layer_from_geotiff", "session_layer_from_geotiff",
+           "geotiff_info", "geotiff_levels", "decode_geotiff", "layer_from_geotiff", "session_layer_from_geotiff",
            "LAYER_NAMES", "DIST_NONE", "DIST_RADTAN",
            "DIST_EQUIDISTANT"]

@@ -444,6 +444,11 @@ void AerialMapperIO::writeDataToDEMGeoTiffColor(const cv::Mat& ortho_image,
 // made for this call knows nothing of it yet), then the whole map is written from them.
 void AerialMapperIO::writeLayerToGeoTiff(const grid_map::GridMap& map, const std::string& layer,
                                          const std::string& filename, int utm_zone, bool northern) {
+  writeLayerToGeoTiff(map, layer, filename, utm_zone, northern, 0);
+}
+
+void AerialMapperIO::writeLayerToGeoTiff(const grid_map::GridMap& map, const std::string& layer,
+                                         const std::string& filename, int utm_zone, bool northern, int overviews) {
   static const char* const kLayers[AMHIP_NUM_LAYERS] = {"ortho", "elevation", "elevation_angle", "num_observations",
                                                         "observation_index", "colored_ortho"};
   int id = -1;
@@ -465,9 +470,12 @@ void AerialMapperIO::writeLayerToGeoTiff(const grid_map::GridMap& map, const std
     amhip_shim::check_status(amhip_layer_upload(amhip_session_context(session, k), id, block.data()),
                              "writeLayerToGeoTiff");
   }
-  const int status = amhip_session_layer_write_geotiff(
-      session, id, id == AMHIP_LAYER_COLORED_ORTHO ? AMHIP_GEOTIFF_RGB8 : AMHIP_GEOTIFF_F32, 0.0f, 255.0f, 0,
-      utm_zone, northern ? 1 : 0, filename.c_str());
+  const int kind = id == AMHIP_LAYER_COLORED_ORTHO ? AMHIP_GEOTIFF_RGB8 : AMHIP_GEOTIFF_F32;
+  const int status =
+      overviews == 0 ? amhip_session_layer_write_geotiff(session, id, kind, 0.0f, 255.0f, 0, utm_zone, northern ? 1 : 0,
+                                                         filename.c_str())
+                     : amhip_session_layer_write_geotiff_ovr(session, id, kind, 0.0f, 255.0f, 0, overviews, utm_zone,
+                                                             northern ? 1 : 0, filename.c_str());
   amhip_shim::release_session(session);
   amhip_shim::check_status(status, "writeLayerToGeoTiff");
 }
@@ -476,6 +484,11 @@ void AerialMapperIO::writeLayerToGeoTiff(const grid_map::GridMap& map, const std
 // file does not reach keep it), places the file's pixels on the GPU and hands the matrix back.
 void AerialMapperIO::loadLayerFromGeoTiff(grid_map::GridMap* map, const std::string& layer,
                                           const std::string& filename) {
+  loadLayerFromGeoTiff(map, layer, filename, 0);
+}
+
+void AerialMapperIO::loadLayerFromGeoTiff(grid_map::GridMap* map, const std::string& layer,
+                                          const std::string& filename, int level) {
   static const char* const kLayers[AMHIP_NUM_LAYERS] = {"ortho", "elevation", "elevation_angle", "num_observations",
                                                         "observation_index", "colored_ortho"};
   int id = -1;
@@ -485,7 +498,8 @@ void AerialMapperIO::loadLayerFromGeoTiff(grid_map::GridMap* map, const std::str
     amhip_shim::fatal("loadLayerFromGeoTiff", ("no layer '" + layer + "' the GPU path holds").c_str());
   grid_map::Matrix& m = (*map)[layer];
   amhip_session* session = amhip_shim::acquire_session(*map, nullptr, "loadLayerFromGeoTiff");
-  const int status = amhip_session_layer_read_geotiff(session, id, filename.c_str(), m.data());
+  const int status = level == 0 ? amhip_session_layer_read_geotiff(session, id, filename.c_str(), m.data())
+                                : amhip_session_layer_read_geotiff_level(session, id, filename.c_str(), level, m.data());
   amhip_shim::release_session(session);
   amhip_shim::check_status(status, "loadLayerFromGeoTiff");
 }

@@ -238,9 +238,13 @@ int layer_image_source(amhip_ctx* h, const char* limit, int layer, int bgr, floa
 // first on every window before the second on any: prepare parses the file and decodes the pixels under
 // the context's window into a raster of its own (no layer is touched; an error leaves nothing behind),
 // place writes the layer.  The job is freed by the caller, after either.
+// level: which level of the file: k >= 0, -1 the automatic choice for the map's
+// resolution, kTiffFirstIfd the exports without the argument (IFD 0, the chain not looked at).
 struct TiffLayerJob;
 struct Ctx;
-int tiff_layer_prepare(Ctx* c, const char* who, int layer, const uint8_t* file, size_t len, TiffLayerJob** job);
+constexpr int kTiffFirstIfd = -2;
+int tiff_layer_prepare(Ctx* c, const char* who, int layer, const uint8_t* file, size_t len, int level,
+                       TiffLayerJob** job);
 int tiff_layer_place(Ctx* c, TiffLayerJob* job);
 void tiff_layer_job_free(TiffLayerJob* job);
 // the whole of `filename`; a failure is AMHIP_ERR_ARG with `what`, the name and errno's text

@@ -1241,9 +1241,9 @@ int amhip_session_layer_write_png(amhip_session* h, int layer, int bgr, float lo
 /* amhip_layer_write_geotiff for the whole map of a session: the north-up raster
  * assembled on the host from every window -- the floats themselves for kind 0, the image of
  * amhip_session_layer_to_image for kinds 1 and 2 -- and encoded on the first window's device. */
-int amhip_session_layer_write_geotiff(amhip_session* h, int layer, int kind, float lower, float upper, int tile,
-                                      int utm_zone, int northern, const char* filename) {
-  static const char kWho[] = "amhip_session_layer_write_geotiff: ";
+static int session_layer_write_geotiff(const std::string& kWho, amhip_session* h, int layer, int kind, float lower,
+                                       float upper, int tile, int overviews, bool ovr, int utm_zone, int northern,
+                                       const char* filename) {
   if (!h || !filename) return arg_failure((std::string(kWho) + "null argument").c_str());
   if (layer < 0 || layer >= AMHIP_NUM_LAYERS) return arg_failure((std::string(kWho) + "layer: no such layer").c_str());
   Session& s = h->impl;
@@ -1255,6 +1255,9 @@ int amhip_session_layer_write_geotiff(amhip_session* h, int layer, int kind, flo
   if (const char* why = tiff::check_tile(tile)) return arg_failure((std::string(kWho) + why).c_str());
   if (utm_zone < 1 || utm_zone > 60) return arg_failure((std::string(kWho) + "utm_zone must be 1..60").c_str());
   if (kind == 1 && !(upper > lower)) return arg_failure((std::string(kWho) + "upper <= lower").c_str());
+  int novr = 0;
+  if (const char* why = tiff::check_overviews((int)rows, (int)cols, tile, overviews, &novr))
+    return arg_failure((std::string(kWho) + why).c_str());
   const amhip_grid_desc& g = s.grid;
   const double gt[6] = {g.pos_x - g.length_x / 2, g.resolution, 0.0, g.pos_y + g.length_y / 2, 0.0, -g.resolution};
   // raster pixel (r, c) is cell (i, j) = (rows - 1 - c, r): width = rows, height = cols
@@ -1293,8 +1296,24 @@ int amhip_session_layer_write_geotiff(amhip_session* h, int layer, int kind, flo
         }
       }
   }
+  if (ovr)
+    return amhip_geotiff_write_ovr(s.ctx[0], filename, raster.data(), /*on_device=*/0, rows * px, (int)rows, (int)cols,
+                                   kind, tile, overviews, gt, utm_zone, northern);
   return amhip_geotiff_write(s.ctx[0], filename, raster.data(), /*on_device=*/0, rows * px, (int)rows, (int)cols, kind,
                              tile, gt, utm_zone, northern);
+}
+
+int amhip_session_layer_write_geotiff(amhip_session* h, int layer, int kind, float lower, float upper, int tile,
+                                      int utm_zone, int northern, const char* filename) {
+  return session_layer_write_geotiff("amhip_session_layer_write_geotiff: ", h, layer, kind, lower, upper, tile, 0, false,
+                                     utm_zone, northern, filename);
+}
+
+/* ... with `overviews` levels behind level 0: the single context's pyramid of the whole map */
+int amhip_session_layer_write_geotiff_ovr(amhip_session* h, int layer, int kind, float lower, float upper, int tile,
+                                          int overviews, int utm_zone, int northern, const char* filename) {
+  return session_layer_write_geotiff("amhip_session_layer_write_geotiff_ovr: ", h, layer, kind, lower, upper, tile,
+                                     overviews, true, utm_zone, northern, filename);
 }
 
 /* amhip_layer_read_geotiff for every window of a session, then the layer into the GridMap's host
@@ -1302,8 +1321,8 @@ int amhip_session_layer_write_geotiff(amhip_session* h, int layer, int kind, flo
  * (tiff_layer_prepare: no layer, no matrix touched), and only when all of them have succeeded does
  * any of them take the host matrix in (sync_in, as a DSM call does), place the pixels and hand the
  * result back (sync_out), which leaves the content sums agreeing with the matrix. */
-int amhip_session_layer_read_geotiff(amhip_session* h, int layer, const char* filename, float* matrix) {
-  static const char kWho[] = "amhip_session_layer_read_geotiff";
+static int session_layer_read_geotiff(const char* kWho, amhip_session* h, int layer, const char* filename, int level,
+                                      float* matrix) {
   if (!h || !filename || !matrix) return arg_failure((std::string(kWho) + ": null argument").c_str());
   if (layer < 0 || layer >= AMHIP_NUM_LAYERS) return arg_failure((std::string(kWho) + ": layer: no such layer").c_str());
   Session& s = h->impl;
@@ -1312,7 +1331,7 @@ int amhip_session_layer_read_geotiff(amhip_session* h, int layer, const char* fi
   if (rc) return rc;
   std::vector<TiffLayerJob*> jobs(s.W(), nullptr);
   rc = for_windows(s, [&](int k) -> int {
-    return tiff_layer_prepare(&s.ctx[k]->impl, kWho, layer, file.data(), file.size(), &jobs[k]);
+    return tiff_layer_prepare(&s.ctx[k]->impl, kWho, layer, file.data(), file.size(), level, &jobs[k]);
   });
   if (rc == AMHIP_OK) {
     std::vector<Hash128> hh;
@@ -1334,6 +1353,20 @@ int amhip_session_layer_read_geotiff(amhip_session* h, int layer, const char* fi
   }
   for (TiffLayerJob* j : jobs) tiff_layer_job_free(j);
   return rc;
+}
+
+int amhip_session_layer_read_geotiff(amhip_session* h, int layer, const char* filename, float* matrix) {
+  return session_layer_read_geotiff("amhip_session_layer_read_geotiff", h, layer, filename, kTiffFirstIfd, matrix);
+}
+
+/* ... from level `level` of the file; -1: every window takes the automatic choice, which
+ * depends on the map's resolution only and so is the same level for all of them */
+int amhip_session_layer_read_geotiff_level(amhip_session* h, int layer, const char* filename, int level,
+                                           float* matrix) {
+  static const char kWho[] = "amhip_session_layer_read_geotiff_level";
+  if (level < -1)
+    return arg_failure((std::string(kWho) + ": level: -1 (automatic) or a level of the file, 0 ..").c_str());
+  return session_layer_read_geotiff(kWho, h, layer, filename, level, matrix);
 }
 
 }  // extern "C"

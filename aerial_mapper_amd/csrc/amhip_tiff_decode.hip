@@ -228,8 +228,9 @@ int bad(const char* who, const std::string& why) { return arg_failure((std::stri
 // The pixel window (x0, y0, w, h) of a parsed file -> out (rows `step` bytes apart), asynchronous on
 // `stream` up to the read-back of the statuses.  The window lies inside the raster; out and step are
 // multiples of the sample's size.  All scratch lives for the call.
-int decode_window(const char* who, hipStream_t stream, const uint8_t* file, const Parsed& P, int x0, int y0, int w,
-                  int h, uint8_t* out, size_t step) {
+// `where`: what stands in front of a chunk's name in an error text ("level 2: " or nothing).
+int decode_window(const char* who, const std::string& where, hipStream_t stream, const uint8_t* file, const Parsed& P,
+                  int x0, int y0, int w, int h, uint8_t* out, size_t step) {
   // ---- host: the chunks the window meets, their streams packed at multiples of 16 -------------
   const uint32_t cw = P.chunk_w, chh = P.chunk_h;
   const uint32_t tx_lo = P.tiled ? (uint32_t)x0 / cw : 0u, tx_hi = P.tiled ? (uint32_t)(x0 + w - 1) / cw : 0u;
@@ -320,7 +321,7 @@ int decode_window(const char* who, hipStream_t stream, const uint8_t* file, cons
     if (st[k]) {
       char name[96];
       tiffd::chunk_name(P, sel[k], name, sizeof(name));
-      return bad(who, std::string(name) + ": inflate status " + std::to_string(st[k]) + ", " + pngd::status_text(st[k]));
+      return bad(who, where + name + ": inflate status " + std::to_string(st[k]) + ", " + pngd::status_text(st[k]));
     }
   return AMHIP_OK;
 }
@@ -332,6 +333,35 @@ bool parse_or_text(const char* who, const uint8_t* file, size_t len, Parsed* P) 
     return false;
   }
   return true;
+}
+
+bool level_or_text(const char* who, const uint8_t* file, size_t len, int level, Parsed* P, int* nlevels = nullptr) {
+  char text[320];
+  if (!tiffd::parse_level(file, len, level, P, nlevels, text, sizeof(text))) {
+    bad(who, text);
+    return false;
+  }
+  return true;
+}
+
+void fill_desc(const Parsed& P, amhip_geotiff_desc* desc) {
+  std::memset(desc, 0, sizeof(*desc));
+  desc->width = P.width;
+  desc->height = P.height;
+  desc->bands = P.bands;
+  desc->kind = P.kind;
+  desc->tiled = P.tiled;
+  desc->tile_width = P.tiled ? (int32_t)P.chunk_w : 0;
+  desc->tile_height = P.tiled ? (int32_t)P.chunk_h : 0;
+  desc->rows_per_strip = P.tiled ? 0 : (int32_t)P.chunk_h;
+  desc->compression = P.compression;
+  desc->predictor = P.predictor;
+  desc->has_geo = P.has_geo;
+  desc->epsg = P.epsg;
+  desc->raster_type = P.raster_type;
+  desc->has_nodata = P.has_nodata;
+  for (int k = 0; k < 6; ++k) desc->geotransform[k] = P.gt[k];
+  desc->nodata = P.nodata;
 }
 
 }  // namespace
@@ -348,7 +378,8 @@ struct TiffLayerJob {
 
 void tiff_layer_job_free(TiffLayerJob* job) { delete job; }
 
-int tiff_layer_prepare(Ctx* c, const char* who, int layer, const uint8_t* file, size_t len, TiffLayerJob** out) {
+int tiff_layer_prepare(Ctx* c, const char* who, int layer, const uint8_t* file, size_t len, int level,
+                       TiffLayerJob** out) {
   *out = nullptr;
   if (layer < 0 || layer >= AMHIP_NUM_LAYERS) return bad(who, "layer: no such layer");
   TiffLayerJob* job = new TiffLayerJob;
@@ -356,7 +387,22 @@ int tiff_layer_prepare(Ctx* c, const char* who, int layer, const uint8_t* file, 
     TiffLayerJob* j;
     ~Guard() { delete j; }
   } guard = {job};
-  if (!parse_or_text(who, file, len, &job->P)) return AMHIP_ERR_ARG;
+  std::string where;
+  if (level == kTiffFirstIfd) {
+    if (!parse_or_text(who, file, len, &job->P)) return AMHIP_ERR_ARG;
+  } else {
+    if (level < -1) return bad(who, "level: -1 (automatic) or a level of the file, 0 ..");
+    if (level == -1) {   // the coarsest level whose pixels are no larger than the map's cells
+      std::vector<tiffd::Ifd> ifds;
+      char text[200];
+      if (!tiffd::walk_chain(file, len, &ifds, text, sizeof(text))) return bad(who, text);
+      Parsed base;
+      if (!tiffd::parse_ifd(file, len, ifds[0].at, &base, text, sizeof(text))) return bad(who, text);
+      level = base.has_geo ? tiffd::auto_level(base, ifds, c->grid.resolution) : 0;
+    }
+    if (!level_or_text(who, file, len, level, &job->P)) return AMHIP_ERR_ARG;
+    where = "level " + std::to_string(level) + ": ";
+  }
   const Parsed& P = job->P;
   if (!P.has_geo) return bad(who, "the file has no geo tags (ModelPixelScale + ModelTiepoint or ModelTransformation)");
   if (P.kind == tiffd::kRgb8 && layer != AMHIP_LAYER_COLORED_ORTHO)
@@ -386,7 +432,7 @@ int tiff_layer_prepare(Ctx* c, const char* who, int layer, const uint8_t* file, 
   if ((rc = ctx_use_device(c))) return rc;
   job->step = ((size_t)job->rw * (size_t)tiffd::pixel_bytes(P.kind) + 3u) & ~(size_t)3u;
   if ((rc = job->raster.alloc(job->step * (size_t)job->rh))) return rc;
-  if ((rc = decode_window(who, c->stream, file, P, job->rx0, job->ry0, job->rw, job->rh, job->raster.as<uint8_t>(),
+  if ((rc = decode_window(who, where, c->stream, file, P, job->rx0, job->ry0, job->rw, job->rh, job->raster.as<uint8_t>(),
                           job->step)))
     return rc;
   *out = job;
@@ -445,32 +491,13 @@ int amhip_geotiff_info(const uint8_t* file, size_t len, amhip_geotiff_desc* desc
   if (!file || !desc) return bad(kWho, "null argument");
   Parsed P;
   if (!parse_or_text(kWho, file, len, &P)) return AMHIP_ERR_ARG;
-  std::memset(desc, 0, sizeof(*desc));
-  desc->width = P.width;
-  desc->height = P.height;
-  desc->bands = P.bands;
-  desc->kind = P.kind;
-  desc->tiled = P.tiled;
-  desc->tile_width = P.tiled ? (int32_t)P.chunk_w : 0;
-  desc->tile_height = P.tiled ? (int32_t)P.chunk_h : 0;
-  desc->rows_per_strip = P.tiled ? 0 : (int32_t)P.chunk_h;
-  desc->compression = P.compression;
-  desc->predictor = P.predictor;
-  desc->has_geo = P.has_geo;
-  desc->epsg = P.epsg;
-  desc->raster_type = P.raster_type;
-  desc->has_nodata = P.has_nodata;
-  for (int k = 0; k < 6; ++k) desc->geotransform[k] = P.gt[k];
-  desc->nodata = P.nodata;
+  fill_desc(P, desc);
   return AMHIP_OK;
 }
 
-int amhip_geotiff_decode_dev(amhip_ctx* h, const uint8_t* file, size_t len, int x0, int y0, int w, int ht,
-                             void* dev_out, size_t step) {
-  static const char kWho[] = "amhip_geotiff_decode_dev";
-  if (!h || !file || !dev_out) return bad(kWho, "null argument");
-  Parsed P;
-  if (!parse_or_text(kWho, file, len, &P)) return AMHIP_ERR_ARG;
+// the pixel window of a parsed level into dev_out: the checks and the call
+static int decode_parsed(const char* kWho, const std::string& where, amhip_ctx* h, const uint8_t* file, const Parsed& P,
+                         int x0, int y0, int w, int ht, void* dev_out, size_t step) {
   if (x0 < 0 || y0 < 0 || w < 1 || ht < 1 || (long long)x0 + w > P.width || (long long)y0 + ht > P.height)
     return bad(kWho, "the pixel window leaves the raster (" + std::to_string(P.width) + " x " + std::to_string(P.height) + ")");
   const size_t bpp = (size_t)tiffd::pixel_bytes(P.kind), unit = bpp == 3 ? 1 : bpp;
@@ -480,7 +507,16 @@ int amhip_geotiff_decode_dev(amhip_ctx* h, const uint8_t* file, size_t len, int 
   int rc;
   if ((rc = ctx_use_device(c))) return rc;
   ScopedTimer timer(c, AMHIP_K_MISC);
-  return decode_window(kWho, c->stream, file, P, x0, y0, w, ht, static_cast<uint8_t*>(dev_out), step);
+  return decode_window(kWho, where, c->stream, file, P, x0, y0, w, ht, static_cast<uint8_t*>(dev_out), step);
+}
+
+int amhip_geotiff_decode_dev(amhip_ctx* h, const uint8_t* file, size_t len, int x0, int y0, int w, int ht,
+                             void* dev_out, size_t step) {
+  static const char kWho[] = "amhip_geotiff_decode_dev";
+  if (!h || !file || !dev_out) return bad(kWho, "null argument");
+  Parsed P;
+  if (!parse_or_text(kWho, file, len, &P)) return AMHIP_ERR_ARG;
+  return decode_parsed(kWho, "", h, file, P, x0, y0, w, ht, dev_out, step);
 }
 
 int amhip_layer_decode_geotiff(amhip_ctx* h, int layer, const uint8_t* file, size_t len) {
@@ -488,7 +524,7 @@ int amhip_layer_decode_geotiff(amhip_ctx* h, int layer, const uint8_t* file, siz
   if (!h || !file) return bad(kWho, "null argument");
   Ctx* c = &h->impl;
   TiffLayerJob* job = nullptr;
-  int rc = tiff_layer_prepare(c, kWho, layer, file, len, &job);
+  int rc = tiff_layer_prepare(c, kWho, layer, file, len, kTiffFirstIfd, &job);
   if (rc) return rc;
   rc = tiff_layer_place(c, job);
   tiff_layer_job_free(job);
@@ -503,7 +539,65 @@ int amhip_layer_read_geotiff(amhip_ctx* h, int layer, const char* filename) {
   if (rc) return rc;
   Ctx* c = &h->impl;
   TiffLayerJob* job = nullptr;
-  if ((rc = tiff_layer_prepare(c, kWho, layer, file.data(), file.size(), &job))) return rc;
+  if ((rc = tiff_layer_prepare(c, kWho, layer, file.data(), file.size(), kTiffFirstIfd, &job))) return rc;
+  rc = tiff_layer_place(c, job);
+  tiff_layer_job_free(job);
+  return rc;
+}
+
+// ---- levels ------------------------------------------------------------------------
+
+int amhip_geotiff_levels(const uint8_t* file, size_t len, int* n) {
+  static const char kWho[] = "amhip_geotiff_levels";
+  if (!file || !n) return bad(kWho, "null argument");
+  std::vector<tiffd::Ifd> ifds;
+  char text[200];
+  if (!tiffd::walk_chain(file, len, &ifds, text, sizeof(text))) return bad(kWho, text);
+  *n = (int)tiffd::levels_of(ifds).size();
+  return AMHIP_OK;
+}
+
+int amhip_geotiff_level_info(const uint8_t* file, size_t len, int level, amhip_geotiff_desc* desc) {
+  static const char kWho[] = "amhip_geotiff_level_info";
+  if (!file || !desc) return bad(kWho, "null argument");
+  Parsed P;
+  if (!level_or_text(kWho, file, len, level, &P)) return AMHIP_ERR_ARG;
+  fill_desc(P, desc);
+  return AMHIP_OK;
+}
+
+int amhip_geotiff_decode_level_dev(amhip_ctx* h, const uint8_t* file, size_t len, int level, int x0, int y0, int w,
+                                   int ht, void* dev_out, size_t step) {
+  static const char kWho[] = "amhip_geotiff_decode_level_dev";
+  if (!h || !file || !dev_out) return bad(kWho, "null argument");
+  Parsed P;
+  if (!level_or_text(kWho, file, len, level, &P)) return AMHIP_ERR_ARG;
+  return decode_parsed(kWho, "level " + std::to_string(level) + ": ", h, file, P, x0, y0, w, ht, dev_out, step);
+}
+
+int amhip_layer_decode_geotiff_level(amhip_ctx* h, int layer, const uint8_t* file, size_t len, int level) {
+  static const char kWho[] = "amhip_layer_decode_geotiff_level";
+  if (!h || !file) return bad(kWho, "null argument");
+  if (level < -1) return bad(kWho, "level: -1 (automatic) or a level of the file, 0 ..");
+  Ctx* c = &h->impl;
+  TiffLayerJob* job = nullptr;
+  int rc = tiff_layer_prepare(c, kWho, layer, file, len, level, &job);
+  if (rc) return rc;
+  rc = tiff_layer_place(c, job);
+  tiff_layer_job_free(job);
+  return rc;
+}
+
+int amhip_layer_read_geotiff_level(amhip_ctx* h, int layer, const char* filename, int level) {
+  static const char kWho[] = "amhip_layer_read_geotiff_level";
+  if (!h || !filename) return bad(kWho, "null argument");
+  if (level < -1) return bad(kWho, "level: -1 (automatic) or a level of the file, 0 ..");
+  std::vector<uint8_t> file;
+  int rc = read_file(kWho, filename, &file);
+  if (rc) return rc;
+  Ctx* c = &h->impl;
+  TiffLayerJob* job = nullptr;
+  if ((rc = tiff_layer_prepare(c, kWho, layer, file.data(), file.size(), level, &job))) return rc;
   rc = tiff_layer_place(c, job);
   tiff_layer_job_free(job);
   return rc;

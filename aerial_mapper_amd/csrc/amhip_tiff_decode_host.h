@@ -1,7 +1,9 @@
 // amhip_tiff_decode_host.h -- the host-only part of the GeoTIFF reader (amhip_tiff_decode.hip): the
-// parser of a classic little-endian TIFF's first IFD, the descriptor of the raster and one entry per
+// parser of one IFD of a classic little-endian TIFF -- the first, or a level's (the chain walk and the
+// level rules of DESIGN 4.18 stand at the end) --, the descriptor of the raster and one entry per
 // chunk (a tile or a strip).  No HIP in here: tests/cpp/tiff_decode_host_main.cc compiles it alone
-// under the address and undefined-behaviour sanitizers.  The accepted set is DESIGN 4.17:
+// under the address and undefined-behaviour sanitizers, tests/cpp/tiff_pyramid_host_main.cc the levels.
+// The accepted set is DESIGN 4.17:
 //
 //   layout        tiles (322 / 323 / 324 / 325; width and length multiples of 16) or strips (273 / 278 /
 //                 279; RowsPerStrip absent or larger than the height: one strip)
@@ -85,8 +87,24 @@ inline int type_bytes(int type) {
   return 0;
 }
 
-// The whole file -> *out, or false with a text in err.
-inline bool parse(const uint8_t* file, size_t len, Parsed* out, char* err, size_t errcap) {
+// The header -> the offset of the first IFD, or false with a text in err.
+inline bool first_ifd(const uint8_t* file, size_t len, uint64_t* at, char* err, size_t errcap) {
+  auto fail = [&](const char* fmt, long long a, long long b) {
+    if (err && errcap) std::snprintf(err, errcap, fmt, a, b);
+    return false;
+  };
+  if (!file || len < 8) return fail("no TIFF header (%lld bytes)", (long long)len, 0);
+  if (file[0] == 'M' && file[1] == 'M') return fail("big-endian TIFF (byte order MM) is not read", 0, 0);
+  if (file[0] != 'I' || file[1] != 'I') return fail("no TIFF header (byte order mark)", 0, 0);
+  const int version = le16(file + 2);
+  if (version == 43) return fail("BigTIFF (version 43) is not read", 0, 0);
+  if (version != 42) return fail("no TIFF header (version %lld)", version, 0);
+  *at = le32(file + 4);
+  return true;
+}
+
+// The IFD at byte `ifd` of the file -> *out, or false with a text in err.
+inline bool parse_ifd(const uint8_t* file, size_t len, uint64_t ifd, Parsed* out, char* err, size_t errcap) {
   auto fail = [&](const char* fmt, long long a, long long b) {
     if (err && errcap) std::snprintf(err, errcap, fmt, a, b);
     return false;
@@ -101,13 +119,6 @@ inline bool parse(const uint8_t* file, size_t len, Parsed* out, char* err, size_
   };
   Parsed& P = *out;
   P = Parsed();
-  if (!file || len < 8) return fail("no TIFF header (%lld bytes)", (long long)len, 0);
-  if (file[0] == 'M' && file[1] == 'M') return fail("big-endian TIFF (byte order MM) is not read", 0, 0);
-  if (file[0] != 'I' || file[1] != 'I') return fail("no TIFF header (byte order mark)", 0, 0);
-  const int version = le16(file + 2);
-  if (version == 43) return fail("BigTIFF (version 43) is not read", 0, 0);
-  if (version != 42) return fail("no TIFF header (version %lld)", version, 0);
-  const uint64_t ifd = le32(file + 4);
   if (ifd < 8 || ifd + 2 > len) return fail("the IFD at byte %lld lies outside the file", (long long)ifd, 0);
   const uint64_t n = le16(file + ifd);
   if (ifd + 2 + 12 * n + 4 > len) return fail("the IFD at byte %lld (%lld entries) runs past the file", (long long)ifd, (long long)n);
@@ -363,6 +374,133 @@ inline bool parse(const uint8_t* file, size_t len, Parsed* out, char* err, size_
     P.nodata = v;
   }
   return true;
+}
+
+// The whole file's first IFD -> *out, or false with a text in err.
+inline bool parse(const uint8_t* file, size_t len, Parsed* out, char* err, size_t errcap) {
+  uint64_t ifd = 0;
+  if (!first_ifd(file, len, &ifd, err, errcap)) return false;
+  return parse_ifd(file, len, ifd, out, err, errcap);
+}
+
+// ---- levels ------------------------------------------------------------------------
+// Level 0 is IFD 0; level k >= 1 is the k-th later IFD of the chain whose NewSubfileType (254) has
+// bit 0 (reduced resolution) set and bit 2 (mask) clear.  Masks and pages (254 absent, or bit 0
+// clear) are passed over.  At most kMaxIfds IFDs; an offset that comes twice is refused.
+constexpr size_t kMaxIfds = 64;
+
+struct Ifd {
+  uint64_t at;               // its offset
+  uint32_t width, height;    // 256 / 257 where they are one SHORT or LONG, else 0
+  bool overview;             // 254: bit 0 set, bit 2 clear
+};
+
+inline bool walk_chain(const uint8_t* file, size_t len, std::vector<Ifd>* ifds, char* err, size_t errcap) {
+  auto fail = [&](const char* fmt, long long a, long long b) {
+    if (err && errcap) std::snprintf(err, errcap, fmt, a, b);
+    return false;
+  };
+  ifds->clear();
+  uint64_t at = 0;
+  if (!first_ifd(file, len, &at, err, errcap)) return false;
+  do {
+    if (ifds->size() == kMaxIfds) return fail("the IFD chain has more than %lld IFDs", (long long)kMaxIfds, 0);
+    for (const Ifd& seen : *ifds)
+      if (seen.at == at) return fail("the IFD chain returns to the IFD at byte %lld", (long long)at, 0);
+    if (at < 8 || at + 2 > len) return fail("the IFD at byte %lld lies outside the file", (long long)at, 0);
+    const uint64_t n = le16(file + at);
+    if (at + 2 + 12 * n + 4 > len) return fail("the IFD at byte %lld (%lld entries) runs past the file", (long long)at, (long long)n);
+    Ifd d = {at, 0, 0, false};
+    for (uint64_t k = 0; k < n; ++k) {
+      const uint8_t* p = file + at + 2 + 12 * k;
+      const int tag = le16(p), type = le16(p + 2);
+      if ((tag != 254 && tag != 256 && tag != 257) || (type != 3 && type != 4) || le32(p + 4) != 1) continue;
+      const uint32_t v = type == 3 ? le16(p + 8) : le32(p + 8);   // (one SHORT or LONG lies in the entry)
+      if (tag == 254) d.overview = (v & 1u) && !(v & 4u);
+      else if (tag == 256) d.width = v;
+      else d.height = v;
+    }
+    ifds->push_back(d);
+    at = le32(file + at + 2 + 12 * n);
+  } while (at != 0);
+  return true;
+}
+
+// the chain's levels: indices into ifds
+inline std::vector<size_t> levels_of(const std::vector<Ifd>& ifds) {
+  std::vector<size_t> lv(1, 0);
+  for (size_t k = 1; k < ifds.size(); ++k)
+    if (ifds[k].overview) lv.push_back(k);
+  return lv;
+}
+
+// Level `level` of the file -> *out, *nlevels (may be null), or false with a text in err.  A level
+// k >= 1 passes the checks of IFD 0 (the text names the level and the IFD), has IFD 0's kind, and
+// no level up to it is larger than the one before it in either dimension, or as large in both.  Its
+// geotransform is the base's with GT1 * W0 / Wk and GT5 * H0 / Hk (GDAL's rule); geo keys and nodata
+// are the base's.
+inline bool parse_level(const uint8_t* file, size_t len, int level, Parsed* out, int* nlevels, char* err, size_t errcap) {
+  std::vector<Ifd> ifds;
+  if (!walk_chain(file, len, &ifds, err, errcap)) return false;
+  const std::vector<size_t> lv = levels_of(ifds);
+  if (nlevels) *nlevels = (int)lv.size();
+  if (level < 0 || (size_t)level >= lv.size()) {
+    if (err && errcap) std::snprintf(err, errcap, "level %d: the file has %zu level%s", level, lv.size(), lv.size() == 1 ? "" : "s");
+    return false;
+  }
+  Parsed base;
+  if (!parse_ifd(file, len, ifds[0].at, &base, err, errcap)) return false;
+  if (level == 0) {
+    *out = base;
+    return true;
+  }
+  for (int j = 1; j <= level; ++j) {
+    const Ifd& a = ifds[lv[(size_t)j - 1]];
+    const Ifd& b = ifds[lv[(size_t)j]];
+    if (!a.width || !a.height || !b.width || !b.height) continue;   // (the level's own parse names the tag)
+    if (b.width > a.width || b.height > a.height || (b.width == a.width && b.height == a.height)) {
+      if (err && errcap)
+        std::snprintf(err, errcap, "level %d (IFD %zu): %u x %u is not smaller than level %d, %u x %u", j, lv[(size_t)j],
+                      b.width, b.height, j - 1, a.width, a.height);
+      return false;
+    }
+  }
+  const size_t m = lv[(size_t)level];
+  char text[200];
+  if (!parse_ifd(file, len, ifds[m].at, out, text, sizeof(text))) {
+    if (err && errcap) std::snprintf(err, errcap, "level %d (IFD %zu at byte %llu): %s", level, m, (unsigned long long)ifds[m].at, text);
+    return false;
+  }
+  if (out->kind != base.kind) {
+    if (err && errcap)
+      std::snprintf(err, errcap, "level %d (IFD %zu at byte %llu): its samples are of kind %d, level 0's of kind %d", level, m,
+                    (unsigned long long)ifds[m].at, (int)out->kind, (int)base.kind);
+    return false;
+  }
+  out->has_geo = base.has_geo;
+  out->epsg = base.epsg;
+  out->raster_type = base.raster_type;
+  for (int k = 0; k < 6; ++k) out->gt[k] = base.gt[k];
+  out->gt[1] = base.gt[1] * (double)base.width / (double)out->width;
+  out->gt[5] = base.gt[5] * (double)base.height / (double)out->height;
+  out->has_nodata = base.has_nodata;
+  out->nodata = base.nodata;
+  return true;
+}
+
+// The automatic choice for a map of resolution `res`: the coarsest level whose pixels are no larger
+// than a cell in either direction (GT1_k <= res and -GT5_k <= res, compared as doubles); none: 0.
+// base: level 0, parsed.
+inline int auto_level(const Parsed& base, const std::vector<Ifd>& ifds, double res) {
+  const std::vector<size_t> lv = levels_of(ifds);
+  for (size_t k = lv.size(); k-- > 1;) {
+    const Ifd& d = ifds[lv[k]];
+    if (!d.width || !d.height) continue;
+    const double gt1 = base.gt[1] * (double)base.width / (double)d.width;
+    const double gt5 = base.gt[5] * (double)base.height / (double)d.height;
+    if (gt1 <= res && -gt5 <= res) return (int)k;
+  }
+  return 0;
 }
 
 // the chunk's place in the layout, for error texts: "tile row 1, column 2" / "strip 3"

@@ -1,11 +1,12 @@
 // amhip_tiff_encode.hip -- map layers and rasters as tiled Deflate GeoTIFF, compressed on the GPU:
-// a classic little-endian TIFF with one IFD, square tiles, Compression 8 (Adobe Deflate),
-// Predictor 3 for 32-bit float samples and 2 for 8-bit ones, the geo tags of
+// a classic little-endian TIFF with one IFD (and one more per overview level), square
+// tiles, Compression 8 (Adobe Deflate), Predictor 3 for 32-bit float samples and 2 for 8-bit ones, the geo tags of
 // amhip_geotiff_write_u8.  Every tile is one zlib stream: byte for byte what zlib 1.2.11 writes for
 // the tile's predictor bytes with deflateInit2(1, Z_DEFLATED, 15, 8, Z_RLE), which
 // tests/geotiff_reference.py restates and tests/golden/geotiff/ pins.  DESIGN 4.16.
 //
 // A tile is a "frame" of the batched Z_RLE coder of the PNG encoder (amhip_deflate_rle.h):
+//   (k_tovr_reduce  amhip_tiff_overview.hip: the overview levels' rasters, each from the one before it)
 //   k_tiff_tile     a workgroup per 4096 predictor bytes of a tile (the tile on blockIdx.y): the rows
 //                   of samples it covers go through LDS -- from a layer, reoriented north-up and
 //                   converted on the way, or from a row-major raster -- then a lane per 16 bytes:
@@ -21,8 +22,8 @@
 #include "amhip_common.h"
 #include "amhip_deflate_rle.h"
 #include "amhip_frame_stack.h"
-#include "amhip_layer_image.h"
 #include "amhip_tiff_host.h"
+#include "amhip_tiff_source.h"
 
 namespace amhip {
 
@@ -36,42 +37,6 @@ using pnge::Share;
 
 constexpr uint32_t kStageBytes = 12288;   // the sample rows one piece of 4096 bytes can touch (plan())
 
-// where a call's samples come from
-struct TileSrc {
-  const void* base;          // layer: the window's floats, column-major; raster: row-major pixels
-  unsigned long long step;   // layer: floats per column (the window's rows); raster: bytes per row
-  int width, height;         // of the raster
-  uint32_t side, across;     // tile side, tiles per row of tiles
-  uint32_t row_bytes;        // side * bytes per pixel
-  uint32_t first;            // the group's first tile
-  float lower, upper;        // u8 from a layer
-};
-
-// Pixel (r, c) of the raster as it lies in the file before the predictor, lowest byte first: the
-// float's bits, the byte, or R | G << 8 | B << 16.  Outside the raster: zero.
-// A layer: raster pixel (r, c) is cell (i, j) = (width - 1 - c, r) of the window, so
-// along a raster row the reads walk a layer column backwards, one float after the other.
-template <int kKind, bool kLayer>
-__device__ __forceinline__ uint32_t fetch(const TileSrc& src, uint32_t r, uint32_t c) {
-  if (r >= (uint32_t)src.height || c >= (uint32_t)src.width) return 0;
-  if (kLayer) {
-    const float v = static_cast<const float*>(src.base)[(size_t)((uint32_t)src.width - 1u - c) + (size_t)r * src.step];
-    if (kKind == tiff::kF32) return __float_as_uint(v);
-    if (kKind == tiff::kU8) return to_image_u8(v, src.lower, src.upper);
-    const uint32_t bits = (v == v) ? __float_as_uint(v) : 0u;   // packed R << 16 | G << 8 | B
-    return ((bits >> 16) & 255u) | (bits & 0xFF00u) | ((bits & 255u) << 16);
-  }
-  const uint8_t* p = static_cast<const uint8_t*>(src.base) + (size_t)r * src.step;
-  if (kKind == tiff::kF32) {
-    p += (size_t)c * 4u;
-    if ((reinterpret_cast<size_t>(p) & 3u) == 0) return *reinterpret_cast<const uint32_t*>(p);
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-  }
-  if (kKind == tiff::kU8) return p[c];
-  p += (size_t)c * 3u;
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-}
-
 // The producer.  Stores: 16 bytes per lane at scan + (f * ntiles + piece) * 4096 + tid * 16, inside
 // the group's ntiles * 4096 bytes per tile; one word per piece.  LDS: the rows [row_lo, row_hi] of
 // the tile, at most kStageBytes (plan() refuses a geometry that would need more).
@@ -82,9 +47,11 @@ __global__ void __launch_bounds__(256) k_tiff_tile(TileSrc src, Share s, Bufs b)
   __shared__ uint32_t stage[kStageBytes / 4];
   __shared__ uint32_t sh[3];
   uint8_t* stage8 = reinterpret_cast<uint8_t*>(stage);
-  const uint32_t tid = threadIdx.x, piece = blockIdx.x, f = blockIdx.y;
+  // (a launch covers the tiles of one level that a group holds: tile src.first + y of that level's
+  // raster is frame src.frame0 + y of the group's buffers)
+  const uint32_t tid = threadIdx.x, piece = blockIdx.x, f = src.frame0 + blockIdx.y;
   if (tid < 3) sh[tid] = 0;
-  const uint32_t t = src.first + f, ty = t / src.across, tx = t - ty * src.across;
+  const uint32_t t = src.first + blockIdx.y, ty = t / src.across, tx = t - ty * src.across;
   const uint32_t side = src.side, rb = src.row_bytes, raw = (uint32_t)s.raw_len;
   const uint32_t r0 = ty * side, c0 = tx * side;
   const uint32_t b0 = piece * kTile, b1 = raw - b0 < kTile ? raw : b0 + kTile;   // (piece < ntiles: b0 < raw)
@@ -201,10 +168,15 @@ __global__ void __launch_bounds__(64) k_tiff_offsets(Bufs b, uint32_t n) {
 // so it lies inside the buffer's zwords); the blocks at the two ends are written byte by byte, the
 // neighbouring streams' bytes in them by their own lanes.  Every byte written lies in
 // [base + offs[f], base + offs[f] + sizes[f]), inside the file the host sized from the sizes.
-__global__ void __launch_bounds__(256) k_tiff_gather(Share s, Bufs b, uint8_t* out, unsigned long long base) {
-  const uint32_t f = blockIdx.y;
+//
+// A launch covers the frames first .. first + gridDim.y - 1 of the group, the tiles of one level,
+// which follow each other in the file from `base` + offs[first] on; the host passes base modulo 2^64
+// (a level's tiles may lie in front of the group's earlier frames), the sum is the true offset.
+__global__ void __launch_bounds__(256) k_tiff_gather(Share s, Bufs b, uint8_t* out, unsigned long long base,
+                                                     uint32_t first) {
+  const uint32_t f = first + blockIdx.y;
   const unsigned long long zlen = b.sizes[f];
-  uint8_t* dst = out + base + b.offs[f];
+  uint8_t* dst = out + (base + b.offs[f]);
   const size_t lead = reinterpret_cast<size_t>(dst) & 15u;   // bytes of the first block in front of the stream
   const unsigned long long blk = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
   if (blk * 16u >= lead + zlen) return;
@@ -227,35 +199,48 @@ __global__ void __launch_bounds__(256) k_tiff_gather(Share s, Bufs b, uint8_t* o
   for (unsigned long long k = lo; k < hi; ++k) dst[k] = src[k];
 }
 
-// One call: the tiles' geometry, the groups (a tile is a frame: it costs its scratch, the budget is the
-// tuning key tiffe_scratch_budget_mb), the scratch of the largest group and, in `sizes`, the lengths of
-// all streams.
+// One call: the levels and their tiles' geometry, the groups (a tile is a frame: it costs its scratch,
+// the budget is the tuning key tiffe_scratch_budget_mb), the scratch of the largest group, the
+// overview rasters and, in `sizes`, the lengths of all streams.  The tiles of all levels are one
+// list -- level 0's, then level 1's, .. -- cut into groups by one budget, so every pass of the coder's
+// middle runs once per group; only the producer and the gather, which know where a tile comes from
+// and where it goes, run once per level a group holds.
 struct TiffEncoder : EncodeGroups {
   Share s = {};
-  TileSrc src = {};
+  std::vector<tiff::Level> levels;
+  std::vector<TileSrc> srcs;           // per level; level 0: the call's source
+  std::vector<uint64_t> dest;          // every tile's place in the file, once the container is built
+  DevBuf overviews;                    // the rasters of levels 1.., row-major, tightly packed
   int kind = 0;
-  bool layer = false;
+  bool layer = false;                  // level 0 comes from a layer
 
   pnge::Layout layout(size_t n) const { return pnge::make_layout(s, n); }
   Bufs bufs(size_t n) { return pnge::make_bufs(scratch.as<uint8_t>(), layout(n), nullptr); }
 
-  // host only: geometry and groups.  false: a piece could touch more rows than the LDS stage holds
-  // (no tile side this writer accepts does).
+  TileSrc source(const void* base, unsigned long long step, int width, int height, uint32_t side) const {
+    TileSrc t = {};
+    t.base = base;
+    t.step = step;
+    t.width = width;
+    t.height = height;
+    t.side = side;
+    t.across = ((uint32_t)width + side - 1u) / side;
+    t.row_bytes = side * (uint32_t)tiff::pixel_bytes(kind);
+    return t;
+  }
+
+  // host only: geometry and groups; novr overview levels (>= 0, checked by the caller).  false: a piece
+  // could touch more rows than the LDS stage holds (no tile side this writer accepts does).
   bool plan(const void* base, bool from_layer, unsigned long long step, int width, int height, int knd, int tile,
-            float lower, float upper) {
+            int novr, float lower, float upper) {
     kind = knd;
     layer = from_layer;
-    src.base = base;
-    src.step = step;
-    src.width = width;
-    src.height = height;
-    src.side = tiff::tile_side(tile);
-    src.across = (uint32_t)tiff::tiles_across(width, tile);
-    src.row_bytes = src.side * (uint32_t)tiff::pixel_bytes(kind);
-    src.first = 0;
-    src.lower = lower;
-    src.upper = upper;
-    const uint32_t rb = src.row_bytes;
+    levels = tiff::make_levels(width, height, tile, novr);
+    srcs.assign(levels.size(), TileSrc());
+    srcs[0] = source(base, step, width, height, tiff::tile_side(tile));
+    srcs[0].lower = lower;
+    srcs[0].upper = upper;
+    const uint32_t rb = srcs[0].row_bytes;
     // a piece starts anywhere in a row: 4096 bytes touch at most this many rows
     const uint32_t rows = kTile % rb == 0 ? kTile / rb : (kTile + rb - 2) / rb + 1;
     if ((size_t)rows * rb > kStageBytes) return false;
@@ -267,17 +252,52 @@ struct TiffEncoder : EncodeGroups {
     s.row_step = 0;
     s.frame_stride = 0;
     pnge::share_set_raw(&s, tiff::tile_raw(kind, tile));
-    plan_uniform((size_t)tiff::tile_count(width, height, tile), layout(1).total, "tiffe_scratch_budget_mb", 4096.0,
-                 kMaxGroupFrames);
+    plan_uniform((size_t)(levels.back().first + levels.back().ntiles), layout(1).total, "tiffe_scratch_budget_mb",
+                 4096.0, kMaxGroupFrames);
     return true;
   }
 
-  int open() { return scratch.alloc(layout(most_group_frames()).total); }
+  size_t raster_bytes(size_t k) const {   // of an overview level, its start kept on a multiple of 16
+    return ((size_t)levels[k].width * (size_t)levels[k].height * (size_t)tiff::pixel_bytes(kind) + 15u) & ~(size_t)15u;
+  }
+
+  // the scratch of most_group_frames() frames; the overview rasters, each reduced from the level before it
+  int open() {
+    int rc;
+    if ((rc = scratch.alloc(layout(most_group_frames()).total))) return rc;
+    if (levels.size() == 1) return AMHIP_OK;
+    size_t total = 0;
+    for (size_t k = 1; k < levels.size(); ++k) total += raster_bytes(k);
+    if ((rc = overviews.alloc(total))) return rc;
+    size_t at = 0;
+    for (size_t k = 1; k < levels.size(); ++k) {
+      uint8_t* raster = overviews.as<uint8_t>() + at;
+      if ((rc = tovr_reduce(stream, kind, layer && k == 1, srcs[k - 1], raster))) return rc;
+      srcs[k] = source(raster, (unsigned long long)levels[k].width * (unsigned)tiff::pixel_bytes(kind), levels[k].width,
+                       levels[k].height, srcs[0].side);
+      at += raster_bytes(k);
+    }
+    return AMHIP_OK;
+  }
 
   template <int kKind>
-  void launch_tiles(const dim3& grid, const TileSrc& ts, const Bufs& b) {
-    if (layer) hipLaunchKernelGGL((k_tiff_tile<kKind, true>), grid, dim3(256), 0, stream, ts, s, b);
+  void launch_tiles(const dim3& grid, bool from_layer, const TileSrc& ts, const Bufs& b) {
+    if (from_layer) hipLaunchKernelGGL((k_tiff_tile<kKind, true>), grid, dim3(256), 0, stream, ts, s, b);
     else hipLaunchKernelGGL((k_tiff_tile<kKind, false>), grid, dim3(256), 0, stream, ts, s, b);
+  }
+
+  // fn(level, lo, hi): the frames [lo, hi) of the call's list that group gi holds of `level`
+  template <typename Fn>
+  int for_segments(size_t gi, Fn fn) {
+    const uint64_t g0 = group_begin[gi], g1 = group_begin[gi + 1];
+    for (size_t k = 0; k < levels.size(); ++k) {
+      const uint64_t l0 = levels[k].first, l1 = l0 + levels[k].ntiles;
+      const uint64_t lo = g0 > l0 ? g0 : l0, hi = g1 < l1 ? g1 : l1;
+      if (lo >= hi) continue;
+      const int rc = fn(k, lo, hi);
+      if (rc) return rc;
+    }
+    return AMHIP_OK;
   }
 
   // every pass of group gi up to the streams and their lengths, which are read back
@@ -285,15 +305,20 @@ struct TiffEncoder : EncodeGroups {
     const uint32_t n = (uint32_t)group_frames(gi);
     const Bufs b = bufs(n);
     AMHIP_TRY(hipMemsetAsync(b.z, 0, (size_t)n * (size_t)s.zwords * 4, stream));
-    TileSrc ts = src;
-    ts.first = (uint32_t)group_begin[gi];
-    const dim3 grid(s.ntiles, n);
-    if (kind == tiff::kF32) launch_tiles<tiff::kF32>(grid, ts, b);
-    else if (kind == tiff::kU8) launch_tiles<tiff::kU8>(grid, ts, b);
-    else launch_tiles<tiff::kRgb8>(grid, ts, b);
-    AMHIP_TRY(hipGetLastError());
-    const int rc = deflate_rle_middle(stream, s, b, n);
+    int rc = for_segments(gi, [&](size_t k, uint64_t lo, uint64_t hi) {
+      TileSrc ts = srcs[k];
+      ts.first = (uint32_t)(lo - levels[k].first);
+      ts.frame0 = (uint32_t)(lo - group_begin[gi]);
+      const dim3 grid(s.ntiles, (uint32_t)(hi - lo));
+      const bool from_layer = layer && k == 0;
+      if (kind == tiff::kF32) launch_tiles<tiff::kF32>(grid, from_layer, ts, b);
+      else if (kind == tiff::kU8) launch_tiles<tiff::kU8>(grid, from_layer, ts, b);
+      else launch_tiles<tiff::kRgb8>(grid, from_layer, ts, b);
+      AMHIP_TRY(hipGetLastError());
+      return (int)AMHIP_OK;
+    });
     if (rc) return rc;
+    if ((rc = deflate_rle_middle(stream, s, b, n))) return rc;
     hipLaunchKernelGGL(k_tiff_offsets, dim3(1), dim3(64), 0, stream, b, n);
     AMHIP_TRY(hipGetLastError());
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the lengths are copied as they lie");
@@ -302,15 +327,33 @@ struct TiffEncoder : EncodeGroups {
     return AMHIP_OK;
   }
 
-  // ... and group gi's streams into the file at `file`, from byte `base` on.  front(gi) ran last.
-  int back(size_t gi, uint8_t* file, uint64_t base) {
+  // every tile's place in the file whose levels start at level_at[k]
+  void place_tiles(const std::vector<uint64_t>& level_at) {
+    dest.assign(F, 0);
+    for (size_t k = 0; k < levels.size(); ++k) {
+      uint64_t at = level_at[k];
+      for (uint64_t t = levels[k].first; t < levels[k].first + levels[k].ntiles; ++t) {
+        dest[t] = at;
+        at += sizes[t];
+      }
+    }
+  }
+
+  // ... and group gi's streams into the file at `file`, every level's to its place (place_tiles ran;
+  // the driver's running offset holds for a file of one level only and is not used).  front(gi) ran last.
+  int back(size_t gi, uint8_t* file, uint64_t) {
     const uint32_t n = (uint32_t)group_frames(gi);
     const Bufs b = bufs(n);
     // (a stream of z bytes behind a lead of at most 15 touches at most (z + 15 + 15) / 16 blocks)
     const unsigned blocks = (unsigned)(((largest_file(gi) + 30) / 16 + 255) / 256);
-    hipLaunchKernelGGL(k_tiff_gather, dim3(blocks, n), dim3(256), 0, stream, s, b, file, (unsigned long long)base);
-    AMHIP_TRY(hipGetLastError());
-    return AMHIP_OK;
+    return for_segments(gi, [&](size_t, uint64_t lo, uint64_t hi) {
+      uint64_t before = 0;   // offs[lo - group_begin[gi]]: the group's streams in front of the segment
+      for (uint64_t f = group_begin[gi]; f < lo; ++f) before += sizes[f];
+      hipLaunchKernelGGL(k_tiff_gather, dim3(blocks, (uint32_t)(hi - lo)), dim3(256), 0, stream, s, b, file,
+                         (unsigned long long)(dest[lo] - before), (uint32_t)(lo - group_begin[gi]));
+      AMHIP_TRY(hipGetLastError());
+      return (int)AMHIP_OK;
+    });
   }
 };
 
@@ -323,6 +366,7 @@ struct TiffJob {
   float lower, upper;
   const double* geotransform;
   int utm_zone, northern;
+  int overviews;   // levels behind level 0, resolved (check_overviews)
 };
 
 // The whole file.  dev_out != null: into it, at most cap bytes, nothing written when it does not fit.
@@ -331,7 +375,8 @@ int tiff_encode(const char* who, hipStream_t stream, const TiffJob& job, uint8_t
                 size_t* bytes) {
   TiffEncoder enc;
   enc.stream = stream;
-  if (!enc.plan(job.base, job.layer, job.step, job.width, job.height, job.kind, job.tile, job.lower, job.upper))
+  if (!enc.plan(job.base, job.layer, job.step, job.width, job.height, job.kind, job.tile, job.overviews, job.lower,
+                job.upper))
     return arg_failure((std::string(who) + ": tile: a piece of the tile would not fit the producer's stage").c_str());
   int rc;
   if ((rc = enc.open())) return rc;
@@ -342,7 +387,7 @@ int tiff_encode(const char* who, hipStream_t stream, const TiffJob& job, uint8_t
       enc, [&](size_t gi) { return enc.front(gi); },
       [&](uint8_t** to, uint64_t* at) {
         const tiff::GeoTags geo = tiff::make_geo_tags(job.geotransform, job.utm_zone, job.northern);
-        if (!tiff::build_container(job.width, job.height, job.kind, job.tile, geo, enc.sizes.data(), enc.F, &file))
+        if (!tiff::build_pyramid(enc.levels, job.kind, job.tile, geo, enc.sizes.data(), &file))
           return arg_failure(
               (std::string(who) + ": the file would exceed 4 GB - 1 (BigTIFF is not written; nothing written)").c_str());
         if (bytes) *bytes = (size_t)file.file_bytes;
@@ -355,11 +400,12 @@ int tiff_encode(const char* who, hipStream_t stream, const TiffJob& job, uint8_t
           *to = owned->as<uint8_t>();
         }
         AMHIP_TRY(hipMemcpyAsync(*to, file.head.data(), file.head.size(), hipMemcpyHostToDevice, stream));
+        enc.place_tiles(file.level_at);
         *at = file.head.size();
         return (int)AMHIP_OK;
       });
   if (rc) return rc;
-  AMHIP_TRY(hipStreamSynchronize(stream));   // (the scratch and the head go with this call)
+  AMHIP_TRY(hipStreamSynchronize(stream));   // (the scratch, the overviews and the head go with this call)
   return AMHIP_OK;
 }
 
@@ -417,37 +463,37 @@ TiffJob layer_job(Ctx* c, int layer, int kind, float lower, float upper, int til
 
 using namespace amhip;
 
-extern "C" {
+namespace {
 
-size_t amhip_geotiff_bound(int width, int height, int kind, int tile) {
-  if (tiff::check_raster(width, height, kind, tile)) return 0;
-  return (size_t)tiff::file_bound(width, height, kind, tile);
-}
-
-int amhip_geotiff_encode_dev(amhip_ctx* h, const void* dev_raster, size_t step, int width, int height, int kind,
-                             int tile, const double* geotransform, int utm_zone, int northern, uint8_t* dev_out,
-                             size_t cap, size_t* bytes) {
-  static const char kWho[] = "amhip_geotiff_encode_dev";
-  if (!h || !dev_raster || !geotransform || !dev_out || !bytes) return bad(kWho, "null argument");
-  int rc = check_raster_call(kWho, step, width, height, kind, tile, geotransform, utm_zone);
+// The bodies of the exports: `who` is the export's name, overviews as the caller gave it (0 for the
+// exports without the argument, which stay what they were).
+int geotiff_encode_dev(const char* who, amhip_ctx* h, const void* dev_raster, size_t step, int width, int height,
+                       int kind, int tile, int overviews, const double* geotransform, int utm_zone, int northern,
+                       uint8_t* dev_out, size_t cap, size_t* bytes) {
+  if (!h || !dev_raster || !geotransform || !dev_out || !bytes) return bad(who, "null argument");
+  int rc = check_raster_call(who, step, width, height, kind, tile, geotransform, utm_zone);
   if (rc) return rc;
+  int novr = 0;
+  if (const char* why = tiff::check_overviews(width, height, tile, overviews, &novr)) return bad(who, why);
   Ctx* c = &h->impl;
   if ((rc = ctx_use_device(c))) return rc;
   ScopedTimer timer(c, AMHIP_K_MISC);
-  const TiffJob job = {dev_raster, false, step, width, height, kind, tile, 0.0f, 0.0f, geotransform, utm_zone, northern};
-  return tiff_encode(kWho, c->stream, job, dev_out, cap, nullptr, bytes);
+  const TiffJob job = {dev_raster, false, step, width, height, kind, tile, 0.0f, 0.0f, geotransform, utm_zone, northern,
+                       novr};
+  return tiff_encode(who, c->stream, job, dev_out, cap, nullptr, bytes);
 }
 
-int amhip_geotiff_write(amhip_ctx* h, const char* filename, const void* raster, int on_device, size_t step,
-                        int width, int height, int kind, int tile, const double* geotransform, int utm_zone,
-                        int northern) {
-  static const char kWho[] = "amhip_geotiff_write";
-  if (!h || !filename || !raster || !geotransform) return bad(kWho, "null argument");
-  int rc = check_raster_call(kWho, step, width, height, kind, tile, geotransform, utm_zone);
+int geotiff_write(const char* who, amhip_ctx* h, const char* filename, const void* raster, int on_device, size_t step,
+                  int width, int height, int kind, int tile, int overviews, const double* geotransform, int utm_zone,
+                  int northern) {
+  if (!h || !filename || !raster || !geotransform) return bad(who, "null argument");
+  int rc = check_raster_call(who, step, width, height, kind, tile, geotransform, utm_zone);
   if (rc) return rc;
+  int novr = 0;
+  if (const char* why = tiff::check_overviews(width, height, tile, overviews, &novr)) return bad(who, why);
   Ctx* c = &h->impl;
   if ((rc = ctx_use_device(c))) return rc;
-  TiffJob job = {raster, false, step, width, height, kind, tile, 0.0f, 0.0f, geotransform, utm_zone, northern};
+  TiffJob job = {raster, false, step, width, height, kind, tile, 0.0f, 0.0f, geotransform, utm_zone, northern, novr};
   DevBuf staged;
   if (!on_device) {
     const size_t row = (size_t)width * (size_t)tiff::pixel_bytes(kind);
@@ -457,37 +503,113 @@ int amhip_geotiff_write(amhip_ctx* h, const char* filename, const void* raster, 
     job.step = row;
   }
   ScopedTimer timer(c, AMHIP_K_MISC);
-  return tiff_write(kWho, c->stream, job, filename);
+  return tiff_write(who, c->stream, job, filename);
+}
+
+// a layer call up to its job; gt: six doubles the job points to
+int layer_call(const char* who, amhip_ctx* h, int layer, int kind, float lower, float upper, int tile, int overviews,
+               int utm_zone, int northern, double* gt, TiffJob* job) {
+  Ctx* c = &h->impl;
+  int rc = check_layer_call(who, layer, kind, lower, upper, tile, utm_zone, c->win_rows, c->win_cols);
+  if (rc) return rc;
+  int novr = 0;
+  if (const char* why = tiff::check_overviews(c->win_rows, c->win_cols, tile, overviews, &novr)) return bad(who, why);
+  if ((rc = ctx_use_device(c))) return rc;
+  if ((rc = ctx_materialize(c, layer))) return rc;
+  *job = layer_job(c, layer, kind, lower, upper, tile, utm_zone, northern, gt);
+  job->overviews = novr;
+  return AMHIP_OK;
+}
+
+int layer_encode_geotiff_dev(const char* who, amhip_ctx* h, int layer, int kind, float lower, float upper, int tile,
+                             int overviews, int utm_zone, int northern, uint8_t* dev_out, size_t cap, size_t* bytes) {
+  if (!h || !dev_out || !bytes) return bad(who, "null argument");
+  double gt[6];
+  TiffJob job;
+  const int rc = layer_call(who, h, layer, kind, lower, upper, tile, overviews, utm_zone, northern, gt, &job);
+  if (rc) return rc;
+  ScopedTimer timer(&h->impl, AMHIP_K_MISC);
+  return tiff_encode(who, h->impl.stream, job, dev_out, cap, nullptr, bytes);
+}
+
+int layer_write_geotiff(const char* who, amhip_ctx* h, int layer, int kind, float lower, float upper, int tile,
+                        int overviews, int utm_zone, int northern, const char* filename) {
+  if (!h || !filename) return bad(who, "null argument");
+  double gt[6];
+  TiffJob job;
+  const int rc = layer_call(who, h, layer, kind, lower, upper, tile, overviews, utm_zone, northern, gt, &job);
+  if (rc) return rc;
+  ScopedTimer timer(&h->impl, AMHIP_K_MISC);
+  return tiff_write(who, h->impl.stream, job, filename);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t amhip_geotiff_bound(int width, int height, int kind, int tile) {
+  if (tiff::check_raster(width, height, kind, tile)) return 0;
+  return (size_t)tiff::file_bound(width, height, kind, tile);
+}
+
+size_t amhip_geotiff_bound_ovr(int width, int height, int kind, int tile, int overviews) {
+  int novr = 0;
+  if (tiff::check_raster(width, height, kind, tile) || tiff::check_overviews(width, height, tile, overviews, &novr))
+    return 0;
+  return (size_t)tiff::file_bound_ovr(width, height, kind, tile, novr);
+}
+
+int amhip_geotiff_encode_dev(amhip_ctx* h, const void* dev_raster, size_t step, int width, int height, int kind,
+                             int tile, const double* geotransform, int utm_zone, int northern, uint8_t* dev_out,
+                             size_t cap, size_t* bytes) {
+  return geotiff_encode_dev("amhip_geotiff_encode_dev", h, dev_raster, step, width, height, kind, tile, 0, geotransform,
+                            utm_zone, northern, dev_out, cap, bytes);
+}
+
+int amhip_geotiff_encode_ovr_dev(amhip_ctx* h, const void* dev_raster, size_t step, int width, int height, int kind,
+                                 int tile, int overviews, const double* geotransform, int utm_zone, int northern,
+                                 uint8_t* dev_out, size_t cap, size_t* bytes) {
+  return geotiff_encode_dev("amhip_geotiff_encode_ovr_dev", h, dev_raster, step, width, height, kind, tile, overviews,
+                            geotransform, utm_zone, northern, dev_out, cap, bytes);
+}
+
+int amhip_geotiff_write(amhip_ctx* h, const char* filename, const void* raster, int on_device, size_t step,
+                        int width, int height, int kind, int tile, const double* geotransform, int utm_zone,
+                        int northern) {
+  return geotiff_write("amhip_geotiff_write", h, filename, raster, on_device, step, width, height, kind, tile, 0,
+                       geotransform, utm_zone, northern);
+}
+
+int amhip_geotiff_write_ovr(amhip_ctx* h, const char* filename, const void* raster, int on_device, size_t step,
+                            int width, int height, int kind, int tile, int overviews, const double* geotransform,
+                            int utm_zone, int northern) {
+  return geotiff_write("amhip_geotiff_write_ovr", h, filename, raster, on_device, step, width, height, kind, tile,
+                       overviews, geotransform, utm_zone, northern);
 }
 
 int amhip_layer_encode_geotiff_dev(amhip_ctx* h, int layer, int kind, float lower, float upper, int tile,
                                    int utm_zone, int northern, uint8_t* dev_out, size_t cap, size_t* bytes) {
-  static const char kWho[] = "amhip_layer_encode_geotiff_dev";
-  if (!h || !dev_out || !bytes) return bad(kWho, "null argument");
-  Ctx* c = &h->impl;
-  int rc = check_layer_call(kWho, layer, kind, lower, upper, tile, utm_zone, c->win_rows, c->win_cols);
-  if (rc) return rc;
-  if ((rc = ctx_use_device(c))) return rc;
-  if ((rc = ctx_materialize(c, layer))) return rc;
-  ScopedTimer timer(c, AMHIP_K_MISC);
-  double gt[6];
-  const TiffJob job = layer_job(c, layer, kind, lower, upper, tile, utm_zone, northern, gt);
-  return tiff_encode(kWho, c->stream, job, dev_out, cap, nullptr, bytes);
+  return layer_encode_geotiff_dev("amhip_layer_encode_geotiff_dev", h, layer, kind, lower, upper, tile, 0, utm_zone,
+                                  northern, dev_out, cap, bytes);
+}
+
+int amhip_layer_encode_geotiff_ovr_dev(amhip_ctx* h, int layer, int kind, float lower, float upper, int tile,
+                                       int overviews, int utm_zone, int northern, uint8_t* dev_out, size_t cap,
+                                       size_t* bytes) {
+  return layer_encode_geotiff_dev("amhip_layer_encode_geotiff_ovr_dev", h, layer, kind, lower, upper, tile, overviews,
+                                  utm_zone, northern, dev_out, cap, bytes);
 }
 
 int amhip_layer_write_geotiff(amhip_ctx* h, int layer, int kind, float lower, float upper, int tile, int utm_zone,
                               int northern, const char* filename) {
-  static const char kWho[] = "amhip_layer_write_geotiff";
-  if (!h || !filename) return bad(kWho, "null argument");
-  Ctx* c = &h->impl;
-  int rc = check_layer_call(kWho, layer, kind, lower, upper, tile, utm_zone, c->win_rows, c->win_cols);
-  if (rc) return rc;
-  if ((rc = ctx_use_device(c))) return rc;
-  if ((rc = ctx_materialize(c, layer))) return rc;
-  ScopedTimer timer(c, AMHIP_K_MISC);
-  double gt[6];
-  const TiffJob job = layer_job(c, layer, kind, lower, upper, tile, utm_zone, northern, gt);
-  return tiff_write(kWho, c->stream, job, filename);
+  return layer_write_geotiff("amhip_layer_write_geotiff", h, layer, kind, lower, upper, tile, 0, utm_zone, northern,
+                             filename);
+}
+
+int amhip_layer_write_geotiff_ovr(amhip_ctx* h, int layer, int kind, float lower, float upper, int tile, int overviews,
+                                  int utm_zone, int northern, const char* filename) {
+  return layer_write_geotiff("amhip_layer_write_geotiff_ovr", h, layer, kind, lower, upper, tile, overviews, utm_zone,
+                             northern, filename);
 }
 
 }  // extern "C"

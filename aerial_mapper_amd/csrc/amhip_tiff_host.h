@@ -1,7 +1,8 @@
 // amhip_tiff_host.h -- the part of the GeoTIFF writers that needs no device: the geo tags of a
 // north-up UTM raster (shared by amhip_geotiff_write_u8, amhip_export.hip, and the tiled Deflate
 // writer, amhip_tiff_encode.hip), the argument checks, and the container of the tiled file: header,
-// IFD, out-of-line values and tile tables from the tiles' byte counts.  No HIP in here:
+// IFDs (level 0 and its overviews), out-of-line values and tile tables from the tiles'
+// byte counts.  No HIP in here:
 // tests/cpp/tiff_host_check.cc compiles it alone under the address and undefined-behaviour
 // sanitizers.  The file is defined in DESIGN 4.16.
 #ifndef AMHIP_TIFF_HOST_H_
@@ -100,104 +101,184 @@ inline const char* check_geo(const double* geotransform, int utm_zone) {
   return nullptr;
 }
 
-// where the tile data start: behind the IFD and the out-of-line values, on a multiple of 16
-struct Container {
-  std::vector<uint8_t> head;   // the file up to the first tile, `data_at` bytes
-  uint64_t file_bytes;         // ... and with the tiles
+// ---- the pyramid -------------------------------------------------------------------
+// Level k >= 1 is ceil(w / 2) x ceil(h / 2) of level k - 1.  The tiles of a call are one list: level
+// 0's in row-major order, then level 1's, and so on.
+constexpr int kMaxOverviews = 16;
+
+struct Level {
+  int width, height;
+  uint64_t first, ntiles;   // its tiles in the call's list
 };
 
-// The file in front of the tile data for tiles of `counts[t]` bytes (row-major tile order), tightly
-// packed from the next multiple of 16 behind the values.  The IFD at offset 8, tags ascending;
-// out-of-line values behind it in tag order, word aligned; tile tables as LONG, inline when there is
-// one tile.  false (nothing built): the file would exceed 2^32 - 1 bytes.
-inline bool build_container(int width, int height, int kind, int tile, const GeoTags& geo,
-                            const uint64_t* counts, uint64_t ntiles, Container* out) {
+// The number of overview levels `overviews` asks for: n >= 0 as given, -1: until both sides of the
+// last level are at most the tile's.  null: fine, *n set; else what is wrong with the field.
+inline const char* check_overviews(int width, int height, int tile, int overviews, int* n) {
+  if (overviews < -1 || overviews > kMaxOverviews) return "overviews must be -1 (automatic) or 0..16";
+  const int side = (int)tile_side(tile);
+  int w = width, h = height, k = 0;
+  while (overviews < 0 ? (w > side || h > side) : k < overviews) {
+    if (w == 1 && h == 1) return "overviews: more levels than the raster has (a 1 x 1 level is not reduced)";
+    w = (w + 1) / 2;
+    h = (h + 1) / 2;
+    ++k;
+  }
+  *n = k;
+  return nullptr;
+}
+
+inline std::vector<Level> make_levels(int width, int height, int tile, int overviews) {
+  std::vector<Level> levels;
+  uint64_t first = 0;
+  for (int k = 0; k <= overviews; ++k) {
+    const Level l = {width, height, first, tile_count(width, height, tile)};
+    levels.push_back(l);
+    first += l.ntiles;
+    width = (width + 1) / 2;
+    height = (height + 1) / 2;
+  }
+  return levels;
+}
+
+struct Container {
+  std::vector<uint8_t> head;        // the file up to the first tile
+  uint64_t file_bytes;              // ... and with the tiles
+  std::vector<uint64_t> level_at;   // where every level's tiles start
+};
+
+// The file in front of the tile data for tiles of `counts[t]` bytes (the call's list).  The header,
+// then IFD 0 at offset 8, IFD 1, ..: tags ascending, each IFD's out-of-line values behind it in tag
+// order, word aligned; tile tables as LONG, inline when a level has one tile; the IFDs chained, the
+// last one's next-IFD offset 0.  IFD 0 carries the geo tags; an overview IFD carries NewSubfileType
+// = 1 and none.  Tile data from the next multiple of 16 behind the last values: the coarsest level
+// first, level 0 last, each level's tiles in row-major order, tightly packed.  With one level this is
+// the file of DESIGN 4.16.  false (nothing built): the file would exceed 2^32 - 1 bytes.
+inline bool build_pyramid(const std::vector<Level>& levels, int kind, int tile, const GeoTags& geo,
+                          const uint64_t* counts, Container* out) {
   const uint32_t side = tile_side(tile);
   const int bands = bands_of(kind);
   const bool f32 = kind == kF32;
-  const int ntags = f32 ? 18 : 17;
-  const uint32_t ifd_at = 8;
-  const uint64_t extra_at = ifd_at + 2 + (uint64_t)ntags * 12 + 4;
+  const size_t L = levels.size();
+  struct Where {
+    uint64_t ifd_at, bits_at, offs_at, cnts_at, fmt_at, scale_at, tie_at, keys_at, ascii_at;
+    int ntags;
+  };
+  std::vector<Where> where(L);
   // sizes first: nothing is allocated for a file that is refused
   auto even = [](uint64_t n) { return n + (n & 1u); };
-  uint64_t at = extra_at;
+  uint64_t at = 8;
   auto place = [&](uint64_t n) {
     const uint64_t a = at;
     at += even(n);
     return a;
   };
-  const uint64_t bits_at = bands == 3 ? place(6) : 0;
-  const uint64_t offs_at = ntiles > 1 ? place(4 * ntiles) : 0;
-  const uint64_t cnts_at = ntiles > 1 ? place(4 * ntiles) : 0;
-  const uint64_t fmt_at = bands == 3 ? place(6) : 0;
-  const uint64_t scale_at = place(sizeof(geo.scale));
-  const uint64_t tie_at = place(sizeof(geo.tie));
-  const uint64_t keys_at = place(sizeof(geo.keys));
-  const uint64_t ascii_at = place(geo.ascii.size() + 1);
+  for (size_t k = 0; k < L; ++k) {
+    Where& w = where[k];
+    const uint64_t ntiles = levels[k].ntiles;
+    w.ntags = k == 0 ? (f32 ? 18 : 17) : (f32 ? 15 : 14);
+    w.ifd_at = place(2 + (uint64_t)w.ntags * 12 + 4);
+    w.bits_at = bands == 3 ? place(6) : 0;
+    w.offs_at = ntiles > 1 ? place(4 * ntiles) : 0;
+    w.cnts_at = ntiles > 1 ? place(4 * ntiles) : 0;
+    w.fmt_at = bands == 3 ? place(6) : 0;
+    w.scale_at = w.tie_at = w.keys_at = w.ascii_at = 0;
+    if (k == 0) {
+      w.scale_at = place(sizeof(geo.scale));
+      w.tie_at = place(sizeof(geo.tie));
+      w.keys_at = place(sizeof(geo.keys));
+      w.ascii_at = place(geo.ascii.size() + 1);
+    }
+    if (at > 0xFFFFFFFFull) return false;
+  }
   const uint64_t data_at = (at + 15u) & ~(uint64_t)15u;
   uint64_t total = data_at;
-  for (uint64_t t = 0; t < ntiles; ++t) {
-    if (counts[t] > 0xFFFFFFFFull || total + counts[t] > 0xFFFFFFFFull) return false;
-    total += counts[t];
+  std::vector<uint64_t> level_at(L);
+  for (size_t k = L; k-- > 0;) {
+    level_at[k] = total;
+    for (uint64_t t = 0; t < levels[k].ntiles; ++t) {
+      const uint64_t n = counts[levels[k].first + t];
+      if (n > 0xFFFFFFFFull || total + n > 0xFFFFFFFFull) return false;
+      total += n;
+    }
   }
   std::vector<uint8_t>& head = out->head;
   head.assign((size_t)data_at, 0);
-  auto put16 = [&](uint64_t where, uint16_t v) { std::memcpy(head.data() + where, &v, 2); };
-  auto put32 = [&](uint64_t where, uint32_t v) { std::memcpy(head.data() + where, &v, 4); };
-  uint64_t run = data_at;
-  for (uint64_t t = 0; t < ntiles && ntiles > 1; ++t) {
-    put32(offs_at + 4 * t, (uint32_t)run);
-    put32(cnts_at + 4 * t, (uint32_t)counts[t]);
-    run += counts[t];
-  }
-  if (bands == 3) {
-    for (int k = 0; k < 3; ++k) {
-      put16(bits_at + 2 * k, 8);
-      put16(fmt_at + 2 * k, 1);
-    }
-  }
-  std::memcpy(head.data() + scale_at, geo.scale, sizeof(geo.scale));
-  std::memcpy(head.data() + tie_at, geo.tie, sizeof(geo.tie));
-  std::memcpy(head.data() + keys_at, geo.keys, sizeof(geo.keys));
-  std::memcpy(head.data() + ascii_at, geo.ascii.c_str(), geo.ascii.size() + 1);
-  const Tag tags[18] = {
-      {256, kLong, 1, (uint32_t)width},
-      {257, kLong, 1, (uint32_t)height},
-      {258, kShort, (uint32_t)bands, bands == 3 ? (uint32_t)bits_at : f32 ? 32u : 8u},
-      {259, kShort, 1, 8},                          // Adobe Deflate
-      {262, kShort, 1, bands == 3 ? 2u : 1u},       // RGB / BlackIsZero
-      {277, kShort, 1, (uint32_t)bands},
-      {284, kShort, 1, 1},                          // pixel interleaved
-      {317, kShort, 1, f32 ? 3u : 2u},              // floating point / horizontal differencing
-      {322, kLong, 1, side},
-      {323, kLong, 1, side},
-      {324, kLong, (uint32_t)ntiles, ntiles > 1 ? (uint32_t)offs_at : (uint32_t)data_at},
-      {325, kLong, (uint32_t)ntiles, ntiles > 1 ? (uint32_t)cnts_at : (uint32_t)counts[0]},
-      {339, kShort, (uint32_t)bands, bands == 3 ? (uint32_t)fmt_at : f32 ? 3u : 1u},
-      {33550, kDouble, 3, (uint32_t)scale_at},
-      {33922, kDouble, 6, (uint32_t)tie_at},
-      {34735, kShort, 32, (uint32_t)keys_at},
-      {34737, kAscii, (uint32_t)geo.ascii.size() + 1, (uint32_t)ascii_at},
-      {42113, kAscii, 4, 0x006E616Eu},              // GDAL_NODATA "nan", inline
-  };
+  auto put16 = [&](uint64_t where_, uint16_t v) { std::memcpy(head.data() + where_, &v, 2); };
+  auto put32 = [&](uint64_t where_, uint32_t v) { std::memcpy(head.data() + where_, &v, 4); };
   head[0] = 'I';
   head[1] = 'I';
   put16(2, 42);
-  put32(4, ifd_at);
-  put16(ifd_at, (uint16_t)ntags);
-  for (int k = 0; k < ntags; ++k) {
-    const uint64_t e = ifd_at + 2 + 12 * (uint64_t)k;
-    put16(e, tags[k].tag);
-    put16(e + 2, tags[k].type);
-    put32(e + 4, tags[k].count);
-    put32(e + 8, tags[k].value);
+  put32(4, (uint32_t)where[0].ifd_at);
+  for (size_t k = 0; k < L; ++k) {
+    const Where& w = where[k];
+    const uint64_t ntiles = levels[k].ntiles;
+    const uint64_t* cnt = counts + levels[k].first;
+    uint64_t run = level_at[k];
+    for (uint64_t t = 0; t < ntiles && ntiles > 1; ++t) {
+      put32(w.offs_at + 4 * t, (uint32_t)run);
+      put32(w.cnts_at + 4 * t, (uint32_t)cnt[t]);
+      run += cnt[t];
+    }
+    if (bands == 3) {
+      for (int b = 0; b < 3; ++b) {
+        put16(w.bits_at + 2 * b, 8);
+        put16(w.fmt_at + 2 * b, 1);
+      }
+    }
+    if (k == 0) {
+      std::memcpy(head.data() + w.scale_at, geo.scale, sizeof(geo.scale));
+      std::memcpy(head.data() + w.tie_at, geo.tie, sizeof(geo.tie));
+      std::memcpy(head.data() + w.keys_at, geo.keys, sizeof(geo.keys));
+      std::memcpy(head.data() + w.ascii_at, geo.ascii.c_str(), geo.ascii.size() + 1);
+    }
+    const Tag tags[19] = {
+        {254, kLong, 1, 1},                           // NewSubfileType: a reduced-resolution image (overviews only)
+        {256, kLong, 1, (uint32_t)levels[k].width},
+        {257, kLong, 1, (uint32_t)levels[k].height},
+        {258, kShort, (uint32_t)bands, bands == 3 ? (uint32_t)w.bits_at : f32 ? 32u : 8u},
+        {259, kShort, 1, 8},                          // Adobe Deflate
+        {262, kShort, 1, bands == 3 ? 2u : 1u},       // RGB / BlackIsZero
+        {277, kShort, 1, (uint32_t)bands},
+        {284, kShort, 1, 1},                          // pixel interleaved
+        {317, kShort, 1, f32 ? 3u : 2u},              // floating point / horizontal differencing
+        {322, kLong, 1, side},
+        {323, kLong, 1, side},
+        {324, kLong, (uint32_t)ntiles, ntiles > 1 ? (uint32_t)w.offs_at : (uint32_t)level_at[k]},
+        {325, kLong, (uint32_t)ntiles, ntiles > 1 ? (uint32_t)w.cnts_at : (uint32_t)cnt[0]},
+        {339, kShort, (uint32_t)bands, bands == 3 ? (uint32_t)w.fmt_at : f32 ? 3u : 1u},
+        {33550, kDouble, 3, (uint32_t)w.scale_at},    // (IFD 0 only, as the three behind it)
+        {33922, kDouble, 6, (uint32_t)w.tie_at},
+        {34735, kShort, 32, (uint32_t)w.keys_at},
+        {34737, kAscii, (uint32_t)geo.ascii.size() + 1, (uint32_t)w.ascii_at},
+        {42113, kAscii, 4, 0x006E616Eu},              // GDAL_NODATA "nan", inline (f32 only)
+    };
+    put16(w.ifd_at, (uint16_t)w.ntags);
+    uint64_t e = w.ifd_at + 2;
+    for (int t = 0; t < 19; ++t) {
+      const bool geo_tag = tags[t].tag >= 33550 && tags[t].tag <= 34737;
+      if ((tags[t].tag == 254 && k == 0) || (geo_tag && k != 0) || (tags[t].tag == 42113 && !f32)) continue;
+      put16(e, tags[t].tag);
+      put16(e + 2, tags[t].type);
+      put32(e + 4, tags[t].count);
+      put32(e + 8, tags[t].value);
+      e += 12;
+    }
+    // (the last IFD's four bytes behind the entries stay zero: no further IFD)
+    if (k + 1 < L) put32(e, (uint32_t)where[k + 1].ifd_at);
   }
-  // (the four bytes behind the entries stay zero: no further IFD)
   out->file_bytes = total;
+  out->level_at = level_at;
   return true;
 }
 
-// the bytes of the file in front of its tiles
+// ... of a file without overviews
+inline bool build_container(int width, int height, int kind, int tile, const GeoTags& geo,
+                            const uint64_t* counts, uint64_t ntiles, Container* out) {
+  (void)ntiles;
+  return build_pyramid(make_levels(width, height, tile, 0), kind, tile, geo, counts, out);
+}
+
+// the bytes of the file in front of its tiles, at the most
 inline uint64_t head_bytes(int kind, uint64_t ntiles) {
   const uint64_t ntags = kind == kF32 ? 18 : 17;
   uint64_t at = 8 + 2 + ntags * 12 + 4;
@@ -212,6 +293,15 @@ inline uint64_t head_bytes(int kind, uint64_t ntiles) {
 inline uint64_t file_bound(int width, int height, int kind, int tile) {
   const uint64_t n = tile_count(width, height, tile);
   return head_bytes(kind, n) + n * pnge::zlib_bound(tile_raw(kind, tile));
+}
+
+// ... with `overviews` (>= 0, checked) levels behind level 0: an overview's IFD and values take no
+// more than IFD 0's
+inline uint64_t file_bound_ovr(int width, int height, int kind, int tile, int overviews) {
+  uint64_t sum = 0;
+  for (const Level& l : make_levels(width, height, tile, overviews))
+    sum += head_bytes(kind, l.ntiles) + l.ntiles * pnge::zlib_bound(tile_raw(kind, tile));
+  return sum;
 }
 
 }  // namespace tiff

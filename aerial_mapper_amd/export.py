@@ -192,30 +192,39 @@ def _geotiff_raster(map_, raster):
     return raster, L.GEOTIFF_KINDS[kind], int(raster.shape[0]), int(raster.shape[1]), int(step)
 
 
-def encode_geotiff(map_, raster, geotransform, utm_zone=32, northern=True, tile=256, cap=None):
+def encode_geotiff(map_, raster, geotransform, utm_zone=32, northern=True, tile=256, cap=None, overviews=0):
     """amhip_geotiff_encode_dev on the map's context: the tiled Deflate GeoTIFF of a north-up raster,
     as bytes.  raster: (H, W) float32 or uint8, or (H, W, 3) uint8 (bands in the order given) -- a
     numpy array, or a torch device tensor (rows may be padded: stride(0) is the step).  cap: bytes
     of the device buffer the file is encoded into (default amhip_geotiff_bound); a file that does
-    not fit raises AMHIP_ERR_ARG."""
+    not fit raises AMHIP_ERR_ARG.  overviews: levels behind level 0, each half the one before it
+    (amhip_geotiff_encode_ovr_dev); -1: until a level fits one tile; 0: none."""
     import torch
     lib = L.load()
     raster, kind, h, w, step = _geotiff_raster(map_, raster)
     if not _is_torch(raster):
         raster = torch.from_numpy(raster).to("cuda:%d" % map_.device)
-    bound = lib.amhip_geotiff_bound(w, h, kind, int(tile))
+    overviews = int(overviews)
+    bound = lib.amhip_geotiff_bound_ovr(w, h, kind, int(tile), overviews) if overviews else \
+        lib.amhip_geotiff_bound(w, h, kind, int(tile))
     out = torch.empty(max(int(bound if cap is None else cap), 1), dtype=torch.uint8, device=raster.device)
     map_.wait_for_torch(raster)
     gt = (C.c_double * 6)(*[float(v) for v in geotransform])
     n = C.c_size_t()
-    L.check(lib.amhip_geotiff_encode_dev(map_._h, C.c_void_p(raster.data_ptr()), step, w, h, kind, int(tile), gt,
-                                         int(utm_zone), int(bool(northern)), C.c_void_p(out.data_ptr()),
-                                         int(out.numel() if cap is None else cap), C.byref(n)))
+    tail = (gt, int(utm_zone), int(bool(northern)), C.c_void_p(out.data_ptr()),
+            int(out.numel() if cap is None else cap), C.byref(n))
+    if overviews:
+        L.check(lib.amhip_geotiff_encode_ovr_dev(map_._h, C.c_void_p(raster.data_ptr()), step, w, h, kind, int(tile),
+                                                 overviews, *tail))
+    else:
+        L.check(lib.amhip_geotiff_encode_dev(map_._h, C.c_void_p(raster.data_ptr()), step, w, h, kind, int(tile),
+                                             *tail))
     return out[:n.value].cpu().numpy().tobytes()
 
 
-def write_geotiff_deflate(map_, filename, raster, geotransform, utm_zone=32, northern=True, tile=256):
-    """amhip_geotiff_write: encode on the map's device, download, write `filename`."""
+def write_geotiff_deflate(map_, filename, raster, geotransform, utm_zone=32, northern=True, tile=256, overviews=0):
+    """amhip_geotiff_write (amhip_geotiff_write_ovr with overviews): encode on the map's device, download,
+    write `filename`."""
     lib = L.load()
     raster, kind, h, w, step = _geotiff_raster(map_, raster)
     gt = (C.c_double * 6)(*[float(v) for v in geotransform])
@@ -224,6 +233,10 @@ def write_geotiff_deflate(map_, filename, raster, geotransform, utm_zone=32, nor
         ptr, on_device = raster.data_ptr(), 1
     else:
         ptr, on_device = raster.ctypes.data, 0
+    if int(overviews):
+        L.check(lib.amhip_geotiff_write_ovr(map_._h, str(filename).encode(), C.c_void_p(ptr), on_device, step, w, h,
+                                            kind, int(tile), int(overviews), gt, int(utm_zone), int(bool(northern))))
+        return
     L.check(lib.amhip_geotiff_write(map_._h, str(filename).encode(), C.c_void_p(ptr), on_device, step, w, h, kind,
                                     int(tile), gt, int(utm_zone), int(bool(northern))))
 
@@ -233,38 +246,55 @@ def _geotiff_kind(kind):
 
 
 def layer_to_geotiff(map_, layer, filename, kind="f32", lower=0.0, upper=255.0, utm_zone=32, northern=True,
-                     tile=256):
+                     tile=256, overviews=0):
     """amhip_layer_write_geotiff: the map's window of a layer as its north-up raster (x easting, y
     northing), georeferenced from the map's own geometry, tiled and Deflate-compressed on the device.
     kind: "f32" (the layer's floats, nodata NaN), "u8" (layer_to_image's rescale) or "rgb8" (the
-    packed colour layer as R, G, B)."""
+    packed colour layer as R, G, B).  overviews: as encode_geotiff's; level 1 reduces the bytes of level 0."""
     lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
+    if int(overviews):
+        L.check(L.load().amhip_layer_write_geotiff_ovr(map_._h, lid, _geotiff_kind(kind), float(lower), float(upper),
+                                                       int(tile), int(overviews), int(utm_zone),
+                                                       int(bool(northern)), str(filename).encode()))
+        return
     L.check(L.load().amhip_layer_write_geotiff(map_._h, lid, _geotiff_kind(kind), float(lower), float(upper),
                                                int(tile), int(utm_zone), int(bool(northern)),
                                                str(filename).encode()))
 
 
 def encode_layer_geotiff(map_, layer, kind="f32", lower=0.0, upper=255.0, utm_zone=32, northern=True, tile=256,
-                         cap=None):
+                         cap=None, overviews=0):
     """amhip_layer_encode_geotiff_dev: layer_to_geotiff's file, as bytes."""
     import torch
     lib = L.load()
     lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
     k = _geotiff_kind(kind)
-    bound = lib.amhip_geotiff_bound(int(map_.window[2]), int(map_.window[3]), k, int(tile))
+    overviews = int(overviews)
+    bound = lib.amhip_geotiff_bound_ovr(int(map_.window[2]), int(map_.window[3]), k, int(tile), overviews) \
+        if overviews else lib.amhip_geotiff_bound(int(map_.window[2]), int(map_.window[3]), k, int(tile))
     out = torch.empty(max(int(bound if cap is None else cap), 1), dtype=torch.uint8,
                       device="cuda:%d" % map_.device)
     n = C.c_size_t()
-    L.check(lib.amhip_layer_encode_geotiff_dev(map_._h, lid, k, float(lower), float(upper), int(tile),
-                                               int(utm_zone), int(bool(northern)), C.c_void_p(out.data_ptr()),
-                                               int(out.numel() if cap is None else cap), C.byref(n)))
+    tail = (int(utm_zone), int(bool(northern)), C.c_void_p(out.data_ptr()),
+            int(out.numel() if cap is None else cap), C.byref(n))
+    if overviews:
+        L.check(lib.amhip_layer_encode_geotiff_ovr_dev(map_._h, lid, k, float(lower), float(upper), int(tile),
+                                                       overviews, *tail))
+    else:
+        L.check(lib.amhip_layer_encode_geotiff_dev(map_._h, lid, k, float(lower), float(upper), int(tile), *tail))
     return out[:n.value].cpu().numpy().tobytes()
 
 
 def session_layer_to_geotiff(session, layer, filename, kind="f32", lower=0.0, upper=255.0, utm_zone=32,
-                             northern=True, tile=256):
-    """amhip_session_layer_write_geotiff: the whole map of a HostSession."""
+                             northern=True, tile=256, overviews=0):
+    """amhip_session_layer_write_geotiff (.._ovr with overviews): the whole map of a HostSession."""
     lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
+    if int(overviews):
+        L.check(L.load().amhip_session_layer_write_geotiff_ovr(session._h, lid, _geotiff_kind(kind), float(lower),
+                                                               float(upper), int(tile), int(overviews),
+                                                               int(utm_zone), int(bool(northern)),
+                                                               str(filename).encode()))
+        return
     L.check(L.load().amhip_session_layer_write_geotiff(session._h, lid, _geotiff_kind(kind), float(lower),
                                                        float(upper), int(tile), int(utm_zone),
                                                        int(bool(northern)), str(filename).encode()))

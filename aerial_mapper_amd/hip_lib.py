@@ -80,6 +80,10 @@ EXPORTS = [
     "amhip_layer_write_geotiff", "amhip_session_layer_write_geotiff",
     "amhip_geotiff_info", "amhip_geotiff_decode_dev", "amhip_layer_decode_geotiff", "amhip_layer_read_geotiff",
     "amhip_session_layer_read_geotiff",
+    "amhip_geotiff_bound_ovr", "amhip_geotiff_encode_ovr_dev", "amhip_geotiff_write_ovr",
+    "amhip_layer_encode_geotiff_ovr_dev", "amhip_layer_write_geotiff_ovr", "amhip_session_layer_write_geotiff_ovr",
+    "amhip_geotiff_levels", "amhip_geotiff_level_info", "amhip_geotiff_decode_level_dev",
+    "amhip_layer_decode_geotiff_level", "amhip_layer_read_geotiff_level", "amhip_session_layer_read_geotiff_level",
 ]
 
 # amhip_geotiff_*: the raster kinds (the writer takes the first three)
@@ -366,6 +370,25 @@ def load():
     lib.amhip_layer_decode_geotiff.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t]
     lib.amhip_layer_read_geotiff.argtypes = [vp, C.c_int, C.c_char_p]
     lib.amhip_session_layer_read_geotiff.argtypes = [vp, C.c_int, C.c_char_p, vp]
+    # ... with overviews, and by level
+    lib.amhip_geotiff_bound_ovr.restype = C.c_size_t
+    lib.amhip_geotiff_bound_ovr.argtypes = [C.c_int] * 5
+    lib.amhip_geotiff_encode_ovr_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f64p,
+                                                 C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.amhip_geotiff_write_ovr.argtypes = [vp, C.c_char_p, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, f64p, C.c_int, C.c_int]
+    lib.amhip_layer_encode_geotiff_ovr_dev.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                                       C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.amhip_layer_write_geotiff_ovr.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                                  C.c_int, C.c_int, C.c_char_p]
+    lib.amhip_session_layer_write_geotiff_ovr.argtypes = lib.amhip_layer_write_geotiff_ovr.argtypes
+    lib.amhip_geotiff_levels.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]
+    lib.amhip_geotiff_level_info.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(GeotiffDesc)]
+    lib.amhip_geotiff_decode_level_dev.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_int, vp, C.c_size_t]
+    lib.amhip_layer_decode_geotiff_level.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t, C.c_int]
+    lib.amhip_layer_read_geotiff_level.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
+    lib.amhip_session_layer_read_geotiff_level.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, vp]
     del u8p
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:

@@ -243,6 +243,10 @@ def geotiff_info(data_or_path):
     data = _file_bytes(data_or_path)
     d = L.GeotiffDesc()
     L.check(L.load().amhip_geotiff_info(data, len(data), C.byref(d)))
+    return _desc_dict(d)
+
+
+def _desc_dict(d):
     out = {n: int(getattr(d, n)) for n in ("width", "height", "bands", "tiled", "tile_width", "tile_height",
                                            "rows_per_strip", "compression", "predictor", "epsg", "raster_type")}
     out["kind"] = _GEOTIFF_KIND_NAMES[int(d.kind)]
@@ -252,13 +256,37 @@ def geotiff_info(data_or_path):
     return out
 
 
-def decode_geotiff(map_, data_or_path, window=None, step=None):
+def geotiff_levels(data_or_path):
+    """amhip_geotiff_levels / amhip_geotiff_level_info (host only): geotiff_info's dict for level 0 and for
+    every overview of the file, coarser and coarser.  A level's geotransform is the base's
+    with the pixel size scaled by the ratio of the widths and of the heights; masks and pages of the IFD
+    chain are passed over."""
+    data = _file_bytes(data_or_path)
+    lib = L.load()
+    n = C.c_int()
+    L.check(lib.amhip_geotiff_levels(data, len(data), C.byref(n)))
+    out = []
+    for k in range(n.value):
+        d = L.GeotiffDesc()
+        L.check(lib.amhip_geotiff_level_info(data, len(data), k, C.byref(d)))
+        out.append(_desc_dict(d))
+    return out
+
+
+def _level_info(data, level):
+    d = L.GeotiffDesc()
+    L.check(L.load().amhip_geotiff_level_info(data, len(data), int(level), C.byref(d)))
+    return _desc_dict(d)
+
+
+def decode_geotiff(map_, data_or_path, window=None, step=None, level=0):
     """amhip_geotiff_decode_dev on the map's context: the pixel window (x0, y0, w, h) of the file (default:
     all of it) as a torch device tensor (h, w) of the file's dtype -- (h, w, 3) uint8 for three bands --
-    and the info.  step: bytes between the tensor's rows (default: packed)."""
+    and the info.  step: bytes between the tensor's rows (default: packed).  level: which level of the file
+    (amhip_geotiff_decode_level_dev); window and info are that level's."""
     import torch
     data = _file_bytes(data_or_path)
-    info = geotiff_info(data)
+    info = _level_info(data, level) if level else geotiff_info(data)
     x0, y0, w, h = (0, 0, info["width"], info["height"]) if window is None else [int(v) for v in window]
     kind = info["kind"]
     dtype = {"f32": torch.float32, "u8": torch.uint8, "rgb8": torch.uint8, "u16": torch.uint16,
@@ -268,19 +296,32 @@ def decode_geotiff(map_, data_or_path, window=None, step=None):
     step = row * item if step is None else int(step)
     buf = torch.zeros((max(h, 1), max(step, item)), dtype=torch.uint8, device="cuda:%d" % map_.device)
     map_.wait_for_torch(buf)
-    L.check(L.load().amhip_geotiff_decode_dev(map_._h, data, len(data), x0, y0, w, h, C.c_void_p(buf.data_ptr()),
-                                              step))
+    if level:
+        L.check(L.load().amhip_geotiff_decode_level_dev(map_._h, data, len(data), int(level), x0, y0, w, h,
+                                                        C.c_void_p(buf.data_ptr()), step))
+    else:
+        L.check(L.load().amhip_geotiff_decode_dev(map_._h, data, len(data), x0, y0, w, h,
+                                                  C.c_void_p(buf.data_ptr()), step))
     out = buf[:, :step - step % item].view(dtype)[:h, :row]
     return (out.unflatten(1, (w, 3)) if kind == "rgb8" else out), info
 
 
-def layer_from_geotiff(map_, layer, data_or_path):
+def layer_from_geotiff(map_, layer, data_or_path, level=0):
     """amhip_layer_decode_geotiff / amhip_layer_read_geotiff: the file under the map's window of `layer`.
     A cell takes the pixel its centre lies in (no resampling, no reprojection); cells outside the raster,
-    on a nodata pixel or on a NaN keep what they hold.  On any error the layer is as it was."""
+    on a nodata pixel or on a NaN keep what they hold.  On any error the layer is as it was.  level: which
+    level of the file (amhip_layer_decode_geotiff_level / .._read_geotiff_level); -1: the coarsest level whose
+    pixels are no larger than the map's cells."""
     lid = L.LAYER_NAMES.index(layer) if isinstance(layer, str) else int(layer)
     lib = L.load()
     map_._touched(L.LAYER_NAMES[lid] if 0 <= lid < len(L.LAYER_NAMES) else layer)
+    if level:
+        if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+            data = bytes(data_or_path)
+            L.check(lib.amhip_layer_decode_geotiff_level(map_._h, lid, data, len(data), int(level)))
+        else:
+            L.check(lib.amhip_layer_read_geotiff_level(map_._h, lid, os.fsencode(data_or_path), int(level)))
+        return
     if isinstance(data_or_path, (bytes, bytearray, memoryview)):
         data = bytes(data_or_path)
         L.check(lib.amhip_layer_decode_geotiff(map_._h, lid, data, len(data)))
@@ -288,7 +329,7 @@ def layer_from_geotiff(map_, layer, data_or_path):
         L.check(lib.amhip_layer_read_geotiff(map_._h, lid, os.fsencode(data_or_path)))
 
 
-def session_layer_from_geotiff(session, layer, path, matrix):
+def session_layer_from_geotiff(session, layer, path, matrix, level=0):
     """amhip_session_layer_read_geotiff: the file under every window of a HostSession, then into `matrix`,
     the layer's host matrix as AerialGridMap.get() shapes it -- float32, shape (cols, rows), C-contiguous --,
     updated in place.  The next session call that is handed the same matrix uploads none of it."""
@@ -296,6 +337,10 @@ def session_layer_from_geotiff(session, layer, path, matrix):
     if not (isinstance(matrix, np.ndarray) and matrix.dtype == np.float32 and matrix.flags.c_contiguous and
             matrix.size == session.grid.rows * session.grid.cols):
         _refuse("session_layer_from_geotiff: matrix: a C-contiguous float32 array of rows * cols cells is expected")
+    if level:
+        L.check(L.load().amhip_session_layer_read_geotiff_level(session._h, lid, os.fsencode(path), int(level),
+                                                                C.c_void_p(matrix.ctypes.data)))
+        return
     L.check(L.load().amhip_session_layer_read_geotiff(session._h, lid, os.fsencode(path),
                                                       C.c_void_p(matrix.ctypes.data)))
 

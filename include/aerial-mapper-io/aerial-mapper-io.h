@@ -140,6 +140,10 @@ class AerialMapperIO {
   // and a file that cannot be written are fatal.
   void writeLayerToGeoTiff(const grid_map::GridMap& map, const std::string& layer, const std::string& filename,
                            int utm_zone, bool northern);
+  // ... with overviews (amhip_session_layer_write_geotiff_ovr): `overviews` levels behind the raster, each
+  // half the one before it, reduced on the GPU; -1: until a level fits one tile; 0: the file above.
+  void writeLayerToGeoTiff(const grid_map::GridMap& map, const std::string& layer, const std::string& filename,
+                           int utm_zone, bool northern, int overviews);
 
   // --- extension: the other way.  A Deflate GeoTIFF -- what writeLayerToGeoTiff wrote, or a terrain model
   // from elsewhere -- under a layer of the map, decoded on the GPU (amhip_session_layer_read_geotiff): a
@@ -149,6 +153,9 @@ class AerialMapperIO {
   // the reader refuses, or one that fails to decode, is fatal with the library's text; the map is then
   // as it was.
   void loadLayerFromGeoTiff(grid_map::GridMap* map, const std::string& layer, const std::string& filename);
+  // ... from a level of the file's pyramid (amhip_session_layer_read_geotiff_level): 0 the raster itself,
+  // k its k-th overview, -1 the coarsest level whose pixels are no larger than the map's cells.
+  void loadLayerFromGeoTiff(grid_map::GridMap* map, const std::string& layer, const std::string& filename, int level);
 
   // --- extension: the same cloud as a binary file (amhip_io_write_point_cloud_binary) and its
   // loader, staged through pinned buffers straight into HBM.

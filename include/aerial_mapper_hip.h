@@ -734,6 +734,59 @@ int amhip_geotiff_decode_dev(amhip_ctx* ctx, const uint8_t* file, size_t len, in
 int amhip_layer_decode_geotiff(amhip_ctx* ctx, int layer, const uint8_t* file, size_t len);
 int amhip_layer_read_geotiff(amhip_ctx* ctx, int layer, const char* filename);
 
+/* ---- GeoTIFF overviews: the pyramid written on the GPU, and read by level (amhip_tiff_overview.hip,
+ * DESIGN 4.18).  Level 0 is the raster as above; level k >= 1 is ceil(w / 2) x ceil(h / 2) of level
+ * k - 1 and is computed from it: pixel (r, c) from rows 2r, 2r + 1 and columns 2c, 2c + 1, clipped at
+ * an odd edge.  f32: the mean of the pixels that are no NaN, added as doubles in the order (2r, 2c),
+ * (2r, 2c + 1), (2r + 1, 2c), (2r + 1, 2c + 1) and rounded to float once; none: the quiet NaN
+ * 0x7FC00000.  u8 / rgb8: (sum + n / 2) / n per band over the n pixels of the block.  For a layer,
+ * level 1 reduces the bytes of level 0 as they lie in the file, not the floats.
+ * `overviews` = n >= 0 writes levels 1..n; -1 writes levels until both sides of the last are at most
+ * the tile's; 0 gives the file of the exports above, byte for byte.  Refused (AMHIP_ERR_ARG, before
+ * any device is touched, the text names the export and `overviews`): n > 16, n < -1, an n that would
+ * reduce a 1 x 1 level.
+ * The file: the header; IFD 0 at byte 8 as above; IFD 1, IFD 2, .. behind it, each word aligned and
+ * followed by its own out-of-line values, chained through the next-IFD offsets.  An overview IFD
+ * carries NewSubfileType (254) = 1, its own size and tile tables, the sample tags of IFD 0, GDAL_NODATA
+ * for f32, and no geo tags.  Tile data from the next multiple of 16: the coarsest level first, level 0
+ * last.  The tiles of all levels are coded as one list in groups bounded by tiffe_scratch_budget_mb;
+ * the bytes do not depend on the grouping.  The 2^32 - 1 byte limit covers the whole file.  No GDAL
+ * ghost header is written: conformance with GDAL's COG validator is not claimed. */
+size_t amhip_geotiff_bound_ovr(int width, int height, int kind, int tile, int overviews);
+int amhip_geotiff_encode_ovr_dev(amhip_ctx* ctx, const void* dev_raster, size_t step, int width, int height,
+                                 int kind, int tile, int overviews, const double* geotransform, int utm_zone,
+                                 int northern, uint8_t* dev_out, size_t cap, size_t* bytes);
+int amhip_geotiff_write_ovr(amhip_ctx* ctx, const char* filename, const void* raster, int on_device,
+                            size_t step, int width, int height, int kind, int tile, int overviews,
+                            const double* geotransform, int utm_zone, int northern);
+int amhip_layer_encode_geotiff_ovr_dev(amhip_ctx* ctx, int layer, int kind, float lower, float upper, int tile,
+                                       int overviews, int utm_zone, int northern, uint8_t* dev_out, size_t cap,
+                                       size_t* bytes);
+int amhip_layer_write_geotiff_ovr(amhip_ctx* ctx, int layer, int kind, float lower, float upper, int tile,
+                                  int overviews, int utm_zone, int northern, const char* filename);
+
+/* Reading by level.  The IFD chain is walked with every IFD and value checked to lie inside the file;
+ * more than 64 IFDs, or an offset that comes twice, is refused.  Level 0 is IFD 0; level k >= 1 is
+ * the k-th later IFD whose NewSubfileType has bit 0 set and bit 2 (mask) clear; masks and pages (254
+ * absent or bit 0 clear) are passed over.  A level passes the checks of IFD 0 when it is asked for
+ * (the text names the level and the IFD), has IFD 0's kind, may be tiled or stripped differently, and
+ * is no larger than the level before it in either dimension and smaller in one.  Its geotransform
+ * is GT0, GT3 of the base, GT1 * W0 / Wk and GT5 * H0 / Hk in IEEE double; nodata is the base's.
+ *   amhip_geotiff_levels       host only: 1 + the number of overview IFDs
+ *   amhip_geotiff_level_info   host only: a level's description; level 0: amhip_geotiff_info's
+ *   amhip_geotiff_decode_level_dev   amhip_geotiff_decode_dev on a level's chunks
+ *   amhip_layer_decode_geotiff_level / amhip_layer_read_geotiff_level   the level under the layer;
+ *                              level -1: the coarsest level with GT1_k <= res and -GT5_k <= res for the
+ *                              map's resolution, level 0 when there is none.  A chunk that fails names
+ *                              the level and the chunk; the layer is then as it was.
+ *   amhip_session_layer_read_geotiff_level   (below) */
+int amhip_geotiff_levels(const uint8_t* file, size_t len, int* n);
+int amhip_geotiff_level_info(const uint8_t* file, size_t len, int level, amhip_geotiff_desc* desc);
+int amhip_geotiff_decode_level_dev(amhip_ctx* ctx, const uint8_t* file, size_t len, int level, int x0, int y0,
+                                   int w, int h, void* dev_out, size_t step);
+int amhip_layer_decode_geotiff_level(amhip_ctx* ctx, int layer, const uint8_t* file, size_t len, int level);
+int amhip_layer_read_geotiff_level(amhip_ctx* ctx, int layer, const char* filename, int level);
+
 /* grid_map_msgs/GridMap in ROS 1 wire format, as GridMapRosConverter::toMessage fills it for
  * AerialGridMap::publishOnce / publishUntilShutdown (aerial-mapper-grid-map.cc:51-72).
  * _bytes: size of the message; _layout: writes everything except the layers' float payloads and
@@ -1118,6 +1171,13 @@ int amhip_session_layer_write_geotiff(amhip_session* s, int layer, int kind, flo
  * afterwards: the next call that is handed the same matrix uploads no byte of it.  On any error no
  * window's layer and no cell of the matrix has changed. */
 int amhip_session_layer_read_geotiff(amhip_session* s, int layer, const char* filename, float* matrix);
+/* ... with overviews (amhip_geotiff_write_ovr of the assembled raster: the single context's pyramid),
+ * and from a level of the file (-1: the automatic choice, the same for every window). */
+int amhip_session_layer_write_geotiff_ovr(amhip_session* s, int layer, int kind, float lower, float upper,
+                                          int tile, int overviews, int utm_zone, int northern,
+                                          const char* filename);
+int amhip_session_layer_read_geotiff_level(amhip_session* s, int layer, const char* filename, int level,
+                                           float* matrix);
 
 /* ---- tuning knobs: the ONE door for switches that select among correct implementations ----------
  * (tests force every path through them, A-B timing flips them; none is needed in normal use).
