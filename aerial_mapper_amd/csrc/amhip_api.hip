@@ -474,7 +474,9 @@ static int make_dsm_params(const Ctx& c, int radius_sq,
   // one lane per cell on the global bins, the round-1 kernel)
   if (p.knn_k && tuning_on("knn_global_bins")) p.lds_ok = 0;
   p.fx_ok = 0;
-  if (p.lds_ok && mode == 0 && !c.dsm_exact && !c.dsm_exact_now && rec_fits) {
+  // (the capped mode always runs the FP64 pipeline -- sorted doubles, no records: its gathers read
+  // nothing else, whatever the precision mode)
+  if (p.lds_ok && mode == 0 && !c.dsm_exact && !c.dsm_exact_now && !c.dsm_knn && rec_fits) {
     int S = 28;
     while (((long long)(w0 + 2) << S) >= (1LL << 31)) --S;
     const double scale2 = std::ldexp(1.0, 2 * S);

@@ -28,6 +28,7 @@
 
 #include "amhip_common.h"
 #include "amhip_device.h"
+#include "amhip_knn_set.h"
 
 #ifndef AMHIP_GATHER_UNROLL
 #define AMHIP_GATHER_UNROLL 2
@@ -330,55 +331,8 @@ __device__ __forceinline__ bool cell_fallback_global(const DsmParams& p,
 }
 
 // ---- OPTIONAL capped mode (amhip_ctx_set_dsm_knn; not a reference code path) ----------
-// The k nearest points of the search result, kept sorted by ascending d2 in registers
-// (nanoflann::KNNResultSet::addPoint, nanoflann.hpp:100-125: a later arrival never
-// displaces an equal distance).
-constexpr int kMaxKnn = 8;
-template <int K>
-struct KnnSetT {
-  double d2[K], z[K];
-  double worst;   // d2 of the k-th entry once the set is full, +inf before: what a candidate has to beat
-  int n;          // (a scalar of its own: s->d2[k - 1] with a run-time k would move the arrays to scratch memory)
-};
-typedef KnnSetT<kMaxKnn> KnnSet;
-
-// (K: the registers the set takes, k <= K the cap in force)
-template <int K>
-__device__ __forceinline__ void knn_add(KnnSetT<K>* s, int k, double d2, double z) {
-  if (!(d2 < s->worst)) return;
-  // shift the strictly greater entries up (static indices only: the set lives in registers)
-  double cd = d2, cz = z;
-  bool inserted = false;  // from the insertion point on every entry moves up by one
-#pragma unroll
-  for (int q = 0; q < K; ++q) {
-    if (q < k) {
-      const bool here = inserted || q >= s->n || cd < s->d2[q];
-      const double od = s->d2[q], oz = s->z[q];
-      if (here) {
-        s->d2[q] = cd;
-        s->z[q] = cz;
-        cd = od;
-        cz = oz;
-        inserted = true;
-      }
-    }
-  }
-  if (s->n < k) ++s->n;
-  if (s->n == k) {
-#pragma unroll
-    for (int q = 0; q < K; ++q)
-      if (q == k - 1) s->worst = s->d2[q];
-  }
-}
-
-template <int K>
-__device__ __forceinline__ void knn_init(KnnSetT<K>* s) {
-  s->n = 0;
-  s->worst = __builtin_huge_val();
-#pragma unroll
-  for (int q = 0; q < K; ++q) s->d2[q] = s->z[q] = 0.0;
-}
-
+// The k nearest points of the search result, kept sorted by ascending d2 in registers:
+// KnnSetT, knn_add, knn_init of amhip_knn_set.h (host-testable: tests/cpp/knn_set_emul.cc).
 __device__ __forceinline__ void knn_scan(const DsmParams& p, const uint32_t* __restrict__ start,
                                          const Pts P, double qx, double qy,
                                          int i, int j, int w, double T, KnnSet* s) {
@@ -2607,8 +2561,9 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
       }
       if (p.knn_k > 0) {
         AMHIP_TRY(hipGetLastError());
-        // (known wart, ADVICE: this return leaves host_tile_stats as the previous call wrote them;
-        // the follow-up that refreshes them for the capped mode removes it -- not this change)
+        // (a capped call is always the FP64 pipeline -- make_dsm_params: no fx_ok under the cap --, so
+        // the prologue's last workgroup has mirrored this call's tile counters into host_tile_stats
+        // and last_call_f32 is false: nothing of the tail below is owed)
         return AMHIP_OK;
       }
       if (f32)

@@ -177,9 +177,9 @@ int amhip_ctx_set_dsm_precision(amhip_ctx* ctx, int mode);
  * take part in the weighting.  k = 0 (default) = the reference's behaviour: every point of
  * the search.  NOT a reference code path -- dsm.cc:127-172 has no k -- so its parity is
  * unpinned by the reference (oracle: KNNResultSet on the reference's vendored tree); it is a
- * separately reported extra, never the graded mode.  1 <= k <= 8; runs one lane per cell on
- * the global bins (FP64, true divisions in ascending-distance order: bit-identical to the
- * oracle but for exact distance ties). */
+ * separately reported extra, never the graded mode.  1 <= k <= 8; always the FP64 pipeline,
+ * whatever amhip_ctx_set_dsm_precision says (true divisions in ascending-distance order:
+ * bit-identical to the oracle but for exact distance ties). */
 int amhip_ctx_set_dsm_knn(amhip_ctx* ctx, int k);
 
 /* Wait for everything enqueued on the context and return the sticky status

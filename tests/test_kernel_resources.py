@@ -55,6 +55,10 @@ BUDGETS = [
     ("k_dsm_gather_f32_wideILi512ELi16ELi7680E", 2, 0),
     ("18k_dsm_gather_denseILb0E", 3, 0),
     ("18k_dsm_gather_denseILb1E", 3, 26),                 # (cold spills, all outside the candidate loop: DESIGN 4.2)
+    # the capped mode (amhip_knn_set.h: a set of 8 in registers).  No margin: the numbers of the commit before
+    # the set moved into its header (103 / 92 VGPRs); the (16, 2048) and (32, 2048) shapes are the same
+    ("k_dsm_gather_tiled_knnILi512ELi16ELi1024E", 4, 0),
+    ("16k_dsm_gather_knnE", 5, 0),
 ]
 
 
@@ -63,3 +67,10 @@ def test_hot_kernel_budget(needle, min_waves, max_spill):
     k = _one(_kernels(), needle)
     assert k["Occupancy"] >= min_waves, k
     assert k["VGPRs Spill"] <= max_spill, k
+
+
+@pytest.mark.parametrize("needle", ["k_dsm_gather_tiled_knnILi512ELi16ELi1024E", "16k_dsm_gather_knnE"])
+def test_capped_gather_keeps_its_set_out_of_scratch(needle):
+    """KnnSetT is indexed statically and `worst` is cached so that the arrays stay in registers."""
+    k = _one(_kernels(), needle)
+    assert k["ScratchSize"] == 0 and k["VGPRs Spill"] == 0, k
