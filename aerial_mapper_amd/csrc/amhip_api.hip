@@ -178,13 +178,7 @@ HPose hpose_compose(const HPose& A, const HPose& B) {
 // ---------------------------------------------------------------------------
 // parameter set-up
 // ---------------------------------------------------------------------------
-static void grid_bases(const amhip_grid_desc& g, double* bx, double* by) {
-  // getPosition: (mapPosition + (0.5*length - 0.5*resolution)) + resolution*(-i)
-  const double off_x = 0.5 * g.length_x - 0.5 * g.resolution;
-  const double off_y = 0.5 * g.length_y - 0.5 * g.resolution;
-  *bx = g.pos_x + off_x;
-  *by = g.pos_y + off_y;
-}
+// grid_bases: amhip_dsm_plan.h
 
 // The opt-in single-precision mode protects itself on rough terrain.  A
 // tile whose height range leaves no room under the error bound is done by the FP64 kernel, which
@@ -197,21 +191,47 @@ static void grid_bases(const amhip_grid_desc& g, double* bx, double* by) {
 // bar of the single-precision mode holds.  tuning knob dsm_no_rough_switch disables the switch.
 static void dsm_rough_policy(Ctx* c) {
   const bool off = tuning_on("dsm_no_rough_switch");  // (looked up per call: tests toggle it)
-  c->dsm_exact_now = 0;
-  if (c->dsm_exact || c->dsm_knn || off) return;
-  if (c->rough_hold > 0) {
-    --c->rough_hold;
-    c->dsm_exact_now = 1;
-    return;
-  }
-  if (c->last_call_f32 && c->last_ntiles > 0 && c->host_tile_stats) {
-    const volatile unsigned* hs = c->host_tile_stats;
-    const double rejected = (double)hs[4] + (double)hs[5] + (double)hs[6] + (double)hs[7];
-    if (rejected * 2.0 > (double)c->last_ntiles) {
-      c->rough_hold = 15;
-      c->dsm_exact_now = 1;
-    }
-  }
+  RoughState s = {c->rough_hold, c->last_call_f32, c->last_ntiles};
+  c->dsm_exact_now = rough_policy_step(&s, !(c->dsm_exact || c->dsm_knn || off), c->host_tile_stats);
+  c->rough_hold = s.hold;
+}
+
+// The plan of a DSM call on window (i0, j0, rows, cols) of the context's map (amhip_dsm_plan.h: plan_dsm;
+// mode and pcl_lambda as there): the context's precision state and the tuning knobs of this moment.
+static int make_dsm_plan(const Ctx& c, int i0, int j0, int rows, int cols, int radius_sq, double center_easting,
+                         double center_northing, DsmParams* out, int mode, int pcl_lambda, size_t num_points) {
+  DsmPlanInput in = {};
+  in.grid = c.grid;
+  in.win_i0 = i0;
+  in.win_j0 = j0;
+  in.win_rows = rows;
+  in.win_cols = cols;
+  in.radius_sq = radius_sq;
+  in.center_easting = center_easting;
+  in.center_northing = center_northing;
+  in.mode = mode;
+  in.pcl_lambda = pcl_lambda;
+  in.num_points = num_points;
+  in.dsm_exact = c.dsm_exact;
+  in.dsm_exact_now = c.dsm_exact_now;
+  in.dsm_knn = c.dsm_knn;
+  in.canon_all = tuning_on("dsm_canon_all") ? 1 : 0;
+  in.p3_min_points = (size_t)tuning("p3_min_points", (double)(1u << 20));
+  in.p3_target = tuning("p3_target", 1536.0);
+  in.p3_cap = (int)tuning("p3_cap", 2048.0);
+  in.knn_global_bins = tuning_on("knn_global_bins") ? 1 : 0;
+#ifdef AMHIP_TIMING_PROBES
+  in.gather_tj = tuning("gather_tj", 0.0);
+  in.fx_theta = tuning("fx_theta", 0.0);
+#endif
+  const char* why = "";
+  return plan_dsm(in, out, &why) ? arg_fail(why) : AMHIP_OK;
+}
+// ... on the context's whole window
+static int make_dsm_params(const Ctx& c, int radius_sq, double center_easting, double center_northing,
+                           DsmParams* out, int mode, int pcl_lambda, size_t num_points) {
+  return make_dsm_plan(c, c.win_i0, c.win_j0, c.win_rows, c.win_cols, radius_sq, center_easting, center_northing,
+                       out, mode, pcl_lambda, num_points);
 }
 
 // A SMALL cloud onto a LARGE resident map (the incremental demo: one stereo pair's 360 K points
@@ -226,8 +246,6 @@ static void dsm_rough_policy(Ctx* c) {
 // written everywhere).  tuning knob dsm_no_subwindow: never.
 // Returns 1: *p_sub is the call's parameter set; 0: run on the whole window; 2: no point near the
 // window, nothing to do; < 0: error.
-static int make_dsm_params(const Ctx& c, int radius_sq, double center_easting, double center_northing,
-                           DsmParams* out, int mode, int pcl_lambda, size_t num_points);
 static int dsm_subwindow(Ctx* c, const double* dev_xyz, size_t n, int radius_sq, double center_easting,
                          double center_northing, const DsmParams& p_full, DsmParams* p_sub) {
   if (n > (1u << 20) || c->cells < (size_t)(4u << 20) || !c->dev_bbox || !c->host_bbox ||
@@ -249,263 +267,13 @@ static int dsm_subwindow(Ctx* c, const double* dev_xyz, size_t n, int radius_sq,
   const size_t sub = (size_t)(i_hi - i_lo + 1) * (size_t)(j_hi - j_lo + 1);
   if (sub * 4 > c->cells) return 0;                     // not small against the map: nothing to win
   // the same context, seen through the sub-window
-  const int wi0 = c->win_i0, wj0 = c->win_j0, wr = c->win_rows, wc = c->win_cols;
-  c->win_i0 = wi0 + i_lo;
-  c->win_j0 = wj0 + j_lo;
-  c->win_rows = i_hi - i_lo + 1;
-  c->win_cols = j_hi - j_lo + 1;
-  rc = make_dsm_params(*c, radius_sq, center_easting, center_northing, p_sub, 0, 1, n);
-  c->win_i0 = wi0;
-  c->win_j0 = wj0;
-  c->win_rows = wr;
-  c->win_cols = wc;
+  rc = make_dsm_plan(*c, c->win_i0 + i_lo, c->win_j0 + j_lo, i_hi - i_lo + 1, j_hi - j_lo + 1, radius_sq,
+                     center_easting, center_northing, p_sub, 0, 1, n);
   if (rc) return -rc;
   p_sub->out_i0 = i_lo;
   p_sub->out_j0 = j_lo;
-  p_sub->out_pitch = wr;
+  p_sub->out_pitch = c->win_rows;
   return 1;
-}
-
-// mode 0: dsm::Dsm ladder.  mode 1: ortho::OrthoFromPcl, one search with the
-// squared radius `radius_sq * pcl_lambda` (pcl_lambda = 1 for the first search,
-// 10, 100, ... for the adaptive retries, ortho-from-pcl.cc:63-71).
-static int make_dsm_params(const Ctx& c, int radius_sq,
-                           double center_easting, double center_northing,
-                           DsmParams* out, int mode, int pcl_lambda,
-                           size_t num_points) {
-  const amhip_grid_desc& g = c.grid;
-  DsmParams p;
-  std::memset(&p, 0, sizeof(p));
-  grid_bases(g, &p.base_x, &p.base_y);
-  p.res = g.resolution;
-  p.inv_res = 1.0 / g.resolution;
-  p.rows = c.win_rows;
-  p.cols = c.win_cols;
-  p.i_off = c.win_i0;
-  p.j_off = c.win_j0;
-  p.sub_x = center_northing;  // dsm.cc:42
-  p.sub_y = center_easting;   // dsm.cc:43
-  {
-    p.canon_all = tuning_on("dsm_canon_all") ? 1 : 0;
-  }
-
-  // Squared search radii in the order dsm.cc:127-144 tries them: the initial
-  // search with T = R, then lambda*R for lambda = 1, 1.1, 1.1^2, ... where
-  // lambda is updated by `lambda *= 1.1` and the loop stops once lambda*R > 7.
-  int n = 0;
-  p.pcl_mode = mode;
-  if (mode == 0) {
-    p.T[n++] = static_cast<double>(radius_sq);
-    double lambda = 1.0;
-    for (;;) {
-      if (n >= kMaxLevels) return arg_fail("radius ladder too long");
-      p.T[n++] = lambda * radius_sq;
-      lambda *= 1.1;
-      if (lambda * radius_sq > 7.0) break;
-    }
-  } else {
-    p.T[n++] = static_cast<double>(pcl_lambda * radius_sq);  // int product, like the reference
-  }
-  p.nlevels = n;
-  double tmax = 0.0;
-  for (int k = 0; k < n; ++k) {
-    // a point within sqrt(T) of the centre of cell i lies in a cell whose index
-    // differs from i by at most floor(sqrt(T)/res + 0.5) (+ slack for rounding)
-    p.w[k] = static_cast<int>(
-        std::floor(std::sqrt(p.T[k]) / g.resolution + 0.5 + 1e-6));
-    if (p.T[k] > tmax) tmax = p.T[k];
-  }
-  int wmax = 0;
-  for (int k = 0; k < n; ++k)
-    if (p.w[k] > wmax) wmax = p.w[k];
-
-  // Bin edge = the first search radius in cells: the LDS gather then needs
-  // exactly one ring of bins around a tile.
-  int B = p.w[0];
-  if (B < 1) B = 1;
-  if (B > 8) B = 8;
-  if (mode == 1 && pcl_lambda > 1) {
-    // adaptive retries: huge radii -> coarse bins, global gather only
-    B = p.w[0] / 4;
-    if (B < 1) B = 1;
-  }
-  p.B = B;
-  p.M = ((wmax + B - 1) / B) * B;
-  const long long ex = (long long)p.rows + 2LL * p.M;
-  const long long ey = (long long)p.cols + 2LL * p.M;
-  p.nbx = static_cast<int>((ex + B - 1) / B);
-  p.nby = static_cast<int>((ey + B - 1) / B);
-  const unsigned long long nbins =
-      (unsigned long long)p.nbx * (unsigned long long)p.nby;
-  if (nbins + 1 >= 0xFFFFFFFFull) return arg_fail("grid too large for 32-bit bin ids");
-
-  // ---- three-pass partition sort plan (amhip_dsm.hip) ---------------------------
-  // Worth it once the cloud is large enough that the sort is bandwidth bound;
-  // sub-partitions are sized for ~1.5 K points (a pass-3 workgroup sorts up to
-  // p3_cap of them in LDS, more through a direct-placement fallback).
-  p.p3_n1 = 0;
-  {
-    const size_t min_pts = (size_t)tuning("p3_min_points", (double)(1u << 20));
-    const int r1 = (p.nby + 127) / 128;
-    const int n1 = (p.nby + r1 - 1) / r1;
-    int cmax = 256 / r1;
-    if (r1 <= 256 && cmax >= 1 && num_points >= min_pts) {
-      const double target = tuning("p3_target", 1536.0);
-      int cc = static_cast<int>((double)num_points / ((double)p.nby * target) + 0.5);
-      if (cc < 1) cc = 1;
-      if (cc > cmax) cc = cmax;
-      if (cc > p.nbx) cc = p.nbx;
-      const int w = (p.nbx + cc - 1) / cc;
-      if (w <= 4096 && (long long)n1 * r1 * cc <= 32768) {
-        p.p3_r1 = r1;
-        p.p3_c = cc;
-        p.p3_w = w;
-        p.p3_n1 = n1;
-        p.p3_n2 = r1 * cc;
-        p.p3_cap = (int)tuning("p3_cap", 2048.0);
-        if (p.p3_cap > 2048) p.p3_cap = 2048;  // kP3PlaceMaxCap
-        if (p.p3_cap < 64) p.p3_cap = 64;
-      }
-    }
-  }
-
-  // ---- division-free keys for the sort passes (DsmParams::mul_*) --------------------------
-  {
-    auto magic = [](unsigned long long n_max, int d) -> unsigned {
-      if (d <= 1) return 0u;
-      if (n_max * (unsigned long long)d >= (1ull << 32)) return 0xFFFFFFFFu;
-      return (unsigned)((1ull << 32) / (unsigned long long)d) + 1u;
-    };
-    const unsigned long long cells_max =
-        (unsigned long long)std::max(p.rows, p.cols) + 2ull * (unsigned long long)p.M + 1ull;
-    p.mul_B = magic(cells_max, p.B);
-    p.mul_r1 = p.p3_n1 ? magic((unsigned long long)p.nby + 1ull, p.p3_r1) : 0xFFFFFFFFu;
-    p.mul_w = p.p3_n1 ? magic((unsigned long long)p.nbx + 1ull, p.p3_w) : 0xFFFFFFFFu;
-  }
-
-  // ---- LDS-tiled gather set-up (amhip_dsm.hip: k_dsm_gather_tiled) ----------
-  const int kTileI = 64;
-  // (the single-precision mode's sort records hold a cell in 16 + 16 bits and a row of the cloud
-  // in 32: larger maps / clouds stay in FP64)
-  const bool rec_fits = (long long)p.rows + 2LL * p.M <= 65535 && (long long)p.cols + 2LL * p.M <= 65535 &&
-                        num_points < 0xFFFFFFFFull;
-  // Tile height and LDS point capacity from the cloud's MEAN density (points
-  // per cell): the tile's region must hold E + 5 sqrt(E) points.  64x16 tiles
-  // with 1024 slots need ~37 KB of LDS -> 4 workgroups per CU; denser clouds
-  // take 64x32 / 2048 (2 per CU), then 64x16 / 2048.  A tile that still
-  // overflows (clustered cloud) takes the global-memory path on its own.
-  int kTileJ = 32;
-  int cap = 2048;
-  {
-    const int w0h = p.w[0];
-    const double rho = (double)num_points / ((double)p.rows * (double)p.cols);
-    auto need = [&](int tj) {
-      // bins an interior tile's region spans (same integer arithmetic as the kernel)
-      const int bi = (kTileI + kTileI - 1 + w0h + p.M) / B - (kTileI - w0h + p.M) / B + 1;
-      const int bj = (tj + tj - 1 + w0h + p.M) / B - (tj - w0h + p.M) / B + 1;
-      const double e = rho * (double)(bi * B) * (double)(bj * B);
-      return e + 5.0 * std::sqrt(e);
-    };
-    // (single-precision mode: 16-byte records, so 4096 points still leave two workgroups per
-    // CU -- clouds of ~1.2 .. 2.2 points per cell keep the one-workgroup-per-tile launch)
-    const bool want_f32 = mode == 0 && !c.dsm_exact && !c.dsm_exact_now && !c.dsm_knn && rec_fits;
-    if (need(16) <= 1024.0) {
-      kTileJ = 16;
-      cap = 1024;
-    } else if (need(32) <= 2048.0) {
-      kTileJ = 32;
-      cap = 2048;
-    } else if (need(16) <= 2048.0 || !want_f32 || need(16) > 7680.0) {
-      kTileJ = 16;
-      cap = 2048;
-    } else {
-      kTileJ = 16;
-      cap = need(16) <= 4096.0 ? 4096 : 7680;  // (7680: one workgroup per CU)
-    }
-#ifdef AMHIP_TIMING_PROBES
-    if (tuning("gather_tj", 0.0) != 0.0) {  // tuning knob
-      kTileJ = (int)tuning("gather_tj", 0.0) == 16 ? 16 : 32;
-      cap = (kTileJ == 16 && need(16) <= 1024.0) ? 1024 : 2048;  // (the density still picks the capacity)
-    }
-#endif
-  }
-  p.tile_j = kTileJ;
-  p.tiles_i = (p.rows + kTileI - 1) / kTileI;
-  p.tiles_j = (p.cols + kTileJ - 1) / kTileJ;
-  const int w0 = p.w[0];
-  p.lds_ok = (w0 >= 1 && w0 <= kMaxW0 && !(mode == 1 && pcl_lambda > 1)) ? 1 : 0;
-  if (p.lds_ok) {
-    // disc-shaped window: a point whose cell row differs by dj from the query's
-    // is at least (|dj| - 0.5) * res away in y; what is left of the radius
-    // bounds its column distance.
-    const double r2 = p.T[0] / (g.resolution * g.resolution);  // in cells^2
-    for (int dj = -w0; dj <= w0; ++dj) {
-      const double dy = std::fabs((double)dj) - 0.5 - 1e-6;
-      const double rem = dy > 0.0 ? r2 - dy * dy : r2;
-      int wr = rem > 0.0 ? static_cast<int>(std::floor(std::sqrt(rem) + 0.5 + 1e-6)) : 0;
-      if (wr > w0) wr = w0;
-      p.wr[dj + w0] = wr;
-    }
-    for (int r = 0; r <= 2 * w0 + 1; ++r) {
-      const int a = r <= 2 * w0 ? p.wr[r] : 0;
-      const int b = r >= 1 ? p.wr[r - 1] : 0;
-      p.wr2[r] = a > b ? a : b;
-    }
-    const int rw = kTileI + 2 * w0 + 2 * (B - 1);
-    const int rh = kTileJ + 2 * w0 + 2 * (B - 1);
-    for (int k = 0; k <= w0; ++k)
-      p.wrp[k] = p.wr2[2 * k] > p.wr2[2 * k + 1] ? p.wr2[2 * k] : p.wr2[2 * k + 1];
-    // row pairs, +1 pair for the parity shift, +1 spill; (lds_cells + 1) entries, a multiple of
-    // four with three to spare: the single-precision gather clears / scans the table in quads
-    p.lds_cells = ((rw * (rh + 4) + 4 + 3) & ~3) - 1;
-    p.lds_cap = cap;  // == kCap of the kernel instance
-    const size_t bytes = ((size_t)p.lds_cap + 2) * 24 + ((size_t)p.lds_cells + 1) * 4 +
-                         (96 + 97 + 24 + 4 + 4 * kMaxW0 + 4) * 4 + (size_t)kTileI * kTileJ * 2 + 64;
-    p.lds_bytes = static_cast<unsigned>((bytes + 15) & ~size_t(15));
-    // (a 4096- / 7680-point main launch exists in single precision only; the FP64 kernels then
-    // run on lists with images of their own size, amhip_dsm.hip: dsm_run)
-    if (p.lds_bytes > 150 * 1024 && cap <= 2048) p.lds_ok = 0;
-  }
-  // ---- single-precision gather with exact guards (amhip_dsm.hip: k_dsm_gather_f32) ----
-  // Only for dsm::Dsm (heights): OrthoFromPcl interpolates 8-bit intensities whose spread
-  // (up to 255) leaves no room under the error bound.
-  p.knn_k = mode == 0 ? c.dsm_knn : 0;
-  // (capped mode: the LDS-tiled gather's own build, k_dsm_gather_tiled_knn; tuning knob knn_global_bins:
-  // one lane per cell on the global bins, the round-1 kernel)
-  if (p.knn_k && tuning_on("knn_global_bins")) p.lds_ok = 0;
-  p.fx_ok = 0;
-  // (the capped mode always runs the FP64 pipeline -- sorted doubles, no records: its gathers read
-  // nothing else, whatever the precision mode)
-  if (p.lds_ok && mode == 0 && !c.dsm_exact && !c.dsm_exact_now && !c.dsm_knn && rec_fits) {
-    int S = 28;
-    while (((long long)(w0 + 2) << S) >= (1LL << 31)) --S;
-    const double scale2 = std::ldexp(1.0, 2 * S);
-    const double tc = p.T[0] / (g.resolution * g.resolution) * scale2;
-    // |d2_f32 - d2_reference| <= 3e-7 relative at the search radius; anything
-    // inside +-2e-6 is decided by the FP64 routine
-    const double margin = 2e-6;
-    // (cells within theta of a point go to the FP64 routine: 0.02 -> 0.005 takes 0.07 ms of
-    // redo tails off the 50 M-point gather and costs the error budget a factor 2.2 in eps_w --
-    // a tile's height half-range limit goes from 7.6 to 6.2 m; measured)
-    double theta = 0.005;  // cells
-#ifdef AMHIP_TIMING_PROBES
-    theta = tuning("fx_theta", theta);
-#endif
-    const double q = std::ldexp(1.0, -(S + 1));
-    p.fx_S = S;
-    p.fx_thi = static_cast<float>(tc * (1.0 + margin));
-    p.fx_tlo = static_cast<float>(tc * (1.0 - margin));
-    p.fx_denmax = static_cast<float>(1.0 / (theta * theta * scale2));
-    p.fx_epsw = static_cast<float>(2.0 * std::sqrt(2.0) * q / theta + 4e-7);
-    const size_t bytes = ((size_t)p.lds_cap + 2) * 16 + ((size_t)p.lds_cells + 1) * 4 +
-                         (96 + 97 + 24 + 8 + 4 * kMaxW0 + 4) * 4 + 64 + (size_t)kTileI * kTileJ * 2 + 64;
-    p.lds_bytes_f32 = static_cast<unsigned>((bytes + 15) & ~size_t(15));
-    p.fx_ok = 1;
-  }
-  p.out_i0 = p.out_j0 = 0;
-  p.out_pitch = p.rows;
-  *out = p;
-  return AMHIP_OK;
 }
 
 static void normalize3(double* v) {

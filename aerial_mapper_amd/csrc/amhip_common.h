@@ -12,6 +12,7 @@
 
 #include "aerial_mapper_hip.h"
 #include "amhip_tuning.h"
+#include "amhip_dsm_plan.h"
 #include "amhip_ortho_fold.h"
 
 namespace amhip {
@@ -31,71 +32,8 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line);
 // ---------------------------------------------------------------------------
 // device-side constants
 // ---------------------------------------------------------------------------
-constexpr int kMaxLevels = 24;  // radius ladder: R, then lambda_k * R (<= 22 for R = 1)
-constexpr int kMaxW0 = 16;      // largest first-level window (cells) the LDS gather handles
-
-// Geometry + search parameters of one DSM call, passed by value to kernels.
-struct DsmParams {
-  // grid_map_core getPosition: x_i = base_x + res * (-(double)i)
-  double base_x, base_y, res;
-  int rows, cols;    // size of the window this context owns
-  int i_off, j_off;  // its position inside the (global) map
-  // dsm.cc:42-43: px = p.x - center_northing, py = p.y - center_easting
-  double sub_x, sub_y;
-  // 0: dsm::Dsm (exact hit = CHECK failure); 1: ortho::OrthoFromPcl (exact hit
-  // = that point's value, ortho-from-pcl.cc:91-96)
-  int pcl_mode;
-  // adaptive OrthoFromPcl passes: touch only cells no earlier pass has filled
-  int only_unfilled;
-  // binning: bins of B x B cells, grid extended by M cells on every side
-  double inv_res;
-  int B, M, nbx, nby;
-  // radius ladder (squared radii, exactly the doubles dsm.cc:127-144 uses)
-  int nlevels;
-  double T[kMaxLevels];
-  int w[kMaxLevels];  // conservative window half-width in cells for T[k]
-  // LDS-tiled gather (first level only): per window row dj in [-w0, w0] the
-  // half-width in cells of the disc of squared radius T[0]
-  int lds_ok;                 // 0 -> every tile takes the global-memory path
-  // three-pass partition sort plan (p3_n1 == 0: not used)
-  int p3_r1;                  // bin rows per first-pass partition
-  int p3_c, p3_w;             // column blocks per bin row, bins per column block
-  int p3_n1, p3_n2;           // partitions of pass 1; sub-partitions of each (= p3_r1 * p3_c)
-  int p3_cap;                 // points a pass-3 workgroup can sort in LDS
-  // Every sort pass turns every point into its keys again: four integer divisions by
-  // B / p3_r1 / p3_w per point and pass were ~half of the passes' VALU time.  Multipliers
-  // m = floor(2^32 / d) + 1: n / d == umulhi(n, m) for n * d < 2^32 (0: d == 1; ~0: n * d may
-  // reach 2^32 on this grid -> the real division); div_by() in amhip_sort.hip
-  unsigned mul_B, mul_r1, mul_w;
-  int wr[2 * kMaxW0 + 1];
-  int wr2[2 * kMaxW0 + 2];    // the same for a pair of cells (j, j+1): max of both
-  int wrp[kMaxW0 + 1];        // per trip (window rows 2k, 2k+1 of the pair): max of wr2
-  int lds_cap;                // points the tile's LDS image can hold
-  int lds_cells;              // cell-offset table entries reserved (+1 sentinel)
-  int tile_j;                 // tile height in cells: 32, or 16 for dense clouds
-  int tiles_i, tiles_j;
-  unsigned lds_bytes;
-  // single-precision gather with exact guards (k_dsm_gather_f32): point
-  // positions as 32-bit fixed point in units of 2^-fx_S cells (wrapping: only differences of
-  // at most w0 + 2 cells are ever formed), squared distances in f32 in (2^-fx_S cells)^2
-  // OPTIONAL capped mode (not a reference code path): only the knn_k nearest points of a
-  // cell's search result take part (0 = off = the reference's behaviour)
-  int knn_k;
-  int fx_ok;                  // 0 -> the FP64 gather only; 1 -> the sort leaves 16-byte records
-                              // (amhip_sort.hip, "the record pipeline") and the single-precision
-                              // gather runs on them
-  int fx_S;
-  float fx_thi, fx_tlo;       // T[0] in those units, widened / narrowed by the decision margin
-  float fx_denmax;            // a hit nearer than fx_theta cells makes the weight sum exceed this
-  float fx_epsw;              // bound on the relative error of one weight
-  unsigned lds_bytes_f32;
-  int canon_all;              // tests: every FP64 quotient goes through canonical_search (amhip_dsm.hip)
-  // Where cell (i, j) of THIS call's window lives in the layer it writes: out_i0 + i + (out_j0 + j)
-  // * out_pitch.  A call on the context's whole window: 0, 0, rows.  A small cloud onto a large map
-  // runs on a SUB-window around the cloud's bounding box (amhip_api.hip: dsm_subwindow) and
-  // writes into the full layer.
-  int out_i0, out_j0, out_pitch;
-};
+// kMaxLevels, kMaxW0, kTileI, kMaxRegionRows, DsmParams (geometry + search parameters of one DSM call,
+// passed by value to kernels), the tile lists' numbers: amhip_dsm_plan.h
 
 // The binned cloud as the gather sees it (amhip_dsm.hip: pts_x / pts_y / pts_z; filled by
 // dsm_sort): the doubles pipeline (sorted), the record pipeline of the single-precision

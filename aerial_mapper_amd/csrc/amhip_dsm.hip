@@ -574,25 +574,7 @@ k_dsm_gather_knn(DsmParams p, const uint32_t* __restrict__ start,
 // of its 8 cells, the 2*w0+1 rows of the disc-shaped window: one contiguous
 // span of LDS points per row.  Cells whose first search is empty are queued
 // in LDS and finished by the fallback path on the global bins.
-constexpr int kTileI = 64;
-constexpr int kMaxRegionRows = 96;  // bin rows of a region
-constexpr int kListHdr = 8;         // counters in front of the tile lists
-constexpr int kNumLists = 7;
-// The tile lists of one call: [kListHdr counters] then kNumLists arrays of ntiles tile ids (the device
-// side indexes them by these numbers: wave_append_tile, tile_occupancy_block).  Who writes, who walks:
-enum TileList : int {
-  kListMain = 0,           // occupied class-0 tiles, filled by the pre-pass on sparse calls only; walked by
-                           // the main launch of a sparse call (FP64 or single-precision list kernel)
-  kListClass1 = 1,         // class-1 / class-2 tiles (pre-pass); walked by the list launches with the
-  kListClass2 = 2,         // larger LDS images, FP64 or single precision
-  kListWaveBlock = 3,      // class 3: more points than any LDS image holds (pre-pass); k_dsm_gather_dense
-  kListRedoOwn = 4,        // FP64 redo with an image of cap0 points: class-0 tiles the single-precision main
-                           // launch hands back, or the pre-pass files for it (bin_z, rej_own); FP64 list launch
-  kListRedoBig = 5,        // FP64 redo with the largest image (cap2): tiles the single-precision class launches
-                           // (or a main launch whose own FP64 image fits no CU) hand back, or the pre-pass files
-  kListRedoWaveBlock = 6,  // redo beyond the largest image; k_dsm_gather_dense<false>
-};
-constexpr int kStatRedoUnlisted = 7;  // counter only: pre-classified tiles on NO list (a dense launch takes them)
+// kTileI, kMaxRegionRows, the tile lists (kListHdr, kNumLists, TileList, kStatRedoUnlisted): amhip_dsm_plan.h
 struct TileLists {
   int* base;
   unsigned ntiles;
@@ -843,15 +825,15 @@ __device__ __forceinline__ void gather_tile(const DsmParams& p, const uint32_t* 
                                             const int tile, unsigned char* smem, int my_class) {
   constexpr int kWaves = NT / 64;
   constexpr int kCellsPerLane = kTileJ / kWaves;
-  // [xy: cap+1 double2][z: cap+1 double (+pad)][cell offsets][rows][ctl][flags]
+  // [xy: cap+1 double2][z: cap+1 double (+pad)][cell offsets][rows][ctl][flags] (amhip_dsm_plan.h: the LDS image)
   double2* s_xy = reinterpret_cast<double2*>(smem);
-  double* s_z = reinterpret_cast<double*>(smem + (size_t)(p.lds_cap + 1) * 16);
-  uint32_t* s_off = reinterpret_cast<uint32_t*>(smem + (size_t)(p.lds_cap + 2) * 24);
+  double* s_z = reinterpret_cast<double*>(smem + (size_t)(p.lds_cap + 1) * sizeof(double2));
+  uint32_t* s_off = reinterpret_cast<uint32_t*>(smem + (size_t)(p.lds_cap + kLdsSpareSlots) * kLdsPointBytes64);
   uint32_t* s_rowg = s_off + p.lds_cells + 1;        // global start of a region bin-row
-  uint32_t* s_rowp = s_rowg + kMaxRegionRows;        // prefix of the row lengths (+1)
-  uint32_t* s_scan = s_rowp + kMaxRegionRows + 1;    // block-scan scratch
-  uint32_t* s_ctl = s_scan + 24;                     // [0] np, [1] nflag, [2] np_ext
-  uint16_t* s_flag = reinterpret_cast<uint16_t*>(s_ctl + 4);  // kTileI*kTileJ entries
+  uint32_t* s_rowp = s_rowg + kLdsRowStartWords;     // prefix of the row lengths (+1)
+  uint32_t* s_scan = s_rowp + kLdsRowPrefixWords;    // block-scan scratch
+  uint32_t* s_ctl = s_scan + kLdsScanWords;          // [0] np, [1] nflag, [2] np_ext
+  uint16_t* s_flag = reinterpret_cast<uint16_t*>(s_ctl + kLdsCtlWords64);  // kTileI*kTileJ entries
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1520,15 +1502,15 @@ __device__ __forceinline__ void gather_tile_f32(const DsmParams& p, const uint32
   // (the 1024-point instance serves ~0.5 points per cell: a trip is ~10 candidates, one run)
   constexpr bool kChunked = kCap > 1024 && kVar == 0;
   constexpr int kFlush = 32;
-  // [rec: cap+1 uint4 (U, V, dz, -)][cell offsets][rows][scan][ctl][z range][flags]
+  // [rec: cap+1 uint4 (U, V, dz, -)][cell offsets][rows][scan][ctl][z range][flags] (amhip_dsm_plan.h: the LDS image)
   uint4* s_rec = reinterpret_cast<uint4*>(smem);
-  uint32_t* s_off = reinterpret_cast<uint32_t*>(smem + (size_t)(p.lds_cap + 2) * 16);
+  uint32_t* s_off = reinterpret_cast<uint32_t*>(smem + (size_t)(p.lds_cap + kLdsSpareSlots) * kLdsPointBytes32);
   uint32_t* s_rowg = s_off + p.lds_cells + 1;
-  uint32_t* s_rowp = s_rowg + kMaxRegionRows;
-  uint32_t* s_scan = s_rowp + kMaxRegionRows + 1;
-  uint32_t* s_ctl = s_scan + 24;  // [0] np, [1] nflag, [2..3] pad, [4..7] zmin / zmax keys
-  uint32_t* s_zkey = s_ctl + 4;  // [0] min, [1] max of the region's heights (ordered f32 keys)
-  uint16_t* s_flag = reinterpret_cast<uint16_t*>(s_ctl + 8);
+  uint32_t* s_rowp = s_rowg + kLdsRowStartWords;
+  uint32_t* s_scan = s_rowp + kLdsRowPrefixWords;
+  uint32_t* s_ctl = s_scan + kLdsScanWords;  // [0] np, [1] nflag, [2] allowed additions, [3] pad, [4..7] zmin / zmax keys
+  uint32_t* s_zkey = s_ctl + kLdsCtlWords64;  // [0] min, [1] max of the region's heights (ordered f32 keys)
+  uint16_t* s_flag = reinterpret_cast<uint16_t*>(s_ctl + kLdsCtlWords32);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -2237,38 +2219,30 @@ int launch_lds(Ctx* c, void (*kernel)(P...), unsigned grid, unsigned nt, unsigne
   return AMHIP_OK;
 }
 
-// What the LDS-tiled gather launches of one dsm_run call share (dsm_run decides, launch_gathers<> launches).
-struct GatherPlan {
+// What the LDS-tiled gather launches of one dsm_run call share: what plan_gather_classes (amhip_dsm_plan.h)
+// decided, and what launch_gathers<> launches it on.
+struct GatherPlan : GatherClasses {
   Ctx* c;
   const DsmParams& p;
   PtsView pts;        // what dsm_sort left: doubles, records or both
   CellOut out;
   TileLists lists;
   unsigned ntiles;
-  bool f32;           // single-precision mode
-  bool sparse;        // only the occupied tiles are visited, by a fixed grid walking kListMain
-  bool rej_own;       // the FP64 kernel's image of cap0 points fits a CU: redo tiles go to kListRedoOwn
-  bool rej_dense;     // ... and are taken by a dense launch filtering on occ instead of the list
-  bool skip_classes;  // no class launches: the main launch takes every class
-  int cap0;           // points of the main launch's LDS image
-  int cap1, cap2;     // FP64 images of classes 1, 2
-  int capf1, capf2;   // single-precision images of classes 1, 2
 #ifdef AMHIP_TIMING_PROBES
   int nt;             // tuning knob gather_nt: threads per gather workgroup (512 measured best)
   int f32_variant;    // tuning knob f32_variant: timing probes of the 64 x 16 / 1024-point instance
 #endif
-  // p with the LDS image resized to `cap` points: the FP64 kernels' 24-byte records, the
-  // single-precision kernels' 16-byte records
+  // p with the LDS image resized to `cap` points: the FP64 kernels' image, the single-precision kernels'
   DsmParams with_cap(int cap) const {
     DsmParams q = p;
     q.lds_cap = cap;
-    q.lds_bytes = (unsigned)((int)p.lds_bytes + (cap - cap0) * 24);
+    q.lds_bytes = lds_image_bytes(false, cap, p.lds_cells, p.tile_j);
     return q;
   }
   DsmParams with_cap_f32(int cap) const {
     DsmParams q = p;
     q.lds_cap = cap;
-    q.lds_bytes_f32 = (unsigned)((int)p.lds_bytes_f32 + (cap - cap0) * 16);
+    q.lds_bytes_f32 = lds_image_bytes(true, cap, p.lds_cells, p.tile_j);
     return q;
   }
 };
@@ -2347,7 +2321,7 @@ int launch_gathers(const GatherPlan& g) {
     }
   }
   if constexpr (kWide) {
-    // (make_dsm_params picks 4096 / 7680 only for the single-precision mode)
+    // (plan_tile_shape picks 4096 / 7680 only for the single-precision mode)
     if (!g.f32) return arg_failure("internal: 4096-point tiles outside the single-precision mode");
     // (rejected tiles: the FP64 kernel with an image of cap0 points while that fits a CU --
     // kListRedoOwn --, else its largest image -- kListRedoBig -- or the wave-per-block kernel --
@@ -2399,16 +2373,16 @@ int launch_gathers(const GatherPlan& g) {
   if (g.f32) {
     // single-precision list launches of classes 1, 2: images of capf1 / capf2 points; rejected
     // tiles -> kListRedoBig (FP64, image cap2) / kListRedoWaveBlock (wave per block)
-    if ((rc = launch_f32_list<kTileJ, 4096>(g, g.capf1, kListClass1, 2048, kListRedoBig, true, g.cap2))) return rc;
-    if ((rc = launch_f32_list<kTileJ, 7680>(g, g.capf2, kListClass2, 1024, kListRedoBig, true, g.cap2))) return rc;
-    return launch_fp64_list<kTileJ, kTileJ == 16 ? 5600 : 5200>(g, g.cap2, kListRedoBig, 1024);
+    if ((rc = launch_f32_list<kTileJ, kClass1CeilingF32>(g, g.capf1, kListClass1, 2048, kListRedoBig, true, g.cap2))) return rc;
+    if ((rc = launch_f32_list<kTileJ, kClass2CeilingF32>(g, g.capf2, kListClass2, 1024, kListRedoBig, true, g.cap2))) return rc;
+    return launch_fp64_list<kTileJ, class2_ceiling(kTileJ)>(g, g.cap2, kListRedoBig, 1024);
   }
-  constexpr int kCap1 = kTileJ == 16 ? 2752 : 2432, kCap2 = kTileJ == 16 ? 5600 : 5200;
+  constexpr int kCap1 = class1_ceiling(kTileJ), kCap2 = class2_ceiling(kTileJ);
   if ((rc = launch_fp64_list<kTileJ, kCap1>(g, std::min(kCap1, g.cap1), kListClass1, 2048))) return rc;
   return launch_fp64_list<kTileJ, kCap2>(g, std::min(kCap2, g.cap2), kListClass2, 1024);
 }
 
-// (tile height, LDS point capacity) picked by make_dsm_params from the
+// (tile height, LDS point capacity) picked by plan_tile_shape (amhip_dsm_plan.h) from the
 // cloud's mean density: 64x16 / 1024 points runs 4 workgroups per CU
 typedef int (*GatherLauncher)(const GatherPlan&);
 static GatherLauncher gather_launcher(int tile_j, int cap0) {
@@ -2456,85 +2430,28 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
         int rc;
         if ((rc = ensure_capacity(&c->tile_occ, &c->tile_occ_cap, (size_t)ntiles + 16))) return rc;
       }
-      // Sparse call (few points per map cell, the layer already materialized):
-      // only the occupied tiles are visited, by a fixed grid walking their list.
-      const bool sparse = !fill_untouched && ntiles > 8192 &&
-                          (double)n * 16.0 < (double)p.rows * (double)p.cols;
-      // Capacity classes (k_dsm_tile_occupancy): tiles whose first-level region
-      // holds more points than the main launch's LDS image go to list launches
-      // with 2x / 4x the capacity (fewer workgroups per CU, still LDS-resident);
-      // beyond that gather_tile() takes the global-memory path, as before.
-      // Capacities follow the workgroups a CU's 160 KB of LDS can hold: 1024
-      // points -> 4 per CU; class 1 = the most that still leaves two per CU;
-      // class 2 = everything one workgroup can take.
-      const int cap0 = p.lds_cap;
-      // (the rest of the LDS image -- cell table, row tables, flags -- grows with the
-      // search window: wide radii / coarse grids leave less room for points; a class
-      // that cannot hold more than the one below it stays empty)
-      const long fixed_bytes = (long)p.lds_bytes - ((long)cap0 + 2) * 24;
-      // (even: the cell table behind the points is read and written in 16-byte quads)
-      auto cap_fit = [&](long limit) { return (int)((limit - fixed_bytes) / 24 - 2) & ~1; };
-      // (cap0 > 2048: a single-precision main launch -- the FP64 images keep their own sizes)
-      const int cap0_64 = std::min(cap0, 2048);
-      const int cap1 = std::max(cap0_64, std::min(p.tile_j == 16 ? 2752 : 2432, cap_fit(80 * 1024)));
-      const int cap2 = std::max(cap1, std::min(p.tile_j == 16 ? 5600 : 5200, cap_fit(150 * 1024)));
+      // what the launches below follow: amhip_dsm_plan.h (the previous call's tile counters come from a
+      // pinned mirror that call filled -- no synchronisation: a value one call late is as good)
+      const GatherCallFlags flags = {fill_untouched, mask != nullptr, unfilled != nullptr, c->bin_z_valid};
+      const GatherClasses k = plan_gather_classes(p, n, flags, c->host_tile_stats, prev_ntiles, c->tile_stats_sig,
+                                                  no_launch_skips());
       {
         int rc;
         if ((rc = ensure_capacity(&c->tile_list, &c->tile_list_cap,
                                   kNumLists * (size_t)ntiles + kListHdr)))
           return rc;
       }
+      c->tile_stats_sig = k.sig;
       const TileLists lists = {c->tile_list, ntiles};
-      const bool f32 = p.fx_ok && !p.pcl_mode && !p.only_unfilled && !mask && !unfilled;
-      // Single-precision mode: its records take 16 bytes against the FP64 kernel's 24, so the
-      // same two LDS budgets (two workgroups per CU / one) hold more points: classes 1 and 2
-      // are cut at capf1 / capf2 and walked by list launches of the single-precision kernel
-      // (4096- / 7680-point register instances); what those hand back goes to the FP64
-      // kernel's largest image (kListRedoBig) or, beyond it, to the wave-per-block kernel
-      // (kListRedoWaveBlock).
-      const long fixed32 = (long)p.lds_bytes_f32 - ((long)cap0 + 2) * 16;
-      auto cap_fit32 = [&](long limit) { return (int)((limit - fixed32) / 16 - 2) & ~1; };
-      const int capf1 = std::max(cap0, std::min(4096, cap_fit32(80 * 1024)));
-      const int capf2 = std::max(capf1, std::min(7680, cap_fit32(150 * 1024)));
-      int ccap0 = cap0, ccap1 = f32 ? capf1 : cap1, ccap2 = f32 ? capf2 : cap2;  // classification
+      const bool f32 = k.f32;
+      int ccap0 = k.ccap0, ccap1 = k.ccap1, ccap2 = k.ccap2;  // classification
 #ifdef AMHIP_TIMING_PROBES
       ccap0 = (int)tuning("gather_class_cap0", ccap0);   // (debugging)
       ccap1 = (int)tuning("gather_class_cap1", ccap1);
       ccap2 = (int)tuning("gather_class_cap2", ccap2);
 #endif
-      // single-precision mode after the three-pass sort: tiles whose height range leaves no room
-      // under the error bound go straight onto the FP64 list the kernel would hand them to --
-      // kListRedoOwn while the FP64 kernel's image of cap0 points fits a CU (rej_own), else
-      // kListRedoBig, or kListRedoWaveBlock beyond its largest image
-      const bool rej_own = cap0 <= 2048 || ((long)cap0 + 2) * 24 + fixed_bytes <= 150 * 1024;
-      const uint2* bin_z = (f32 && c->bin_z_valid) ? reinterpret_cast<const uint2*>(c->bin_z) : nullptr;
+      const uint2* bin_z = k.use_bin_z ? reinterpret_cast<const uint2*>(c->bin_z) : nullptr;
       c->last_call_f32 = bin_z != nullptr;  // (its tile counters say how rough the scene is)
-      // Rough scenes: when the PREVIOUS call on this context pre-classified more than a tenth
-      // of its tiles for the FP64 kernel, that kernel is launched densely over the tiles (one
-      // workgroup each, filtering on occ) instead of walking a list of tens of thousands with a
-      // fixed grid; a tenth or less: the list (an empty dense launch would cost 0.18 ms of
-      // idle workgroups on smooth terrain).  Either is correct for any count -- the counts only
-      // pick the faster one; they come from a pinned mirror the previous call filled (no
-      // synchronisation: a value one call late is as good).
-      bool rej_dense = false;
-      if (bin_z && cap0 <= 2048 && !sparse && c->host_tile_stats && prev_ntiles > 0) {
-        const volatile unsigned* hs = c->host_tile_stats;
-        const double rejected = (double)hs[kListRedoOwn] + (double)hs[kListRedoBig] +
-                                (double)hs[kListRedoWaveBlock] + (double)hs[kStatRedoUnlisted];
-        rej_dense = rejected * 10.0 > (double)prev_ntiles;
-      }
-      // The capacity-class launches behind the main one (denser tiles: classes 1, 2, the wave-per-
-      // block kernel) are SKIPPED when the previous call of this kind left all three lists empty
-      // (pinned counters, never waited for): the main launch then takes every class -- a stray
-      // denser tile walks the global bins (gather_tile: use_lds false), slower, same result -- and
-      // the counters this call leaves bring the class launches back for the next one.
-      unsigned long long tsig = 1469598103934665603ull;
-      for (const int v : {p.rows, p.cols, p.i_off, p.j_off, p.tile_j, p.lds_cap, p.B, p.M, p.w[0], p.pcl_mode, cap1, cap2})
-        tsig = (tsig ^ (unsigned long long)(unsigned)v) * 1099511628211ull;
-      const volatile unsigned* hst = c->host_tile_stats;
-      const bool skip_classes = !f32 && !sparse && hst && c->tile_stats_sig == tsig && hst[kListClass1] == 0u &&
-                                hst[kListClass2] == 0u && hst[kListWaveBlock] == 0u && !no_launch_skips();
-      c->tile_stats_sig = tsig;
       ProloguePart pp;
       pp.zpart = c->range_parts ? c->zpart : nullptr;
       pp.nparts = c->range_parts;
@@ -2547,21 +2464,20 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
       pp.host_stats = f32 ? nullptr : c->host_tile_stats;
       c->range_parts = 0;
       hipLaunchKernelGGL(k_dsm_tile_occupancy, dim3(pp.nocc + pp.nrange), dim3(256), 0, c->stream,
-                         p, p.tile_j, c->bin_start, c->tile_occ, lists.base, sparse ? 1 : 0, ccap0, ccap1, ccap2,
-                         bin_z, rej_own ? 1 : 0, cap2, rej_dense ? 1 : 0, pts_view.zref, pp);
-      GatherPlan plan = {c, p, pts_view, cell_out, lists, ntiles, f32, sparse, rej_own, rej_dense, skip_classes,
-                         cap0, cap1, cap2, capf1, capf2};
+                         p, p.tile_j, c->bin_start, c->tile_occ, lists.base, k.sparse ? 1 : 0, ccap0, ccap1, ccap2,
+                         bin_z, k.rej_own ? 1 : 0, k.cap2, k.rej_dense ? 1 : 0, pts_view.zref, pp);
+      GatherPlan plan = {k, c, p, pts_view, cell_out, lists, ntiles};
 #ifdef AMHIP_TIMING_PROBES
       plan.nt = (int)tuning("gather_nt", 512.0);
       plan.f32_variant = (int)tuning("f32_variant", 0.0);
 #endif
       {
-        const int rc = gather_launcher(p.tile_j, cap0)(plan);
+        const int rc = gather_launcher(p.tile_j, k.cap0)(plan);
         if (rc) return rc;
       }
       if (p.knn_k > 0) {
         AMHIP_TRY(hipGetLastError());
-        // (a capped call is always the FP64 pipeline -- make_dsm_params: no fx_ok under the cap --, so
+        // (a capped call is always the FP64 pipeline -- runs_single_precision: no fx_ok under the cap --, so
         // the prologue's last workgroup has mirrored this call's tile counters into host_tile_stats
         // and last_call_f32 is false: nothing of the tail below is owed)
         return AMHIP_OK;
@@ -2570,7 +2486,7 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
         hipLaunchKernelGGL(k_dsm_gather_dense<true>, dim3(4096), dim3(256), 0, c->stream, p, p.tile_j,
                            c->bin_start, pts_view, lists.ids(kListWaveBlock), lists.count(kListWaveBlock),
                            cell_out);
-      else if (!skip_classes)
+      else if (!k.skip_classes)
         hipLaunchKernelGGL(k_dsm_gather_dense<false>, dim3(4096), dim3(256), 0, c->stream, p, p.tile_j,
                            c->bin_start, pts_view, lists.ids(kListWaveBlock), lists.count(kListWaveBlock),
                            cell_out);

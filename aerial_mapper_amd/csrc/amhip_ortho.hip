@@ -38,7 +38,7 @@
 
 namespace amhip {
 
-constexpr int kTileI = 64;
+// kTileI = 64 (amhip_dsm_plan.h): as in the DSM's gather, one cell per lane of a wave along i
 constexpr int kTileJ = 64;   // a workgroup's tile ...
 // ... is folded in slabs of kSlab cell columns (template parameter of the kernels): 16 = four
 // cells per lane for the kernel that folds every pair in the reference's arithmetic, 8 = two for
