@@ -239,6 +239,8 @@ inline bool plan_bins(const DsmPlanInput& in, DsmParams* p) {
   return nbins + 1 < 0xFFFFFFFFull;
 }
 
+constexpr int kP3PlaceMaxCap = 2048;  // LDS capacity (points) the sort's register-resident placement handles
+
 // Three-pass partition sort plan (amhip_sort.hip; p3_n1 == 0: not used).  Worth it once the cloud is
 // large enough that the sort is bandwidth bound; sub-partitions are sized for ~1.5 K points (a pass-3
 // workgroup sorts up to p3_cap of them in LDS, more through a direct-placement fallback).
@@ -257,7 +259,7 @@ inline void plan_sort(const DsmPlanInput& in, DsmParams* p) {
   p->p3_w = w;
   p->p3_n1 = n1;
   p->p3_n2 = r1 * cc;
-  p->p3_cap = std::max(std::min(in.p3_cap, 2048 /* kP3PlaceMaxCap */), 64);
+  p->p3_cap = std::max(std::min(in.p3_cap, kP3PlaceMaxCap), 64);
 }
 
 // Division-free keys for the sort passes (DsmParams::mul_*): the multiplier of n / d for n <= n_max

@@ -17,6 +17,7 @@
 
 #include "amhip_common.h"
 #include "amhip_device.h"
+#include "amhip_sort_plan.h"
 
 namespace amhip {
 
@@ -160,29 +161,9 @@ __device__ __forceinline__ bool point_bin_xy(const DsmParams& p, double px, doub
 //            contiguous coalesced copy out.
 // Sub-partitions are ordered (bin row, column block), so the result is the
 // same row-major-by-bin order the gather kernels expect.
-constexpr int kP3CountThreads = 1024;
-#ifndef AMHIP_P3_THREADS
-#define AMHIP_P3_THREADS 512
-#endif
-#ifndef AMHIP_P3_PER
-#define AMHIP_P3_PER 5
-#endif
-constexpr int kP3Threads = AMHIP_P3_THREADS;
-constexpr int kP3Chunk = AMHIP_P3_THREADS * AMHIP_P3_PER;  // points staged per scatter workgroup (2560: 70 KB of LDS, 2 per CU)
+// (the kernels' compile-time shape -- kP3*, kRec*, kScan*, the run caches -- and the layout of every
+// dynamic-LDS image: amhip_sort_plan.h)
 constexpr int kP3PerThread = kP3Chunk / kP3Threads;
-constexpr int kP3MaxKeys = 256;
-constexpr int kP3PlaceThreads = 256;
-constexpr int kP3PlaceMaxCap = 2048;  // LDS capacity (points) the register-resident path handles
-constexpr int kP3PlacePer = kP3PlaceMaxCap / kP3PlaceThreads;
-constexpr int kP3BigThreads = 1024;
-constexpr int kP3BigPer = 6;
-constexpr int kP3BigCap = kP3BigThreads * kP3BigPer;  // 6144 points = 147 KB of LDS
-constexpr int kRecWords = 5;  // 20-byte sort records of the single-precision mode (below)
-// points a thread of the big placement kernel keeps in registers across the rounds of a
-// sub-partition beyond one LDS image (place_rounds): 14 x 24 bytes / 16 x 20 bytes
-constexpr int kP3RoundsPer = 14;
-constexpr int kP3RoundsPerRec = 16;
-constexpr size_t kLdsMaxBytes = 160 * 1024 - 512;  // per workgroup on gfx950 (160 KB per CU), a margin kept
 
 __device__ __forceinline__ bool p3_keys(const DsmParams& p, double px, double py, int* k1,
                                         int* k2) {
@@ -210,6 +191,7 @@ struct HaloStage {
   double lo_i[kMaxHaloDests], hi_i[kMaxHaloDests], lo_j[kMaxHaloDests], hi_j[kMaxHaloDests];
   unsigned long long entry[kHaloStage];  // point index | destination << 32 | local slot << 36
 };
+static_assert(sizeof(HaloStage) == kHaloStageBytes, "the count pass's LDS image (amhip_sort_plan.h) ends with it");
 
 __device__ __forceinline__ void halo_stage_init(HaloStage* st, const HaloParams& hp) {
   if (threadIdx.x == 0) {
@@ -528,7 +510,6 @@ struct RunTabs {
   uint32_t* pre2;   // same layout: exclusive prefix of the lengths
   uint32_t g1, r1s, p1s;
 };
-constexpr int kRunsCache = 2048;   // runs of a pass-2 segment kept in LDS (more: searched in memory)
 
 template <bool kFirst, bool kRuns = false>
 __device__ __forceinline__ void p3_scatter_body(const unsigned vb, const double* __restrict__ src,
@@ -858,7 +839,6 @@ __device__ __forceinline__ uint32_t place_zkey(double z) {
 // the segments of its k1 partition (pass 2 left one run per segment, scan 2 their prefixes);
 // point j = idx - g0 lies in the LAST run that begins at or before j.  Rows of up to kPlaceRunsCache
 // segments are searched in LDS (cfg3: ~150), longer ones in memory -- any length is served.
-constexpr int kPlaceRunsCache = 512;
 template <bool kRuns>
 struct PlaceSource {
   const uint32_t* pre;
@@ -935,9 +915,9 @@ __device__ __forceinline__ void place_subpartition(const double* __restrict__ sr
   extern __shared__ double s_pts[];                                  // 3 * cap
   uint32_t* s_bins = reinterpret_cast<uint32_t*>(s_pts + 3 * cap);   // p3_w
   uint32_t* s_scan = s_bins + p.p3_w;                                // 24
-  uint32_t* s_zlo = s_scan + 24;                                     // p3_w (bin_z only)
+  uint32_t* s_zlo = s_scan + kLdsSortScanWords;                      // p3_w (bin_z only)
   uint32_t* s_zhi = s_zlo + p.p3_w;                                  // p3_w
-  uint32_t* s_cache = s_scan + 24 + (bin_z ? 2 * p.p3_w : 0);        // 2 * kPlaceRunsCache (kRuns only)
+  uint32_t* s_cache = s_scan + kLdsSortScanWords + (bin_z ? 2 * p.p3_w : 0);  // 2 * kPlaceRunsCache (kRuns only)
   const int tid = threadIdx.x;
   const int k1 = sp / p.p3_n2, k2 = sp - k1 * p.p3_n2;
   const int rr = k2 / p.p3_c;
@@ -1103,7 +1083,7 @@ __device__ __forceinline__ void place_rounds(const void* __restrict__ src_v, con
   uint32_t* s_bins = s_words + (size_t)kWordsPer * cap;                 // p3_w + 1: starts (+ total)
   uint32_t* s_cur = s_bins + p.p3_w + 1;                                // p3_w: cursors of the round
   uint32_t* s_scan = s_cur + p.p3_w;                                    // 24
-  uint32_t* s_zlo = s_scan + 24;                                        // p3_w (bin_z only)
+  uint32_t* s_zlo = s_scan + kLdsSortScanWords;                         // p3_w (bin_z only)
   uint32_t* s_zhi = s_zlo + p.p3_w;                                     // p3_w
   uint32_t* s_cache = s_zhi + p.p3_w;                                   // 2 * kPlaceRunsCache (kRuns only)
   const double* srcd = reinterpret_cast<const double*>(src_v);
@@ -1384,8 +1364,6 @@ k_dsm_runs_place_big(const double* __restrict__ src, DsmParams p,
 // The reference's doubles are NOT lost: they stay where the caller put them.
 // (20-byte records: 3072 points per scatter workgroup fit the LDS budget of two workgroups per
 // CU that 2560 24-byte points use -- longer runs)
-constexpr int kRecPerThread = 6;
-constexpr int kRecChunk = kP3Threads * kRecPerThread;
 
 // zref[0] = middle of [min, max] over the partials the count pass left, [1] / [2] the range
 __global__ void __launch_bounds__(1024)
@@ -1596,7 +1574,7 @@ __device__ __forceinline__ void place_records(const uint32_t* __restrict__ src, 
   extern __shared__ uint32_t s_words[];                 // kRecWords * cap
   uint32_t* s_bins = s_words + (size_t)kRecWords * cap; // p3_w
   uint32_t* s_scan = s_bins + p.p3_w;                   // 24
-  uint32_t* s_zlo = s_scan + 24;                        // p3_w
+  uint32_t* s_zlo = s_scan + kLdsSortScanWords;         // p3_w
   uint32_t* s_zhi = s_zlo + p.p3_w;                     // p3_w
   const int tid = threadIdx.x;
   const int k1 = sp / p.p3_n2, k2 = sp - k1 * p.p3_n2;
@@ -1854,9 +1832,6 @@ int dsm_bbox_run(Ctx* c, const double* dev_xyz, size_t n, const DsmParams& p, in
 // ---------------------------------------------------------------------------
 // exclusive scan of a u32 array, in place (3 launches)
 // ---------------------------------------------------------------------------
-constexpr int kScanT = 256;
-constexpr int kScanI = 16;
-constexpr int kScanE = kScanT * kScanI;
 
 __global__ void __launch_bounds__(kScanT)
 k_scan_partials(const uint32_t* __restrict__ in, size_t n,
@@ -1943,19 +1918,19 @@ k_scan_final(uint32_t* __restrict__ data, size_t n,
 }
 
 
+// ---------------------------------------------------------------------------
+// host driver: sort `n` points into c->sorted / c->bin_start
+// ---------------------------------------------------------------------------
+// What a call does is decided by plan_sort_call (amhip_sort_plan.h) from a SortPlanInput; the tuning table
+// is read here, into that input.
 // tuning knob p3_rounds_cap=n (tests): sub-partitions above n points are placed in rounds over an
 // image of n points -- exercises place_rounds (and its one-bin-beyond-the-image direct case)
 // on clouds of test size; normally only contexts beyond ~130 M points get there
 // tuning knob p3_rounds_reread: the rounds re-read the sub-partition instead of keeping it in registers
 // (the path of sub-partitions beyond 14 K points)
-static void p3_rounds_knob(int* cap_rounds, unsigned* rounds_above, unsigned* reg_max) {
-  const int knob = (int)tuning("p3_rounds_cap", 0.0);
-  const bool reread = tuning_on("p3_rounds_reread");
-  if (knob >= 16 && knob < *cap_rounds) {
-    *cap_rounds = knob;
-    *rounds_above = (unsigned)knob;
-  }
-  if (reread) *reg_max = 0u;
+static void p3_rounds_knob(SortPlanInput* in) {
+  in->p3_rounds_cap = (int)tuning("p3_rounds_cap", 0.0);
+  in->p3_rounds_reread = tuning_on("p3_rounds_reread");
 }
 
 // tuning knob no_launch_skips (tests, A-B): every capacity-class / big-list launch is made whatever the
@@ -1964,422 +1939,336 @@ bool no_launch_skips() {
   return tuning_on("no_launch_skips");
 }
 
-// what a call's pinned launch-policy counters are counters OF: the window's geometry and the sort's plan
-static unsigned long long sort_geometry_signature(const DsmParams& p) {
-  unsigned long long h = 1469598103934665603ull;
-  auto mix = [&](const void* v, size_t bytes) {
-    const unsigned char* b = static_cast<const unsigned char*>(v);
-    for (size_t k = 0; k < bytes; ++k) h = (h ^ b[k]) * 1099511628211ull;
-  };
-  const int ints[] = {p.rows, p.cols, p.M, p.B, p.nbx, p.nby, p.i_off, p.j_off, p.p3_r1, p.p3_c,
-                      p.p3_w, p.p3_n1, p.p3_n2, p.p3_cap};
-  const double dbls[] = {p.base_x, p.base_y, p.res, p.inv_res, p.sub_x, p.sub_y};
-  mix(ints, sizeof(ints));
-  mix(dbls, sizeof(dbls));
-  return h ? h : 1ull;
+// the tables of c->stripe_ws (SortWs) as pointers
+struct SortTables {
+  uint32_t *hist_rows, *cnt, *start2, *cursor2, *start1, *cursor1, *blk2, *big_list, *tot1;
+  RunTabs rt;
+};
+static SortTables sort_tables(uint32_t* ws, const SortPlan& s) {
+  const SortWs& w = s.ws;
+  SortTables t = {ws + w.hist_rows, ws + w.cnt, ws + w.start2, ws + w.cursor2, ws + w.start1,
+                  ws + w.cursor1, ws + w.blk2, ws + w.big_list, ws + w.tot1, {}};
+  t.rt = RunTabs{ws + w.run1, ws + w.pre1, ws + w.seg1, ws + w.run2, ws + w.pre2,
+                 (uint32_t)s.g1, (uint32_t)w.r1s, (uint32_t)w.p1s};
+  return t;
 }
 
-// ---------------------------------------------------------------------------
-// host driver: sort `n` points into c->sorted / c->bin_start
-// ---------------------------------------------------------------------------
+// one call of the driver: its arguments, its plan, and what every pipeline hands to its kernels
+struct SortCall {
+  Ctx* c;
+  const double* dev_xyz;
+  const int32_t* dev_values;
+  size_t n;
+  const DsmParams& p;
+  const SortSplit* split;  // (of a three-pass call, else null)
+  const SortPlan& s;
+  SortTables t;
+  // [min z, max z] of the binned points (for the mosaic's coarse cull): every workgroup of the first
+  // scatter pass -- it loads z anyway -- writes a partial, k_range_reduce (amhip_dsm.hip: the gather's
+  // prologue) folds zpart[0 .. range_parts) into the call's own range -- c->dev_zrange[2], [3], which
+  // bounds max |z| for the gather's rounding guard -- and the running range, which may be null
+  double* zpart;
+  // What the single-workgroup kernel in front of the first scatter resets: the call's own range and --
+  // when dsm_run asked for it -- the counters of the gather's tile lists.
+  SortAux aux;
+};
 
-static int dsm_sort_impl(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
-                         const DsmParams& p, unsigned long long* zrange, const SortSplit* split);
+static int set_dynamic_lds(const void* kernel, size_t bytes) {
+  AMHIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return AMHIP_OK;
+}
+#define AMHIP_SET_LDS(kernel, bytes) \
+  do { if (int rc_ = set_dynamic_lds(reinterpret_cast<const void*>(kernel), bytes)) return rc_; } while (0)
+
+// The placement pair of the two doubles pipelines: k_dsm_p3_place / _big, or k_dsm_runs_place / _big with
+// the run lists (`pr`) behind their arguments.  bin_z: none (the doubles pipelines leave no bin ranges).
+template <class Place, class PlaceBig, class... Runs>
+static int launch_place_doubles(const SortCall& k, Place place, PlaceBig place_big, Runs... pr) {
+  Ctx* c = k.c;
+  const SortPlan& s = k.s;
+  const PlacePolicy& q = s.place;
+  ScopedTimer t(c, AMHIP_K_DSM_SCAN);
+  uint2* const bin_z = nullptr;
+  AMHIP_SET_LDS(place, s.lds_place);
+  c->sort_stats_sig = q.geo_sig;
+  hipLaunchKernelGGL(place, dim3((unsigned)(k.p.p3_n1 * k.p.p3_n2)), dim3(kP3PlaceThreads), s.lds_place,
+                     c->stream, c->tmp_points, k.p, k.p.p3_cap, k.t.start2, c->bin_start, c->sorted, q.skip_lo,
+                     q.skip_hi, bin_z, (const uint32_t*)k.t.big_list, c->host_sort_stats, pr...);
+  AMHIP_SET_LDS(place_big, s.lds_place_big);
+  if (q.want_big)
+    hipLaunchKernelGGL(place_big, dim3(256), dim3(kP3BigThreads), s.lds_place_big, c->stream,
+                       c->tmp_points, k.p, k.t.start2, c->bin_start, c->sorted, k.t.big_list, bin_z,
+                       q.cap_rounds, q.rounds_above, q.reg_max, pr...);
+  AMHIP_TRY(hipGetLastError());
+  return AMHIP_OK;
+}
 
 // The run pipeline: local sort of every chunk -> scan 1 -> local sort of every segment of a k1
 // partition, its runs gathered -> scan 2 (the plan) -> placement through the run lists.
 // Buffers as in the counting pipeline: c->sorted, c->tmp_points, c->sorted.
-static int dsm_sort_runs(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
-                         const DsmParams& p, double* zpart, const SortAux& aux, unsigned long long geo_sig) {
-  const int n1 = p.p3_n1, n2 = p.p3_n2, nk = n1 * n2;
-  const size_t g1 = (n + kP3Chunk - 1) / kP3Chunk;   // chunks of pass 1; pass 2 has at most g1 + n1 segments
-  const size_t r1s = (g1 + 3) & ~(size_t)3, p1s = r1s + 4;
-  auto up4 = [](size_t w) { return (w + 3) & ~(size_t)3; };
-  const size_t plan_words = up4(4 * (size_t)nk + 4 * (size_t)n1 + 64);
-  const size_t rows2 = (g1 + (size_t)n1) * (size_t)n2;
-  const size_t ws_words = plan_words + up4((size_t)n1) + (size_t)n1 * (r1s + 2 * p1s) + 2 * up4(rows2) + 16;
-  int rc;
-  if ((rc = ensure_capacity(&c->tmp_points, &c->tmp_points_cap, 3 * n))) return rc;
-  if ((rc = ensure_capacity(&c->stripe_ws, &c->stripe_ws_cap, ws_words))) return rc;
-  uint32_t* cnt = c->stripe_ws;
-  uint32_t* start2 = cnt + nk;       // nk + 1
-  uint32_t* cursor2 = start2 + nk + 1;
-  uint32_t* start1 = cursor2 + nk;   // n1 + 1
-  uint32_t* cursor1 = start1 + n1 + 1;
-  uint32_t* blk2 = cursor1 + n1;     // n1 + 1
-  uint32_t* big_list = blk2 + n1 + 1;  // [count] + up to nk sub-partition ids
-  uint32_t* tot1 = c->stripe_ws + plan_words;
-  RunTabs rt;
-  rt.run1 = tot1 + up4((size_t)n1);
-  rt.pre1 = rt.run1 + (size_t)n1 * r1s;
-  rt.seg1 = rt.pre1 + (size_t)n1 * p1s;
-  rt.run2 = rt.seg1 + (size_t)n1 * p1s;
-  rt.pre2 = rt.run2 + up4(rows2);
-  rt.g1 = (uint32_t)g1;
-  rt.r1s = (uint32_t)r1s;
-  rt.p1s = (uint32_t)p1s;
-  const size_t lds_sort = (size_t)kP3Chunk * 28 + (3 * kP3MaxKeys + 32) * sizeof(uint32_t);
-  static_assert(2 * kRunsCache * sizeof(uint32_t) <= (size_t)kP3Chunk * 24, "the run table lies in the points' image");
-  AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_runs_sort1),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort));
-  AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_runs_sort2),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort));
+static int sort_runs(const SortCall& k) {
+  Ctx* c = k.c;
+  const SortPlan& s = k.s;
+  const DsmParams& p = k.p;
+  const SortTables& t = k.t;
+  const int n1 = p.p3_n1, n2 = p.p3_n2;
+  AMHIP_SET_LDS(k_dsm_runs_sort1, s.lds_scatter);
+  AMHIP_SET_LDS(k_dsm_runs_sort2, s.lds_scatter);
   {
-    ScopedTimer t(c, AMHIP_K_DSM_SCATTER);
-    hipLaunchKernelGGL(k_dsm_runs_sort1, dim3((unsigned)g1), dim3(kP3Threads), lds_sort, c->stream,
-                       dev_xyz, dev_values, n, p, c->sorted, zpart, rt);
-    c->range_parts = g1 * (kP3Threads / 64);
+    ScopedTimer tm(c, AMHIP_K_DSM_SCATTER);
+    hipLaunchKernelGGL(k_dsm_runs_sort1, dim3((unsigned)s.g1), dim3(kP3Threads), s.lds_scatter, c->stream,
+                       k.dev_xyz, k.dev_values, k.n, p, c->sorted, k.zpart, t.rt);
     AMHIP_TRY(hipGetLastError());
   }
   {
-    ScopedTimer t(c, AMHIP_K_DSM_BIN_COUNT);
-    hipLaunchKernelGGL(k_dsm_runs_scan1, dim3((unsigned)n1), dim3(1024), 0, c->stream, rt, n1, tot1,
-                       start1, blk2, (unsigned)kP3Chunk, aux, c->dev_tickets + 2);
+    ScopedTimer tm(c, AMHIP_K_DSM_BIN_COUNT);
+    hipLaunchKernelGGL(k_dsm_runs_scan1, dim3((unsigned)n1), dim3(1024), 0, c->stream, t.rt, n1, t.tot1,
+                       t.start1, t.blk2, s.chunk, k.aux, c->dev_tickets + 2);
     c->aux_done = true;
     AMHIP_TRY(hipGetLastError());
   }
   {
-    ScopedTimer t(c, AMHIP_K_DSM_SCATTER);
-    hipLaunchKernelGGL(k_dsm_runs_sort2, dim3((unsigned)(g1 + n1)), dim3(kP3Threads), lds_sort, c->stream,
-                       c->sorted, n, p, start1, blk2, c->tmp_points, rt);
+    ScopedTimer tm(c, AMHIP_K_DSM_SCATTER);
+    hipLaunchKernelGGL(k_dsm_runs_sort2, dim3((unsigned)s.g2), dim3(kP3Threads), s.lds_scatter, c->stream,
+                       c->sorted, k.n, p, t.start1, t.blk2, c->tmp_points, t.rt);
     AMHIP_TRY(hipGetLastError());
   }
   {
-    ScopedTimer t(c, AMHIP_K_DSM_BIN_COUNT);
-    const unsigned grid = (unsigned)std::min<size_t>(((size_t)nk + 15) / 16, 2048);
-    hipLaunchKernelGGL(k_dsm_runs_scan2, dim3(grid), dim3(1024), 0, c->stream, rt, cnt, n1, n2,
-                       (const uint32_t*)blk2);
-    hipLaunchKernelGGL(k_dsm_runs_plan2, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)cnt, n1, n2,
-                       start2, cursor2, start1, cursor1, blk2, (unsigned)p.p3_cap, (unsigned)kP3BigCap,
-                       big_list, (unsigned)kP3Chunk);
+    ScopedTimer tm(c, AMHIP_K_DSM_BIN_COUNT);
+    hipLaunchKernelGGL(k_dsm_runs_scan2, dim3((unsigned)s.grid_scan2), dim3(1024), 0, c->stream, t.rt, t.cnt,
+                       n1, n2, (const uint32_t*)t.blk2);
+    hipLaunchKernelGGL(k_dsm_runs_plan2, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)t.cnt, n1, n2,
+                       t.start2, t.cursor2, t.start1, t.cursor1, t.blk2, (unsigned)p.p3_cap, (unsigned)kP3BigCap,
+                       t.big_list, s.chunk);
+    AMHIP_TRY(hipGetLastError());
+  }
+  return launch_place_doubles(k, k_dsm_runs_place, k_dsm_runs_place_big, PlaceRuns{t.rt, t.start1, t.blk2, k.n});
+}
+
+// The count pass of the counting pipelines (zall: the records' height partials, else null), then the
+// reduction of its rows and the scan.  Phase 1 of a tiled call stops behind the count pass, which selects
+// the halo on the way: amhip_dsm_tiled_finish_dev comes back with phase 2.
+static int sort_count_pass(const SortCall& k, double* zall) {
+  Ctx* c = k.c;
+  const SortPlan& s = k.s;
+  const DsmParams& p = k.p;
+  const SortTables& t = k.t;
+  const SortSplit* split = k.split;
+  const int n1 = p.p3_n1, n2 = p.p3_n2, nk = n1 * n2;
+  ScopedTimer tm(c, AMHIP_K_DSM_BIN_COUNT);
+  AMHIP_SET_LDS(k_dsm_p3_count<false>, s.lds_count);
+  AMHIP_SET_LDS(k_dsm_p3_count<true>, s.lds_count_halo);
+  const HaloParams no_halo = {};
+  if (s.phase == 1) {
+    AMHIP_TRY(hipMemsetAsync(split->halo_counts, 0, sizeof(unsigned long long) * split->hp.nd, c->stream));
+    hipLaunchKernelGGL(k_dsm_p3_count<true>, dim3((unsigned)s.g_a), dim3(kP3CountThreads), s.lds_count_halo,
+                       c->stream, k.dev_xyz, s.n_a, p, t.hist_rows, split->hp, split->halo_out,
+                       split->halo_counts, zall);
+    AMHIP_TRY(hipGetLastError());
+    return AMHIP_OK;
+  }
+  // (tiled call, phase 2: the prefix was counted in phase 1; the received rows write their own histogram rows)
+  if (!split)
+    hipLaunchKernelGGL(k_dsm_p3_count<false>, dim3((unsigned)s.g_a), dim3(kP3CountThreads), s.lds_count,
+                       c->stream, k.dev_xyz, s.n_a, p, t.hist_rows, no_halo, (double*)nullptr,
+                       (unsigned long long*)nullptr, zall);
+  else if (s.g_b)
+    hipLaunchKernelGGL(k_dsm_p3_count<false>, dim3((unsigned)s.g_b), dim3(kP3CountThreads), s.lds_count,
+                       c->stream, k.dev_xyz + 3 * s.n_a, k.n - s.n_a, p, t.hist_rows + s.g_a * (size_t)nk,
+                       no_halo, (double*)nullptr, (unsigned long long*)nullptr,
+                       zall ? zall + 2 * s.g_a * (kP3CountThreads / 64) : nullptr);
+  // (the records' reference height: the middle of the range every count workgroup left)
+  if (s.rec)
+    hipLaunchKernelGGL(k_dsm_zref, dim3(1), dim3(1024), 0, c->stream, zall, s.zref_parts, c->zref);
+  // (reduction of the count workgroups' rows + the scan by the workgroup that finishes last: one launch)
+  hipLaunchKernelGGL(k_dsm_p3_reduce_scan, dim3((unsigned)s.grid_reduce), dim3(1024), 0, c->stream,
+                     t.hist_rows, (int)s.gcount, t.cnt, n1, n2, t.start2, t.cursor2, t.start1, t.cursor1, t.blk2,
+                     (unsigned)p.p3_cap, (unsigned)kP3BigCap, t.big_list, s.chunk, k.aux, (unsigned*)nullptr,
+                     c->dev_tickets);
+  c->aux_done = true;
+  AMHIP_TRY(hipGetLastError());
+  return AMHIP_OK;
+}
+
+// The record pipeline (the single-precision gather's mode): 20-byte records through c->rec_a, c->rec_b; the
+// placement leaves 16-byte records + rows and every bin's height range (the occupancy pre-pass sorts tiles
+// without room under the error bound onto the FP64 lists before anything is staged); bins no
+// sub-partition covers keep "empty".
+// (ahead of sort_count_doubles: the template kernels reach the code object in the order the host code first
+// names them, and that order is the record pipeline's first)
+static int sort_count_records(const SortCall& k) {
+  Ctx* c = k.c;
+  const SortPlan& s = k.s;
+  const DsmParams& p = k.p;
+  const SortTables& t = k.t;
+  const PlacePolicy& q = s.place;
+  if (const int rc = sort_count_pass(k, c->zall)) return rc;
+  if (s.phase == 1) return AMHIP_OK;
+  {
+    ScopedTimer tm(c, AMHIP_K_DSM_SCATTER);
+    AMHIP_SET_LDS(k_dsm_p3_scatter_rec<true>, s.lds_scatter);
+    AMHIP_SET_LDS(k_dsm_p3_scatter_rec<false>, s.lds_scatter);
+    hipLaunchKernelGGL(k_dsm_p3_scatter_rec<true>, dim3((unsigned)s.g1), dim3(kP3Threads), s.lds_scatter,
+                       c->stream, k.dev_xyz, (const uint32_t*)nullptr, k.n, p, c->zref, t.start1, t.blk2,
+                       t.cursor1, c->rec_a, k.zpart);
+    hipLaunchKernelGGL(k_dsm_p3_scatter_rec<false>, dim3((unsigned)s.g2), dim3(kP3Threads), s.lds_scatter,
+                       c->stream, (const double*)nullptr, c->rec_a, k.n, p, c->zref, t.start1, t.blk2,
+                       t.cursor2, c->rec_b, (double*)nullptr);
     AMHIP_TRY(hipGetLastError());
   }
   {
-    ScopedTimer t(c, AMHIP_K_DSM_SCAN);
-    // (the launch policy of the counting pipeline's placement, word for word)
-    const PlaceRuns pr = {rt, start1, blk2, n};
-    uint2* bin_z = nullptr;
-    const size_t cache = 2 * (size_t)kPlaceRunsCache * sizeof(uint32_t);
-    const size_t lds = (size_t)p.p3_cap * 24 + ((size_t)p.p3_w + 32) * sizeof(uint32_t) + cache;
-    AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_runs_place),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const bool want_big = !(c->sort_stats_sig == geo_sig && c->host_sort_stats && c->host_sort_stats[0] == 0u) ||
-                          no_launch_skips();
-    c->sort_stats_sig = geo_sig;
-    hipLaunchKernelGGL(k_dsm_runs_place, dim3((unsigned)nk), dim3(kP3PlaceThreads), lds, c->stream,
-                       c->tmp_points, p, p.p3_cap, start2, c->bin_start, c->sorted,
-                       want_big ? (unsigned)p.p3_cap : 0xFFFFFFFFu, 0xFFFFFFFFu, bin_z,
-                       (const uint32_t*)big_list, c->host_sort_stats, pr);
-    const size_t tables = (4 * (size_t)p.p3_w + 64) * sizeof(uint32_t) + cache;
-    int cap_rounds = (int)std::min<size_t>(kP3BigCap, (kLdsMaxBytes - tables) / 24);
-    unsigned rounds_above = kP3BigCap, reg_max = 0xFFFFFFFFu;
-    p3_rounds_knob(&cap_rounds, &rounds_above, &reg_max);
-    const size_t lds_big = std::max((size_t)kP3BigCap * 24 + ((size_t)p.p3_w + 32) * sizeof(uint32_t) + cache,
-                                    (size_t)cap_rounds * 24 + tables);
-    AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_runs_place_big),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big));
-    if (want_big)
-      hipLaunchKernelGGL(k_dsm_runs_place_big, dim3(256), dim3(kP3BigThreads), lds_big, c->stream,
-                         c->tmp_points, p, start2, c->bin_start, c->sorted, big_list, bin_z, cap_rounds,
-                         rounds_above, reg_max, pr);
-    c->bin_z_valid = false;
+    ScopedTimer tm(c, AMHIP_K_DSM_SCAN);
+    uint2* bin_z = reinterpret_cast<uint2*>(c->bin_z);
+    uint4* rec16 = reinterpret_cast<uint4*>(c->rec16);
+    AMHIP_SET_LDS(k_dsm_p3_place_rec, s.lds_place);
+    hipLaunchKernelGGL(k_dsm_p3_place_rec, dim3((unsigned)(p.p3_n1 * p.p3_n2)), dim3(kP3PlaceThreads),
+                       s.lds_place, c->stream, c->rec_b, p, p.p3_cap, t.start2, c->bin_start, rec16, c->sidx,
+                       bin_z, q.skip_lo, q.skip_hi);
+    AMHIP_SET_LDS(k_dsm_p3_place_rec_big, s.lds_place_big);
+    hipLaunchKernelGGL(k_dsm_p3_place_rec_big, dim3(256), dim3(kP3BigThreads), s.lds_place_big, c->stream,
+                       c->rec_b, p, t.start2, c->bin_start, rec16, c->sidx, bin_z, t.big_list, q.cap_rounds,
+                       q.rounds_above, q.reg_max);
+    AMHIP_TRY(hipGetLastError());
+    c->bin_z_valid = true;
+    c->pts = PtsView{nullptr, rec16, c->sidx, k.dev_xyz, c->zref, p.sub_x, p.sub_y};
+  }
+  return AMHIP_OK;
+}
+
+// Three-pass partition sort on doubles: c->sorted, c->tmp_points, c->sorted.
+static int sort_count_doubles(const SortCall& k) {
+  Ctx* c = k.c;
+  const SortPlan& s = k.s;
+  const SortTables& t = k.t;
+  if (const int rc = sort_count_pass(k, nullptr)) return rc;
+  if (s.phase == 1) return AMHIP_OK;
+  {
+    ScopedTimer tm(c, AMHIP_K_DSM_SCATTER);
+    AMHIP_SET_LDS(k_dsm_p3_scatter<true>, s.lds_scatter);
+    AMHIP_SET_LDS(k_dsm_p3_scatter<false>, s.lds_scatter);
+    hipLaunchKernelGGL(k_dsm_p3_scatter<true>, dim3((unsigned)s.g1), dim3(kP3Threads), s.lds_scatter,
+                       c->stream, k.dev_xyz, k.dev_values, k.n, k.p, t.start1, t.blk2, t.cursor1, c->sorted,
+                       k.zpart);
+    hipLaunchKernelGGL(k_dsm_p3_scatter<false>, dim3((unsigned)s.g2), dim3(kP3Threads), s.lds_scatter,
+                       c->stream, c->sorted, (const int32_t*)nullptr, k.n, k.p, t.start1, t.blk2, t.cursor2,
+                       c->tmp_points, (double*)nullptr);
+    AMHIP_TRY(hipGetLastError());
+  }
+  return launch_place_doubles(k, k_dsm_p3_place, k_dsm_p3_place_big);
+}
+
+// One-level counting sort (clouds below the partition sort's threshold); with records: both the doubles
+// and the records.
+static int sort_one_level(const SortCall& k) {
+  Ctx* c = k.c;
+  const SortPlan& s = k.s;
+  const DsmParams& p = k.p;
+  const size_t nbins = s.nbins;
+  {
+    ScopedTimer tm(c, AMHIP_K_MISC);
+    AMHIP_TRY(hipMemsetAsync(c->bin_start, 0, (nbins + 1) * sizeof(uint32_t), c->stream));
+  }
+  {
+    ScopedTimer tm(c, AMHIP_K_DSM_BIN_COUNT);
+    double* const zall = s.rec ? c->zall : nullptr;
+    hipLaunchKernelGGL(k_dsm_bin_count, dim3((unsigned)s.grid_pts), dim3(kOneLevelThreads), 0, c->stream,
+                       k.dev_xyz, k.n, p, c->bin_start, c->rank, zall);
+    if (s.rec)
+      hipLaunchKernelGGL(k_dsm_zref, dim3(1), dim3(1024), 0, c->stream, zall, s.zref_parts, c->zref);
+    AMHIP_TRY(hipGetLastError());
+  }
+  {
+    ScopedTimer tm(c, AMHIP_K_DSM_SCAN);
+    hipLaunchKernelGGL(k_scan_partials, dim3((unsigned)s.nblocks_scan), dim3(kScanT), 0,
+                       c->stream, c->bin_start, nbins, c->scan_partials);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, c->stream, c->scan_partials,
+                       s.nblocks_scan, c->bin_start + nbins, k.aux);
+    c->aux_done = true;
+    hipLaunchKernelGGL(k_scan_final, dim3((unsigned)s.nblocks_scan), dim3(kScanT), 0, c->stream,
+                       c->bin_start, nbins, c->scan_partials);
+    AMHIP_TRY(hipGetLastError());
+  }
+  {
+    ScopedTimer tm(c, AMHIP_K_DSM_SCATTER);
+    hipLaunchKernelGGL(k_dsm_scatter, dim3((unsigned)s.grid_pts), dim3(kOneLevelThreads), 0, c->stream,
+                       k.dev_xyz, k.dev_values, k.n, p, c->bin_start, c->rank, c->sorted, k.zpart,
+                       s.rec ? reinterpret_cast<uint4*>(c->rec16) : (uint4*)nullptr,
+                       s.rec ? c->sidx : (uint32_t*)nullptr, s.rec ? c->zref : (const double*)nullptr);
+    if (s.rec)
+      c->pts = PtsView{c->sorted, reinterpret_cast<const uint4*>(c->rec16), c->sidx, k.dev_xyz, c->zref,
+                       p.sub_x, p.sub_y};
     AMHIP_TRY(hipGetLastError());
   }
   return AMHIP_OK;
+}
+
+#undef AMHIP_SET_LDS
+
+template <class T>
+static int ensure_if_asked(T** ptr, size_t* cap, size_t need) {
+  return need ? ensure_capacity(ptr, cap, need) : AMHIP_OK;
 }
 
 int dsm_sort(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
              const DsmParams& p, unsigned long long* zrange, const SortSplit* split) {
-  const int rc = dsm_sort_impl(c, dev_xyz, dev_values, n, p, zrange, split);
-  if (rc) return rc;
-  // (every sort hands SortAux to one of its single-workgroup kernels)
-  if (!c->aux_done && !(split && split->phase == 1)) return arg_failure("dsm_sort: the call's range was not reset");
-  return AMHIP_OK;
-}
+  SortPlanInput in = {};
+  in.n = n;
+  in.split_present = split != nullptr;
+  in.split_phase = split ? split->phase : 0;
+  in.split_n_prefix = split ? split->n_prefix : 0;
+  in.has_values = dev_values != nullptr;
+  in.windowed = c->windowed;
+  in.sort_one_level = tuning_on("sort_one_level");
+  in.sort_runs = tuning("sort_runs", 1.0) != 0.0;
+  p3_rounds_knob(&in);
+  in.no_launch_skips = no_launch_skips();
+  // (the pinned word the previous call's placement left, never waited for: a value one call late is as good)
+  in.prev_sig = c->sort_stats_sig;
+  in.have_host_stats = c->host_sort_stats != nullptr;
+  in.prev_big_count = c->host_sort_stats ? c->host_sort_stats[0] : 0u;
+  const SortPlan s = plan_sort_call(in, p);
 
-static int dsm_sort_impl(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
-                         const DsmParams& p, unsigned long long* zrange, const SortSplit* split) {
-  // [min z, max z] of the binned points (for the mosaic's coarse cull): every
-  // workgroup of the first scatter pass -- it loads z anyway -- writes a
-  // partial, k_range_reduce folds them into *zrange
-  // (always: the call's own range -- c->dev_zrange[2], [3] -- bounds max |z| for the gather's
-  // rounding guard; `zrange`, the running range, may be null)
-  double* zpart = nullptr;
-  {
-    const size_t max_waves = 8 * std::max<size_t>((n + 2047) / 2048 + 1, 256 * 16);
-    const int rc = ensure_capacity(&c->zpart, &c->zpart_cap, 2 * max_waves + 16);
-    if (rc) return rc;
-    zpart = c->zpart;
-  }
-  // What the single-workgroup kernel in front of the first scatter resets (SortAux): the call's own
-  // range and -- when dsm_run asked for it -- the counters of the gather's tile lists.
-  // k_range_reduce (amhip_dsm.hip: the gather's prologue) folds zpart[0 .. range_parts) afterwards.
-  const SortAux aux = {c->dev_zrange + 2, c->aux_zero_words, c->aux_zero_words ? c->aux_nzero : 0};
+  const SortCaps& cap = s.cap;
+  int rc;
+  if ((rc = ensure_capacity(&c->zpart, &c->zpart_cap, cap.zpart))) return rc;
+  if ((rc = ensure_capacity(&c->sorted, &c->sorted_cap, cap.sorted))) return rc;
+  if ((rc = ensure_capacity(&c->bin_start, &c->bin_cap, cap.bin_start))) return rc;
+  if ((rc = ensure_if_asked(&c->tmp_points, &c->tmp_points_cap, cap.tmp_points))) return rc;
+  if ((rc = ensure_if_asked(&c->rec16, &c->rec16_cap, cap.rec16))) return rc;
+  if ((rc = ensure_if_asked(&c->sidx, &c->sidx_cap, cap.sidx))) return rc;
+  if ((rc = ensure_if_asked(&c->zref, &c->zref_cap, cap.zref))) return rc;
+  if ((rc = ensure_if_asked(&c->rec_a, &c->rec_a_cap, cap.rec_a))) return rc;
+  if ((rc = ensure_if_asked(&c->rec_b, &c->rec_b_cap, cap.rec_b))) return rc;
+  if ((rc = ensure_if_asked(&c->zall, &c->zall_cap, cap.zall))) return rc;
+  if ((rc = ensure_if_asked(&c->bin_z, &c->bin_z_cap, cap.bin_z))) return rc;
+  if ((rc = ensure_if_asked(&c->rank, &c->rank_cap, cap.rank))) return rc;
+  if ((rc = ensure_if_asked(&c->scan_partials, &c->partial_cap, cap.scan_partials))) return rc;
+  if ((rc = ensure_if_asked(&c->stripe_ws, &c->stripe_ws_cap, cap.stripe_ws))) return rc;
+
   c->aux_done = false;
-  c->range_parts = 0;
+  c->range_parts = s.range_parts;
   c->range_running = zrange;
-  const size_t nbins = (size_t)p.nbx * (size_t)p.nby;
-  const size_t nblocks_scan = (nbins + kScanE - 1) / kScanE;
-  const bool force_one_level_ = tuning_on("sort_one_level");
-  const unsigned long long geo_sig = sort_geometry_signature(p);   // (window geometry + sort plan)
-  {
-    int rc;
-    if ((rc = ensure_capacity(&c->sorted, &c->sorted_cap, 3 * n))) return rc;
-    if ((rc = ensure_capacity(&c->bin_start, &c->bin_cap, nbins + 4))) return rc;
-  }
-  c->last_num_bins = (int64_t)nbins;
+  c->last_num_bins = (int64_t)s.nbins;
   c->last_bin_cells = p.B;
   c->bin_z_valid = false;
   c->pts = PtsView{c->sorted, nullptr, nullptr, dev_xyz, nullptr, p.sub_x, p.sub_y};
-  // the record pipeline (the single-precision gather's mode): 16-byte records + rows + zref
-  const bool rec = p.fx_ok && !p.pcl_mode && !dev_values;
-  if (rec) {
-    int rc;
-    if ((rc = ensure_capacity(&c->rec16, &c->rec16_cap, 4 * n + 16))) return rc;
-    if ((rc = ensure_capacity(&c->sidx, &c->sidx_cap, n + 16))) return rc;
-    if ((rc = ensure_capacity(&c->zref, &c->zref_cap, (size_t)8))) return rc;
-  }
+  c->last_sort_pipeline = s.reported;
 
-  const bool force_one_level = force_one_level_;
-  const bool three_pass = p.p3_n1 > 0 && !force_one_level;
-  c->last_sort_pipeline = AMHIP_SORT_ONE_LEVEL;
-  if (split && split->phase == 1 && !three_pass)  // small clouds: selection in a pass of its own
-    return halo_select_run(c, dev_xyz, split->n_prefix, split->hp, split->halo_out,
-                           split->halo_counts);
-  if (split && !three_pass) split = nullptr;
-  if (three_pass) {
-    // ---- three-pass partition sort ---------------------------------------------
-    const int n1 = p.p3_n1, n2 = p.p3_n2, nk = n1 * n2;
-    auto count_grid = [](size_t len) {
-      return std::min<size_t>(std::max<size_t>((len + 8191) / 8192, 1), 256);
-    };
-    // (tiled call: the prefix is counted -- and its halo selected -- before the caller's
-    // exchange, the received rows after it; each part writes its own histogram rows)
-    const size_t n_a = split ? split->n_prefix : n;
-    const size_t g_a = count_grid(n_a), g_b = n > n_a ? count_grid(n - n_a) : 0;
-    const size_t gcount = g_a + g_b;
-    int rc;
-    // The run pipeline serves the doubles of a whole, untiled context; the records
-    // (their zref has to exist before the first is written), tiled calls and windows (the halo
-    // selection rides on the count pass), and clouds whose rows do not fit the run tables' 32-bit
-    // addresses with room to spare keep the counting pipeline (so do column blocks of more than
-    // 2048 bins: the run lists' 4 KB of LDS have to fit next to the big placement's image).
-    // tuning key sort_runs=0: always.
-    const bool runs = !rec && !split && !c->windowed && n <= ((size_t)1 << 27) && n1 <= kP3MaxKeys &&
-                      n2 <= kP3MaxKeys && p.p3_w <= 2048 && tuning("sort_runs", 1.0) != 0.0;
-    c->last_sort_pipeline = runs ? AMHIP_SORT_RUNS : AMHIP_SORT_COUNT;
-    if (runs) return dsm_sort_runs(c, dev_xyz, dev_values, n, p, zpart, aux, geo_sig);
-    if (rec) {
-      if ((rc = ensure_capacity(&c->rec_a, &c->rec_a_cap, (size_t)kRecWords * n + 16))) return rc;
-      if ((rc = ensure_capacity(&c->rec_b, &c->rec_b_cap, (size_t)kRecWords * n + 16))) return rc;
-      if ((rc = ensure_capacity(&c->zall, &c->zall_cap, 2 * gcount * (kP3CountThreads / 64) + 16))) return rc;
-    } else if ((rc = ensure_capacity(&c->tmp_points, &c->tmp_points_cap, 3 * n))) {
-      return rc;
-    }
-    double* const zall = rec ? c->zall : nullptr;
-    const size_t ws_words = gcount * (size_t)nk + 4 * (size_t)nk + 4 * (size_t)n1 + 64;
-    if ((rc = ensure_capacity(&c->stripe_ws, &c->stripe_ws_cap, ws_words))) return rc;
-    uint32_t* hist_rows = c->stripe_ws;
-    uint32_t* cnt = hist_rows + gcount * (size_t)nk;
-    uint32_t* start2 = cnt + nk;       // nk + 1
-    uint32_t* cursor2 = start2 + nk + 1;
-    uint32_t* start1 = cursor2 + nk;   // n1 + 1
-    uint32_t* cursor1 = start1 + n1 + 1;
-    uint32_t* blk2 = cursor1 + n1;     // n1 + 1
-    uint32_t* big_list = blk2 + n1 + 1;  // [count] + up to nk sub-partition ids
-    {
-      ScopedTimer t(c, AMHIP_K_DSM_BIN_COUNT);
-      const size_t lds = (size_t)nk * sizeof(uint32_t);
-      const size_t lds_halo = (size_t)((nk + 1) & ~1) * sizeof(uint32_t) + sizeof(HaloStage);
-      AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_p3_count<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_p3_count<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_halo));
-      const HaloParams no_halo = {};
-      if (split && split->phase == 1) {
-        AMHIP_TRY(hipMemsetAsync(split->halo_counts, 0,
-                                 sizeof(unsigned long long) * split->hp.nd, c->stream));
-        hipLaunchKernelGGL(k_dsm_p3_count<true>, dim3((unsigned)g_a), dim3(kP3CountThreads),
-                           lds_halo, c->stream, dev_xyz, n_a, p, hist_rows, split->hp, split->halo_out,
-                           split->halo_counts, zall);
-        AMHIP_TRY(hipGetLastError());
-        return AMHIP_OK;  // amhip_dsm_tiled_finish_dev comes back with phase 2
-      }
-      if (!split)
-        hipLaunchKernelGGL(k_dsm_p3_count<false>, dim3((unsigned)g_a), dim3(kP3CountThreads), lds,
-                           c->stream, dev_xyz, n_a, p, hist_rows, no_halo, (double*)nullptr,
-                           (unsigned long long*)nullptr, zall);
-      else if (g_b)
-        hipLaunchKernelGGL(k_dsm_p3_count<false>, dim3((unsigned)g_b), dim3(kP3CountThreads), lds,
-                           c->stream, dev_xyz + 3 * n_a, n - n_a, p, hist_rows + g_a * (size_t)nk,
-                           no_halo, (double*)nullptr, (unsigned long long*)nullptr,
-                           zall ? zall + 2 * g_a * (kP3CountThreads / 64) : nullptr);
-      // (the records' reference height: the middle of the range every count workgroup left --
-      // in a tiled call both parts', the second of which may be absent: its rows hold the first
-      // call's partials or the initial "empty" pairs)
-      if (rec)
-        hipLaunchKernelGGL(k_dsm_zref, dim3(1), dim3(1024), 0, c->stream, zall,
-                           (split && !g_b ? g_a : gcount) * (size_t)(kP3CountThreads / 64), c->zref);
-      // (reduction of the count workgroups' rows + the scan by the workgroup that finishes last: one launch)
-      hipLaunchKernelGGL(k_dsm_p3_reduce_scan, dim3((unsigned)((nk + 63) / 64)), dim3(1024), 0, c->stream,
-                         hist_rows, (int)gcount, cnt, n1, n2, start2, cursor2, start1, cursor1, blk2,
-                         (unsigned)p.p3_cap, (unsigned)kP3BigCap, big_list, (unsigned)(rec ? kRecChunk : kP3Chunk),
-                         aux, (unsigned*)nullptr, c->dev_tickets);
-      c->aux_done = true;
-      AMHIP_TRY(hipGetLastError());
-    }
-    if (rec) {
-      {
-        ScopedTimer t(c, AMHIP_K_DSM_SCATTER);
-        const size_t lds = (size_t)kRecChunk * (kRecWords + 1) * 4 + (3 * kP3MaxKeys + 32) * sizeof(uint32_t);
-        AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_p3_scatter_rec<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_p3_scatter_rec<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const size_t g1 = (n + kRecChunk - 1) / kRecChunk;
-        hipLaunchKernelGGL(k_dsm_p3_scatter_rec<true>, dim3((unsigned)g1), dim3(kP3Threads), lds,
-                           c->stream, dev_xyz, (const uint32_t*)nullptr, n, p, c->zref, start1, blk2,
-                           cursor1, c->rec_a, zpart);
-        c->range_parts = (size_t)g1 * (kP3Threads / 64);
-        hipLaunchKernelGGL(k_dsm_p3_scatter_rec<false>, dim3((unsigned)(g1 + n1)), dim3(kP3Threads),
-                           lds, c->stream, (const double*)nullptr, c->rec_a, n, p, c->zref, start1, blk2,
-                           cursor2, c->rec_b, (double*)nullptr);
-        AMHIP_TRY(hipGetLastError());
-      }
-      {
-        ScopedTimer t(c, AMHIP_K_DSM_SCAN);
-        if ((rc = ensure_capacity(&c->bin_z, &c->bin_z_cap, 2 * (nbins + 4)))) return rc;
-        uint2* bin_z = reinterpret_cast<uint2*>(c->bin_z);
-        uint4* rec16 = reinterpret_cast<uint4*>(c->rec16);
-        const size_t lds = (size_t)p.p3_cap * kRecWords * 4 + (3 * (size_t)p.p3_w + 32) * sizeof(uint32_t);
-        AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_p3_place_rec),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_dsm_p3_place_rec, dim3((unsigned)nk), dim3(kP3PlaceThreads), lds,
-                           c->stream, c->rec_b, p, p.p3_cap, start2, c->bin_start, rec16, c->sidx, bin_z,
-                           (unsigned)p.p3_cap, 0xFFFFFFFFu);
-        // (sub-partitions beyond one image: rounds over an image of cap_rounds points next to
-        // the rounds' tables -- place_rounds)
-        const size_t tables = (4 * (size_t)p.p3_w + 64) * sizeof(uint32_t);
-        int cap_rounds = (int)std::min<size_t>(kP3BigCap, (kLdsMaxBytes - tables) / (kRecWords * 4));
-        unsigned rounds_above = kP3BigCap, reg_max = 0xFFFFFFFFu;
-        p3_rounds_knob(&cap_rounds, &rounds_above, &reg_max);
-        const size_t lds_big = std::max((size_t)kP3BigCap * kRecWords * 4 + (3 * (size_t)p.p3_w + 32) * sizeof(uint32_t),
-                                        (size_t)cap_rounds * kRecWords * 4 + tables);
-        AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_p3_place_rec_big),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big));
-        hipLaunchKernelGGL(k_dsm_p3_place_rec_big, dim3(256), dim3(kP3BigThreads), lds_big, c->stream,
-                           c->rec_b, p, start2, c->bin_start, rec16, c->sidx, bin_z, big_list, cap_rounds, rounds_above, reg_max);
-        AMHIP_TRY(hipGetLastError());
-        c->bin_z_valid = true;
-        c->pts = PtsView{nullptr, rec16, c->sidx, dev_xyz, c->zref, p.sub_x, p.sub_y};
-      }
-      return AMHIP_OK;
-    }
-    {
-      ScopedTimer t(c, AMHIP_K_DSM_SCATTER);
-      const size_t lds = (size_t)kP3Chunk * 28 + (3 * kP3MaxKeys + 32) * sizeof(uint32_t);
-      AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_p3_scatter<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_p3_scatter<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      const size_t g1 = (n + kP3Chunk - 1) / kP3Chunk;
-      hipLaunchKernelGGL(k_dsm_p3_scatter<true>, dim3((unsigned)g1), dim3(kP3Threads), lds,
-                         c->stream, dev_xyz, dev_values, n, p, start1, blk2, cursor1, c->sorted,
-                         zpart);
-      c->range_parts = (size_t)g1 * (kP3Threads / 64);
-      hipLaunchKernelGGL(k_dsm_p3_scatter<false>, dim3((unsigned)(g1 + n1)), dim3(kP3Threads),
-                         lds, c->stream, c->sorted, (const int32_t*)nullptr, n, p, start1, blk2,
-                         cursor2, c->tmp_points, (double*)nullptr);
-      AMHIP_TRY(hipGetLastError());
-    }
-    {
-      ScopedTimer t(c, AMHIP_K_DSM_SCAN);
-      // single-precision gather: the placement pass also leaves every bin's height range
-      // (the occupancy pre-pass sorts tiles without room under the error bound onto the FP64
-      // lists before anything is staged); bins no sub-partition covers keep "empty"
-      uint2* bin_z = nullptr;  // (the record pipeline returned above; the doubles pipeline needs none)
-      const size_t zlds = bin_z ? 2 * (size_t)p.p3_w * sizeof(uint32_t) : 0;
-      const size_t lds = (size_t)p.p3_cap * 24 + ((size_t)p.p3_w + 32) * sizeof(uint32_t) + zlds;
-      AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_p3_place),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      // Sub-partitions beyond the placement workgroup's registers (denser parts of a non-uniform
-      // cloud) are k_dsm_p3_place_big's.  Its launch is skipped when the PREVIOUS three-pass call of
-      // this geometry had none (the scan leaves their number in a pinned word, never waited for):
-      // k_dsm_p3_place then keeps nothing back and places a stray over-full sub-partition itself,
-      // directly (slower, same result) -- the word it leaves brings the big kernel back next call.
-      const bool want_big = !(c->sort_stats_sig == geo_sig && c->host_sort_stats && c->host_sort_stats[0] == 0u) ||
-                            no_launch_skips();
-      c->sort_stats_sig = geo_sig;
-      hipLaunchKernelGGL(k_dsm_p3_place, dim3((unsigned)nk), dim3(kP3PlaceThreads), lds,
-                         c->stream, c->tmp_points, p, p.p3_cap, start2, c->bin_start, c->sorted,
-                         want_big ? (unsigned)p.p3_cap : 0xFFFFFFFFu, 0xFFFFFFFFu, bin_z,
-                         (const uint32_t*)big_list, c->host_sort_stats);
-      const size_t tables = (4 * (size_t)p.p3_w + 64) * sizeof(uint32_t);
-      int cap_rounds = (int)std::min<size_t>(kP3BigCap, (kLdsMaxBytes - tables) / 24);
-      unsigned rounds_above = kP3BigCap, reg_max = 0xFFFFFFFFu;
-      p3_rounds_knob(&cap_rounds, &rounds_above, &reg_max);
-      const size_t lds_big = std::max((size_t)kP3BigCap * 24 + ((size_t)p.p3_w + 32) * sizeof(uint32_t) + zlds,
-                                      (size_t)cap_rounds * 24 + tables);
-      AMHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsm_p3_place_big),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big));
-      if (want_big)
-        hipLaunchKernelGGL(k_dsm_p3_place_big, dim3(256), dim3(kP3BigThreads), lds_big, c->stream,
-                           c->tmp_points, p, start2, c->bin_start, c->sorted, big_list, bin_z, cap_rounds, rounds_above, reg_max);
-      c->bin_z_valid = bin_z != nullptr;
-      AMHIP_TRY(hipGetLastError());
-    }
-  } else {
-    // ---- one-level counting sort (clouds below the partition sort's threshold) --------
-    {
-      int rc;
-      if ((rc = ensure_capacity(&c->rank, &c->rank_cap, n))) return rc;
-      if ((rc = ensure_capacity(&c->scan_partials, &c->partial_cap, nblocks_scan + 4))) return rc;
-    }
-    {
-      ScopedTimer t(c, AMHIP_K_MISC);
-      AMHIP_TRY(hipMemsetAsync(c->bin_start, 0, (nbins + 1) * sizeof(uint32_t), c->stream));
-    }
-    const int block = 256;
-    size_t grid_pts = (n + block - 1) / block;
-    if (grid_pts > 256 * 16) grid_pts = 256 * 16;
-    {
-      ScopedTimer t(c, AMHIP_K_DSM_BIN_COUNT);
-      double* zall = nullptr;
-      if (rec) {
-        int rc;
-        if ((rc = ensure_capacity(&c->zall, &c->zall_cap, 2 * grid_pts * 4 + 16))) return rc;
-        zall = c->zall;
-      }
-      hipLaunchKernelGGL(k_dsm_bin_count, dim3((unsigned)grid_pts), dim3(block), 0, c->stream,
-                         dev_xyz, n, p, c->bin_start, c->rank, zall);
-      if (rec)
-        hipLaunchKernelGGL(k_dsm_zref, dim3(1), dim3(1024), 0, c->stream, zall, grid_pts * 4, c->zref);
-      AMHIP_TRY(hipGetLastError());
-    }
-    {
-      ScopedTimer t(c, AMHIP_K_DSM_SCAN);
-      hipLaunchKernelGGL(k_scan_partials, dim3((unsigned)nblocks_scan), dim3(kScanT), 0,
-                         c->stream, c->bin_start, nbins, c->scan_partials);
-      hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, c->stream, c->scan_partials,
-                         nblocks_scan, c->bin_start + nbins, aux);
-      c->aux_done = true;
-      hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nblocks_scan), dim3(kScanT), 0, c->stream,
-                         c->bin_start, nbins, c->scan_partials);
-      AMHIP_TRY(hipGetLastError());
-    }
-    {
-      ScopedTimer t(c, AMHIP_K_DSM_SCATTER);
-      hipLaunchKernelGGL(k_dsm_scatter, dim3((unsigned)grid_pts), dim3(block), 0, c->stream,
-                         dev_xyz, dev_values, n, p, c->bin_start, c->rank, c->sorted, zpart,
-                         rec ? reinterpret_cast<uint4*>(c->rec16) : (uint4*)nullptr,
-                         rec ? c->sidx : (uint32_t*)nullptr, rec ? c->zref : (const double*)nullptr);
-      if (rec)
-        c->pts = PtsView{c->sorted, reinterpret_cast<const uint4*>(c->rec16), c->sidx, dev_xyz, c->zref,
-                         p.sub_x, p.sub_y};
-      c->range_parts = (size_t)grid_pts * 4;
-      AMHIP_TRY(hipGetLastError());
-    }
+  const bool three_pass = s.pipeline != kSortOneLevel && s.pipeline != kSortHaloOnly;
+  const SortCall k = {c, dev_xyz, dev_values, n, p, three_pass ? split : nullptr, s,
+                      sort_tables(c->stripe_ws, s), c->zpart,
+                      SortAux{c->dev_zrange + 2, c->aux_zero_words, c->aux_zero_words ? c->aux_nzero : 0}};
+  switch (s.pipeline) {
+    case kSortHaloOnly:
+      return halo_select_run(c, dev_xyz, split->n_prefix, split->hp, split->halo_out, split->halo_counts);
+    case kSortOneLevel: rc = sort_one_level(k); break;
+    case kSortCountDoubles: rc = sort_count_doubles(k); break;
+    case kSortCountRecords: rc = sort_count_records(k); break;
+    case kSortRuns: rc = sort_runs(k); break;
   }
+  if (rc) return rc;
+  // (every sort hands SortAux to one of its single-workgroup kernels)
+  if (!c->aux_done && s.phase != 1) return arg_failure("dsm_sort: the call's range was not reset");
   return AMHIP_OK;
 }
 
