@@ -9,6 +9,7 @@
 #include <new>
 
 #include "amhip_common.h"
+#include "amhip_ortho_plan.h"
 
 namespace amhip {
 
@@ -107,78 +108,9 @@ static void drain_timers(Ctx* c) {
 }
 
 // ---------------------------------------------------------------------------
-// host-side pose math (minkindr; mirrors oracle/amo_compat.h)
-// ---------------------------------------------------------------------------
-struct H3 {
-  double x, y, z;
-};
-static H3 hcross(const H3& a, const H3& b) {
-  H3 r;
-  r.x = a.y * b.z - a.z * b.y;
-  r.y = a.z * b.x - a.x * b.z;
-  r.z = a.x * b.y - a.y * b.x;
-  return r;
-}
-static H3 hrotate(double qw, double qx, double qy, double qz, const H3& v) {
-  const H3 qv = {qx, qy, qz};
-  H3 uv = hcross(qv, v);
-  uv.x = uv.x + uv.x;
-  uv.y = uv.y + uv.y;
-  uv.z = uv.z + uv.z;
-  const H3 c2 = hcross(qv, uv);
-  H3 r;
-  r.x = (v.x + qw * uv.x) + c2.x;
-  r.y = (v.y + qw * uv.y) + c2.y;
-  r.z = (v.z + qw * uv.z) + c2.z;
-  return r;
-}
-
-HPose hpose_from7(const double* p) {
-  HPose r;
-  r.tx = p[0];
-  r.ty = p[1];
-  r.tz = p[2];
-  r.qw = p[3];
-  r.qx = p[4];
-  r.qy = p[5];
-  r.qz = p[6];
-  return r;
-}
-
-// inverse() = (q*, -(q* (x) t))
-HPose hpose_inverse(const HPose& T) {
-  HPose r;
-  r.qw = T.qw;
-  r.qx = -T.qx;
-  r.qy = -T.qy;
-  r.qz = -T.qz;
-  const H3 t = {T.tx, T.ty, T.tz};
-  const H3 rt = hrotate(r.qw, r.qx, r.qy, r.qz, t);
-  r.tx = -rt.x;
-  r.ty = -rt.y;
-  r.tz = -rt.z;
-  return r;
-}
-
-// A * B = (qA qB, tA + qA (x) tB)
-HPose hpose_compose(const HPose& A, const HPose& B) {
-  HPose r;
-  r.qw = A.qw * B.qw - A.qx * B.qx - A.qy * B.qy - A.qz * B.qz;
-  r.qx = A.qw * B.qx + A.qx * B.qw + A.qy * B.qz - A.qz * B.qy;
-  r.qy = A.qw * B.qy + A.qy * B.qw + A.qz * B.qx - A.qx * B.qz;
-  r.qz = A.qw * B.qz + A.qz * B.qw + A.qx * B.qy - A.qy * B.qx;
-  const H3 tb = {B.tx, B.ty, B.tz};
-  const H3 rt = hrotate(A.qw, A.qx, A.qy, A.qz, tb);
-  r.tx = A.tx + rt.x;
-  r.ty = A.ty + rt.y;
-  r.tz = A.tz + rt.z;
-  return r;
-}
-
-// ---------------------------------------------------------------------------
 // parameter set-up
 // ---------------------------------------------------------------------------
-// grid_bases: amhip_dsm_plan.h
+// grid_bases: amhip_dsm_plan.h.  The mosaic's poses, view bounds and plan: amhip_ortho_plan.h
 
 // The opt-in single-precision mode protects itself on rough terrain.  A
 // tile whose height range leaves no room under the error bound is done by the FP64 kernel, which
@@ -274,262 +206,6 @@ static int dsm_subwindow(Ctx* c, const double* dev_xyz, size_t n, int radius_sq,
   p_sub->out_j0 = j_lo;
   p_sub->out_pitch = c->win_rows;
   return 1;
-}
-
-static void normalize3(double* v) {
-  const double n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-  v[0] /= n;
-  v[1] /= n;
-  v[2] /= n;
-}
-
-// Conservative view cone of a camera WITH distortion: the largest normalised
-// radius rho = sqrt(x^2 + y^2) / z a landmark can have and still project into
-// the image (plus margins).  The reference tests nothing but the image box
-// (ortho-backward-grid.cc:164-171), so where the distortion polynomial folds
-// back, far off-axis landmarks DO count as visible -- the bound covers that.
-// A landmark is visible only if |distort(p)| <= B, B = farthest image corner
-// (+1 pixel) in distorted normalised coordinates; |distort(p)| is bounded from
-// below by g(|p|), and the supremum of {r : g(r) <= B} is found on a grid with
-// a Lipschitz margin per step (so no dip between samples is missed) plus an
-// analytic tail.  false = no usable bound (the kernel then tests every frame).
-static bool distorted_view_cone(const amhip_camera& cam, double* cone) {
-  double B = 0.0;
-  const double us[2] = {-1.0, (double)cam.width}, vs[2] = {-1.0, (double)cam.height};
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      const double x = (us[a] - cam.cu) / cam.fu, y = (vs[b] - cam.cv) / cam.fv;
-      B = std::max(B, std::sqrt(x * x + y * y));
-    }
-  B = B * (1.0 + 1e-9) + 1e-9;
-  if (cam.distortion == AMHIP_DIST_RADTAN) {
-    const double k1 = cam.dist[0], k2 = cam.dist[1];
-    const double c = 4.5 * (std::fabs(cam.dist[2]) + std::fabs(cam.dist[3]));  // tangential <= c r^2
-    auto g = [&](double r) {
-      const double r2 = r * r;
-      return r * std::fabs(1.0 + k1 * r2 + k2 * r2 * r2) - c * r2;
-    };
-    auto lip = [&](double r) {
-      const double r2 = r * r;
-      return 1.0 + 3.0 * std::fabs(k1) * r2 + 5.0 * std::fabs(k2) * r2 * r2 + 2.0 * c * r;
-    };
-    const double Rmax = 1e4;
-    // tail r >= Rmax: the leading term must dominate for good
-    if (k2 != 0.0) {
-      const double lead = std::fabs(k2) * Rmax * Rmax * Rmax * Rmax;
-      if (!(lead > 2.0 * (std::fabs(k1) * Rmax * Rmax + 1.0 + c * Rmax)) ||
-          !(0.5 * lead * Rmax > 2.0 * B))
-        return false;
-    } else if (k1 != 0.0) {
-      const double lead = std::fabs(k1) * Rmax * Rmax;
-      if (!(lead > 2.0 * (1.0 + c * Rmax)) || !(0.5 * lead * Rmax > 2.0 * B)) return false;
-    } else if (c != 0.0) {
-      return false;  // r - c r^2: no bound
-    }
-    double rstar = 0.0;
-    double r = 0.0;
-    while (r < Rmax) {
-      const double h = r < 20.0 ? 5e-4 : r * 2.5e-5;
-      const double rn = r + h;
-      if (g(r) <= B + h * lip(rn)) rstar = rn;
-      r = rn;
-    }
-    if (!(rstar < 0.5 * Rmax)) return false;
-    *cone = rstar * (1.0 + 1e-6) + 1e-6;
-    return true;
-  }
-  if (cam.distortion == AMHIP_DIST_EQUIDISTANT) {
-    const double* k = cam.dist;
-    auto td = [&](double th) {
-      const double t2 = th * th, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
-      return std::fabs(th * (1.0 + k[0] * t2 + k[1] * t4 + k[2] * t6 + k[3] * t8));
-    };
-    const double half_pi = 1.5707963267948966;
-    const double t2 = half_pi * half_pi, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
-    const double L = 1.0 + 3.0 * std::fabs(k[0]) * t2 + 5.0 * std::fabs(k[1]) * t4 +
-                     7.0 * std::fabs(k[2]) * t6 + 9.0 * std::fabs(k[3]) * t8;
-    const double h = 2e-5;
-    double tstar = 0.0;
-    for (double th = 0.0; th < half_pi; th += h)
-      if (td(th) <= B + h * L) tstar = th + h;
-    if (!(tstar < half_pi - 2e-3)) return false;  // sees (numerically) the whole half space
-    *cone = std::tan(tstar) * (1.0 + 1e-6) + 1e-6;
-    return true;
-  }
-  return false;
-}
-
-// Tighter bounds for cameras with a distortion model, given the view cone
-// `cone` of distorted_view_cone() (every visible landmark has |p| <= cone * z):
-//   ax, ay  outer rectangle: visible => |x| <= ax z and |y| <= ay z.  From
-//           x_d = x s(r) + t_x with |t_x| <= c r^2 (radtan; s = the radial
-//           factor, t = the tangential terms) resp. x_d = x s(r) (equidistant)
-//           and |x_d| <= Bx for a visible landmark:  |x| <= (Bx + c cone^2) / min s.
-//   rin     inner cone: |p| <= rin z  =>  visible by a clear margin.  The
-//           distorted point of such a landmark has |x_d|, |y_d| <= r |s(r)| + c r^2
-//           =: g(r); rin = the largest r with g <= (smallest distance of the
-//           principal point to an image edge, normalised) on [0, r].
-// Both scans carry a Lipschitz margin per step.  Values of 0 mean "no bound".
-static void distorted_rectangle_and_inner_cone(const amhip_camera& cam, double cone, double* ax,
-                                               double* ay, double* rin) {
-  *ax = *ay = cone;
-  *rin = 0.0;
-  const double W = cam.width, H = cam.height;
-  // (the same one-pixel allowance as distorted_view_cone)
-  const double Bx = std::max(std::fabs(-1.0 - cam.cu), std::fabs(W - cam.cu)) / cam.fu;
-  const double By = std::max(std::fabs(-1.0 - cam.cv), std::fabs(H - cam.cv)) / cam.fv;
-  const double bmin = std::min(std::min(cam.cu / cam.fu, (W - cam.cu) / cam.fu),
-                               std::min(cam.cv / cam.fv, (H - cam.cv) / cam.fv));
-  double c = 0.0;
-  // s(r): radial factor; ds: an upper bound of |s'| that grows with r
-  auto s_of = [&](double r) {
-    if (cam.distortion == AMHIP_DIST_RADTAN) {
-      const double r2 = r * r;
-      return 1.0 + cam.dist[0] * r2 + cam.dist[1] * r2 * r2;
-    }
-    if (r < 1e-8) return 1.0;
-    const double th = std::atan(r);
-    const double t2 = th * th, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
-    return th * (1.0 + cam.dist[0] * t2 + cam.dist[1] * t4 + cam.dist[2] * t6 + cam.dist[3] * t8) / r;
-  };
-  auto ds_of = [&](double r) {
-    if (cam.distortion == AMHIP_DIST_RADTAN)
-      return 2.0 * std::fabs(cam.dist[0]) * r + 4.0 * std::fabs(cam.dist[1]) * r * r * r;
-    // s = theta_d(theta) / r, theta = atan r, theta_d = theta P(theta^2):
-    //   s' = [P (r / (1 + r^2) - theta) + 2 theta^2 P' r / (1 + r^2)] / r^2
-    // |theta_d'| <= L, |theta_d| <= L theta <= L r            =>  |s'| <= 2 L / r
-    // |r / (1 + r^2) - atan r| <= r^3, theta <= r, |P| <= L   =>  |s'| <= (L + 2 Lp) r
-    const double hp = 1.5707963267948966, t2 = hp * hp, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
-    const double L = 1.0 + 3.0 * std::fabs(cam.dist[0]) * t2 + 5.0 * std::fabs(cam.dist[1]) * t4 +
-                     7.0 * std::fabs(cam.dist[2]) * t6 + 9.0 * std::fabs(cam.dist[3]) * t8;
-    const double Lp = std::fabs(cam.dist[0]) + 2.0 * std::fabs(cam.dist[1]) * t2 +
-                      3.0 * std::fabs(cam.dist[2]) * t4 + 4.0 * std::fabs(cam.dist[3]) * t6;
-    return std::min(2.0 * L / std::max(r, 1e-12), (L + 2.0 * Lp) * r);
-  };
-  if (cam.distortion == AMHIP_DIST_RADTAN)
-    c = 4.5 * (std::fabs(cam.dist[2]) + std::fabs(cam.dist[3]));
-  if (!(cone > 0.0) || !(cone < 1e3)) return;
-  // ---- outer rectangle: min |s| on [0, cone]
-  {
-    const int n = 20000;
-    const double h = cone / n;
-    double smin = 1e300;
-    for (int k = 0; k <= n; ++k) {
-      const double r = k * h;
-      smin = std::min(smin, std::fabs(s_of(r)) - h * ds_of(r + h));
-    }
-    if (smin > 0.05) {
-      const double tx = c * cone * cone;
-      *ax = std::min(cone, ((Bx + tx) / smin) * (1.0 + 1e-6) + 1e-6);
-      *ay = std::min(cone, ((By + tx) / smin) * (1.0 + 1e-6) + 1e-6);
-    }
-  }
-  // ---- inner cone
-  if (bmin > 0.0) {
-    const double bound = bmin * (1.0 - 1e-6) - 1e-9;
-    const double h = 2e-5;
-    double r = 0.0, best = 0.0;
-    while (r < cone) {
-      const double rn = r + h;
-      // g(r) = r |s(r)| + c r^2;  |g'| <= |s| + r |s'| + 2 c r
-      const double g = r * std::fabs(s_of(r)) + c * r * r;
-      const double lip = std::fabs(s_of(rn)) + h * ds_of(rn) + rn * ds_of(rn) + 2.0 * c * rn;
-      if (!(g + h * lip <= bound)) break;
-      best = rn;
-      r = rn;
-    }
-    *rin = best;
-  }
-}
-
-static void make_ortho_params(Ctx& c, const amhip_camera& cam,
-                              size_t F, size_t frame_stride, size_t row_step,
-                              int channels, int colored, OrthoParams* out) {
-  const amhip_grid_desc& g = c.grid;
-  OrthoParams p;
-  std::memset(&p, 0, sizeof(p));
-  grid_bases(g, &p.base_x, &p.base_y);
-  p.res = g.resolution;
-  p.rows = c.win_rows;
-  p.cols = c.win_cols;
-  p.i_off = c.win_i0;
-  p.j_off = c.win_j0;
-  p.fu = cam.fu;
-  p.fv = cam.fv;
-  p.cu = cam.cu;
-  p.cv = cam.cv;
-  for (int k = 0; k < 4; ++k) p.dist[k] = cam.dist[k];
-  p.width = cam.width;
-  p.height = cam.height;
-  p.distortion = cam.distortion;
-  p.num_frames = static_cast<int>(F);
-  p.channels = channels;
-  p.colored = colored;
-  p.frame_stride = frame_stride;
-  p.row_step = row_step;
-  // Side planes of the undistorted pinhole frustum, camera frame, through the
-  // optical centre; a landmark with z > 0 projects into [0,W) x [0,H) only if
-  // it is on the inner side of all four.
-  p.cull = (cam.distortion == AMHIP_DIST_NONE && cam.fu > 0.0 && cam.fv > 0.0) ? 1 : 0;
-  double cone = 0.0;
-  bool have_cone = false;
-  if (cam.distortion != AMHIP_DIST_NONE && cam.fu > 0.0 && cam.fv > 0.0 &&
-      !tuning_on("no_distorted_cull")) {
-    // (a few hundred thousand evaluations: cached per camera)
-    if (c.cone_state == 0 || std::memcmp(&c.cone_cam, &cam, sizeof(cam)) != 0) {
-      c.cone_cam = cam;
-      c.cone_state = distorted_view_cone(cam, &c.cone) ? 1 : 2;
-      c.cone_state_rect = 0;
-    }
-    have_cone = c.cone_state == 1;
-    cone = c.cone;
-  }
-  double ax = cone, ay = cone;
-  p.r_in = 0.0;
-  if (have_cone) {
-    if (c.cone_state_rect != 1 || c.cone_rect_cone != cone) {
-      distorted_rectangle_and_inner_cone(cam, cone, &c.cone_ax, &c.cone_ay, &c.cone_rin);
-      c.cone_state_rect = 1;
-      c.cone_rect_cone = cone;
-    }
-    ax = c.cone_ax;
-    ay = c.cone_ay;
-    if (!tuning_on("no_distorted_prune")) p.r_in = c.cone_rin;
-    if (tuning_on("distorted_square_cull")) ax = ay = cone;  // (A/B: the circumscribed square)
-  }
-  if (have_cone) {
-    // every visible landmark has |x| <= ax * z and |y| <= ay * z
-    p.cull = 1;
-    double l[3] = {1.0, 0.0, ax}, r[3] = {-1.0, 0.0, ax};
-    double t[3] = {0.0, 1.0, ay}, b[3] = {0.0, -1.0, ay};
-    normalize3(l);
-    normalize3(r);
-    normalize3(t);
-    normalize3(b);
-    for (int k = 0; k < 3; ++k) {
-      p.pl[0][k] = l[k];
-      p.pl[1][k] = r[k];
-      p.pl[2][k] = t[k];
-      p.pl[3][k] = b[k];
-    }
-  } else if (p.cull) {
-    const double W = cam.width, H = cam.height;
-    double l[3] = {cam.fu, 0.0, cam.cu};          // u >= 0
-    double r[3] = {-cam.fu, 0.0, W - cam.cu};     // u <  W
-    double t[3] = {0.0, cam.fv, cam.cv};          // v >= 0
-    double b[3] = {0.0, -cam.fv, H - cam.cv};     // v <  H
-    normalize3(l);
-    normalize3(r);
-    normalize3(t);
-    normalize3(b);
-    for (int k = 0; k < 3; ++k) {
-      p.pl[0][k] = l[k];
-      p.pl[1][k] = r[k];
-      p.pl[2][k] = t[k];
-      p.pl[3][k] = b[k];
-    }
-  }
-  *out = p;
 }
 
 static float layer_init_value(int layer) {
@@ -1250,16 +926,11 @@ int amhip_camera_view_bounds(const amhip_camera* cam, double* out4) {
   if (!cam || !out4) return arg_fail("amhip_camera_view_bounds: null argument");
   if (!(cam->fu > 0.0) || !(cam->fv > 0.0) || cam->width <= 0 || cam->height <= 0)
     return arg_fail("amhip_camera_view_bounds: bad camera");
-  out4[0] = out4[1] = out4[2] = out4[3] = 0.0;
-  if (cam->distortion == AMHIP_DIST_NONE) {
-    out4[1] = std::max(cam->cu, (double)cam->width - cam->cu) / cam->fu;
-    out4[2] = std::max(cam->cv, (double)cam->height - cam->cv) / cam->fv;
-    return AMHIP_OK;
-  }
-  double cone = 0.0;
-  if (!distorted_view_cone(*cam, &cone)) return AMHIP_OK;
-  out4[0] = cone;
-  distorted_rectangle_and_inner_cone(*cam, cone, &out4[1], &out4[2], &out4[3]);
+  const ViewBounds b = camera_view_bounds(*cam);
+  out4[0] = b.cone;
+  out4[1] = b.ax;
+  out4[2] = b.ay;
+  out4[3] = b.rin;
   return AMHIP_OK;
 }
 
@@ -1281,85 +952,56 @@ int amhip_ortho_backward_process_dev(amhip_ctx* h, const amhip_camera* cam,
   Ctx* c = &h->impl;
   int rc = use_device(c);
   if (rc) return rc;
-  // one buffer, one upload: FramePose[F], then FrameFast[F + 2] (two FramePose
-  // slots each; the two extra entries carry the camera for exact_view(),
-  // doubles 0..5, and the atan table of fold_finish(), doubles 8..24)
-  const size_t slots = F + 2 * (F + 2);
-  if ((rc = ensure_capacity(&c->frame_poses, &c->frame_pose_cap, slots))) return rc;
-
-  // T_C_G[f] = T_G_C[f].inverse()  (ortho-backward-grid.cc:157-158; the
-  // reference recomputes it per cell and frame, the value is the same)
-  static_assert(sizeof(FrameFast) == 2 * sizeof(FramePose), "frame table layout");
-  std::vector<FramePose> inv(slots);
-  FrameFast* fast = reinterpret_cast<FrameFast*>(inv.data() + F);
-  double qdev = 0.0;  // max | |q|^2 - 1 |
-  bool fast_ok = cam->distortion == AMHIP_DIST_NONE && cam->fu > 0.0 && cam->fv > 0.0 &&
-                 !tuning_on("ortho_exact_fold");
-  for (size_t f = 0; f < F; ++f) {
-    const HPose T = hpose_inverse(hpose_from7(host_T_G_C + 7 * f));
-    inv[f].qw = T.qw;
-    inv[f].qx = T.qx;
-    inv[f].qy = T.qy;
-    inv[f].qz = T.qz;
-    inv[f].tx = T.tx;
-    inv[f].ty = T.ty;
-    inv[f].tz = T.tz;
-    inv[f]._pad = 0.0;
-    // (non-unit quaternion / non-finite pose: the whole call takes the exact kernel)
-    if (!make_frame_fast(inv[f], &fast[f])) fast_ok = false;
-    const double dev = std::fabs(T.qw * T.qw + T.qx * T.qx + T.qy * T.qy + T.qz * T.qz - 1.0);
-    if (!(dev <= qdev)) qdev = dev;  // (NaN sticks)
-  }
-  {
-    double* camd = reinterpret_cast<double*>(&fast[F]);
-    std::memset(camd, 0, 2 * sizeof(FrameFast));
-    make_atan_table(camd + 8);
-    camd[0] = cam->fu;
-    camd[1] = cam->fv;
-    camd[2] = cam->cu;
-    camd[3] = cam->cv;
-    camd[4] = (double)cam->width;
-    camd[5] = (double)cam->height;
-  }
-  // pageable source: hipMemcpyAsync returns once it has been staged
-  AMHIP_TRY(hipMemcpyAsync(c->frame_poses, inv.data(), slots * sizeof(FramePose),
-                           hipMemcpyHostToDevice, c->stream));
-
-  OrthoParams p;
-  make_ortho_params(*c, *cam, F, frame_stride, row_step, channels, colored, &p);
-  // layer states (lazy reset): the kernel reads elevation; elevation_angle,
-  // observation_index and the output layer are either all produced with a
-  // fused fill or all materialized; num_observations stays logically 0
+  // ---- what the plan depends on: the context's window, the layers' states, the knobs of this moment
   const int out_layer = colored ? AMHIP_LAYER_COLORED_ORTHO : AMHIP_LAYER_ORTHO;
+  OrthoPlanInput in = {};
+  in.grid = c->grid;
+  in.win_i0 = c->win_i0;
+  in.win_j0 = c->win_j0;
+  in.win_rows = c->win_rows;
+  in.win_cols = c->win_cols;
+  in.cam = *cam;
+  in.F = F;
+  in.frame_stride = frame_stride;
+  in.row_step = row_step;
+  in.channels = channels;
+  in.colored = colored;
+  in.zrange_valid = c->zrange_valid;
+  in.state_angle = c->layer_state[AMHIP_LAYER_ELEVATION_ANGLE];
+  in.state_index = c->layer_state[AMHIP_LAYER_OBSERVATION_INDEX];
+  in.state_out = c->layer_state[out_layer];
+  in.state_nobs = c->layer_state[AMHIP_LAYER_NUM_OBSERVATIONS];
+  in.knobs.no_distorted_cull = tuning_on("no_distorted_cull");
+  in.knobs.no_distorted_prune = tuning_on("no_distorted_prune");
+  in.knobs.distorted_square_cull = tuning_on("distorted_square_cull");
+  in.knobs.ortho_exact_fold = tuning_on("ortho_exact_fold");
+  in.knobs.no_coarse_cull = tuning_on("no_coarse_cull");
+  in.knobs.ortho_no_prune = tuning_on("ortho_no_prune");
+  in.knobs.ortho_no_tile_list = tuning_on("ortho_no_tile_list");
+  // ---- the frame table and the plan (amhip_ortho_plan.h)
+  const size_t slots = frame_table_slots(F);
+  std::vector<FramePose> table(slots);
+  const FrameTable frames = build_frame_table(*cam, host_T_G_C, F, in.knobs.ortho_exact_fold, table.data());
+  const OrthoPlan plan = plan_ortho_call(in, frames, &c->view_bounds);
+  // ---- one buffer, one upload (pageable source: hipMemcpyAsync returns once it has been staged)
+  if ((rc = ensure_capacity(&c->frame_poses, &c->frame_pose_cap, slots))) return rc;
+  AMHIP_TRY(hipMemcpyAsync(c->frame_poses, table.data(), slots * sizeof(FramePose),
+                           hipMemcpyHostToDevice, c->stream));
+  // ---- layer states (lazy reset): the kernel reads elevation; elevation_angle, observation_index
+  // and the output layer are either all produced with a fused fill or all materialized;
+  // num_observations stays in its state while it is logically 0.  (The dirty box is ortho_run's
+  // to set: every error return before it comes out of materialize -- nothing written yet -- or out
+  // of touch(), which has marked the whole window by then.)
   if ((rc = materialize(c, AMHIP_LAYER_ELEVATION))) return rc;
   const int outs[3] = {AMHIP_LAYER_ELEVATION_ANGLE, AMHIP_LAYER_OBSERVATION_INDEX, out_layer};
-  p.virt_out = 1;
-  for (int k = 0; k < 3; ++k)
-    if (c->layer_state[outs[k]] != 3) p.virt_out = 0;
-  dirty_full(c);  // (ortho_run narrows it to the tile list's box where one is walked)
   for (int k = 0; k < 3; ++k) {
-    if (p.virt_out)
+    if (plan.p.virt_out)
       c->layer_state[outs[k]] = 1;
     else if ((rc = touch(c, outs[k])))
       return rc;
   }
-  p.radius_scale = 1.0 + 2.0 * qdev;
-  if (!(qdev < 0.25)) p.cull = 0;  // not a rotation at all (or NaN): every frame is tested
-  // small batches on a big map: most tiles are out of every frame's sight
-  p.coarse = (p.cull && c->zrange_valid && F <= 64 && !tuning_on("no_coarse_cull")) ? 1 : 0;
-  // num_observations is zero everywhere while it holds its initial value,
-  // filled (0) or not (3): `+= itself` keeps it zero, the kernel neither reads
-  // nor writes it and the layer stays in that state
-  {
-    const unsigned char st = c->layer_state[AMHIP_LAYER_NUM_OBSERVATIONS];
-    p.virt_nobs = (st == 3 || st == 0) ? 1 : 0;
-  }
-  if (!p.virt_nobs && (rc = touch(c, AMHIP_LAYER_NUM_OBSERVATIONS))) return rc;
-  p.prune = (p.cull && (cam->distortion == AMHIP_DIST_NONE || p.r_in > 0.0) && p.virt_nobs &&
-             !tuning_on("ortho_no_prune")) ? 1 : 0;
-  p.fast = fast_ok ? 1 : 0;
-  p.fold = make_fold_cam(cam->fu, cam->fv, cam->cu, cam->cv, cam->width, cam->height);
-  return ortho_run(c, p, c->frame_poses, reinterpret_cast<const FrameFast*>(c->frame_poses + F),
+  if (!plan.p.virt_nobs && (rc = touch(c, AMHIP_LAYER_NUM_OBSERVATIONS))) return rc;
+  return ortho_run(c, plan, c->frame_poses, reinterpret_cast<const FrameFast*>(c->frame_poses + F),
                    dev_frames);
 }
 

@@ -14,6 +14,7 @@
 #include "amhip_tuning.h"
 #include "amhip_dsm_plan.h"
 #include "amhip_ortho_fold.h"
+#include "amhip_ortho_plan.h"
 
 namespace amhip {
 
@@ -50,45 +51,8 @@ struct PtsView {
 };
 
 // FramePose / FrameFast (per-frame inverse pose T_C_G = T_G_C^-1): amhip_ortho_fold.h
-
-struct OrthoParams {
-  double base_x, base_y, res;
-  int rows, cols;
-  int i_off, j_off;
-  // camera
-  double fu, fv, cu, cv;
-  double dist[4];
-  int width, height, distortion;
-  // frames
-  int num_frames;
-  int channels, colored;
-  size_t frame_stride, row_step;
-  // frustum side planes in the camera frame (unit normals, inside = n.p >= 0),
-  // only valid when distortion == NONE
-  double pl[4][3];
-  int cull;
-  // lazy reset: elevation_angle / observation_index / the output layer are
-  // logically in their initial state but their memory is not filled -- do not
-  // read them, and write the initial values into every cell no view is
-  // accepted for; same for num_observations (initial 0: `+= itself` keeps it)
-  int virt_out, virt_nobs;
-  // the global elevation range is available: pre-cull the frames with it and
-  // leave the tile before touching its elevation when nothing can see it
-  int coarse;
-  // margin-guarded fold (amhip_ortho_fold.h): undistorted pinhole, unit
-  // quaternions; the frame table follows the poses in the same buffer
-  int fast;
-  FoldCam fold;
-  // dominance pruning of a tile's frame list (frame_bounds / dominated):
-  // undistorted pinhole, num_observations logically zero
-  int prune;
-  // the bounding spheres assume rigid poses; |q|^2 = 1 + dev scales distances
-  // by that much: radii are multiplied by 1 + 2 max|dev|
-  double radius_scale;
-  // cameras with a distortion model: |p| <= r_in z  =>  visible by a clear
-  // margin (0: unknown); lets frame_bounds() call a frame fully visible
-  double r_in;
-};
+// OrthoParams (geometry, camera and switches of one mosaic call, passed by value to kernels), HPose and
+// the host pose arithmetic: amhip_ortho_plan.h
 
 // Device error word bits (sticky until amhip_ctx_synchronize).
 enum : unsigned { kDevErrExactHit = 1u, kDevErrAlphaNonPos = 2u, kDevErrHaloOverflow = 4u,
@@ -273,11 +237,7 @@ struct Ctx {
   size_t stage_points_cap = 0;
 
   // ortho workspaces
-  amhip_camera cone_cam = {};    // camera the cached view cone belongs to
-  double cone = 0.0;             // distorted_view_cone() result
-  int cone_state = 0;            // 0: none cached, 1: usable bound, 2: no bound
-  int cone_state_rect = 0;       // distorted_rectangle_and_inner_cone() cached for `cone_rect_cone`
-  double cone_rect_cone = 0.0, cone_ax = 0.0, cone_ay = 0.0, cone_rin = 0.0;
+  ViewBoundsCache view_bounds;   // of the last camera with a distortion model (plan_ortho_call)
   FramePose* frame_poses = nullptr;
   size_t frame_pose_cap = 0;
   uint8_t* stage_frames = nullptr;
@@ -454,9 +414,9 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
             const DsmParams& p, float* out, unsigned char* mask, unsigned* unfilled,
             bool fill_untouched = false, float init_value = 0.0f,
             unsigned long long* zrange = nullptr, const SortSplit* split = nullptr);
-// dev_fast: FrameFast[num_frames] followed by one entry holding the camera
-// (fu fv cu cv W H) for exact_view(); only read when p.fast
-int ortho_run(Ctx* c, const OrthoParams& p, const FramePose* dev_poses, const FrameFast* dev_fast,
+// the launches of one mosaic call as plan_ortho_call (amhip_ortho_plan.h) decided them.  dev_fast:
+// FrameFast[num_frames] followed by the camera and the atan table (build_frame_table); only read when p.fast
+int ortho_run(Ctx* c, const OrthoPlan& plan, const FramePose* dev_poses, const FrameFast* dev_fast,
               const uint8_t* dev_frames);
 
 // context internals shared with amhip_session.hip (defined in amhip_api.hip)
@@ -471,16 +431,6 @@ int ctx_fetch_status(Ctx* c);                // synchronize + sticky device stat
 float ctx_layer_init_value(int layer);
 bool ctx_layer_is_initial(const Ctx* c, int layer);
 int arg_failure(const char* msg);
-
-// host-side restatements of the external pose math (minkindr), used to build
-// T_G_C and T_C_G; kept in one place so the composition and the per-cell
-// transform agree operation for operation.
-struct HPose {
-  double qw, qx, qy, qz, tx, ty, tz;
-};
-HPose hpose_from7(const double* p);
-HPose hpose_inverse(const HPose& T);
-HPose hpose_compose(const HPose& A, const HPose& B);
 
 }  // namespace amhip
 

@@ -39,7 +39,7 @@
 namespace amhip {
 
 // kTileI = 64 (amhip_dsm_plan.h): as in the DSM's gather, one cell per lane of a wave along i
-constexpr int kTileJ = 64;   // a workgroup's tile ...
+constexpr int kTileJ = kOrthoTileJ;   // (amhip_ortho_plan.h) a workgroup's tile ...
 // ... is folded in slabs of kSlab cell columns (template parameter of the kernels): 16 = four
 // cells per lane for the kernel that folds every pair in the reference's arithmetic, 8 = two for
 // the margin-guarded one (it then fits 128 VGPRs = 4 waves per SIMD almost without spills:
@@ -962,35 +962,29 @@ __global__ void k_ortho_tile_list_reset(int* __restrict__ hdr) {
   hdr[7] = -1;
 }
 
-int ortho_run(Ctx* c, const OrthoParams& p, const FramePose* dev_poses, const FrameFast* dev_fast,
+// What is launched, with which grids and how large the list is: plan_ortho_call (amhip_ortho_plan.h).
+int ortho_run(Ctx* c, const OrthoPlan& plan, const FramePose* dev_poses, const FrameFast* dev_fast,
               const uint8_t* dev_frames) {
   ScopedTimer t(c, AMHIP_K_ORTHO);
-  dim3 grid((unsigned)((p.rows + kTileI - 1) / kTileI),
-            (unsigned)((p.cols + kTileJ - 1) / kTileJ));
+  const OrthoParams& p = plan.p;
+  const OrthoLaunch& l = plan.launch;
   float* out = p.colored ? c->layers[AMHIP_LAYER_COLORED_ORTHO]
                          : c->layers[AMHIP_LAYER_ORTHO];
-  auto kernel = !p.fast ? k_ortho_backward : k_ortho_backward_fast4;
   c->dirty_on_device = false;  // (a dense launch can write anywhere in the window)
   c->dirty[0] = c->dirty[1] = 0;
   c->dirty[2] = c->win_rows;
   c->dirty[3] = c->win_cols;
-  // small batch, big map, the output layers materialized: only the tiles some frame can see
-  // (tuning knob ortho_no_tile_list: the dense launch -- A-B and tests).  num_observations may stay
-  // lazily initial: the kernels neither read nor write it then.
-  const size_t ntiles = (size_t)grid.x * (size_t)grid.y;
-  // (from 16 K tiles: below, dispatching every tile costs less than the list's extra launch)
-  if (p.coarse && !p.virt_out && ntiles >= 16384 && !tuning_on("ortho_no_tile_list")) {
+  if (l.tile_list) {
     int rc;
-    if ((rc = ensure_capacity(&c->ortho_list, &c->ortho_list_cap, ntiles + 16))) return rc;
+    if ((rc = ensure_capacity(&c->ortho_list, &c->ortho_list_cap, l.list_elems))) return rc;
     unsigned* cnt = reinterpret_cast<unsigned*>(c->ortho_list);
     hipLaunchKernelGGL(k_ortho_tile_list_reset, dim3(1), dim3(1), 0, c->stream, c->ortho_list);
-    hipLaunchKernelGGL(k_ortho_tile_list, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_ortho_tile_list, dim3(l.builder_grid), dim3(256), 0, c->stream,
                        p, dev_poses, c->dev_zrange, c->ortho_list + 8, cnt);
     c->dirty_on_device = true;  // (ctx_last_dirty reads the listed tiles' box back on demand)
     OrthoParams q = p;
     q.coarse = 0;  // (the list kernel asked the question already)
-    const dim3 lgrid((unsigned)std::min<size_t>(ntiles, 256 * 16));
-    hipLaunchKernelGGL(p.fast ? k_ortho_backward_fast4_list : k_ortho_backward_list, lgrid,
+    hipLaunchKernelGGL(p.fast ? k_ortho_backward_fast4_list : k_ortho_backward_list, dim3(l.list_grid),
                        dim3(kOrthoThreads), 0, c->stream, q, dev_poses, dev_fast, dev_frames,
                        c->layers[AMHIP_LAYER_ELEVATION], c->layers[AMHIP_LAYER_ELEVATION_ANGLE],
                        c->layers[AMHIP_LAYER_OBSERVATION_INDEX],
@@ -1000,7 +994,8 @@ int ortho_run(Ctx* c, const OrthoParams& p, const FramePose* dev_poses, const Fr
     AMHIP_TRY(hipGetLastError());
     return AMHIP_OK;
   }
-  hipLaunchKernelGGL(kernel, grid, dim3(kOrthoThreads), 0, c->stream,
+  hipLaunchKernelGGL(!p.fast ? k_ortho_backward : k_ortho_backward_fast4, dim3(l.grid_x, l.grid_y),
+                     dim3(kOrthoThreads), 0, c->stream,
                      p, dev_poses, dev_fast, dev_frames,
                      c->layers[AMHIP_LAYER_ELEVATION],
                      c->layers[AMHIP_LAYER_ELEVATION_ANGLE],

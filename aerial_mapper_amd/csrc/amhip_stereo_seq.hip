@@ -25,6 +25,7 @@
 #include <new>
 
 #include "amhip_common.h"
+#include "amhip_ortho_plan.h"  // HPose, hpose_*
 
 namespace amhip {
 

@@ -12,29 +12,9 @@
 #include <vector>
 
 #include "amhip_ortho_fold.h"
+#include "amhip_ortho_plan.h"  // the product's hpose_inverse and side_planes
 
 using namespace amhip;
-
-namespace {
-
-// minkindr inverse(): (q*, -(q* (x) t)), through the header's transform
-FramePose inverse_pose(const double* T7) {
-  FramePose r;
-  r.qw = T7[3];
-  r.qx = -T7[4];
-  r.qy = -T7[5];
-  r.qz = -T7[6];
-  r.tx = r.ty = r.tz = 0.0;
-  r._pad = 0.0;
-  const V3 t = {T7[0], T7[1], T7[2]};
-  const V3 rt = transform_point(r, t);  // + 0.0 leaves the rotation's doubles as they are
-  r.tx = -rt.x;
-  r.ty = -rt.y;
-  r.tz = -rt.z;
-  return r;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -54,7 +34,8 @@ int emul_ortho_fold(int rows, int cols, double base_x, double base_y, double res
   std::vector<FrameFast> fast(F);
   bool all_ok = true;
   for (int f = 0; f < F; ++f) {
-    poses[f] = inverse_pose(T_G_C + 7 * f);
+    const HPose T = hpose_inverse(hpose_from7(T_G_C + 7 * f));  // T_C_G, as build_frame_table makes it
+    poses[f] = {T.qw, T.qx, T.qy, T.qz, T.tx, T.ty, T.tz, 0.0};
     if (!make_frame_fast(poses[f], &fast[f])) {
       all_ok = false;
       stats[5]++;
@@ -66,17 +47,10 @@ int emul_ortho_fold(int rows, int cols, double base_x, double base_y, double res
   double atan_tab[kAtanTabSize];
   make_atan_table(atan_tab);
   bool bad = false;
-  // side planes of the undistorted view pyramid, unit inward normals
-  // (amhip_api.hip: make_ortho_params)
-  double pl[4][3] = {{camera[0], 0.0, camera[2]},
-                     {-camera[0], 0.0, camera[4] - camera[2]},
-                     {0.0, camera[1], camera[3]},
-                     {0.0, -camera[1], camera[5] - camera[3]}};
-  for (auto& n : pl) {
-    const double len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-    for (double& v : n) v /= len;
-  }
-  const int kTileI = 64, kTileJ = 64;  // amhip_ortho.hip
+  // side planes of the undistorted view pyramid, unit inward normals, as plan_ortho_call makes them
+  double pl[4][3];
+  side_planes(camera[0], camera[2], camera[4] - camera[2], camera[1], camera[3], camera[5] - camera[3], pl);
+  const int kTileJ = kOrthoTileJ;  // (kTileI: amhip_dsm_plan.h)
   std::vector<int> cand;
   for (int j0 = 0; j0 < cols; j0 += kTileJ) {
     for (int i0 = 0; i0 < rows; i0 += kTileI) {
