@@ -277,10 +277,11 @@ inline void plan_multipliers(DsmParams* p) {
 }
 
 // This call runs in single precision (given an LDS image: fx_ok): dsm::Dsm only -- OrthoFromPcl
-// interpolates 8-bit intensities whose spread (up to 255) leaves no room under the error bound --, not
-// in the exact mode or under its rough-terrain hold, not in the capped mode (always the FP64 pipeline:
-// sorted doubles, no records), and only while the sort's records hold the call: a cell in 16 + 16 bits,
-// a row of the cloud in 32 -- larger maps / clouds stay in FP64.
+// interpolates int32 values (8-bit intensities in the pipeline, any int32 through the ABI: the FP64
+// pipeline holds the whole range, tests/test_gpu_ortho_from_pcl_edges.py) whose spread leaves no room
+// under the error bound --, not in the exact mode or under its rough-terrain hold, not in the capped mode
+// (always the FP64 pipeline: sorted doubles, no records), and only while the sort's records hold the call:
+// a cell in 16 + 16 bits, a row of the cloud in 32 -- larger maps / clouds stay in FP64.
 inline bool runs_single_precision(const DsmPlanInput& in, const DsmParams& p) {
   const bool rec_fits = (long long)p.rows + 2LL * p.M <= 65535 && (long long)p.cols + 2LL * p.M <= 65535 &&
                         in.num_points < 0xFFFFFFFFull;

@@ -2226,7 +2226,15 @@ int dsm_sort(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
   in.prev_sig = c->sort_stats_sig;
   in.have_host_stats = c->host_sort_stats != nullptr;
   in.prev_big_count = c->host_sort_stats ? c->host_sort_stats[0] : 0u;
-  const SortPlan s = plan_sort_call(in, p);
+  SortPlan s = plan_sort_call(in, p);
+  // plan_sort cuts a bin row into column blocks of up to 4096 bins, but the big placement's image of kP3BigCap
+  // points holds 3936 of them next to the points on doubles, 3360 on records (few points on a wide map: one
+  // block per bin row).  Beyond that hipFuncSetAttribute would fail the call: it keeps the one-level sort, as
+  // under the knob -- in both phases of a tiled call, which see the same geometry.
+  if (s.lds_place_big > kLdsMaxBytes) {
+    in.sort_one_level = true;
+    s = plan_sort_call(in, p);
+  }
 
   const SortCaps& cap = s.cap;
   int rc;

@@ -377,3 +377,30 @@ def test_rough_scene_switches_to_the_fp64_pipeline(tuning):
         st = m.dsm_gather_stats()
         frac, _ = _check(m.get("elevation"), want_smooth)
         assert st["f32_to_fp64"] == 0 and frac < 0.99999   # (f32 sums: a float spacing here and there)
+
+
+@pytest.mark.parametrize("exact,rows,pipeline", [(False, 3300, "count"), (False, 3400, "one-level"),
+                                                 (False, 4000, "one-level"), (True, 3900, "count"),
+                                                 (True, 4000, "one-level")])
+def test_column_blocks_too_wide_for_the_three_pass_sort_keep_the_one_level_sort(tuning, exact, rows, pipeline):
+    """Few points on a wide map: one column block per bin row (rows + 6 bin columns).  More than 3360 of them
+    on records, 3936 on doubles, do not fit the big placement's LDS image next to its points
+    (amhip_sort.hip: dsm_sort): the call keeps the one-level sort.  It used to fail with a HIP
+    error (hipFuncSetAttribute: invalid argument)."""
+    import aerial_mapper_amd as A
+    from aerial_mapper_amd import synth
+    g = O.make_grid(float(rows), 16.0, 1.0, 12.0, -7.0)
+    rng = np.random.default_rng(310 + rows)
+    pts = np.empty((3000, 3))
+    pts[:, 0] = rng.uniform(g.pos_x - rows / 2 - 2, g.pos_x + rows / 2 + 2, 3000)
+    pts[:, 1] = rng.uniform(g.pos_y - 10.0, g.pos_y + 10.0, 3000)
+    pts[:, 2] = synth.terrain_height(pts[:, 0], pts[:, 1])
+    rc, want, _ = O.dsm_process(pts, g, 1, 0.0, 0.0)
+    assert rc == O.OK
+    tuning(p3_min_points=1000)
+    with A.AerialGridMap(A.GridMapSettings(g.pos_x, g.pos_y, g.length_x, g.length_y, g.resolution)) as m:
+        m.set_dsm_precision(exact)
+        A.Dsm(A.DsmSettings(1), m).process(pts, m)
+        got = m.get("elevation")
+        assert m.dsm_stats()["sort_pipeline"] == pipeline
+    _check(got, want)
