@@ -57,14 +57,28 @@ void OrthoBackwardGrid::process(const Poses& T_G_Bs, const Images& images,
     data[f] = images[f].data;
     steps[f] = static_cast<size_t>(images[f].step);
   }
+  const int colored = settings_.colored_ortho ? 1 : 0;
+  float* const elevation = (*map)["elevation"].data();
+  float* const elevation_angle = (*map)["elevation_angle"].data();
+  float* const observation_index = (*map)["observation_index"].data();
+  float* const num_observations = (*map)["num_observations"].data();
+  float* const ortho = (*map)["ortho"].data();
+  float* const colored_ortho = (*map)["colored_ortho"].data();
   amhip_shim::check_status(
-      amhip_session_ortho_backward_process(
-          session_, &cam, T_G_C.data(), F, data.data(), steps.data(), channels,
-          settings_.colored_ortho ? 1 : 0, (*map)["elevation"].data(),
-          (*map)["elevation_angle"].data(), (*map)["observation_index"].data(),
-          (*map)["num_observations"].data(), (*map)["ortho"].data(),
-          (*map)["colored_ortho"].data()),
+      occlusion_test_
+          ? amhip_session_ortho_backward_process_occl(
+                session_, &cam, T_G_C.data(), F, data.data(), steps.data(), channels, colored, elevation,
+                elevation_angle, observation_index, num_observations, ortho, colored_ortho,
+                occlusion_margin_m_)
+          : amhip_session_ortho_backward_process(
+                session_, &cam, T_G_C.data(), F, data.data(), steps.data(), channels, colored, elevation,
+                elevation_angle, observation_index, num_observations, ortho, colored_ortho),
       "OrthoBackwardGrid::process");
+}
+
+void OrthoBackwardGrid::setOcclusionTest(bool enabled, double margin_m) {
+  occlusion_test_ = enabled;
+  occlusion_margin_m_ = margin_m;
 }
 
 void OrthoBackwardGrid::printParams() const {

@@ -934,11 +934,24 @@ int amhip_camera_view_bounds(const amhip_camera* cam, double* out4) {
   return AMHIP_OK;
 }
 
-int amhip_ortho_backward_process_dev(amhip_ctx* h, const amhip_camera* cam,
-                                     const double* host_T_G_C, size_t F,
-                                     const uint8_t* dev_frames,
-                                     size_t frame_stride, size_t row_step,
-                                     int channels, int colored) {
+// The occlusion-tested mosaic's own refusals (before any device work): the margin, and a context
+// that holds a window of the map -- the ray leaves the window.
+static int occl_args_check(const amhip_ctx* h, double margin_m) {
+  if (!h) return arg_fail("null context / camera");
+  if (!(margin_m >= 0.0))
+    return arg_fail("occlusion test: margin_m must be >= 0 (+inf is legal: nothing occludes), not negative or NaN");
+  if (h->impl.windowed)
+    return arg_fail(
+        "occlusion test: the context holds a window of the map (amhip_ctx_create_window) and the ray "
+        "towards the camera leaves it; windows need an elevation halo, which is not built yet");
+  return AMHIP_OK;
+}
+
+// occl_margin: null = the reference's mosaic; else the occlusion-tested one with that margin
+// (checked by the caller: occl_args_check)
+static int ortho_backward_dev(amhip_ctx* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+                              const uint8_t* dev_frames, size_t frame_stride, size_t row_step,
+                              int channels, int colored, const double* occl_margin) {
   if (!h || !cam) return arg_fail("null context / camera");
   if (F == 0 || !host_T_G_C) return arg_fail("empty pose list (CHECK(!T_G_Bs.empty()))");
   if (!dev_frames) return arg_fail("null frame pointer");
@@ -974,15 +987,31 @@ int amhip_ortho_backward_process_dev(amhip_ctx* h, const amhip_camera* cam,
   in.knobs.no_distorted_cull = tuning_on("no_distorted_cull");
   in.knobs.no_distorted_prune = tuning_on("no_distorted_prune");
   in.knobs.distorted_square_cull = tuning_on("distorted_square_cull");
-  in.knobs.ortho_exact_fold = tuning_on("ortho_exact_fold");
+  in.knobs.ortho_exact_fold = occl_margin != nullptr || tuning_on("ortho_exact_fold");
   in.knobs.no_coarse_cull = tuning_on("no_coarse_cull");
   in.knobs.ortho_no_prune = tuning_on("ortho_no_prune");
   in.knobs.ortho_no_tile_list = tuning_on("ortho_no_tile_list");
   // ---- the frame table and the plan (amhip_ortho_plan.h)
-  const size_t slots = frame_table_slots(F);
+  // (the occlusion test: the camera centres -- the translations of T_G_C -- and one word for the
+  // map's largest elevation, key(-inf) until reduced, ride behind the table)
+  const size_t table_slots = frame_table_slots(F);
+  const size_t occl_slots = occl_margin ? (3 * F * sizeof(double) + sizeof(FramePose) - 1) / sizeof(FramePose) + 1 : 0;
+  const size_t slots = table_slots + occl_slots;
   std::vector<FramePose> table(slots);
   const FrameTable frames = build_frame_table(*cam, host_T_G_C, F, in.knobs.ortho_exact_fold, table.data());
-  const OrthoPlan plan = plan_ortho_call(in, frames, &c->view_bounds);
+  OrthoPlan plan = plan_ortho_call(in, frames, &c->view_bounds);
+  if (occl_margin) {
+    double* centres = reinterpret_cast<double*>(table.data() + table_slots);
+    for (size_t f = 0; f < F; ++f)
+      for (int k = 0; k < 3; ++k) centres[3 * f + k] = host_T_G_C[7 * f + k];
+    static const unsigned long long minus_inf_key = 0x000FFFFFFFFFFFFFull;  // (amhip_device.h)
+    std::memcpy(table.data() + slots - 1, &minus_inf_key, sizeof(minus_inf_key));
+    // dominated() assumes that a fully visible frame beats the pruned one at every landmark: not
+    // once the dominator can be occluded.  The kernel writes into real memory, tile by tile.
+    plan.p.prune = 0;
+    plan.p.virt_out = 0;
+    plan.launch.tile_list = false;
+  }
   // ---- one buffer, one upload (pageable source: hipMemcpyAsync returns once it has been staged)
   if ((rc = ensure_capacity(&c->frame_poses, &c->frame_pose_cap, slots))) return rc;
   AMHIP_TRY(hipMemcpyAsync(c->frame_poses, table.data(), slots * sizeof(FramePose),
@@ -1001,16 +1030,43 @@ int amhip_ortho_backward_process_dev(amhip_ctx* h, const amhip_camera* cam,
       return rc;
   }
   if (!plan.p.virt_nobs && (rc = touch(c, AMHIP_LAYER_NUM_OBSERVATIONS))) return rc;
+  if (occl_margin) {
+    OcclParams q;
+    q.margin = *occl_margin;
+    q.centres = reinterpret_cast<const double*>(c->frame_poses + table_slots);
+    // the height cut-off of the march: the range the DSM calls wrote, or the layer's own maximum
+    unsigned long long* own_key = reinterpret_cast<unsigned long long*>(c->frame_poses + slots - 1);
+    q.zmax_key = c->zrange_valid ? c->dev_zrange + 1 : own_key;
+    return ortho_occl_run(c, plan, q, c->frame_poses, dev_frames, c->zrange_valid ? nullptr : own_key);
+  }
   return ortho_run(c, plan, c->frame_poses, reinterpret_cast<const FrameFast*>(c->frame_poses + F),
                    dev_frames);
 }
 
-int amhip_ortho_backward_process(
+int amhip_ortho_backward_process_dev(amhip_ctx* h, const amhip_camera* cam,
+                                     const double* host_T_G_C, size_t F,
+                                     const uint8_t* dev_frames,
+                                     size_t frame_stride, size_t row_step,
+                                     int channels, int colored) {
+  return ortho_backward_dev(h, cam, host_T_G_C, F, dev_frames, frame_stride, row_step, channels, colored,
+                            nullptr);
+}
+
+int amhip_ortho_backward_process_occl_dev(amhip_ctx* h, const amhip_camera* cam, const double* host_T_G_C,
+                                          size_t F, const uint8_t* dev_frames, size_t frame_stride,
+                                          size_t row_step, int channels, int colored, double margin_m) {
+  const int rc = occl_args_check(h, margin_m);
+  if (rc) return rc;
+  return ortho_backward_dev(h, cam, host_T_G_C, F, dev_frames, frame_stride, row_step, channels, colored,
+                            &margin_m);
+}
+
+static int ortho_backward_host(
     amhip_ctx* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
     const uint8_t* const* images, const size_t* steps, int channels,
     int colored, const float* elevation, float* elevation_angle,
     float* observation_index, float* num_observations, float* ortho,
-    float* colored_ortho) {
+    float* colored_ortho, const double* occl_margin) {
   if (!h || !cam) return arg_fail("null context / camera");
   if (F == 0 || !host_T_G_C || !images || !steps)
     return arg_fail("empty pose / image list (CHECK(!T_G_Bs.empty()))");
@@ -1043,8 +1099,8 @@ int amhip_ortho_backward_process(
                                  row, (size_t)cam->height, hipMemcpyHostToDevice,
                                  c->stream));
   }
-  if ((rc = amhip_ortho_backward_process_dev(h, cam, host_T_G_C, F, c->stage_frames,
-                                             frame, row, channels, colored)))
+  if ((rc = ortho_backward_dev(h, cam, host_T_G_C, F, c->stage_frames, frame, row, channels, colored,
+                               occl_margin)))
     return rc;
   float* downs[AMHIP_NUM_LAYERS] = {ortho,           nullptr,
                                     elevation_angle, num_observations,
@@ -1056,6 +1112,30 @@ int amhip_ortho_backward_process(
                                c->stream));
     }
   return fetch_status(c);
+}
+
+int amhip_ortho_backward_process(
+    amhip_ctx* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+    const uint8_t* const* images, const size_t* steps, int channels,
+    int colored, const float* elevation, float* elevation_angle,
+    float* observation_index, float* num_observations, float* ortho,
+    float* colored_ortho) {
+  return ortho_backward_host(h, cam, host_T_G_C, F, images, steps, channels, colored, elevation,
+                             elevation_angle, observation_index, num_observations, ortho, colored_ortho,
+                             nullptr);
+}
+
+int amhip_ortho_backward_process_occl(
+    amhip_ctx* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+    const uint8_t* const* images, const size_t* steps, int channels,
+    int colored, const float* elevation, float* elevation_angle,
+    float* observation_index, float* num_observations, float* ortho,
+    float* colored_ortho, double margin_m) {
+  const int rc = occl_args_check(h, margin_m);
+  if (rc) return rc;
+  return ortho_backward_host(h, cam, host_T_G_C, F, images, steps, channels, colored, elevation,
+                             elevation_angle, observation_index, num_observations, ortho, colored_ortho,
+                             &margin_m);
 }
 
 // ---- measurement ------------------------------------------------------------

@@ -418,6 +418,18 @@ int dsm_run(Ctx* c, const double* dev_xyz, const int32_t* dev_values, size_t n,
 // FrameFast[num_frames] followed by the camera and the atan table (build_frame_table); only read when p.fast
 int ortho_run(Ctx* c, const OrthoPlan& plan, const FramePose* dev_poses, const FrameFast* dev_fast,
               const uint8_t* dev_frames);
+// The occlusion-tested mosaic (amhip_ortho_occl.hip): what its kernel gets
+// beside the mosaic's own parameter set.
+struct OcclParams {
+  double margin;                       // metres a sample must rise above the ray (>= 0, +inf legal)
+  const double* centres;               // device: the camera centre of frame f in the map frame at [3 f]
+  const unsigned long long* zmax_key;  // device: ordered key of (a bound of) the map's largest elevation
+};
+// plan: plan_ortho_call's with the exact fold, no pruning, no lazily initial output layer and the
+// dense launch.  own_zmax_key: null, or q.zmax_key as a word to reduce the elevation layer into
+// first (it holds key(-inf)).
+int ortho_occl_run(Ctx* c, const OrthoPlan& plan, const OcclParams& q, const FramePose* dev_poses,
+                   const uint8_t* dev_frames, unsigned long long* own_zmax_key);
 
 // context internals shared with amhip_session.hip (defined in amhip_api.hip)
 // i0, j0, rows, cols (window coordinates) of what the last DSM / mosaic call can have written;

@@ -951,11 +951,12 @@ int amhip_session_dsm_process(amhip_session* h, const double* host_xyz, size_t n
 }
 
 // ortho::OrthoBackwardGrid::process (ortho-backward-grid.cc:223-239) on host buffers.
-int amhip_session_ortho_backward_process(
+// occl_margin: null = the reference's mosaic; else the occlusion-tested one (one window only)
+static int session_ortho_backward(
     amhip_session* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
     const uint8_t* const* images, const size_t* steps, int channels, int colored,
     const float* elevation, float* elevation_angle, float* observation_index,
-    float* num_observations, float* ortho, float* colored_ortho) {
+    float* num_observations, float* ortho, float* colored_ortho, const double* occl_margin) {
   if (!h || !cam) return arg_failure("null session / camera");
   if (F == 0 || !host_T_G_C || !images || !steps)
     return arg_failure("empty pose / image list (CHECK(!T_G_Bs.empty()))");
@@ -1032,8 +1033,10 @@ int amhip_session_ortho_backward_process(
         return r;
     if (k == 0) clock.mark("sync_in");
     AMHIP_TRY(hipEventRecord(s.ev_k0[k], c->stream));
-    if ((r = amhip_ortho_backward_process_dev(s.ctx[k], cam, host_T_G_C, F, c->stage_frames, frame,
-                                              row, channels, colored)))
+    if ((r = occl_margin ? amhip_ortho_backward_process_occl_dev(s.ctx[k], cam, host_T_G_C, F, c->stage_frames,
+                                                                 frame, row, channels, colored, *occl_margin)
+                         : amhip_ortho_backward_process_dev(s.ctx[k], cam, host_T_G_C, F, c->stage_frames, frame,
+                                                            row, channels, colored)))
       return r;
     if (k == 0) clock.mark("mosaic enqueued");
     const int lay[5] = {AMHIP_LAYER_ORTHO, AMHIP_LAYER_ELEVATION_ANGLE, AMHIP_LAYER_NUM_OBSERVATIONS,
@@ -1045,6 +1048,33 @@ int amhip_session_ortho_backward_process(
   });
   s.prof.total_ms = ms_since(call0);
   return rc_all;
+}
+
+int amhip_session_ortho_backward_process(
+    amhip_session* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+    const uint8_t* const* images, const size_t* steps, int channels, int colored,
+    const float* elevation, float* elevation_angle, float* observation_index,
+    float* num_observations, float* ortho, float* colored_ortho) {
+  return session_ortho_backward(h, cam, host_T_G_C, F, images, steps, channels, colored, elevation,
+                                elevation_angle, observation_index, num_observations, ortho, colored_ortho,
+                                nullptr);
+}
+
+int amhip_session_ortho_backward_process_occl(
+    amhip_session* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+    const uint8_t* const* images, const size_t* steps, int channels, int colored,
+    const float* elevation, float* elevation_angle, float* observation_index,
+    float* num_observations, float* ortho, float* colored_ortho, double margin_m) {
+  if (!h || !cam) return arg_failure("null session / camera");
+  if (!(margin_m >= 0.0))
+    return arg_failure("occlusion test: margin_m must be >= 0 (+inf is legal: nothing occludes), not negative or NaN");
+  if (h->impl.W() != 1)
+    return arg_failure(
+        "occlusion test: the session holds more than one window and the ray towards the camera leaves "
+        "a window; windows need an elevation halo, which is not built yet");
+  return session_ortho_backward(h, cam, host_T_G_C, F, images, steps, channels, colored, elevation,
+                                elevation_angle, observation_index, num_observations, ortho, colored_ortho,
+                                &margin_m);
 }
 
 // ortho::OrthoFromPcl::process (ortho-from-pcl.cc:20-113) on host buffers: `ortho` = the

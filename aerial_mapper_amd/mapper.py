@@ -330,12 +330,16 @@ class Dsm(object):
 
 class OrthoSettings(object):
     """ortho::Settings (ortho-backward-grid.h:32-41); only colored_ortho and
-    use_multi_threads influence the result."""
+    use_multi_threads influence the result.
+
+    occlusion_test / occlusion_margin_m (an extension; off = the reference's rule): a view whose
+    ray from the cell to the camera passes more than occlusion_margin_m below the elevation layer
+    is skipped ("true ortho": amhip_ortho_backward_process_occl)."""
 
     def __init__(self, show_orthomosaic_opencv=True, save_orthomosaic_jpg=True,
                  orthomosaic_jpg_filename="", orthomosaic_elevation_m=0.0,
                  use_digital_elevation_map=True, colored_ortho=False,
-                 use_multi_threads=True):
+                 use_multi_threads=True, occlusion_test=False, occlusion_margin_m=0.0):
         self.show_orthomosaic_opencv = show_orthomosaic_opencv
         self.save_orthomosaic_jpg = save_orthomosaic_jpg
         self.orthomosaic_jpg_filename = orthomosaic_jpg_filename
@@ -343,6 +347,8 @@ class OrthoSettings(object):
         self.use_digital_elevation_map = use_digital_elevation_map
         self.colored_ortho = colored_ortho
         self.use_multi_threads = use_multi_threads
+        self.occlusion_test = occlusion_test
+        self.occlusion_margin_m = occlusion_margin_m
 
 
 class NCamera(object):
@@ -400,6 +406,8 @@ class OrthoBackwardGrid(object):
                      "colored_ortho")
         cam = self.ncameras.camera
         colored = bool(self.settings.colored_ortho)
+        occl = bool(getattr(self.settings, "occlusion_test", False))
+        margin = (float(self.settings.occlusion_margin_m),) if occl else ()
         T_G_C = compose_T_G_C(T_G_Bs, self.ncameras.T_C_B)
         f64p = C.POINTER(C.c_double)
         if _is_torch(images):
@@ -409,9 +417,9 @@ class OrthoBackwardGrid(object):
             frame = row * cam.height
             assert images.shape[1] == cam.height and images.shape[2] == cam.width
             map.wait_for_torch(images)
-            L.check(lib.amhip_ortho_backward_process_dev(
-                map.handle, C.byref(cam), T_G_C.ctypes.data_as(f64p), F,
-                C.c_void_p(images.data_ptr()), frame, row, ch, int(colored)))
+            entry = lib.amhip_ortho_backward_process_occl_dev if occl else lib.amhip_ortho_backward_process_dev
+            L.check(entry(map.handle, C.byref(cam), T_G_C.ctypes.data_as(f64p), F,
+                          C.c_void_p(images.data_ptr()), frame, row, ch, int(colored), *margin))
             if sync:
                 map.synchronize()
             return
@@ -430,9 +438,9 @@ class OrthoBackwardGrid(object):
             ptrs[k] = im.ctypes.data
             steps[k] = im.strides[0]
         # layers are already device resident: pass NULL for all of them
-        L.check(lib.amhip_ortho_backward_process(
-            map.handle, C.byref(cam), T_G_C.ctypes.data_as(f64p), F, ptrs, steps, ch,
-            int(colored), None, None, None, None, None, None))
+        entry = lib.amhip_ortho_backward_process_occl if occl else lib.amhip_ortho_backward_process
+        L.check(entry(map.handle, C.byref(cam), T_G_C.ctypes.data_as(f64p), F, ptrs, steps, ch,
+                      int(colored), None, None, None, None, None, None, *margin))
 
 
 LAYER_INIT = {"ortho": 255.0, "elevation": float("nan"), "elevation_angle": 0.0,
@@ -544,12 +552,16 @@ class HostSession(object):
             ptrs[k] = im.ctypes.data
             steps[k] = im.strides[0]
         lay = self.layers
-        L.check(self._lib.amhip_session_ortho_backward_process(
+        occl = bool(getattr(ortho_settings, "occlusion_test", False))
+        margin = (float(ortho_settings.occlusion_margin_m),) if occl else ()
+        entry = self._lib.amhip_session_ortho_backward_process_occl if occl else \
+            self._lib.amhip_session_ortho_backward_process
+        L.check(entry(
             self._h, C.byref(ncameras.camera), T_G_C.ctypes.data_as(C.POINTER(C.c_double)), F, ptrs,
             steps, 3 if colored else 1, int(colored), lay["elevation"].ctypes.data,
             lay["elevation_angle"].ctypes.data, lay["observation_index"].ctypes.data,
             lay["num_observations"].ctypes.data, lay["ortho"].ctypes.data,
-            lay["colored_ortho"].ctypes.data))
+            lay["colored_ortho"].ctypes.data, *margin))
 
 
 class OrthoFromPclSettings(object):

@@ -43,6 +43,11 @@ class OrthoBackwardGrid {
   // reading its elevation layer.
   void process(const Poses& T_G_Bs, const Images& images, grid_map::GridMap* map) const;
 
+  // An extension (the reference has no such method; off by default): the process() calls that
+  // follow skip a view whose ray from the cell to the camera passes more than margin_m metres
+  // below the map's elevation layer ("true ortho": amhip_session_ortho_backward_process_occl).
+  void setOcclusionTest(bool enabled, double margin_m = 0.0);
+
  private:
   void ensureSession(const grid_map::GridMap& map) const;
   void printParams() const;
@@ -52,6 +57,8 @@ class OrthoBackwardGrid {
   Settings settings_;
   // the map's session, shared with dsm::Dsm on the same grid_map::GridMap
   mutable amhip_session* session_;
+  bool occlusion_test_ = false;
+  double occlusion_margin_m_ = 0.0;
 };
 
 }  // namespace ortho

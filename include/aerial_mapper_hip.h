@@ -344,6 +344,34 @@ int amhip_ortho_backward_process(
     float* observation_index, float* num_observations, float* ortho,
     float* colored_ortho);
 
+/* The same two with an occlusion test ("true ortho"; an extension: the reference has none).  The
+ * reference's visibility rule (ortho-backward-grid.cc:164-171) gets one more term,
+ *   visible = in_box && z > 1e-10 && !occluded(cell, frame),
+ * and nothing else of the fold changes.  occluded(i, j, f) marches the ELEVATION layer from the
+ * cell towards the camera, one cell per step along the ray's major axis (FP64, every operation
+ * rounded on its own, in this order): h = elevation(i, j), NaN: not occluded; (x_c, y_c) =
+ * amhip_cell_position(i, j), (tx, ty, tz) = the translation of T_G_C[f];
+ *   di = (x_c - tx) / res, dj = (y_c - ty) / res, m = max(|di|, |dj|), dz = tz - h;
+ *   !(dz > 0): not occluded; for k = 1, 2, ... while k < m: s = k / m,
+ *   ii = i + (int)rint(s * di), jj = j + (int)rint(s * dj) (round half to even); outside the map:
+ *   not occluded; z = h + s * dz; elevation(ii, jj) > z + margin_m: occluded (strict; a NaN
+ *   sample does not occlude).
+ * A cell every view of which is occluded keeps what the layers held.  margin_m >= 0 in metres
+ * (+inf: nothing occludes, the layers are the plain mosaic's); negative or NaN: AMHIP_ERR_ARG.
+ * The ray leaves a window of the map: a context of amhip_ctx_create_window is refused
+ * (AMHIP_ERR_ARG) until windows carry an elevation halo. */
+int amhip_ortho_backward_process_occl_dev(amhip_ctx* ctx, const amhip_camera* cam,
+                                          const double* host_T_G_C, size_t F,
+                                          const uint8_t* dev_frames,
+                                          size_t frame_stride, size_t row_step,
+                                          int channels, int colored, double margin_m);
+int amhip_ortho_backward_process_occl(
+    amhip_ctx* ctx, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+    const uint8_t* const* images, const size_t* steps, int channels,
+    int colored, const float* elevation, float* elevation_angle,
+    float* observation_index, float* num_observations, float* ortho,
+    float* colored_ortho, double margin_m);
+
 /* ---- ortho::OrthoForwardHomography
  *      (aerial_mapper_ortho/src/ortho-forward-homography.cc; SURVEY section 8b/8f,
  *      named in the API surface to keep) --
@@ -1106,6 +1134,13 @@ int amhip_session_ortho_backward_process(
     const uint8_t* const* images, const size_t* steps, int channels, int colored,
     const float* elevation, float* elevation_angle, float* observation_index,
     float* num_observations, float* ortho, float* colored_ortho);
+/* ... with the occlusion test of amhip_ortho_backward_process_occl.  A session of one window runs
+ * it; a session of several windows is refused (AMHIP_ERR_ARG: the ray leaves the window). */
+int amhip_session_ortho_backward_process_occl(
+    amhip_session* s, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+    const uint8_t* const* images, const size_t* steps, int channels, int colored,
+    const float* elevation, float* elevation_angle, float* observation_index,
+    float* num_observations, float* ortho, float* colored_ortho, double margin_m);
 
 /* With timing enabled every launch is bracketed by hipEvents on the
  * context's stream.  amhip_ctx_kernel_time() synchronises, then reports the

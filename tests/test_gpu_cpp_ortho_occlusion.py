@@ -1,0 +1,45 @@
+"""GPU: ortho::OrthoBackwardGrid::setOcclusionTest of the C++ drop-in (tests/cpp/shim_occlusion.cc,
+built like the programs of test_gpu_cpp_shim.py) on the block scene of
+tests/ortho_occlusion_scenes.py: with the call the layers of the rule's numpy statement, without
+it the plain mosaic's."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import ortho_occlusion_reference as R
+import ortho_occlusion_scenes as SC
+import scenarios as S
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    from aerial_mapper_amd import build
+    if not (os.path.exists(build.LIB_PATH) and os.path.exists(build.SHIM_PATH)):
+        build.build_all()
+    out = str(tmp_path_factory.mktemp("shim_occlusion") / "shim_occlusion")
+    lib = os.path.join(ROOT, "aerial_mapper_amd", "lib")
+    subprocess.check_call(["g++", "-O2", "-std=c++11", "-pthread", "-ffp-contract=off",
+                           "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "shim_occlusion.cc"), "-o", out,
+                           "-L" + lib, "-laerial_mapper_shim", "-laerial_mapper_hip", "-Wl,-rpath," + lib])
+    return out
+
+
+@pytest.mark.parametrize("mode", ["on", "off"])
+def test_cpp_dropin_set_occlusion_test(exe, tmp_path, mode):
+    SC.block_elevation().tofile(str(tmp_path / "elevation.f32"))
+    SC.block_poses().tofile(str(tmp_path / "poses.f64"))
+    np.stack(SC.frames(2)).tofile(str(tmp_path / "frames.u8"))
+    env = dict(os.environ)
+    env.pop("AERIAL_MAPPER_HIP_DEVICES", None)
+    r = subprocess.run([exe, str(tmp_path), mode, repr(SC.MARGIN)], stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout.decode()[-2000:]
+    got = {n: np.fromfile(str(tmp_path / ("%s.%s.f32" % (n, mode))), np.float32).reshape(SC.COLS, SC.ROWS)
+           for n in R.LAYERS}
+    S.assert_layers_equal(got, SC.expected("block", margin=SC.MARGIN if mode == "on" else None), R.LAYERS)
