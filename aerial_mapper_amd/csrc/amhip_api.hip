@@ -441,33 +441,40 @@ int amhip_ctx_synchronize(amhip_ctx* h) {
   return fetch_status(c);
 }
 
+// every elevation is NaN again: empty height range
+static int zrange_reset(Ctx* c) {
+  static const unsigned long long empty[2] = {0xFFF0000000000000ull, 0x000FFFFFFFFFFFFFull};
+  AMHIP_TRY(hipMemcpyAsync(c->dev_zrange, empty, sizeof(empty), hipMemcpyHostToDevice, c->stream));
+  c->zrange_valid = true;
+  return AMHIP_OK;
+}
+
+// a transition of amhip_session_plan.h: the fill it asks for, then the state it gives
+static int apply_step(Ctx* c, int layer, LayerStep step) {
+  if (step.fill) {
+    const int rc = launch_fill(c, c->layers[layer], c->cells, layer_init_value(layer));
+    if (rc) return rc;
+  }
+  c->layer_state[layer] = step.state;
+  return AMHIP_OK;
+}
+
 int amhip_layers_reset(amhip_ctx* h) {
   if (!h) return arg_fail("null context");
   Ctx* c = &h->impl;
   int rc = use_device(c);
   if (rc) return rc;
   // Lazy: nothing is written here.  A layer that is already in its initial
-  // state (physically, 0, or logically, 3) stays as it is; a written one becomes
+  // state (physically or logically) stays as it is; a written one becomes
   // "logically initial": the next kernel that produces it writes the initial
   // value into the cells it leaves alone (fused fill), anything else that
   // needs the memory (download, device pointer, a partial writer) fills it
   // first (materialize()).  Layers whose device pointer was handed out are
   // refilled eagerly.  tuning knob eager_reset restores the plain fills.
   const bool eager = tuning_on("eager_reset");
-  {  // every elevation is NaN again: empty height range
-    static const unsigned long long empty[2] = {0xFFF0000000000000ull, 0x000FFFFFFFFFFFFFull};
-    AMHIP_TRY(hipMemcpyAsync(c->dev_zrange, empty, sizeof(empty), hipMemcpyHostToDevice, c->stream));
-    c->zrange_valid = true;
-  }
+  if ((rc = zrange_reset(c))) return rc;
   for (int l = 0; l < AMHIP_NUM_LAYERS; ++l) {
-    unsigned char& st = c->layer_state[l];
-    if (st == 0 || st == 3) continue;
-    if (st == 1 && !eager) {
-      st = 3;
-      continue;
-    }
-    if ((rc = launch_fill(c, c->layers[l], c->cells, layer_init_value(l)))) return rc;
-    if (st == 1) st = 0;
+    if ((rc = apply_step(c, l, layer_reset(c->layer_state[l], eager)))) return rc;
   }
   return AMHIP_OK;
 }
@@ -475,11 +482,7 @@ int amhip_layers_reset(amhip_ctx* h) {
 // the layer's memory is about to be read or partially written by someone who
 // does not know about the lazy state
 static int materialize(Ctx* c, int layer) {
-  if (c->layer_state[layer] != 3) return AMHIP_OK;
-  const int rc = launch_fill(c, c->layers[layer], c->cells, layer_init_value(layer));
-  if (rc) return rc;
-  c->layer_state[layer] = 0;
-  return AMHIP_OK;
+  return apply_step(c, layer, layer_materialize(c->layer_state[layer]));
 }
 
 // What the last writing call can have written: the whole window, unless the call narrows it
@@ -496,16 +499,22 @@ static void dirty_full(Ctx* c) {
 // partial writer: materialize, then dirty
 static int touch(Ctx* c, int layer) {
   dirty_full(c);
-  const int rc = materialize(c, layer);
-  if (rc) return rc;
-  if (c->layer_state[layer] == 0) c->layer_state[layer] = 1;
-  return AMHIP_OK;
+  return apply_step(c, layer, layer_touch(c->layer_state[layer]));
+}
+
+// a kernel that produces the whole layer claims it; true: the layer was logically initial and the
+// kernel has to write the initial value into the cells it leaves alone (fused fill)
+static bool claim_output(Ctx* c, int layer) {
+  dirty_full(c);
+  const LayerStep step = layer_claim_output(c->layer_state[layer]);
+  c->layer_state[layer] = step.state;
+  return step.fill;
 }
 
 // full overwrite (upload): no need to fill first
 static void overwrite(Ctx* c, int layer) {
   dirty_full(c);
-  if (c->layer_state[layer] != 2) c->layer_state[layer] = 1;
+  c->layer_state[layer] = layer_overwrite(c->layer_state[layer]);
   if (layer == AMHIP_LAYER_ELEVATION) c->zrange_valid = false;  // heights from outside
 }
 
@@ -539,22 +548,41 @@ void ctx_overwrite(Ctx* c, int layer) { overwrite(c, layer); }
 int ctx_fetch_status(Ctx* c) { return fetch_status(c); }
 float ctx_layer_init_value(int layer) { return layer_init_value(layer); }
 bool ctx_layer_is_initial(const Ctx* c, int layer) {
-  return c->layer_state[layer] == 0 || c->layer_state[layer] == 3;
+  return layer_is_initial(c->layer_state[layer]);
 }
 int arg_failure(const char* msg) { return arg_fail(msg); }
+int ctx_stage_cloud(Ctx* c, const double* host_xyz, const int32_t* host_values, size_t n) {
+  int rc = ensure_capacity(&c->stage_points, &c->stage_points_cap, 3 * n);
+  if (rc == AMHIP_OK && host_values) rc = ensure_capacity(&c->stage_values, &c->stage_values_cap, n);
+  if (rc) return rc;
+  AMHIP_TRY(hipMemcpyAsync(c->stage_points, host_xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (host_values)
+    AMHIP_TRY(hipMemcpyAsync(c->stage_values, host_values, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  return AMHIP_OK;
+}
+int ctx_stage_frames(Ctx* c, const uint8_t* const* images, const size_t* steps, size_t F, size_t row, size_t height) {
+  for (size_t f = 0; f < F; ++f) {
+    if (!images[f]) return arg_fail("null image");
+    if (steps[f] < row) return arg_fail("image step smaller than a row");
+  }
+  const size_t frame = row * height;
+  const int rc = ensure_capacity(&c->stage_frames, &c->stage_frames_cap, frame * F);
+  if (rc) return rc;
+  for (size_t f = 0; f < F; ++f) {
+    if (steps[f] == row)
+      AMHIP_TRY(hipMemcpyAsync(c->stage_frames + f * frame, images[f], frame, hipMemcpyHostToDevice, c->stream));
+    else
+      AMHIP_TRY(hipMemcpy2DAsync(c->stage_frames + f * frame, row, images[f], steps[f], row, height,
+                                 hipMemcpyHostToDevice, c->stream));
+  }
+  return AMHIP_OK;
+}
 int ctx_layer_set_initial(Ctx* c, int layer) {
-  unsigned char& st = c->layer_state[layer];
-  if (layer == AMHIP_LAYER_ELEVATION) {  // every elevation is NaN again: empty height range
-    static const unsigned long long empty[2] = {0xFFF0000000000000ull, 0x000FFFFFFFFFFFFFull};
-    AMHIP_TRY(hipMemcpyAsync(c->dev_zrange, empty, sizeof(empty), hipMemcpyHostToDevice, c->stream));
-    c->zrange_valid = true;
+  if (layer == AMHIP_LAYER_ELEVATION) {
+    const int rc = zrange_reset(c);
+    if (rc) return rc;
   }
-  if (st == 0 || st == 3) return AMHIP_OK;
-  if (st == 1) {
-    st = 3;
-    return AMHIP_OK;
-  }
-  return launch_fill(c, c->layers[layer], c->cells, layer_init_value(layer));  // (handed out: eager)
+  return apply_step(c, layer, layer_set_initial(c->layer_state[layer]));  // (handed out: eager)
 }
 }  // namespace amhip
 
@@ -588,7 +616,7 @@ void* amhip_layer_device_ptr(amhip_ctx* h, int layer) {
   if (!h || !valid_layer(layer)) return nullptr;
   Ctx* c = &h->impl;
   if (use_device(c) != AMHIP_OK || materialize(c, layer) != AMHIP_OK) return nullptr;
-  c->layer_state[layer] = 2;  // the caller may write through the pointer at any time
+  c->layer_state[layer] = kLayerHandedOut;  // the caller may write through the pointer at any time
   if (layer == AMHIP_LAYER_ELEVATION) c->zrange_valid = false;
   return c->layers[layer];
 }
@@ -617,12 +645,7 @@ int amhip_dsm_process_dev(amhip_ctx* h, const double* dev_xyz, size_t n,
   if ((rc = make_dsm_params(*c, radius_sq, center_easting, center_northing, &p, 0, 1, n)))
     return rc;
   // a logically-initial elevation layer is filled by the gather itself
-  const bool fused_fill = c->layer_state[AMHIP_LAYER_ELEVATION] == 3;
-  if (fused_fill)
-    c->layer_state[AMHIP_LAYER_ELEVATION] = 1;
-  else if ((rc = touch(c, AMHIP_LAYER_ELEVATION)))
-    return rc;
-  dirty_full(c);
+  const bool fused_fill = claim_output(c, AMHIP_LAYER_ELEVATION);
   if (!fused_fill) {  // a small cloud onto a large materialized map: its bounding box is the window
     DsmParams ps;
     const int sw = dsm_subwindow(c, dev_xyz, n, radius_sq, center_easting, center_northing, p, &ps);
@@ -653,12 +676,10 @@ int amhip_dsm_process(amhip_ctx* h, const double* host_xyz, size_t n,
   Ctx* c = &h->impl;
   int rc = use_device(c);
   if (rc) return rc;
-  if ((rc = ensure_capacity(&c->stage_points, &c->stage_points_cap, 3 * n))) return rc;
   overwrite(c, AMHIP_LAYER_ELEVATION);
   AMHIP_TRY(hipMemcpyAsync(c->layers[AMHIP_LAYER_ELEVATION], elevation,
                            c->cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  AMHIP_TRY(hipMemcpyAsync(c->stage_points, host_xyz, 3 * n * sizeof(double),
-                           hipMemcpyHostToDevice, c->stream));
+  if ((rc = ctx_stage_cloud(c, host_xyz, nullptr, n))) return rc;
   if ((rc = amhip_dsm_process_dev(h, c->stage_points, n, radius_sq, center_easting,
                                   center_northing)))
     return rc;
@@ -684,12 +705,7 @@ int amhip_ortho_from_pcl_process_dev(amhip_ctx* h, const double* dev_xyz,
   DsmParams p;
   if ((rc = make_dsm_params(*c, radius_sq, 0.0, 0.0, &p, 1, 1, n))) return rc;
   if (!adaptive) {
-    const bool fused_fill = c->layer_state[AMHIP_LAYER_ORTHO] == 3;
-    dirty_full(c);
-    if (fused_fill)
-      c->layer_state[AMHIP_LAYER_ORTHO] = 1;
-    else if ((rc = touch(c, AMHIP_LAYER_ORTHO)))
-      return rc;
+    const bool fused_fill = claim_output(c, AMHIP_LAYER_ORTHO);
     return dsm_run(c, dev_xyz, dev_intensities, n, p, out, nullptr, nullptr, fused_fill,
                    layer_init_value(AMHIP_LAYER_ORTHO));
   }
@@ -728,15 +744,10 @@ int amhip_ortho_from_pcl_process(amhip_ctx* h, const double* host_xyz,
   Ctx* c = &h->impl;
   int rc = use_device(c);
   if (rc) return rc;
-  if ((rc = ensure_capacity(&c->stage_points, &c->stage_points_cap, 3 * n))) return rc;
-  if ((rc = ensure_capacity(&c->stage_values, &c->stage_values_cap, n))) return rc;
   overwrite(c, AMHIP_LAYER_ORTHO);
   AMHIP_TRY(hipMemcpyAsync(c->layers[AMHIP_LAYER_ORTHO], ortho, c->cells * sizeof(float),
                            hipMemcpyHostToDevice, c->stream));
-  AMHIP_TRY(hipMemcpyAsync(c->stage_points, host_xyz, 3 * n * sizeof(double),
-                           hipMemcpyHostToDevice, c->stream));
-  AMHIP_TRY(hipMemcpyAsync(c->stage_values, host_intensities, n * sizeof(int32_t),
-                           hipMemcpyHostToDevice, c->stream));
+  if ((rc = ctx_stage_cloud(c, host_xyz, host_intensities, n))) return rc;
   if ((rc = amhip_ortho_from_pcl_process_dev(h, c->stage_points, c->stage_values, n, radius_sq,
                                              adaptive)))
     return rc;
@@ -893,12 +904,7 @@ int amhip_dsm_tiled_finish_dev(amhip_ctx* h) {
   sp.phase = 2;
   hipLaunchKernelGGL(k_halo_overflow_check, dim3(1), dim3(64), 0, c->stream, sp.halo_counts,
                      sp.hp.nd, sp.hp.cap, c->dev_err);
-  const bool fused_fill = c->layer_state[AMHIP_LAYER_ELEVATION] == 3;
-  dirty_full(c);
-  if (fused_fill)
-    c->layer_state[AMHIP_LAYER_ELEVATION] = 1;
-  else if ((rc = touch(c, AMHIP_LAYER_ELEVATION)))
-    return rc;
+  const bool fused_fill = claim_output(c, AMHIP_LAYER_ELEVATION);
   return dsm_run(c, c->tiled_xyz, nullptr, c->tiled_n, p, c->layers[AMHIP_LAYER_ELEVATION],
                  nullptr, nullptr, fused_fill, layer_init_value(AMHIP_LAYER_ELEVATION),
                  c->zrange_valid ? c->dev_zrange : nullptr, &sp);
@@ -1025,7 +1031,7 @@ static int ortho_backward_dev(amhip_ctx* h, const amhip_camera* cam, const doubl
   const int outs[3] = {AMHIP_LAYER_ELEVATION_ANGLE, AMHIP_LAYER_OBSERVATION_INDEX, out_layer};
   for (int k = 0; k < 3; ++k) {
     if (plan.p.virt_out)
-      c->layer_state[outs[k]] = 1;
+      c->layer_state[outs[k]] = kLayerWritten;
     else if ((rc = touch(c, outs[k])))
       return rc;
   }
@@ -1084,21 +1090,9 @@ static int ortho_backward_host(
       AMHIP_TRY(hipMemcpyAsync(c->layers[l], ups[l], bytes, hipMemcpyHostToDevice,
                                c->stream));
     }
-  // stage the frames densely: [F][H][W*channels]
   const size_t row = (size_t)cam->width * (size_t)channels;
   const size_t frame = row * (size_t)cam->height;
-  if ((rc = ensure_capacity(&c->stage_frames, &c->stage_frames_cap, frame * F))) return rc;
-  for (size_t f = 0; f < F; ++f) {
-    if (!images[f]) return arg_fail("null image");
-    if (steps[f] < row) return arg_fail("image step smaller than a row");
-    if (steps[f] == row)  // dense rows (the usual cv::Mat): one linear copy
-      AMHIP_TRY(hipMemcpyAsync(c->stage_frames + f * frame, images[f], frame,
-                               hipMemcpyHostToDevice, c->stream));
-    else
-      AMHIP_TRY(hipMemcpy2DAsync(c->stage_frames + f * frame, row, images[f], steps[f],
-                                 row, (size_t)cam->height, hipMemcpyHostToDevice,
-                                 c->stream));
-  }
+  if ((rc = ctx_stage_frames(c, images, steps, F, row, (size_t)cam->height))) return rc;
   if ((rc = ortho_backward_dev(h, cam, host_T_G_C, F, c->stage_frames, frame, row, channels, colored,
                                occl_margin)))
     return rc;

@@ -15,6 +15,7 @@
 #include "amhip_dsm_plan.h"
 #include "amhip_ortho_fold.h"
 #include "amhip_ortho_plan.h"
+#include "amhip_session_plan.h"
 
 namespace amhip {
 
@@ -178,11 +179,9 @@ struct Ctx {
 
   float* layers[AMHIP_NUM_LAYERS] = {nullptr, nullptr, nullptr,
                                      nullptr, nullptr, nullptr};
-  // 0: holds its initial value since the last reset (a reset need not touch
-  // it); 1: possibly written; 2: its device pointer was handed out (the caller
-  // may write at any time: always refilled); 3: logically initial, memory not
-  // filled (lazy reset: the next producer kernel fuses the fill)
-  unsigned char layer_state[AMHIP_NUM_LAYERS] = {1, 1, 1, 1, 1, 1};
+  // the lazy-reset state of every layer (amhip_session_plan.h: LayerState and its transitions)
+  LayerState layer_state[AMHIP_NUM_LAYERS] = {kLayerWritten, kLayerWritten, kLayerWritten,
+                                              kLayerWritten, kLayerWritten, kLayerWritten};
   // [min, max] of the heights every DSM call since the last reset could have
   // written (ordered 64-bit keys, amhip_device.h); lets the mosaic kernel drop
   // tiles no frame of a small batch can see before it reads their elevation.
@@ -442,6 +441,11 @@ int ctx_layer_set_initial(Ctx* c, int layer);  // one layer back to its (lazy) i
 int ctx_fetch_status(Ctx* c);                // synchronize + sticky device status
 float ctx_layer_init_value(int layer);
 bool ctx_layer_is_initial(const Ctx* c, int layer);
+// host cloud -> stage_points (and stage_values, where the points carry intensities), asynchronously
+int ctx_stage_cloud(Ctx* c, const double* host_xyz, const int32_t* host_values, size_t n);
+// F host images of `height` rows of `row` bytes -> stage_frames, dense [F][height][row]: one linear
+// copy per frame with dense rows (the usual cv::Mat), a pitched one otherwise
+int ctx_stage_frames(Ctx* c, const uint8_t* const* images, const size_t* steps, size_t F, size_t row, size_t height);
 int arg_failure(const char* msg);
 
 }  // namespace amhip

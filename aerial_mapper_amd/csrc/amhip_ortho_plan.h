@@ -15,6 +15,7 @@
 #include "aerial_mapper_hip.h"
 #include "amhip_dsm_plan.h"  // grid_bases, kTileI
 #include "amhip_ortho_fold.h"
+#include "amhip_session_plan.h"  // LayerState
 
 namespace amhip {
 
@@ -428,7 +429,7 @@ struct OrthoPlanInput {
   int channels, colored;
   bool zrange_valid;  // the context knows the range of the heights the DSM wrote
   // Ctx::layer_state of the layers the call looks at, before it
-  unsigned char state_angle, state_index, state_out, state_nobs;
+  unsigned char state_angle, state_index, state_out, state_nobs;  // (LayerState values)
   OrthoKnobs knobs;
 };
 
@@ -490,7 +491,8 @@ inline OrthoPlan plan_ortho_call(const OrthoPlanInput& in, const FrameTable& fra
   }
   // ---- layer states (lazy reset): elevation_angle, observation_index and the output layer are
   // either all produced with a fused fill or all materialized
-  p.virt_out = (in.state_angle == 3 && in.state_index == 3 && in.state_out == 3) ? 1 : 0;
+  p.virt_out = (in.state_angle == kLayerLazyInitial && in.state_index == kLayerLazyInitial &&
+                in.state_out == kLayerLazyInitial) ? 1 : 0;
   p.radius_scale = 1.0 + 2.0 * frames.qdev;
   if (!(frames.qdev < 0.25)) p.cull = 0;  // not a rotation at all (or NaN): every frame is tested
   // small batches on a big map: most tiles are out of every frame's sight
@@ -498,7 +500,7 @@ inline OrthoPlan plan_ortho_call(const OrthoPlanInput& in, const FrameTable& fra
   // num_observations is zero everywhere while it holds its initial value,
   // filled (0) or not (3): `+= itself` keeps it zero, the kernel neither reads
   // nor writes it and the layer stays in that state
-  p.virt_nobs = (in.state_nobs == 3 || in.state_nobs == 0) ? 1 : 0;
+  p.virt_nobs = layer_is_initial((LayerState)in.state_nobs) ? 1 : 0;
   p.prune = (p.cull && (cam.distortion == AMHIP_DIST_NONE || p.r_in > 0.0) && p.virt_nobs &&
              !in.knobs.ortho_no_prune) ? 1 : 0;
   p.fast = frames.fast_ok ? 1 : 0;

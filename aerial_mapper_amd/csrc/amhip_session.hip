@@ -22,6 +22,8 @@
 //                of an upload; anything else is uploaded.  Outputs the kernels did not change
 //                (num_observations: `+= itself`, ortho-backward-grid.cc:183) are not downloaded.
 //                tuning knob session_always_copy: every matrix up and down, like round 1.
+// What is transferred and what the session may believe afterwards is decided in
+// amhip_session_plan.h; this file enqueues what the plan says and stores what it returns.
 #include <sched.h>
 
 #include <algorithm>
@@ -41,32 +43,6 @@
 
 namespace amhip {
 
-struct Win {
-  int i0, j0, rows, cols;
-};
-
-struct Hash128 {
-  unsigned long long a = 0, b = 0;
-  bool operator==(const Hash128& o) const { return a == o.a && b == o.b; }
-  bool operator!=(const Hash128& o) const { return !(*this == o); }
-};
-
-// What the session knows about one layer of one window.  `device_valid`: the device layer holds
-// a matrix with content sum `device`.  It is cleared BEFORE any kernel that writes the layer is
-// enqueued and set again only by sync_out, from the device's own sum: a call that fails midway
-// leaves it cleared, so the retry uploads the host matrix instead of trusting a half-written
-// layer.  `host`: content sum of the host matrix as this session last saw or wrote it.
-struct LayerSync {
-  bool device_valid = false;
-  Hash128 device;
-  bool host_known = false;
-  Hash128 host;
-  // sync_in found (or put) the device layer in its lazily-reset initial state AND the host matrix
-  // holds that constant: once a kernel has materialised the layer, sync_out downloads it without
-  // waiting for its content sum (the sum then runs on a second stream beside the download)
-  bool fresh_in = false;
-};
-
 // Where the last host-buffer call spent its time (amhip_session_last_profile; window 0's view):
 // wall-clock phases on the host, HIP-event times for what the stream did.
 struct CallProfile {
@@ -74,38 +50,50 @@ struct CallProfile {
   double up_bytes = 0, down_bytes = 0;
 };
 
-struct Session {
-  amhip_grid_desc grid;
-  int ti = 1, tj = 1;
-  std::vector<int> edges_i, edges_j;
-  std::vector<amhip_ctx*> ctx;
-  std::vector<Win> win;
-  std::vector<int> dev;
-  std::vector<LayerSync> sync;                 // [window][layer]
-  std::vector<Hash128> const_hash;             // [window][layer]: content sum of the initial constant
-  bool always_copy = false;
+constexpr size_t kSumBytes = sizeof(unsigned long long) * 2 * AMHIP_NUM_LAYERS;
+
+// everything of one window
+struct Window {
+  amhip_ctx* ctx = nullptr;
+  Win win = {0, 0, 0, 0};
+  int dev = 0;
+  LayerSync sync[AMHIP_NUM_LAYERS];
+  Hash128 const_hash[AMHIP_NUM_LAYERS];        // content sums of the initial constants
   // DSM routing (W > 1): count, then compact -- a slice's selections for all windows take
   // (points selected) rows, not (slice x windows)
-  std::vector<double*> route_out;
-  std::vector<size_t> route_cap;               // doubles
-  std::vector<long long*> route_counts;        // device, W per window
-  std::vector<hipEvent_t> route_done;          // window k's selections are complete
-  std::vector<double*> cloud;
-  std::vector<size_t> cloud_cap;               // doubles
-  std::vector<unsigned long long*> dev_hash;   // device scratch: two u64 per layer
-  std::vector<unsigned long long*> pin_hash;   // its pinned host mirror
-  std::vector<float*> pin;                     // pinned host staging of partial downloads
-  std::vector<size_t> pin_cap;                 // floats
+  double* route_out = nullptr;
+  size_t route_cap = 0;                        // doubles
+  long long* route_counts = nullptr;           // device, W words
+  hipEvent_t route_done = nullptr;             // this window's selections are complete
+  double* cloud = nullptr;
+  size_t cloud_cap = 0;                        // doubles
+  unsigned long long* dev_hash = nullptr;      // device scratch: two u64 per layer
+  unsigned long long* pin_hash = nullptr;      // its pinned host mirror
+  float* pin = nullptr;                        // pinned host staging of partial downloads
+  size_t pin_cap = 0;                          // floats
+  // a second stream for the content sums that run beside a download, and the events that time a
+  // call's kernels / downloads (CallProfile)
+  hipStream_t aux_stream = nullptr;
+  hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_s1 = nullptr, ev_d1 = nullptr;
+  Ctx* c() const { return &ctx->impl; }
+};
+
+struct Session {
+  amhip_grid_desc grid;
+  int ti = 1;
+  std::vector<int> edges_i, edges_j;
+  std::vector<Window> windows;
+  bool always_copy = false;
   bool verify_partial = false;                 // tuning knob session_verify_partial: re-sum the host matrix
   std::atomic<unsigned long long> up_bytes{0}, down_bytes{0};  // layer traffic (amhip_session_transfer_stats)
-  // per window: a second stream for the content sums that run beside a download, and the events
-  // that time a call's kernels / downloads (CallProfile)
-  std::vector<hipStream_t> aux_stream;
-  std::vector<hipEvent_t> ev_k0, ev_k1, ev_s1, ev_d1;
   CallProfile prof;
   std::atomic<unsigned long long> prof_down{0};   // (the windows' threads add to it: the call's downloads)
-  int W() const { return (int)ctx.size(); }
+  int W() const { return (int)windows.size(); }
 };
+
+static double ms_since(std::chrono::steady_clock::time_point t) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
 
 // tuning knob session_trace: wall time of every phase of a call on stderr (where does a host-matrix
 // call spend its time: content sums, uploads, kernels, downloads?)
@@ -283,40 +271,29 @@ static hipError_t copy_window(void* dst_host_or_dev, const void* src, const Sess
                                     (size_t)w.cols, hipMemcpyHostToDevice, stream);
 }
 
-// host matrix -> window layer, as far as needed (asynchronous on the context's stream).
-// will_write: the call that follows writes this layer on the device.
+static unsigned long long window_bytes(const Win& w) {
+  return (unsigned long long)w.rows * (unsigned long long)w.cols * 4ull;
+}
+
+// host matrix -> window layer, as far as needed (asynchronous on the context's stream; the caller
+// has made its device current).  will_write: the call that follows writes this layer on the device.
 static int sync_in(Session& s, int k, int layer, const float* host, const Hash128& host_hash,
                    bool will_write) {
-  Ctx* c = &s.ctx[k]->impl;
-  LayerSync& st = s.sync[(size_t)k * AMHIP_NUM_LAYERS + layer];
-  int rc = ctx_use_device(c);
-  if (rc) return rc;
-  st.host = host_hash;
-  st.host_known = !s.always_copy;
-  st.fresh_in = false;
-  bool have = false;
-  if (!s.always_copy) {
-    const bool host_is_const = host_hash == s.const_hash[(size_t)k * AMHIP_NUM_LAYERS + layer];
-    if (st.device_valid && st.device == host_hash) {
-      have = true;  // the device holds exactly this
-      st.fresh_in = host_is_const && ctx_layer_is_initial(c, layer);
-    } else if (host_is_const) {
-      // (any matrix with these sums is taken for the initial constant: 2^-128)
-      if ((rc = ctx_layer_set_initial(c, layer))) return rc;
-      have = true;
-      st.fresh_in = ctx_layer_is_initial(c, layer);
-    }
-  }
-  if (!have) {
-    const Win& w = s.win[k];
-    st.device_valid = false;
+  Window& x = s.windows[k];
+  Ctx* c = x.c();
+  LayerSync& st = x.sync[layer];
+  const SyncInPlan p =
+      plan_sync_in(st, host_hash, x.const_hash[layer], c->layer_state[layer], s.always_copy, will_write);
+  st = p.before;
+  if (p.action == InAction::kLazyReset) {
+    const int rc = ctx_layer_set_initial(c, layer);
+    if (rc) return rc;
+  } else if (p.action == InAction::kUpload) {
     ctx_overwrite(c, layer);
-    AMHIP_TRY(copy_window(c->layers[layer], map_at(host, s, w), s, w, false, c->stream));
-    s.up_bytes += (unsigned long long)w.rows * (unsigned long long)w.cols * 4ull;
+    AMHIP_TRY(copy_window(c->layers[layer], map_at(host, s, x.win), s, x.win, false, c->stream));
+    s.up_bytes += window_bytes(x.win);
   }
-  st.device = host_hash;
-  // (a layer the next kernel writes is unknown until sync_out has summed it again)
-  st.device_valid = !s.always_copy && !will_write;
+  st = p.after;
   return AMHIP_OK;
 }
 
@@ -337,194 +314,159 @@ static void unpack_block(const float* packed, float* host, const Session& s, int
   for (auto& x : th) x.join();
 }
 
+// pinned staging of `need` floats for window x's rectangle downloads; false: none to be had
+static bool ensure_pinned(Window& x, size_t need) {
+  if (need == 0) return false;
+  if (need <= x.pin_cap) return true;
+  if (x.pin) (void)hipHostFree(x.pin);
+  x.pin = nullptr;
+  x.pin_cap = 0;
+  if (hipHostMalloc(reinterpret_cast<void**>(&x.pin), need * 4, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    x.pin = nullptr;
+    return false;
+  }
+  x.pin_cap = need;
+  return true;
+}
+
+// the whole window of a layer -> its place in the host matrix, counted
+static int download_window(Session& s, Window& x, int layer, float* host) {
+  Ctx* c = x.c();
+  AMHIP_TRY(copy_window(map_at(host, s, x.win), c->layers[layer], s, x.win, true, c->stream));
+  s.down_bytes += window_bytes(x.win);
+  s.prof_down += window_bytes(x.win);
+  return AMHIP_OK;
+}
+
+// stage 1's device work: the sums of the layers that need one (on the second stream when a download
+// runs beside them, ordered behind the kernels by their end event), the early downloads on the
+// context's stream, and the one wait for the sums
+static int run_out_sums(Session& s, Window& x, OutLayer* L, float* const* hosts, int nl, bool beside) {
+  Ctx* c = x.c();
+  const Win& w = x.win;
+  hipStream_t hs = beside ? x.aux_stream : c->stream;
+  if (beside) AMHIP_TRY(hipStreamWaitEvent(hs, x.ev_k1, 0));
+  AMHIP_TRY(hipMemsetAsync(x.dev_hash, 0, kSumBytes, hs));
+  for (int q = 0; q < nl; ++q)
+    if (L[q].sum)
+      hipLaunchKernelGGL(k_layer_hash, dim3(2048), dim3(256), 0, hs, c->layers[L[q].layer], 0.0f, w.rows,
+                         w.cols, w.i0, w.j0, s.grid.rows, x.dev_hash + 2 * q);
+  // (pinned: the copy must not block the host)
+  AMHIP_TRY(hipMemcpyAsync(x.pin_hash, x.dev_hash, kSumBytes, hipMemcpyDeviceToHost, hs));
+  // (a download into pageable memory keeps the calling thread until it is done: the sums are
+  // already running on the second stream by then)
+  for (int q = 0; q < nl; ++q) {
+    if (!L[q].early) continue;
+    out_copy_pending(&x.sync[L[q].layer]);
+    const int rc = download_window(s, x, L[q].layer, hosts[q]);
+    if (rc) return rc;
+  }
+  // (the downloads' own start, where the sums ran in front of them on the same stream)
+  AMHIP_TRY(hipEventRecord(x.ev_s1, c->stream));
+  AMHIP_TRY(hipStreamSynchronize(hs));
+  for (int q = 0; q < nl; ++q)
+    if (L[q].sum) L[q].h = {x.pin_hash[2 * q], x.pin_hash[2 * q + 1]};
+  return AMHIP_OK;
+}
+
+// tuning knob session_verify_partial (tests): a matrix that took a rectangle must carry the device's sums as a whole
+static int verify_rects(Session& s, int k, const OutLayer* L, float* const* hosts, int nl) {
+  for (int q = 0; q < nl; ++q) {
+    if (L[q].action != OutAction::kRect) continue;
+    std::vector<Hash128> hv;
+    const float* m[1] = {hosts[q]};
+    host_hashes(s, m, 1, &hv);
+    if (hv[(size_t)k] != L[q].h)
+      return arg_failure("session: a partial download left the host matrix different from the device layer");
+  }
+  return AMHIP_OK;
+}
+
+// the call's profile: window 0's view.  sum_wait_ms: the sums' share of the wall clock, the whole
+// wait when nothing was downloaded beside them
+static int record_profile(Session& s, Window& x, bool beside, double sum_wait_ms) {
+  AMHIP_TRY(hipEventSynchronize(x.ev_d1));
+  float ms = 0.0f;
+  if (hipEventElapsedTime(&ms, x.ev_k0, x.ev_k1) == hipSuccess) s.prof.kernel_ms = ms;
+  if (hipEventElapsedTime(&ms, beside || s.always_copy ? x.ev_k1 : x.ev_s1, x.ev_d1) == hipSuccess)
+    s.prof.d2h_ms = ms;
+  (void)hipGetLastError();
+  s.prof.dev_sum_wait_ms = beside ? 0.0 : sum_wait_ms;
+  return AMHIP_OK;
+}
+
 // window layers -> host matrices where the device content differs from what the host holds.
 // dirty_ok: the call before was a DSM / backward-mosaic call, whose context knows which cells of
 // the window it can have written (ctx_last_dirty): a small cloud's sub-window, the bounding box of
 // a small batch's tile list.  A host matrix that equalled the device layer BEFORE the call (what
 // sync_in establishes) differs from it only there: that rectangle is downloaded (device -> pinned
 // staging -> the matrix's columns) instead of the window -- the incremental use case on a large
-// map downloads megabytes instead of gigabytes per call.  tuning knob session_no_partial: always the
-// whole window (A-B, tests).
-static int sync_out(Session& s, int k, const int* layers, float* const* hosts, int nl,
-                    bool dirty_ok = false) {
+// map downloads megabytes instead of gigabytes per call.
+// The three stages of amhip_session_plan.h around the two points where the device answers: (1) which
+// layers download at once, beside their sums, and which are summed; (2) after the sums, what every
+// other layer downloads -- marked "host unknown" BEFORE the copy --; (3) after the stream has
+// synchronised, the host matrices are known to hold what the device summed.
+// (the caller has made the window's device current)
+static int sync_out(Session& s, int k, const int* layers, float* const* hosts, int nl, bool dirty_ok) {
   PhaseClock clock("sync_out");
-  Ctx* c = &s.ctx[k]->impl;
-  int rc = ctx_use_device(c);
-  if (rc) return rc;
-  const Win& w = s.win[k];
-  Hash128 h[AMHIP_NUM_LAYERS];
-  bool run[AMHIP_NUM_LAYERS] = {};
+  Window& x = s.windows[k];
+  Ctx* c = x.c();
+  int rc;
+  const Win& w = x.win;
+  const SessionKnobs knobs = {s.always_copy, tuning_on("session_no_partial"), tuning_on("session_serial_sums")};
+  OutLayer L[AMHIP_NUM_LAYERS];
+  for (int q = 0; q < nl; ++q) {
+    L[q].layer = layers[q];
+    L[q].want = hosts[q] != nullptr;
+  }
   int rect[4] = {0, 0, w.rows, w.cols};
   bool partial = false;
-  if (dirty_ok && !s.always_copy && !tuning_on("session_no_partial")) {
+  if (rect_wanted(dirty_ok, knobs)) {
     if ((rc = ctx_last_dirty(c, rect))) return rc;
-    partial = rect[2] > 0 && rect[3] > 0 && rect[0] >= 0 && rect[1] >= 0 &&
-              rect[0] + rect[2] <= w.rows && rect[1] + rect[3] <= w.cols &&
-              2 * (size_t)rect[2] * (size_t)rect[3] <= (size_t)w.rows * (size_t)w.cols;
+    partial = rect_is_partial(rect, w.rows, w.cols);
   }
-  AMHIP_TRY(hipEventRecord(s.ev_k1[k], c->stream));  // (the call's kernels end here)
+  AMHIP_TRY(hipEventRecord(x.ev_k1, c->stream));  // (the call's kernels end here)
   clock.mark("kernels (wait)", c->stream, true);
-  // A download is asynchronous: until the stream has synchronised without an error the host
-  // matrix may be stale or half written, so the layers being downloaded are marked "host
-  // unknown" FIRST and "host == device sum" only after the wait (a failed copy must
-  // not leave the session believing the host holds h[q] -- the next call would skip it).
-  bool copied[AMHIP_NUM_LAYERS] = {};
-  bool packed[AMHIP_NUM_LAYERS] = {};
-  bool early[AMHIP_NUM_LAYERS] = {};
-  bool any = false;
   const auto wall0 = std::chrono::steady_clock::now();
-  // (1) "fresh" layers -- the host holds the initial constant, the device layer was lazily initial
-  // when the call began and a kernel has materialised it since: their download starts NOW, on the
-  // context's stream, and their content sums (which only decide what LATER calls may skip) run
-  // beside it on the second stream.  A layer whose every written cell happens to equal the
-  // constant is downloaded for nothing; nothing else changes.
-  if (!s.always_copy && !partial && !tuning_on("session_serial_sums")) {
-    for (int q = 0; q < nl; ++q) {
-      if (!hosts[q]) continue;
-      const LayerSync& st = s.sync[(size_t)k * AMHIP_NUM_LAYERS + layers[q]];
-      early[q] = st.fresh_in && st.host_known && !ctx_layer_is_initial(c, layers[q]);
-      any = any || early[q];
-    }
-  }
-  const bool beside = any;
-  unsigned long long* const got = s.pin_hash[k];   // (pinned: the copy below must not block the host)
-  if (!s.always_copy) {
-    hipStream_t hs = c->stream;
-    if (beside) {  // (beside the downloads; ordered behind the kernels by their end event)
-      hs = s.aux_stream[k];
-      AMHIP_TRY(hipStreamWaitEvent(hs, s.ev_k1[k], 0));
-    }
-    AMHIP_TRY(hipMemsetAsync(s.dev_hash[k], 0, sizeof(unsigned long long) * 2 * AMHIP_NUM_LAYERS, hs));
-    for (int q = 0; q < nl; ++q) {
-      if (!hosts[q]) continue;
-      const int l = layers[q];
-      if (ctx_layer_is_initial(c, l)) {  // nothing wrote it since its (lazy) reset
-        h[q] = s.const_hash[(size_t)k * AMHIP_NUM_LAYERS + l];
-        continue;
-      }
-      run[q] = true;
-      hipLaunchKernelGGL(k_layer_hash, dim3(2048), dim3(256), 0, hs, c->layers[l], 0.0f, w.rows,
-                         w.cols, w.i0, w.j0, s.grid.rows, s.dev_hash[k] + 2 * q);
-    }
-    AMHIP_TRY(hipMemcpyAsync(got, s.dev_hash[k], sizeof(unsigned long long) * 2 * AMHIP_NUM_LAYERS,
-                             hipMemcpyDeviceToHost, hs));
-    // (a download into pageable memory keeps the calling thread until it is done: the sums are
-    // already running on the second stream by then)
-    for (int q = 0; q < nl; ++q) {
-      if (!early[q]) continue;
-      LayerSync& st = s.sync[(size_t)k * AMHIP_NUM_LAYERS + layers[q]];
-      st.host_known = false;
-      AMHIP_TRY(copy_window(map_at(hosts[q], s, w), c->layers[layers[q]], s, w, true, c->stream));
-      s.down_bytes += (unsigned long long)w.rows * (unsigned long long)w.cols * 4ull;
-      s.prof_down += (unsigned long long)w.rows * (unsigned long long)w.cols * 4ull;
-      copied[q] = true;
-    }
-    // (the downloads' own start, where the sums ran in front of them on the same stream)
-    AMHIP_TRY(hipEventRecord(s.ev_s1[k], c->stream));
-    AMHIP_TRY(hipStreamSynchronize(hs));
-    for (int q = 0; q < nl; ++q)
-      if (run[q]) {
-        h[q].a = got[2 * q];
-        h[q].b = got[2 * q + 1];
-      }
-  }
+  // (1) the sums; beside them, on the context's stream, the downloads that need not wait for them
+  const bool beside = plan_out_sums(L, nl, x.sync, x.const_hash, c->layer_state, partial, knobs);
+  bool any = beside;
+  if (!s.always_copy && (rc = run_out_sums(s, x, L, hosts, nl, beside))) return rc;
   clock.mark("device content sums");
-  const auto wall1 = std::chrono::steady_clock::now();
-  const size_t block = (size_t)rect[2] * (size_t)rect[3];
-  if (partial) {  // (staging for every layer of the call, at most 1 GiB: beyond, the plain way)
-    const size_t need = block * (size_t)nl;
-    if (need * 4 > (1ull << 30)) {
-      partial = false;
-    } else if (need > s.pin_cap[k]) {
-      if (s.pin[k]) (void)hipHostFree(s.pin[k]);
-      s.pin[k] = nullptr;
-      s.pin_cap[k] = 0;
-      if (hipHostMalloc(reinterpret_cast<void**>(&s.pin[k]), need * 4, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        s.pin[k] = nullptr;
-        partial = false;
-      } else {
-        s.pin_cap[k] = need;
-      }
-    }
-  }
+  const double sum_wait_ms = ms_since(wall0);
   // (2) every other layer: downloaded where the device's sum differs from what the host holds
+  const size_t block = (size_t)rect[2] * (size_t)rect[3];
+  partial = partial && ensure_pinned(x, rect_staging_floats(block, nl));
   for (int q = 0; q < nl; ++q) {
-    if (!hosts[q]) continue;
-    const int l = layers[q];
-    LayerSync& st = s.sync[(size_t)k * AMHIP_NUM_LAYERS + l];
-    const bool host_has_it = !s.always_copy && st.host_known && st.host == h[q];
-    // (the host matrix is what the device layer was before the call)
-    const bool host_is_before = !s.always_copy && st.host_known && st.host == st.device;
-    st.device_valid = !s.always_copy;
-    st.device = h[q];
-    if (early[q]) continue;
-    if (!host_has_it) {
-      st.host_known = false;
-      if ((rc = ctx_materialize(c, l))) return rc;
-      if (partial && host_is_before) {
-        AMHIP_TRY(hipMemcpy2DAsync(s.pin[k] + block * (size_t)q, (size_t)rect[2] * 4,
-                                   c->layers[l] + (size_t)rect[0] + (size_t)rect[1] * (size_t)w.rows,
-                                   (size_t)w.rows * 4, (size_t)rect[2] * 4, (size_t)rect[3],
-                                   hipMemcpyDeviceToHost, c->stream));
-        packed[q] = true;
-        s.down_bytes += (unsigned long long)block * 4ull;
-        s.prof_down += (unsigned long long)block * 4ull;
-      } else {
-        AMHIP_TRY(copy_window(map_at(hosts[q], s, w), c->layers[l], s, w, true, c->stream));
-        s.down_bytes += (unsigned long long)w.rows * (unsigned long long)w.cols * 4ull;
-        s.prof_down += (unsigned long long)w.rows * (unsigned long long)w.cols * 4ull;
-      }
-      copied[q] = true;
-      any = true;
+    if (!L[q].want) continue;
+    const int l = L[q].layer;
+    const OutAction act = plan_out_layer(&L[q], &x.sync[l], partial, s.always_copy);
+    if (L[q].early || act == OutAction::kNone) continue;
+    if ((rc = ctx_materialize(c, l))) return rc;
+    if (act == OutAction::kRect) {
+      AMHIP_TRY(hipMemcpy2DAsync(x.pin + block * (size_t)q, (size_t)rect[2] * 4,
+                                 c->layers[l] + (size_t)rect[0] + (size_t)rect[1] * (size_t)w.rows,
+                                 (size_t)w.rows * 4, (size_t)rect[2] * 4, (size_t)rect[3],
+                                 hipMemcpyDeviceToHost, c->stream));
+      s.down_bytes += (unsigned long long)block * 4ull;
+      s.prof_down += (unsigned long long)block * 4ull;
+    } else if ((rc = download_window(s, x, l, hosts[q]))) {
+      return rc;
     }
+    any = true;
   }
-  AMHIP_TRY(hipEventRecord(s.ev_d1[k], c->stream));
+  AMHIP_TRY(hipEventRecord(x.ev_d1, c->stream));
   if (any) AMHIP_TRY(hipStreamSynchronize(c->stream));
   clock.mark("downloads");
   for (int q = 0; q < nl; ++q)
-    if (packed[q])
-      unpack_block(s.pin[k] + block * (size_t)q, hosts[q], s, w.i0 + rect[0], w.j0 + rect[1], rect[2],
-                   rect[3]);
+    if (L[q].action == OutAction::kRect)
+      unpack_block(x.pin + block * (size_t)q, hosts[q], s, w.i0 + rect[0], w.j0 + rect[1], rect[2], rect[3]);
   clock.mark("unpack");
-  if (s.verify_partial) {  // (tests: the matrix as a whole must now carry the device's sums)
-    for (int q = 0; q < nl; ++q) {
-      if (!packed[q]) continue;
-      std::vector<Hash128> hv;
-      const float* m[1] = {hosts[q]};
-      host_hashes(s, m, 1, &hv);
-      if (hv[(size_t)k] != h[q])
-        return arg_failure("session: a partial download left the host matrix different from the device layer");
-    }
-  }
-  for (int q = 0; q < nl; ++q) {
-    if (!hosts[q] || !copied[q]) continue;
-    LayerSync& st = s.sync[(size_t)k * AMHIP_NUM_LAYERS + layers[q]];
-    st.host_known = !s.always_copy;
-    st.host = h[q];
-  }
-  if (k == 0) {  // (the call's profile: window 0's view)
-    AMHIP_TRY(hipEventSynchronize(s.ev_d1[k]));
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, s.ev_k0[k], s.ev_k1[k]) == hipSuccess) s.prof.kernel_ms = ms;
-    if (hipEventElapsedTime(&ms, beside || s.always_copy ? s.ev_k1[k] : s.ev_s1[k], s.ev_d1[k]) == hipSuccess)
-      s.prof.d2h_ms = ms;
-    (void)hipGetLastError();
-    // (the sums' share of the wall clock: the whole wait when nothing was downloaded beside them)
-    s.prof.dev_sum_wait_ms = beside ? 0.0 : std::chrono::duration<double, std::milli>(wall1 - wall0).count();
-  }
-  return AMHIP_OK;
-}
-
-// dsm.cc:127-144: the largest squared radius of the ladder -> metres a window grows by
-static double halo_margin_m(int radius_sq, double res) {
-  double tmax = (double)radius_sq, lambda = 1.0;
-  for (;;) {
-    tmax = std::max(tmax, lambda * radius_sq);
-    lambda *= 1.1;
-    if (lambda * radius_sq > 7.0) break;
-  }
-  return std::sqrt(tmax) + res;
+  if (s.verify_partial && (rc = verify_rects(s, k, L, hosts, nl))) return rc;
+  // (3) the stream has synchronised without an error
+  for (int q = 0; q < nl; ++q) out_commit(L[q], &x.sync[L[q].layer], s.always_copy);
+  return k == 0 ? record_profile(s, x, beside, sum_wait_ms) : AMHIP_OK;
 }
 
 template <typename F>
@@ -548,6 +490,74 @@ static int for_windows(Session& s, F fn) {
   return AMHIP_OK;
 }
 
+// What every host-matrix call does around its device work: the profile is reset; the host
+// matrices are summed (sums()); every window takes in the matrices the call reads or partially
+// writes (enter()) and, behind the call's own work, hands back those it wrote (leave()).
+struct HostCall {
+  Session& s;
+  const std::chrono::steady_clock::time_point call0 = std::chrono::steady_clock::now();
+  int nin = 0, nout = 0;
+  int in_layer[AMHIP_NUM_LAYERS], out_layer[AMHIP_NUM_LAYERS];
+  const float* in[AMHIP_NUM_LAYERS];
+  bool in_written[AMHIP_NUM_LAYERS];
+  float* out[AMHIP_NUM_LAYERS];
+  std::vector<Hash128> hh;  // [nin][W]
+
+  HostCall(Session& session, double up_bytes) : s(session) {
+    s.prof = CallProfile();
+    s.prof_down = 0;
+    s.prof.up_bytes = up_bytes;
+  }
+  // the device needs what `matrix` holds of `layer` (null: not part of this call)
+  void reads(int layer, const float* matrix, bool will_write) {
+    if (!matrix) return;
+    in_layer[nin] = layer;
+    in[nin] = matrix;
+    in_written[nin++] = will_write;
+  }
+  // `matrix` has to hold the layer afterwards (null: listed, not handed back)
+  void returns(int layer, float* matrix) {
+    out_layer[nout] = layer;
+    out[nout++] = matrix;
+  }
+  // content sums of the matrices the call reads, with host threads (always_copy: nothing is compared)
+  void sums() {
+    const auto t = std::chrono::steady_clock::now();
+    if (!s.always_copy) host_hashes(s, in, nin, &hh);
+    else hh.assign((size_t)nin * s.W(), Hash128());
+    s.prof.host_sum_ms = ms_since(t);
+  }
+  int enter(int k) {
+    int r = ctx_use_device(s.windows[k].c());
+    for (int q = 0; q < nin && r == AMHIP_OK; ++q)
+      r = sync_in(s, k, in_layer[q], in[q], hh[(size_t)q * s.W() + k], in_written[q]);
+    return r;
+  }
+  // body(k): the call's device work on window k, enqueued on its context's stream
+  template <typename Body>
+  int leave(int k, bool dirty_ok, Body body) {
+    Window& x = s.windows[k];
+    AMHIP_TRY(hipEventRecord(x.ev_k0, x.c()->stream));
+    int r = body(k);
+    if (r == AMHIP_OK) r = sync_out(s, k, out_layer, out, nout, dirty_ok);
+    return r ? r : ctx_fetch_status(x.c());
+  }
+  int done(int rc) {
+    s.prof.total_ms = ms_since(call0);
+    return rc;
+  }
+  // the whole of it where nothing runs beside the sums; staged(k): uploads in front of the kernels' clock
+  template <typename Staged, typename Body>
+  int run(bool dirty_ok, Staged staged, Body body) {
+    sums();
+    return done(for_windows(s, [&](int k) -> int {
+      int r = enter(k);
+      if (r == AMHIP_OK) r = staged(k);
+      return r ? r : leave(k, dirty_ok, body);
+    }));
+  }
+};
+
 }  // namespace amhip
 
 using namespace amhip;
@@ -555,6 +565,54 @@ using namespace amhip;
 struct amhip_session {
   amhip::Session impl;
 };
+
+// what create_window() made, in any state of completion
+static void release_window(Window& x) {
+  if (!x.ctx) return;
+  (void)ctx_use_device(x.c());
+  (void)hipStreamSynchronize(x.c()->stream);
+  for (void* p : {(void*)x.route_out, (void*)x.route_counts, (void*)x.cloud, (void*)x.dev_hash})
+    if (p) (void)hipFree(p);
+  for (void* p : {(void*)x.pin, (void*)x.pin_hash})
+    if (p) (void)hipHostFree(p);
+  if (x.aux_stream) (void)hipStreamDestroy(x.aux_stream);
+  for (hipEvent_t e : {x.route_done, x.ev_k0, x.ev_k1, x.ev_s1, x.ev_d1})
+    if (e) (void)hipEventDestroy(e);
+  amhip_ctx_destroy(x.ctx);
+  x = Window();
+}
+
+// window k of the session: its context, the scratch of its content sums, its second stream and
+// events, and the sums of its initial constants
+static int create_window(Session& s, int k, int device) {
+  Window& x = s.windows[k];
+  x.win = window_of(s.edges_i, s.edges_j, k);
+  x.dev = device;
+  int rc = amhip_ctx_create_window(&s.grid, x.win.i0, x.win.j0, x.win.rows, x.win.cols, device, &x.ctx);
+  if (rc) return rc;
+  Ctx* c = x.c();
+  if ((rc = ctx_use_device(c))) return rc;
+  if (hipMalloc(reinterpret_cast<void**>(&x.dev_hash), kSumBytes) != hipSuccess)
+    return hip_fail(hipGetLastError(), "hipMalloc(session scratch)", __FILE__, __LINE__);
+  if (hipHostMalloc(reinterpret_cast<void**>(&x.pin_hash), kSumBytes, hipHostMallocDefault) != hipSuccess)
+    return hip_fail(hipGetLastError(), "hipHostMalloc(session scratch)", __FILE__, __LINE__);
+  if (hipStreamCreateWithFlags(&x.aux_stream, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreate(&x.ev_k0) != hipSuccess || hipEventCreate(&x.ev_k1) != hipSuccess ||
+      hipEventCreate(&x.ev_d1) != hipSuccess || hipEventCreate(&x.ev_s1) != hipSuccess)
+    return hip_fail(hipGetLastError(), "session: second stream / timing events", __FILE__, __LINE__);
+  // content sums of the window's initial constants: summed on the device without reading
+  // memory (the non-linear mix has no closed form)
+  hipError_t e = hipMemsetAsync(x.dev_hash, 0, kSumBytes, c->stream);
+  for (int l = 0; l < AMHIP_NUM_LAYERS && e == hipSuccess; ++l)
+    hipLaunchKernelGGL(k_layer_hash, dim3(1024), dim3(256), 0, c->stream, (const float*)nullptr,
+                       ctx_layer_init_value(l), x.win.rows, x.win.cols, x.win.i0, x.win.j0, s.grid.rows,
+                       x.dev_hash + 2 * l);
+  if (e == hipSuccess) e = hipMemcpyAsync(x.pin_hash, x.dev_hash, kSumBytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return hip_fail(e, "session: content sums of the initial layers", __FILE__, __LINE__);
+  for (int l = 0; l < AMHIP_NUM_LAYERS; ++l) x.const_hash[l] = {x.pin_hash[2 * l], x.pin_hash[2 * l + 1]};
+  return AMHIP_OK;
+}
 
 extern "C" {
 
@@ -570,115 +628,28 @@ int amhip_session_create(const amhip_grid_desc* grid, int tiles_i, int tiles_j,
   Session& s = h->impl;
   s.grid = *grid;
   s.ti = tiles_i;
-  s.tj = tiles_j;
   s.always_copy = tuning_on("session_always_copy");
   s.verify_partial = tuning_on("session_verify_partial");
   // window edges on multiples of the gather tile (64 x 32 cells) except at the map border
-  auto edges = [](int n, int parts, int align, std::vector<int>* e) {
-    e->assign(1, 0);
-    for (int k = 1; k < parts; ++k) {
-      int v = (int)std::llround((double)n * k / parts / align) * align;
-      v = std::min(std::max(v, e->back() + 1), n - (parts - k));
-      e->push_back(v);
-    }
-    e->push_back(n);
-  };
-  edges(grid->rows, tiles_i, 64, &s.edges_i);
-  edges(grid->cols, tiles_j, 32, &s.edges_j);
+  window_edges(grid->rows, tiles_i, 64, &s.edges_i);
+  window_edges(grid->cols, tiles_j, 32, &s.edges_j);
   const int W = tiles_i * tiles_j;
-  int rc = AMHIP_OK;
-  for (int k = 0; k < W && rc == AMHIP_OK; ++k) {
-    const int a = k % tiles_i, b = k / tiles_i;
-    Win w = {s.edges_i[a], s.edges_j[b], s.edges_i[a + 1] - s.edges_i[a],
-             s.edges_j[b + 1] - s.edges_j[b]};
-    amhip_ctx* c = nullptr;
-    const int d = devices ? devices[k] : 0;
-    rc = amhip_ctx_create_window(grid, w.i0, w.j0, w.rows, w.cols, d, &c);
-    if (rc) break;
-    s.ctx.push_back(c);
-    s.win.push_back(w);
-    s.dev.push_back(d);
-    if ((rc = ctx_use_device(&c->impl))) break;
-    unsigned long long* dh = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&dh), sizeof(unsigned long long) * 2 * AMHIP_NUM_LAYERS) !=
-        hipSuccess) {
-      rc = hip_fail(hipGetLastError(), "hipMalloc(session scratch)", __FILE__, __LINE__);
-      break;
-    }
-    s.dev_hash.push_back(dh);
-    unsigned long long* ph = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void**>(&ph), sizeof(unsigned long long) * 2 * AMHIP_NUM_LAYERS,
-                      hipHostMallocDefault) != hipSuccess) {
-      rc = hip_fail(hipGetLastError(), "hipHostMalloc(session scratch)", __FILE__, __LINE__);
-      break;
-    }
-    s.pin_hash.push_back(ph);
-    hipStream_t aux = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    if (hipStreamCreateWithFlags(&aux, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
-        hipEventCreate(&e1) != hipSuccess || hipEventCreate(&e2) != hipSuccess || hipEventCreate(&e3) != hipSuccess) {
-      rc = hip_fail(hipGetLastError(), "session: second stream / timing events", __FILE__, __LINE__);
-      if (aux) (void)hipStreamDestroy(aux);
-      for (hipEvent_t e : {e0, e1, e2, e3})
-        if (e) (void)hipEventDestroy(e);
-      break;
-    }
-    s.aux_stream.push_back(aux);
-    s.ev_k0.push_back(e0);
-    s.ev_k1.push_back(e1);
-    s.ev_d1.push_back(e2);
-    s.ev_s1.push_back(e3);
-  }
-  if (rc) {
-    amhip_session_destroy(h);
-    return rc;
-  }
-  s.sync.assign((size_t)W * AMHIP_NUM_LAYERS, LayerSync());
-  // content sums of the windows' initial constants: summed on the device without reading
-  // memory (the non-linear mix has no closed form)
-  s.const_hash.resize((size_t)W * AMHIP_NUM_LAYERS);
-  for (int k = 0; k < W && rc == AMHIP_OK; ++k) {
-    Ctx* c = &s.ctx[k]->impl;
-    if ((rc = ctx_use_device(c))) break;
-    hipError_t e = hipMemsetAsync(s.dev_hash[k], 0, sizeof(unsigned long long) * 2 * AMHIP_NUM_LAYERS,
-                                  c->stream);
-    for (int l = 0; l < AMHIP_NUM_LAYERS && e == hipSuccess; ++l)
-      hipLaunchKernelGGL(k_layer_hash, dim3(1024), dim3(256), 0, c->stream, (const float*)nullptr,
-                         ctx_layer_init_value(l), s.win[k].rows, s.win[k].cols, s.win[k].i0,
-                         s.win[k].j0, s.grid.rows, s.dev_hash[k] + 2 * l);
-    unsigned long long got[2 * AMHIP_NUM_LAYERS];
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(got, s.dev_hash[k], sizeof(got), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-      rc = hip_fail(e, "session: content sums of the initial layers", __FILE__, __LINE__);
-      break;
-    }
-    for (int l = 0; l < AMHIP_NUM_LAYERS; ++l) {
-      s.const_hash[(size_t)k * AMHIP_NUM_LAYERS + l].a = got[2 * l];
-      s.const_hash[(size_t)k * AMHIP_NUM_LAYERS + l].b = got[2 * l + 1];
+  s.windows.resize(W);
+  for (int k = 0; k < W; ++k) {
+    const int rc = create_window(s, k, devices ? devices[k] : 0);
+    if (rc) {
+      amhip_session_destroy(h);
+      return rc;
     }
   }
-  if (rc) {
-    amhip_session_destroy(h);
-    return rc;
-  }
-  s.route_out.assign(W, nullptr);
-  s.route_done.assign(W, nullptr);
-  s.route_cap.assign(W, 0);
-  s.route_counts.assign(W, nullptr);
-  s.cloud.assign(W, nullptr);
-  s.cloud_cap.assign(W, 0);
-  s.pin.assign(W, nullptr);
-  s.pin_cap.assign(W, 0);
   // direct device-to-device copies where the hardware allows them (xGMI)
   for (int a = 0; a < W; ++a)
     for (int b = 0; b < W; ++b)
-      if (s.dev[a] != s.dev[b]) {
+      if (s.windows[a].dev != s.windows[b].dev) {
         int can = 0;
-        if (hipDeviceCanAccessPeer(&can, s.dev[a], s.dev[b]) == hipSuccess && can &&
-            hipSetDevice(s.dev[a]) == hipSuccess)
-          (void)hipDeviceEnablePeerAccess(s.dev[b], 0);
+        if (hipDeviceCanAccessPeer(&can, s.windows[a].dev, s.windows[b].dev) == hipSuccess && can &&
+            hipSetDevice(s.windows[a].dev) == hipSuccess)
+          (void)hipDeviceEnablePeerAccess(s.windows[b].dev, 0);
         (void)hipGetLastError();  // (already enabled is fine)
       }
   *out = h;
@@ -687,24 +658,7 @@ int amhip_session_create(const amhip_grid_desc* grid, int tiles_i, int tiles_j,
 
 void amhip_session_destroy(amhip_session* h) {
   if (!h) return;
-  Session& s = h->impl;
-  for (size_t k = 0; k < s.ctx.size(); ++k) {
-    if (s.ctx[k]) {
-      (void)ctx_use_device(&s.ctx[k]->impl);
-      (void)hipStreamSynchronize(s.ctx[k]->impl.stream);
-      if (k < s.route_out.size() && s.route_out[k]) (void)hipFree(s.route_out[k]);
-      if (k < s.route_counts.size() && s.route_counts[k]) (void)hipFree(s.route_counts[k]);
-      if (k < s.route_done.size() && s.route_done[k]) (void)hipEventDestroy(s.route_done[k]);
-      if (k < s.cloud.size() && s.cloud[k]) (void)hipFree(s.cloud[k]);
-      if (k < s.dev_hash.size() && s.dev_hash[k]) (void)hipFree(s.dev_hash[k]);
-      if (k < s.pin.size() && s.pin[k]) (void)hipHostFree(s.pin[k]);
-      if (k < s.pin_hash.size() && s.pin_hash[k]) (void)hipHostFree(s.pin_hash[k]);
-      if (k < s.aux_stream.size() && s.aux_stream[k]) (void)hipStreamDestroy(s.aux_stream[k]);
-      for (auto* v : {&s.ev_k0, &s.ev_k1, &s.ev_s1, &s.ev_d1})
-        if (k < v->size() && (*v)[k]) (void)hipEventDestroy((*v)[k]);
-      amhip_ctx_destroy(s.ctx[k]);
-    }
-  }
+  for (Window& x : h->impl.windows) release_window(x);
   delete h;
 }
 
@@ -712,24 +666,23 @@ int amhip_session_num_windows(const amhip_session* h) { return h ? h->impl.W() :
 
 amhip_ctx* amhip_session_context(amhip_session* h, int k) {
   if (!h || k < 0 || k >= h->impl.W()) return nullptr;
-  return h->impl.ctx[k];
+  return h->impl.windows[k].ctx;
 }
 
 int amhip_session_window(const amhip_session* h, int k, int32_t* i0_j0_rows_cols) {
   if (!h || k < 0 || k >= h->impl.W() || !i0_j0_rows_cols)
     return arg_failure("amhip_session_window: bad argument");
-  const Win& w = h->impl.win[k];
-  i0_j0_rows_cols[0] = w.i0;
-  i0_j0_rows_cols[1] = w.j0;
-  i0_j0_rows_cols[2] = w.rows;
-  i0_j0_rows_cols[3] = w.cols;
+  const Win& w = h->impl.windows[k].win;
+  const int32_t v[4] = {w.i0, w.j0, w.rows, w.cols};
+  std::copy(v, v + 4, i0_j0_rows_cols);
   return AMHIP_OK;
 }
 
 int amhip_session_set_always_copy(amhip_session* h, int on) {
   if (!h) return arg_failure("null session");
   h->impl.always_copy = on != 0;
-  for (auto& st : h->impl.sync) st.device_valid = st.host_known = false;
+  for (Window& x : h->impl.windows)
+    for (LayerSync& st : x.sync) st.device_valid = st.host_known = false;
   return AMHIP_OK;
 }
 
@@ -744,21 +697,16 @@ int amhip_session_transfer_stats(const amhip_session* h, uint64_t* uploaded_byte
 int amhip_session_last_profile(const amhip_session* h, double* out8) {
   if (!h || !out8) return arg_failure("amhip_session_last_profile: null argument");
   const CallProfile& p = h->impl.prof;
-  out8[0] = p.total_ms;
-  out8[1] = p.h2d_ms;
-  out8[2] = p.host_sum_ms;
-  out8[3] = p.kernel_ms;
-  out8[4] = p.dev_sum_wait_ms;
-  out8[5] = p.d2h_ms;
-  out8[6] = p.up_bytes;
-  out8[7] = (double)h->impl.prof_down.load();
+  const double v[8] = {p.total_ms, p.h2d_ms, p.host_sum_ms, p.kernel_ms, p.dev_sum_wait_ms, p.d2h_ms, p.up_bytes,
+                       (double)h->impl.prof_down.load()};
+  std::copy(v, v + 8, out8);
   return AMHIP_OK;
 }
 
 int amhip_session_set_dsm_precision(amhip_session* h, int mode) {
   if (!h) return arg_failure("null session");
-  for (amhip_ctx* c : h->impl.ctx) {
-    const int rc = amhip_ctx_set_dsm_precision(c, mode);
+  for (Window& x : h->impl.windows) {
+    const int rc = amhip_ctx_set_dsm_precision(x.ctx, mode);
     if (rc) return rc;
   }
   return AMHIP_OK;
@@ -776,73 +724,53 @@ int amhip_session_dsm_process(amhip_session* h, const double* host_xyz, size_t n
   const int W = s.W();
   // (1) what do the devices already hold of `elevation`?  (host threads; the cloud's upload
   // is enqueued first where there is a single window, so that both overlap)
-  std::vector<Hash128> hh;
-  const float* mats[1] = {elevation};
+  HostCall call(s, (double)n * 24.0);
+  call.reads(AMHIP_LAYER_ELEVATION, elevation, true);
+  call.returns(AMHIP_LAYER_ELEVATION, elevation);
   int rc;
-  const auto call0 = std::chrono::steady_clock::now();
-  auto ms_since = [](std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-  };
-  s.prof = CallProfile();
-  s.prof_down = 0;
-  s.prof.up_bytes = (double)n * 24.0;
   if (W == 1) {
     PhaseClock clock("dsm");
-    Ctx* c = &s.ctx[0]->impl;
+    Window& x = s.windows[0];
+    Ctx* c = x.c();
     if ((rc = ctx_use_device(c))) return rc;
-    if (n >= 0x7FFFFFFFull) return arg_failure("more than 2^31-1 points");
-    if ((rc = ensure_capacity(&c->stage_points, &c->stage_points_cap, 3 * n))) return rc;
-    // (a pageable source makes this call return only once the data is staged; the sums run
+    if (n >= kMaxCallPoints) return arg_failure("more than 2^31-1 points");
+    // (a pageable source makes the upload return only once the data is staged; the sums run
     // in a second thread meanwhile)
-    double sum_ms = 0.0;
-    std::thread hasher([&]() {
-      const auto t = std::chrono::steady_clock::now();
-      if (!s.always_copy) host_hashes(s, mats, 1, &hh);
-      else hh.assign(1, Hash128());
-      sum_ms = ms_since(t);
-    });
-    hipError_t e = hipMemcpyAsync(c->stage_points, host_xyz, 3 * n * sizeof(double),
-                                  hipMemcpyHostToDevice, c->stream);
-    s.prof.h2d_ms = ms_since(call0);
+    std::thread hasher([&]() { call.sums(); });
+    const int rc_up = ctx_stage_cloud(c, host_xyz, nullptr, n);
+    s.prof.h2d_ms = ms_since(call.call0);
     clock.mark("cloud enqueued");
     hasher.join();
-    s.prof.host_sum_ms = sum_ms;
     clock.mark("host content sum");
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(cloud)", __FILE__, __LINE__);
-    if ((rc = sync_in(s, 0, AMHIP_LAYER_ELEVATION, elevation, hh[0], true))) return rc;
-    AMHIP_TRY(hipEventRecord(s.ev_k0[0], c->stream));
-    if ((rc = amhip_dsm_process_dev(s.ctx[0], c->stage_points, n, radius_sq, center_easting,
-                                    center_northing)))
+    if (rc_up) return rc_up;
+    if ((rc = call.enter(0))) return rc;
+    if ((rc = call.leave(0, true, [&](int) -> int {
+          const int r = amhip_dsm_process_dev(x.ctx, c->stage_points, n, radius_sq, center_easting, center_northing);
+          if (r == AMHIP_OK) clock.mark("sync_in + dsm enqueued");
+          return r;
+        })))
       return rc;
-    clock.mark("sync_in + dsm enqueued");
-    const int lay[1] = {AMHIP_LAYER_ELEVATION};
-    float* outs[1] = {elevation};
-    if ((rc = sync_out(s, 0, lay, outs, 1, true))) return rc;
-    rc = ctx_fetch_status(c);
-    s.prof.total_ms = ms_since(call0);
-    return rc;
+    return call.done(AMHIP_OK);
   }
 
-  if (!s.always_copy) host_hashes(s, mats, 1, &hh);
-  else hh.assign(W, Hash128());
+  call.sums();
   // (2) slice k of the cloud goes to window k's device, which COUNTS what every window needs
   // of it (its cells grown by the halo margin) -- one pass without output --
   const double margin = halo_margin_m(radius_sq, s.grid.resolution);
   std::vector<int32_t> wins(4 * (size_t)W);
   for (int d = 0; d < W; ++d) {
-    wins[4 * d + 0] = s.win[d].i0;
-    wins[4 * d + 1] = s.win[d].j0;
-    wins[4 * d + 2] = s.win[d].rows;
-    wins[4 * d + 3] = s.win[d].cols;
+    const Win& w = s.windows[d].win;
+    const int32_t v[4] = {w.i0, w.j0, w.rows, w.cols};
+    std::copy(v, v + 4, &wins[4 * (size_t)d]);
   }
-  std::vector<size_t> lo(W + 1);
-  for (int k = 0; k <= W; ++k) lo[k] = n * (size_t)k / (size_t)W;
+  auto slice = [&](int k) { return slice_lo(n, k + 1, W) - slice_lo(n, k, W); };
   std::vector<long long> counts((size_t)W * W, 0);
+  RouteTable route;
   // one selection pass of slice k over destinations [d0, d0 + nd): count only (caps 0) or
-  // compacting into route_out[k] at the offsets the counts gave
-  auto select_pass = [&](int k, bool count_only, const std::vector<unsigned long long>* offs) -> int {
-    Ctx* c = &s.ctx[k]->impl;
-    const size_t nk = lo[k + 1] - lo[k];
+  // compacting into window k's route_out at the offsets the counts gave
+  auto select_pass = [&](int k, bool count_only) -> int {
+    Window& x = s.windows[k];
+    Ctx* c = x.c();
     for (int d0 = 0; d0 < W; d0 += kMaxHaloDests) {
       const int nd = std::min(kMaxHaloDests, W - d0);
       HaloParams hp;
@@ -850,31 +778,27 @@ int amhip_session_dsm_process(amhip_session* h, const double* host_xyz, size_t n
                                0, &hp);
       if (r) return r;
       for (int d = 0; d < nd; ++d) {
-        hp.off[d] = count_only ? 0ull : (*offs)[(size_t)k * W + d0 + d];
+        hp.off[d] = count_only ? 0ull : route.offs[(size_t)k * W + d0 + d];
         hp.cap_d[d] = count_only ? 0ull : (unsigned long long)counts[(size_t)k * W + d0 + d];
       }
-      if ((r = halo_select_run(c, c->stage_points, nk, hp, s.route_out[k],
-                               reinterpret_cast<unsigned long long*>(s.route_counts[k] + d0))))
+      if ((r = halo_select_run(c, c->stage_points, slice(k), hp, x.route_out,
+                               reinterpret_cast<unsigned long long*>(x.route_counts + d0))))
         return r;
     }
     return AMHIP_OK;
   };
   rc = for_windows(s, [&](int k) -> int {
-    Ctx* c = &s.ctx[k]->impl;
-    int r = ctx_use_device(c);
+    Window& x = s.windows[k];
+    Ctx* c = x.c();
+    int r = call.enter(k);
     if (r) return r;
-    const size_t nk = lo[k + 1] - lo[k];
-    if ((r = sync_in(s, k, AMHIP_LAYER_ELEVATION, elevation, hh[k], true))) return r;
-    if (!s.route_done[k])
-      AMHIP_TRY(hipEventCreateWithFlags(&s.route_done[k], hipEventDisableTiming));
-    if (nk == 0) return AMHIP_OK;
-    if ((r = ensure_capacity(&c->stage_points, &c->stage_points_cap, 3 * nk))) return r;
-    AMHIP_TRY(hipMemcpyAsync(c->stage_points, host_xyz + 3 * lo[k], 3 * nk * sizeof(double),
-                             hipMemcpyHostToDevice, c->stream));
-    if (!s.route_counts[k])
-      AMHIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.route_counts[k]), sizeof(long long) * W));
-    if ((r = select_pass(k, true, nullptr))) return r;
-    AMHIP_TRY(hipMemcpyAsync(&counts[(size_t)k * W], s.route_counts[k], sizeof(long long) * W,
+    if (!x.route_done) AMHIP_TRY(hipEventCreateWithFlags(&x.route_done, hipEventDisableTiming));
+    if (slice(k) == 0) return AMHIP_OK;
+    if ((r = ctx_stage_cloud(c, host_xyz + 3 * slice_lo(n, k, W), nullptr, slice(k)))) return r;
+    if (!x.route_counts)
+      AMHIP_TRY(hipMalloc(reinterpret_cast<void**>(&x.route_counts), sizeof(long long) * W));
+    if ((r = select_pass(k, true))) return r;
+    AMHIP_TRY(hipMemcpyAsync(&counts[(size_t)k * W], x.route_counts, sizeof(long long) * W,
                              hipMemcpyDeviceToHost, c->stream));
     // (the one host synchronisation of the routing: the sizes of everything that follows)
     AMHIP_TRY(hipStreamSynchronize(c->stream));
@@ -884,70 +808,53 @@ int amhip_session_dsm_process(amhip_session* h, const double* host_xyz, size_t n
   // (3) the same pass again, now writing: slice k's selections for window d land behind those
   // for windows < d in ONE buffer of (points selected) rows -- not (slice x windows) --, and an
   // event marks them complete; no host synchronisation from here to the DSM's own
-  std::vector<unsigned long long> offs((size_t)W * W, 0ull);
-  for (int k = 0; k < W; ++k) {
-    unsigned long long run = 0;
-    for (int d = 0; d < W; ++d) {
-      offs[(size_t)k * W + d] = run;
-      run += (unsigned long long)counts[(size_t)k * W + d];
-    }
-  }
+  route = route_table(counts, W);
   rc = for_windows(s, [&](int k) -> int {
-    Ctx* c = &s.ctx[k]->impl;
-    int r = ctx_use_device(c);
+    Window& x = s.windows[k];
+    int r = ctx_use_device(x.c());
     if (r) return r;
-    const size_t nk = lo[k + 1] - lo[k];
-    size_t sel = 0;
-    for (int d = 0; d < W; ++d) sel += (size_t)counts[(size_t)k * W + d];
-    if (nk && sel) {
-      if ((r = ensure_capacity(&s.route_out[k], &s.route_cap[k], 3 * sel))) return r;
-      if ((r = select_pass(k, false, &offs))) return r;
+    if (slice(k) && route.sel[k]) {
+      if ((r = ensure_capacity(&x.route_out, &x.route_cap, 3 * route.sel[k]))) return r;
+      if ((r = select_pass(k, false))) return r;
     }
-    AMHIP_TRY(hipEventRecord(s.route_done[k], c->stream));
+    AMHIP_TRY(hipEventRecord(x.route_done, x.c()->stream));
     return AMHIP_OK;
   });
   if (rc) return rc;
   // (4) every window collects its points from all slices, device to device (xGMI peer copies
   // behind the producers' events), and runs Dsm::process on them
   rc = for_windows(s, [&](int d) -> int {
-    Ctx* c = &s.ctx[d]->impl;
+    Window& x = s.windows[d];
+    Ctx* c = x.c();
     int r = ctx_use_device(c);
     if (r) return r;
-    size_t total = 0;
-    for (int k = 0; k < W; ++k) total += (size_t)counts[(size_t)k * W + d];
-    if (total >= 0x7FFFFFFFull) return arg_failure("more than 2^31-1 points in one window");
+    const size_t total = route.total[d];
+    if (route.refused(d)) return arg_failure("more than 2^31-1 points in one window");
     if (total) {
-      if ((r = ensure_capacity(&s.cloud[d], &s.cloud_cap[d], 3 * total))) return r;
+      if ((r = ensure_capacity(&x.cloud, &x.cloud_cap, 3 * total))) return r;
       size_t off = 0;
       for (int k = 0; k < W; ++k) {
+        const Window& from = s.windows[k];
         const size_t cnt = (size_t)counts[(size_t)k * W + d];
         if (!cnt) continue;
-        if (k != d) AMHIP_TRY(hipStreamWaitEvent(c->stream, s.route_done[k], 0));
-        const double* src = s.route_out[k] + 3 * (size_t)offs[(size_t)k * W + d];
-        if (s.dev[k] == s.dev[d])
-          AMHIP_TRY(hipMemcpyAsync(s.cloud[d] + 3 * off, src, cnt * 24, hipMemcpyDeviceToDevice,
-                                   c->stream));
+        if (k != d) AMHIP_TRY(hipStreamWaitEvent(c->stream, from.route_done, 0));
+        const double* src = from.route_out + 3 * (size_t)route.offs[(size_t)k * W + d];
+        if (from.dev == x.dev)
+          AMHIP_TRY(hipMemcpyAsync(x.cloud + 3 * off, src, cnt * 24, hipMemcpyDeviceToDevice, c->stream));
         else
-          AMHIP_TRY(hipMemcpyPeerAsync(s.cloud[d] + 3 * off, s.dev[d], src, s.dev[k], cnt * 24,
-                                       c->stream));
+          AMHIP_TRY(hipMemcpyPeerAsync(x.cloud + 3 * off, x.dev, src, from.dev, cnt * 24, c->stream));
         off += cnt;
       }
-      AMHIP_TRY(hipEventRecord(s.ev_k0[d], c->stream));
-      if ((r = amhip_dsm_process_dev(s.ctx[d], s.cloud[d], total, radius_sq, center_easting,
-                                     center_northing)))
-        return r;
-    } else {
-      AMHIP_TRY(hipEventRecord(s.ev_k0[d], c->stream));
     }
-    const int lay[1] = {AMHIP_LAYER_ELEVATION};
-    float* outs[1] = {elevation};
-    if ((r = sync_out(s, d, lay, outs, 1, total != 0))) return r;  // (no call: no dirty cells on record)
-    return ctx_fetch_status(c);
+    // (no points, no call: no dirty cells on record)
+    return call.leave(d, total != 0, [&](int) -> int {
+      return total ? amhip_dsm_process_dev(x.ctx, x.cloud, total, radius_sq, center_easting, center_northing)
+                   : AMHIP_OK;
+    });
   });
-  // (a later call may overwrite route_out[k] while a slower peer still reads it: every window
+  // (a later call may overwrite route_out while a slower peer still reads it: every window
   // finished its copies before its own sync_out returned, and all threads were joined)
-  s.prof.total_ms = ms_since(call0);
-  return rc;
+  return call.done(rc);
 }
 
 // ortho::OrthoBackwardGrid::process (ortho-backward-grid.cc:223-239) on host buffers.
@@ -965,56 +872,33 @@ static int session_ortho_backward(
       !(colored ? colored_ortho : ortho))
     return arg_failure("amhip_session_ortho_backward_process: null layer");
   Session& s = h->impl;
-  const int W = s.W();
   const size_t row = (size_t)cam->width * (size_t)channels;
   const size_t frame = row * (size_t)cam->height;
-  for (size_t f = 0; f < F; ++f) {
-    if (!images[f]) return arg_failure("null image");
-    if (steps[f] < row) return arg_failure("image step smaller than a row");
+  // (the mosaic reads the elevation and writes the other layers, ONE of the two output layers --
+  // ortho-backward-grid.cc:186-208 --: the other matrix is neither summed, uploaded nor
+  // downloaded; 400 MB of host hashing per call)
+  HostCall call(s, (double)frame * (double)F);
+  float* const mats[AMHIP_NUM_LAYERS] = {colored ? nullptr : ortho, nullptr,           elevation_angle,
+                                         num_observations,          observation_index, colored ? colored_ortho : nullptr};
+  for (int l = 0; l < AMHIP_NUM_LAYERS; ++l) {  // (the context's layer order)
+    call.reads(l, l == AMHIP_LAYER_ELEVATION ? elevation : mats[l], l != AMHIP_LAYER_ELEVATION);
+    if (l != AMHIP_LAYER_ELEVATION) call.returns(l, mats[l]);
   }
-  // layer order of the context: ORTHO, ELEVATION, ELEVATION_ANGLE, NUM_OBSERVATIONS,
-  // OBSERVATION_INDEX, COLORED_ORTHO
-  // (the mosaic touches ONE of the two output layers -- ortho-backward-grid.cc:186-208 --: the
-  // other matrix is neither summed, uploaded nor downloaded; 400 MB of host hashing per call)
-  const float* ins[AMHIP_NUM_LAYERS] = {colored ? nullptr : ortho, elevation, elevation_angle,
-                                        num_observations, observation_index,
-                                        colored ? colored_ortho : nullptr};
-  std::vector<Hash128> hh;
-  auto upload_frames = [&](int k) -> int {
-    Ctx* c = &s.ctx[k]->impl;
-    int r = ctx_use_device(c);
-    if (r) return r;
-    if ((r = ensure_capacity(&c->stage_frames, &c->stage_frames_cap, frame * F))) return r;
-    for (size_t f = 0; f < F; ++f) {
-      if (steps[f] == row)
-        AMHIP_TRY(hipMemcpyAsync(c->stage_frames + f * frame, images[f], frame,
-                                 hipMemcpyHostToDevice, c->stream));
-      else
-        AMHIP_TRY(hipMemcpy2DAsync(c->stage_frames + f * frame, row, images[f], steps[f], row,
-                                   (size_t)cam->height, hipMemcpyHostToDevice, c->stream));
-    }
-    return AMHIP_OK;
-  };
   // the frames go up while host threads hash the six matrices
   PhaseClock clock("ortho_backward");
-  const auto call0 = std::chrono::steady_clock::now();
-  auto ms_since = [](std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-  };
-  s.prof = CallProfile();
-  s.prof_down = 0;
-  s.prof.up_bytes = (double)frame * (double)F;
   int rc_up = AMHIP_OK;
   std::string up_msg;
   double up_ms = 0.0;
   std::thread uploader([&]() {
-    rc_up = for_windows(s, upload_frames);
+    rc_up = for_windows(s, [&](int k) -> int {
+      Ctx* c = s.windows[k].c();
+      const int r = ctx_use_device(c);
+      return r ? r : ctx_stage_frames(c, images, steps, F, row, (size_t)cam->height);
+    });
     if (rc_up) up_msg = amhip_last_error();
-    up_ms = ms_since(call0);
+    up_ms = ms_since(call.call0);
   });
-  if (!s.always_copy) host_hashes(s, ins, AMHIP_NUM_LAYERS, &hh);
-  else hh.assign((size_t)AMHIP_NUM_LAYERS * W, Hash128());
-  s.prof.host_sum_ms = ms_since(call0);
+  call.sums();
   clock.mark("host content sums");
   uploader.join();
   s.prof.h2d_ms = up_ms;
@@ -1023,31 +907,21 @@ static int session_ortho_backward(
     set_last_error(up_msg);
     return rc_up;
   }
-  const int rc_all = for_windows(s, [&](int k) -> int {
-    Ctx* c = &s.ctx[k]->impl;
-    int r = ctx_use_device(c);
+  return call.done(for_windows(s, [&](int k) -> int {
+    int r = call.enter(k);
     if (r) return r;
-    // (the mosaic reads the elevation and writes the other layers)
-    for (int l = 0; l < AMHIP_NUM_LAYERS; ++l)
-      if (ins[l] && (r = sync_in(s, k, l, ins[l], hh[(size_t)l * W + k], l != AMHIP_LAYER_ELEVATION)))
-        return r;
     if (k == 0) clock.mark("sync_in");
-    AMHIP_TRY(hipEventRecord(s.ev_k0[k], c->stream));
-    if ((r = occl_margin ? amhip_ortho_backward_process_occl_dev(s.ctx[k], cam, host_T_G_C, F, c->stage_frames,
-                                                                 frame, row, channels, colored, *occl_margin)
-                         : amhip_ortho_backward_process_dev(s.ctx[k], cam, host_T_G_C, F, c->stage_frames, frame,
-                                                            row, channels, colored)))
-      return r;
-    if (k == 0) clock.mark("mosaic enqueued");
-    const int lay[5] = {AMHIP_LAYER_ORTHO, AMHIP_LAYER_ELEVATION_ANGLE, AMHIP_LAYER_NUM_OBSERVATIONS,
-                        AMHIP_LAYER_OBSERVATION_INDEX, AMHIP_LAYER_COLORED_ORTHO};
-    float* outs[5] = {colored ? nullptr : ortho, elevation_angle, num_observations, observation_index,
-                      colored ? colored_ortho : nullptr};
-    if ((r = sync_out(s, k, lay, outs, 5, true))) return r;
-    return ctx_fetch_status(c);
-  });
-  s.prof.total_ms = ms_since(call0);
-  return rc_all;
+    return call.leave(k, true, [&](int) -> int {
+      Window& x = s.windows[k];
+      const int rr =
+          occl_margin ? amhip_ortho_backward_process_occl_dev(x.ctx, cam, host_T_G_C, F, x.c()->stage_frames, frame,
+                                                              row, channels, colored, *occl_margin)
+                      : amhip_ortho_backward_process_dev(x.ctx, cam, host_T_G_C, F, x.c()->stage_frames, frame, row,
+                                                         channels, colored);
+      if (rr == AMHIP_OK && k == 0) clock.mark("mosaic enqueued");
+      return rr;
+    });
+  }));
 }
 
 int amhip_session_ortho_backward_process(
@@ -1087,39 +961,18 @@ int amhip_session_ortho_from_pcl_process(amhip_session* h, const double* host_xy
   if (!h) return arg_failure("null session");
   if (n == 0 || !host_xyz || !host_intensities || !ortho)
     return arg_failure("empty point cloud / null buffer (CHECK(!pointcloud.empty()))");
-  if (n >= 0x7FFFFFFFull) return arg_failure("more than 2^31-1 points");
+  if (n >= kMaxCallPoints) return arg_failure("more than 2^31-1 points");
   Session& s = h->impl;
-  std::vector<Hash128> hh;
-  const float* mats[1] = {ortho};
-  const auto call0 = std::chrono::steady_clock::now();
-  s.prof = CallProfile();
-  s.prof_down = 0;
-  s.prof.up_bytes = (double)n * 28.0 * (double)s.W();   // (every window gets the whole cloud)
-  if (!s.always_copy) host_hashes(s, mats, 1, &hh);
-  else hh.assign(s.W(), Hash128());
-  s.prof.host_sum_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - call0).count();
-  const int rc_all = for_windows(s, [&](int k) -> int {
-    Ctx* c = &s.ctx[k]->impl;
-    int r = ctx_use_device(c);
-    if (r) return r;
-    if ((r = sync_in(s, k, AMHIP_LAYER_ORTHO, ortho, hh[k], true))) return r;
-    if ((r = ensure_capacity(&c->stage_points, &c->stage_points_cap, 3 * n))) return r;
-    if ((r = ensure_capacity(&c->stage_values, &c->stage_values_cap, n))) return r;
-    AMHIP_TRY(hipMemcpyAsync(c->stage_points, host_xyz, 3 * n * sizeof(double),
-                             hipMemcpyHostToDevice, c->stream));
-    AMHIP_TRY(hipMemcpyAsync(c->stage_values, host_intensities, n * sizeof(int32_t),
-                             hipMemcpyHostToDevice, c->stream));
-    AMHIP_TRY(hipEventRecord(s.ev_k0[k], c->stream));
-    if ((r = amhip_ortho_from_pcl_process_dev(s.ctx[k], c->stage_points, c->stage_values, n,
-                                              radius_sq, adaptive)))
-      return r;
-    const int lay[1] = {AMHIP_LAYER_ORTHO};
-    float* outs[1] = {ortho};
-    if ((r = sync_out(s, k, lay, outs, 1))) return r;
-    return ctx_fetch_status(c);
-  });
-  s.prof.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - call0).count();
-  return rc_all;
+  HostCall call(s, (double)n * 28.0 * (double)s.W());   // (every window gets the whole cloud)
+  call.reads(AMHIP_LAYER_ORTHO, ortho, true);
+  call.returns(AMHIP_LAYER_ORTHO, ortho);
+  return call.run(
+      false, [&](int k) -> int { return ctx_stage_cloud(s.windows[k].c(), host_xyz, host_intensities, n); },
+      [&](int k) -> int {
+        Ctx* c = s.windows[k].c();
+        return amhip_ortho_from_pcl_process_dev(s.windows[k].ctx, c->stage_points, c->stage_values, n, radius_sq,
+                                                adaptive);
+      });
 }
 
 // ---- what leaves the map (formats: amhip_export.hip) ---------------
@@ -1169,10 +1022,10 @@ int amhip_session_grid_map_msg(amhip_session* h, uint64_t stamp_ns, const char* 
     }
   }
   rc = for_windows(s, [&](int k) -> int {
-    Ctx* c = &s.ctx[k]->impl;
+    Ctx* c = &s.windows[k].ctx->impl;
     int r = ctx_use_device(c);
     if (r) return r;
-    const Win& w = s.win[k];
+    const Win& w = s.windows[k].win;
     for (int l = 0; l < num_layers; ++l) {
       const int id = layer_ids[l];
       if (id < 0) continue;
@@ -1202,14 +1055,14 @@ int amhip_session_layer_to_image(amhip_session* h, int layer, int bgr, float low
     return arg_failure("amhip_session_layer_to_image: step smaller than an image row");
   if (!bgr && !(upper > lower)) return arg_failure("amhip_session_layer_to_image: upper <= lower");
   return for_windows(s, [&](int k) -> int {
-    Ctx* c = &s.ctx[k]->impl;
+    Ctx* c = &s.windows[k].ctx->impl;
     int r = ctx_use_device(c);
     if (r) return r;
-    const Win& w = s.win[k];
+    const Win& w = s.windows[k].win;
     const size_t row = (size_t)w.cols * bpp;
     uint8_t* dev = nullptr;
     AMHIP_TRY(hipMalloc(reinterpret_cast<void**>(&dev), row * (size_t)w.rows));
-    r = amhip_layer_to_image_dev(s.ctx[k], layer, bgr, lower, upper, dev, row);
+    r = amhip_layer_to_image_dev(s.windows[k].ctx, layer, bgr, lower, upper, dev, row);
     if (r == AMHIP_OK) {
       hipError_t e = hipMemcpy2DAsync(host_image + (size_t)w.i0 * step + (size_t)w.j0 * bpp, step,
                                       dev, row, row, (size_t)w.rows, hipMemcpyDeviceToHost,
@@ -1247,7 +1100,7 @@ int amhip_session_layer_write_jpeg(amhip_session* h, int layer, int bgr, float l
   const int rc = session_layer_image(h, "amhip_session_layer_write_jpeg: a JPEG file holds 1 x 1 to 65535 x 65535 pixels",
                                      layer, bgr, lower, upper, &image, &row);
   if (rc) return rc;
-  return amhip_jpeg_write(s.ctx[0], filename, image.data(), /*on_device=*/0, row, s.grid.cols, s.grid.rows,
+  return amhip_jpeg_write(s.windows[0].ctx, filename, image.data(), /*on_device=*/0, row, s.grid.cols, s.grid.rows,
                           bgr ? 3 : 1, quality);
 }
 
@@ -1264,7 +1117,7 @@ int amhip_session_layer_write_png(amhip_session* h, int layer, int bgr, float lo
       h, "amhip_session_layer_write_png: a PNG file of this encoder holds 1 x 1 to 65535 x 65535 pixels", layer, bgr,
       lower, upper, &image, &row);
   if (rc) return rc;
-  return amhip_png_write(s.ctx[0], filename, image.data(), /*on_device=*/0, row, s.grid.cols, s.grid.rows,
+  return amhip_png_write(s.windows[0].ctx, filename, image.data(), /*on_device=*/0, row, s.grid.cols, s.grid.rows,
                          bgr ? 3 : 1);
 }
 
@@ -1297,11 +1150,11 @@ static int session_layer_write_geotiff(const std::string& kWho, amhip_session* h
   if (kind == 0) {
     std::vector<float> map(rows * cols);
     rc = for_windows(s, [&](int k) -> int {
-      Ctx* c = &s.ctx[k]->impl;
+      Ctx* c = &s.windows[k].ctx->impl;
       int r = ctx_use_device(c);
       if (r) return r;
       if ((r = ctx_materialize(c, layer))) return r;
-      AMHIP_TRY(copy_window(map_at(map.data(), s, s.win[k]), c->layers[layer], s, s.win[k], true, c->stream));
+      AMHIP_TRY(copy_window(map_at(map.data(), s, s.windows[k].win), c->layers[layer], s, s.windows[k].win, true, c->stream));
       AMHIP_TRY(hipStreamSynchronize(c->stream));
       return AMHIP_OK;
     });
@@ -1327,9 +1180,9 @@ static int session_layer_write_geotiff(const std::string& kWho, amhip_session* h
       }
   }
   if (ovr)
-    return amhip_geotiff_write_ovr(s.ctx[0], filename, raster.data(), /*on_device=*/0, rows * px, (int)rows, (int)cols,
+    return amhip_geotiff_write_ovr(s.windows[0].ctx, filename, raster.data(), /*on_device=*/0, rows * px, (int)rows, (int)cols,
                                    kind, tile, overviews, gt, utm_zone, northern);
-  return amhip_geotiff_write(s.ctx[0], filename, raster.data(), /*on_device=*/0, rows * px, (int)rows, (int)cols, kind,
+  return amhip_geotiff_write(s.windows[0].ctx, filename, raster.data(), /*on_device=*/0, rows * px, (int)rows, (int)cols, kind,
                              tile, gt, utm_zone, northern);
 }
 
@@ -1361,25 +1214,15 @@ static int session_layer_read_geotiff(const char* kWho, amhip_session* h, int la
   if (rc) return rc;
   std::vector<TiffLayerJob*> jobs(s.W(), nullptr);
   rc = for_windows(s, [&](int k) -> int {
-    return tiff_layer_prepare(&s.ctx[k]->impl, kWho, layer, file.data(), file.size(), level, &jobs[k]);
+    return tiff_layer_prepare(&s.windows[k].ctx->impl, kWho, layer, file.data(), file.size(), level, &jobs[k]);
   });
   if (rc == AMHIP_OK) {
-    std::vector<Hash128> hh;
-    const float* mats[1] = {matrix};
-    if (!s.always_copy) host_hashes(s, mats, 1, &hh);
-    else hh.assign(s.W(), Hash128());
-    rc = for_windows(s, [&](int k) -> int {
-      Ctx* c = &s.ctx[k]->impl;
-      int r = ctx_use_device(c);
-      if (r) return r;
-      if ((r = sync_in(s, k, layer, matrix, hh[k], true))) return r;
-      AMHIP_TRY(hipEventRecord(s.ev_k0[k], c->stream));
-      if ((r = tiff_layer_place(c, jobs[k]))) return r;
-      const int lay[1] = {layer};
-      float* outs[1] = {matrix};
-      if ((r = sync_out(s, k, lay, outs, 1))) return r;
-      return ctx_fetch_status(c);
-    });
+    HostCall call(s, 0.0);
+    call.reads(layer, matrix, true);
+    call.returns(layer, matrix);
+    rc = call.run(
+        false, [](int) -> int { return AMHIP_OK; },
+        [&](int k) -> int { return tiff_layer_place(&s.windows[k].ctx->impl, jobs[k]); });
   }
   for (TiffLayerJob* j : jobs) tiff_layer_job_free(j);
   return rc;

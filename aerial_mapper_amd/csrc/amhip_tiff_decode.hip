@@ -468,7 +468,7 @@ int tiff_layer_place(Ctx* c, TiffLayerJob* job) {
   p.has_nodata = P.has_nodata;
   p.nodata = P.nodata;
   // a pending lazy reset: this kernel writes the initial value into the cells it leaves alone
-  p.fill = c->layer_state[job->layer] == 3 ? 1 : 0;
+  p.fill = c->layer_state[job->layer] == kLayerLazyInitial ? 1 : 0;
   p.init = ctx_layer_init_value(job->layer);
   p.layer = c->layers[job->layer];
   ctx_overwrite(c, job->layer);   // (every cell is defined after the kernel; heights now come from outside)
