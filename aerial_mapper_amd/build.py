@@ -20,7 +20,7 @@ SHIM_PATH = os.path.join(LIB_DIR, "libaerial_mapper_shim.so")
 RESOURCES_PATH = os.path.join(LIB_DIR, "kernel_resources.txt")
 OBJ_DIR = os.path.join(ROOT, "build", "hip_obj")
 
-HIP_SOURCES = ["amhip_api.hip", "amhip_sort.hip", "amhip_dsm.hip", "amhip_ortho.hip", "amhip_ortho_occl.hip", "amhip_densify.hip",
+HIP_SOURCES = ["amhip_api.hip", "amhip_sort.hip", "amhip_dsm.hip", "amhip_ortho.hip", "amhip_ortho_occl.hip", "amhip_ortho_blend.hip", "amhip_densify.hip",
                "amhip_forward.hip", "amhip_io.hip", "amhip_session.hip", "amhip_rectify.hip", "amhip_export.hip",
                "amhip_stereo.hip", "amhip_stereo_seq.hip", "amhip_jpeg.hip", "amhip_jpeg_decode.hip",
                "amhip_png_decode.hip", "amhip_png_encode.hip", "amhip_tiff_encode.hip", "amhip_tiff_decode.hip",
@@ -29,7 +29,7 @@ HIP_SOURCES = ["amhip_api.hip", "amhip_sort.hip", "amhip_dsm.hip", "amhip_ortho.
                "amhip_tuning.cc",    # (host-only: the tuning knobs' store, amhip_set_tuning / AMHIP_TUNING)
                "amhip_file_io.cc",   # (host-only: write_file / read_file of every writer and reader)
                "amhip_build_id.cc"]  # (host-only: amhip_build_id(), recompiled whenever anything else is)
-HIP_HEADERS = ["amhip_common.h", "amhip_dsm_plan.h", "amhip_sort_plan.h", "amhip_session_plan.h", "amhip_ortho_plan.h", "amhip_ortho_dev.h", "amhip_ortho_occl.h", "aerial_mapper_hip.h", "amhip_tuning.h", "amhip_device.h", "amhip_ortho_fold.h", "amhip_knn_set.h", "amhip_pow5_table.h", "amhip_atan_cr.h", "amhip_atan_table.h", "amhip_content_sum.h", "amhip_jpeg_host.h", "amhip_jpeg_decode_host.h", "amhip_png_decode_host.h", "amhip_png_encode_host.h", "amhip_frame_plan.h", "amhip_frame_stack.h", "amhip_deflate_rle.h", "amhip_layer_image.h", "amhip_tiff_host.h", "amhip_png_inflate.h", "amhip_tiff_decode_host.h", "amhip_tiff_source.h", os.path.join(ROOT, "include", "aerial_mapper_hip.h")]
+HIP_HEADERS = ["amhip_common.h", "amhip_dsm_plan.h", "amhip_sort_plan.h", "amhip_session_plan.h", "amhip_ortho_plan.h", "amhip_ortho_dev.h", "amhip_ortho_occl.h", "amhip_ortho_blend.h", "aerial_mapper_hip.h", "amhip_tuning.h", "amhip_device.h", "amhip_ortho_fold.h", "amhip_knn_set.h", "amhip_pow5_table.h", "amhip_atan_cr.h", "amhip_atan_table.h", "amhip_content_sum.h", "amhip_jpeg_host.h", "amhip_jpeg_decode_host.h", "amhip_png_decode_host.h", "amhip_png_encode_host.h", "amhip_frame_plan.h", "amhip_frame_stack.h", "amhip_deflate_rle.h", "amhip_layer_image.h", "amhip_tiff_host.h", "amhip_png_inflate.h", "amhip_tiff_decode_host.h", "amhip_tiff_source.h", os.path.join(ROOT, "include", "aerial_mapper_hip.h")]
 
 # -ffp-contract=off: every decision of the path (inside-radius test, image-box
 # test, pixel rounding, best-view comparison) must see the same doubles as the

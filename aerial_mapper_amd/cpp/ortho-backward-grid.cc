@@ -64,8 +64,16 @@ void OrthoBackwardGrid::process(const Poses& T_G_Bs, const Images& images,
   float* const num_observations = (*map)["num_observations"].data();
   float* const ortho = (*map)["ortho"].data();
   float* const colored_ortho = (*map)["colored_ortho"].data();
+  amhip_ortho_blend_opts blend;
+  blend.sharpness = blend_sharpness_;
+  blend.occlusion_test = occlusion_test_ ? 1 : 0;
+  blend.occlusion_margin_m = occlusion_test_ ? occlusion_margin_m_ : 0.0;
   amhip_shim::check_status(
-      occlusion_test_
+      blend_
+          ? amhip_session_ortho_backward_process_blend(
+                session_, &cam, T_G_C.data(), F, data.data(), steps.data(), channels, colored, elevation,
+                elevation_angle, observation_index, num_observations, ortho, colored_ortho, &blend)
+      : occlusion_test_
           ? amhip_session_ortho_backward_process_occl(
                 session_, &cam, T_G_C.data(), F, data.data(), steps.data(), channels, colored, elevation,
                 elevation_angle, observation_index, num_observations, ortho, colored_ortho,
@@ -79,6 +87,11 @@ void OrthoBackwardGrid::process(const Poses& T_G_Bs, const Images& images,
 void OrthoBackwardGrid::setOcclusionTest(bool enabled, double margin_m) {
   occlusion_test_ = enabled;
   occlusion_margin_m_ = margin_m;
+}
+
+void OrthoBackwardGrid::setBlend(bool enabled, int sharpness) {
+  blend_ = enabled;
+  blend_sharpness_ = sharpness;
 }
 
 void OrthoBackwardGrid::printParams() const {

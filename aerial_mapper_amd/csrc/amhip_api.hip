@@ -9,6 +9,7 @@
 #include <new>
 
 #include "amhip_common.h"
+#include "amhip_ortho_blend.h"
 #include "amhip_ortho_plan.h"
 
 namespace amhip {
@@ -395,7 +396,8 @@ void amhip_ctx_destroy(amhip_ctx* h) {
   for (int l = 0; l < AMHIP_NUM_LAYERS; ++l)
     if (c->layers[l]) (void)hipFree(c->layers[l]);
   void* bufs[] = {c->dev_bbox, c->ortho_list, c->zpart, c->dev_zrange, c->tile_list, c->tile_occ, c->fill_mask, c->stage_values, c->dev_err, c->sorted,       c->rank,        c->bin_start, c->bin_z, c->rec_a, c->rec_b, c->rec16, c->sidx, c->zref, c->zall, c->tmp_points, c->stripe_ws,
-                  c->scan_partials, c->stage_points, c->frame_poses, c->stage_frames, c->stereo_ws};
+                  c->scan_partials, c->stage_points, c->frame_poses, c->stage_frames, c->stereo_ws,
+                  c->blend_sums[0], c->blend_sums[1]};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   jpeg_scratch_free(&c->jpeg);
@@ -953,11 +955,25 @@ static int occl_args_check(const amhip_ctx* h, double margin_m) {
   return AMHIP_OK;
 }
 
-// occl_margin: null = the reference's mosaic; else the occlusion-tested one with that margin
-// (checked by the caller: occl_args_check)
+// The blended mosaic's own refusals (before any device work): the options, and with the occlusion
+// test on that mode's.  Without it a window is served: no ray leaves it, and its context holds its
+// own cells' sums.
+static int blend_args_check(const amhip_ctx* h, const amhip_ortho_blend_opts* opts) {
+  if (!h) return arg_fail("null context / camera");
+  if (!opts) return arg_fail("blended mosaic: null options (amhip_ortho_blend_opts)");
+  if (opts->sharpness < 0 || opts->sharpness > kBlendMaxSharpness)
+    return arg_fail("blended mosaic: sharpness must be 0 .. 4 (the weight is sin^2 .. sin^32 of the view angle)");
+  return opts->occlusion_test ? occl_args_check(h, opts->occlusion_margin_m) : AMHIP_OK;
+}
+
+// occl_margin: null = the reference's visibility rule; else the occlusion-tested one with that
+// margin (checked by the caller: occl_args_check).  blend: null = the winning view's pixel; else
+// the weighted mean of every visible view's (checked by the caller: blend_args_check; its
+// occlusion switch is what occl_margin says).
 static int ortho_backward_dev(amhip_ctx* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
                               const uint8_t* dev_frames, size_t frame_stride, size_t row_step,
-                              int channels, int colored, const double* occl_margin) {
+                              int channels, int colored, const double* occl_margin,
+                              const amhip_ortho_blend_opts* blend = nullptr) {
   if (!h || !cam) return arg_fail("null context / camera");
   if (F == 0 || !host_T_G_C) return arg_fail("empty pose list (CHECK(!T_G_Bs.empty()))");
   if (!dev_frames) return arg_fail("null frame pointer");
@@ -993,7 +1009,7 @@ static int ortho_backward_dev(amhip_ctx* h, const amhip_camera* cam, const doubl
   in.knobs.no_distorted_cull = tuning_on("no_distorted_cull");
   in.knobs.no_distorted_prune = tuning_on("no_distorted_prune");
   in.knobs.distorted_square_cull = tuning_on("distorted_square_cull");
-  in.knobs.ortho_exact_fold = occl_margin != nullptr || tuning_on("ortho_exact_fold");
+  in.knobs.ortho_exact_fold = occl_margin != nullptr || blend != nullptr || tuning_on("ortho_exact_fold");
   in.knobs.no_coarse_cull = tuning_on("no_coarse_cull");
   in.knobs.ortho_no_prune = tuning_on("ortho_no_prune");
   in.knobs.ortho_no_tile_list = tuning_on("ortho_no_tile_list");
@@ -1012,11 +1028,21 @@ static int ortho_backward_dev(amhip_ctx* h, const amhip_camera* cam, const doubl
       for (int k = 0; k < 3; ++k) centres[3 * f + k] = host_T_G_C[7 * f + k];
     static const unsigned long long minus_inf_key = 0x000FFFFFFFFFFFFFull;  // (amhip_device.h)
     std::memcpy(table.data() + slots - 1, &minus_inf_key, sizeof(minus_inf_key));
+  }
+  if (occl_margin || blend) {
     // dominated() assumes that a fully visible frame beats the pruned one at every landmark: not
-    // once the dominator can be occluded.  The kernel writes into real memory, tile by tile.
+    // once the dominator can be occluded -- and a dominated view still contributes to a blend.
+    // The kernel writes into real memory, tile by tile.
     plan.p.prune = 0;
     plan.p.virt_out = 0;
     plan.launch.tile_list = false;
+  }
+  // ---- the blended mosaic's sums: allocated, zero, by the first call of their kind
+  const int sums = colored ? 1 : 0;
+  if (blend && !c->blend_sums[sums]) {
+    const size_t bytes = (colored ? 4 : 2) * c->cells * sizeof(double);
+    AMHIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->blend_sums[sums]), bytes));
+    AMHIP_TRY(hipMemsetAsync(c->blend_sums[sums], 0, bytes, c->stream));
   }
   // ---- one buffer, one upload (pageable source: hipMemcpyAsync returns once it has been staged)
   if ((rc = ensure_capacity(&c->frame_poses, &c->frame_pose_cap, slots))) return rc;
@@ -1036,15 +1062,25 @@ static int ortho_backward_dev(amhip_ctx* h, const amhip_camera* cam, const doubl
       return rc;
   }
   if (!plan.p.virt_nobs && (rc = touch(c, AMHIP_LAYER_NUM_OBSERVATIONS))) return rc;
+  OcclParams q = {0.0, nullptr, nullptr};
+  unsigned long long* own_key = nullptr;
   if (occl_margin) {
-    OcclParams q;
     q.margin = *occl_margin;
     q.centres = reinterpret_cast<const double*>(c->frame_poses + table_slots);
     // the height cut-off of the march: the range the DSM calls wrote, or the layer's own maximum
-    unsigned long long* own_key = reinterpret_cast<unsigned long long*>(c->frame_poses + slots - 1);
+    own_key = reinterpret_cast<unsigned long long*>(c->frame_poses + slots - 1);
     q.zmax_key = c->zrange_valid ? c->dev_zrange + 1 : own_key;
-    return ortho_occl_run(c, plan, q, c->frame_poses, dev_frames, c->zrange_valid ? nullptr : own_key);
+    if (c->zrange_valid) own_key = nullptr;
   }
+  if (blend) {
+    BlendParams b;
+    b.sharpness = blend->sharpness;
+    b.plane = c->cells;
+    b.wsum = c->blend_sums[sums];
+    b.acc = c->blend_sums[sums] + c->cells;
+    return ortho_blend_run(c, plan, occl_margin ? &q : nullptr, b, c->frame_poses, dev_frames, own_key);
+  }
+  if (occl_margin) return ortho_occl_run(c, plan, q, c->frame_poses, dev_frames, own_key);
   return ortho_run(c, plan, c->frame_poses, reinterpret_cast<const FrameFast*>(c->frame_poses + F),
                    dev_frames);
 }
@@ -1067,12 +1103,22 @@ int amhip_ortho_backward_process_occl_dev(amhip_ctx* h, const amhip_camera* cam,
                             &margin_m);
 }
 
+int amhip_ortho_backward_process_blend_dev(amhip_ctx* h, const amhip_camera* cam, const double* host_T_G_C,
+                                           size_t F, const uint8_t* dev_frames, size_t frame_stride,
+                                           size_t row_step, int channels, int colored,
+                                           const amhip_ortho_blend_opts* opts) {
+  const int rc = blend_args_check(h, opts);
+  if (rc) return rc;
+  return ortho_backward_dev(h, cam, host_T_G_C, F, dev_frames, frame_stride, row_step, channels, colored,
+                            opts->occlusion_test ? &opts->occlusion_margin_m : nullptr, opts);
+}
+
 static int ortho_backward_host(
     amhip_ctx* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
     const uint8_t* const* images, const size_t* steps, int channels,
     int colored, const float* elevation, float* elevation_angle,
     float* observation_index, float* num_observations, float* ortho,
-    float* colored_ortho, const double* occl_margin) {
+    float* colored_ortho, const double* occl_margin, const amhip_ortho_blend_opts* blend = nullptr) {
   if (!h || !cam) return arg_fail("null context / camera");
   if (F == 0 || !host_T_G_C || !images || !steps)
     return arg_fail("empty pose / image list (CHECK(!T_G_Bs.empty()))");
@@ -1094,7 +1140,7 @@ static int ortho_backward_host(
   const size_t frame = row * (size_t)cam->height;
   if ((rc = ctx_stage_frames(c, images, steps, F, row, (size_t)cam->height))) return rc;
   if ((rc = ortho_backward_dev(h, cam, host_T_G_C, F, c->stage_frames, frame, row, channels, colored,
-                               occl_margin)))
+                               occl_margin, blend)))
     return rc;
   float* downs[AMHIP_NUM_LAYERS] = {ortho,           nullptr,
                                     elevation_angle, num_observations,
@@ -1130,6 +1176,19 @@ int amhip_ortho_backward_process_occl(
   return ortho_backward_host(h, cam, host_T_G_C, F, images, steps, channels, colored, elevation,
                              elevation_angle, observation_index, num_observations, ortho, colored_ortho,
                              &margin_m);
+}
+
+int amhip_ortho_backward_process_blend(
+    amhip_ctx* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+    const uint8_t* const* images, const size_t* steps, int channels,
+    int colored, const float* elevation, float* elevation_angle,
+    float* observation_index, float* num_observations, float* ortho,
+    float* colored_ortho, const amhip_ortho_blend_opts* opts) {
+  const int rc = blend_args_check(h, opts);
+  if (rc) return rc;
+  return ortho_backward_host(h, cam, host_T_G_C, F, images, steps, channels, colored, elevation,
+                             elevation_angle, observation_index, num_observations, ortho, colored_ortho,
+                             opts->occlusion_test ? &opts->occlusion_margin_m : nullptr, opts);
 }
 
 // ---- measurement ------------------------------------------------------------

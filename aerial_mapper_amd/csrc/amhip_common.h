@@ -241,6 +241,10 @@ struct Ctx {
   size_t frame_pose_cap = 0;
   uint8_t* stage_frames = nullptr;
   size_t stage_frames_cap = 0;
+  // the blended mosaic's per-cell FP64 sums (amhip_ortho_blend.hip): [0] gray, 2 planes of
+  // `cells` doubles (wsum, acc); [1] colour, 4 planes (wsum, B, G, R).  Allocated, zero, by the
+  // first blended call of that kind.
+  double* blend_sums[2] = {nullptr, nullptr};
   // The cells of the window the LAST DSM / mosaic call can have written (window coordinates):
   // the whole window, the sub-window of a small cloud, or the bounding box of the mosaic's tile
   // list (then still on the device: dirty_on_device, read back by ctx_last_dirty()).  What the
@@ -429,6 +433,18 @@ struct OcclParams {
 // first (it holds key(-inf)).
 int ortho_occl_run(Ctx* c, const OrthoPlan& plan, const OcclParams& q, const FramePose* dev_poses,
                    const uint8_t* dev_frames, unsigned long long* own_zmax_key);
+// The blended mosaic (amhip_ortho_blend.hip): what its kernel gets beside
+// the mosaic's own parameter set and, with the occlusion test on, the occlusion-tested mosaic's.
+struct BlendParams {
+  int sharpness;  // the weight is sin^2 of the view angle squared this many times (0 .. 4)
+  double* wsum;   // device, per cell of the window (i + j * rows): the sum of the weights ...
+  double* acc;    // ... and of weight * pixel: one plane of `plane` cells, or three (B, G, R)
+  size_t plane;
+};
+// plan: as for ortho_occl_run.  q: null = no occlusion test (own_zmax_key is not looked at then).
+int ortho_blend_run(Ctx* c, const OrthoPlan& plan, const OcclParams* q, const BlendParams& b,
+                    const FramePose* dev_poses, const uint8_t* dev_frames,
+                    unsigned long long* own_zmax_key);
 
 // context internals shared with amhip_session.hip (defined in amhip_api.hip)
 // i0, j0, rows, cols (window coordinates) of what the last DSM / mosaic call can have written;

@@ -858,12 +858,14 @@ int amhip_session_dsm_process(amhip_session* h, const double* host_xyz, size_t n
 }
 
 // ortho::OrthoBackwardGrid::process (ortho-backward-grid.cc:223-239) on host buffers.
-// occl_margin: null = the reference's mosaic; else the occlusion-tested one (one window only)
+// occl_margin: null = the reference's mosaic; else the occlusion-tested one (one window only).
+// blend: null, or the blended mosaic's options (its occlusion switch is what occl_margin says)
 static int session_ortho_backward(
     amhip_session* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
     const uint8_t* const* images, const size_t* steps, int channels, int colored,
     const float* elevation, float* elevation_angle, float* observation_index,
-    float* num_observations, float* ortho, float* colored_ortho, const double* occl_margin) {
+    float* num_observations, float* ortho, float* colored_ortho, const double* occl_margin,
+    const amhip_ortho_blend_opts* blend = nullptr) {
   if (!h || !cam) return arg_failure("null session / camera");
   if (F == 0 || !host_T_G_C || !images || !steps)
     return arg_failure("empty pose / image list (CHECK(!T_G_Bs.empty()))");
@@ -914,7 +916,9 @@ static int session_ortho_backward(
     return call.leave(k, true, [&](int) -> int {
       Window& x = s.windows[k];
       const int rr =
-          occl_margin ? amhip_ortho_backward_process_occl_dev(x.ctx, cam, host_T_G_C, F, x.c()->stage_frames, frame,
+          blend       ? amhip_ortho_backward_process_blend_dev(x.ctx, cam, host_T_G_C, F, x.c()->stage_frames, frame,
+                                                               row, channels, colored, blend)
+          : occl_margin ? amhip_ortho_backward_process_occl_dev(x.ctx, cam, host_T_G_C, F, x.c()->stage_frames, frame,
                                                               row, channels, colored, *occl_margin)
                       : amhip_ortho_backward_process_dev(x.ctx, cam, host_T_G_C, F, x.c()->stage_frames, frame, row,
                                                          channels, colored);
@@ -949,6 +953,29 @@ int amhip_session_ortho_backward_process_occl(
   return session_ortho_backward(h, cam, host_T_G_C, F, images, steps, channels, colored, elevation,
                                 elevation_angle, observation_index, num_observations, ortho, colored_ortho,
                                 &margin_m);
+}
+
+int amhip_session_ortho_backward_process_blend(
+    amhip_session* h, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+    const uint8_t* const* images, const size_t* steps, int channels, int colored,
+    const float* elevation, float* elevation_angle, float* observation_index,
+    float* num_observations, float* ortho, float* colored_ortho, const amhip_ortho_blend_opts* opts) {
+  if (!h || !cam) return arg_failure("null session / camera");
+  if (!opts) return arg_failure("blended mosaic: null options (amhip_ortho_blend_opts)");
+  if (opts->sharpness < 0 || opts->sharpness > 4)
+    return arg_failure("blended mosaic: sharpness must be 0 .. 4 (the weight is sin^2 .. sin^32 of the view angle)");
+  if (opts->occlusion_test) {
+    if (!(opts->occlusion_margin_m >= 0.0))
+      return arg_failure("occlusion test: margin_m must be >= 0 (+inf is legal: nothing occludes), not negative or NaN");
+    if (h->impl.W() != 1)
+      return arg_failure(
+          "occlusion test: the session holds more than one window and the ray towards the camera leaves "
+          "a window; windows need an elevation halo, which is not built yet");
+  }
+  // (without the occlusion test every window runs it: each context holds its own cells' sums)
+  return session_ortho_backward(h, cam, host_T_G_C, F, images, steps, channels, colored, elevation,
+                                elevation_angle, observation_index, num_observations, ortho, colored_ortho,
+                                opts->occlusion_test ? &opts->occlusion_margin_m : nullptr, opts);
 }
 
 // ortho::OrthoFromPcl::process (ortho-from-pcl.cc:20-113) on host buffers: `ortho` = the

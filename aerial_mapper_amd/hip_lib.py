@@ -47,7 +47,8 @@ EXPORTS = [
     "amhip_densify_dev", "amhip_rectify_stereo_pair_dev", "amhip_halo_select_dev", "amhip_dsm_tiled_begin_dev",
     "amhip_dsm_tiled_finish_dev", "amhip_compose_T_G_C", "amhip_ortho_backward_process_dev",
     "amhip_ortho_backward_process", "amhip_ortho_backward_process_occl_dev",
-    "amhip_ortho_backward_process_occl", "amhip_ctx_enable_timing", "amhip_ctx_timing_reset",
+    "amhip_ortho_backward_process_occl", "amhip_ortho_backward_process_blend_dev",
+    "amhip_ortho_backward_process_blend", "amhip_ctx_enable_timing", "amhip_ctx_timing_reset",
     "amhip_ctx_kernel_time", "amhip_kernel_name", "amhip_ctx_dsm_stats", "amhip_ctx_dsm_sort_pipeline", "amhip_ctx_dsm_gather_stats", "amhip_ctx_order_after", "amhip_session_last_profile", "amhip_build_id", "amhip_set_tuning", "amhip_get_tuning", "amhip_default_dsm_precision",
     "amhip_mosaic_create", "amhip_mosaic_destroy", "amhip_mosaic_set_stream",
     "amhip_mosaic_synchronize", "amhip_mosaic_reset", "amhip_mosaic_batch",
@@ -58,7 +59,7 @@ EXPORTS = [
     "amhip_session_context", "amhip_session_window", "amhip_session_set_always_copy",
     "amhip_session_set_dsm_precision", "amhip_session_transfer_stats",
     "amhip_session_dsm_process", "amhip_session_ortho_backward_process",
-    "amhip_session_ortho_backward_process_occl",
+    "amhip_session_ortho_backward_process_occl", "amhip_session_ortho_backward_process_blend",
     "amhip_session_ortho_from_pcl_process",
     "amhip_io_parse_point_cloud_text", "amhip_io_download_point_cloud", "amhip_io_free",
     "amhip_layer_to_image_dev", "amhip_layer_to_image", "amhip_geotiff_write_u8",
@@ -115,6 +116,12 @@ class Camera(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32),
                 ("distortion", C.c_int32), ("_pad", C.c_int32),
                 ("dist", C.c_double * 4)]
+
+
+class OrthoBlendOpts(C.Structure):
+    """amhip_ortho_blend_opts"""
+    _fields_ = [("sharpness", C.c_int32), ("occlusion_test", C.c_int32),
+                ("occlusion_margin_m", C.c_double)]
 
 
 class MosaicDesc(C.Structure):
@@ -216,6 +223,9 @@ def load():
     lib.amhip_ortho_backward_process_occl_dev.argtypes = \
         lib.amhip_ortho_backward_process_dev.argtypes + [C.c_double]
     lib.amhip_ortho_backward_process_occl.argtypes = lib.amhip_ortho_backward_process.argtypes + [C.c_double]
+    bp = C.POINTER(OrthoBlendOpts)
+    lib.amhip_ortho_backward_process_blend_dev.argtypes = lib.amhip_ortho_backward_process_dev.argtypes + [bp]
+    lib.amhip_ortho_backward_process_blend.argtypes = lib.amhip_ortho_backward_process.argtypes + [bp]
     lib.amhip_session_create.argtypes = [gp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(vp)]
     lib.amhip_session_destroy.restype = None
     lib.amhip_session_destroy.argtypes = [vp]
@@ -235,6 +245,8 @@ def load():
         vp, vp, vp, vp, vp, vp]
     lib.amhip_session_ortho_backward_process_occl.argtypes = \
         lib.amhip_session_ortho_backward_process.argtypes + [C.c_double]
+    lib.amhip_session_ortho_backward_process_blend.argtypes = \
+        lib.amhip_session_ortho_backward_process.argtypes + [bp]
     lib.amhip_rectify_stereo_pair_dev.argtypes = [vp, f64p, f64p, f64p, f64p, f64p, C.c_int, C.c_int,
                                                   vp, C.c_size_t, vp, C.c_size_t, f64p, f64p, vp, vp, vp, vp]
     lib.amhip_sgbm_default_params.restype = None

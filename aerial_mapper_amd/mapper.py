@@ -334,12 +334,19 @@ class OrthoSettings(object):
 
     occlusion_test / occlusion_margin_m (an extension; off = the reference's rule): a view whose
     ray from the cell to the camera passes more than occlusion_margin_m below the elevation layer
-    is skipped ("true ortho": amhip_ortho_backward_process_occl)."""
+    is skipped ("true ortho": amhip_ortho_backward_process_occl).
+
+    blend / blend_sharpness (an extension; off = the winning view's pixel): every view that is
+    visible from a cell -- and unoccluded, with occlusion_test -- contributes its nearest pixel,
+    weighted by sin^2 of its view angle squared blend_sharpness times (0 .. 4), and the cell gets
+    the weighted mean; the sums live with the map, so frames may come in several calls
+    (amhip_ortho_backward_process_blend)."""
 
     def __init__(self, show_orthomosaic_opencv=True, save_orthomosaic_jpg=True,
                  orthomosaic_jpg_filename="", orthomosaic_elevation_m=0.0,
                  use_digital_elevation_map=True, colored_ortho=False,
-                 use_multi_threads=True, occlusion_test=False, occlusion_margin_m=0.0):
+                 use_multi_threads=True, occlusion_test=False, occlusion_margin_m=0.0,
+                 blend=False, blend_sharpness=2):
         self.show_orthomosaic_opencv = show_orthomosaic_opencv
         self.save_orthomosaic_jpg = save_orthomosaic_jpg
         self.orthomosaic_jpg_filename = orthomosaic_jpg_filename
@@ -349,6 +356,21 @@ class OrthoSettings(object):
         self.use_multi_threads = use_multi_threads
         self.occlusion_test = occlusion_test
         self.occlusion_margin_m = occlusion_margin_m
+        self.blend = blend
+        self.blend_sharpness = blend_sharpness
+
+
+def _ortho_mode(settings):
+    """Which family of mosaic exports OrthoSettings selects: the suffix of their names ("", "_occl",
+    "_blend") and the arguments that follow the plain export's."""
+    occl = bool(getattr(settings, "occlusion_test", False))
+    if getattr(settings, "blend", False):
+        opts = L.OrthoBlendOpts(int(settings.blend_sharpness), int(occl),
+                                float(settings.occlusion_margin_m) if occl else 0.0)
+        return "_blend", (C.byref(opts),)
+    if occl:
+        return "_occl", (float(settings.occlusion_margin_m),)
+    return "", ()
 
 
 class NCamera(object):
@@ -406,8 +428,7 @@ class OrthoBackwardGrid(object):
                      "colored_ortho")
         cam = self.ncameras.camera
         colored = bool(self.settings.colored_ortho)
-        occl = bool(getattr(self.settings, "occlusion_test", False))
-        margin = (float(self.settings.occlusion_margin_m),) if occl else ()
+        mode, extra = _ortho_mode(self.settings)
         T_G_C = compose_T_G_C(T_G_Bs, self.ncameras.T_C_B)
         f64p = C.POINTER(C.c_double)
         if _is_torch(images):
@@ -417,9 +438,9 @@ class OrthoBackwardGrid(object):
             frame = row * cam.height
             assert images.shape[1] == cam.height and images.shape[2] == cam.width
             map.wait_for_torch(images)
-            entry = lib.amhip_ortho_backward_process_occl_dev if occl else lib.amhip_ortho_backward_process_dev
+            entry = getattr(lib, "amhip_ortho_backward_process%s_dev" % mode)
             L.check(entry(map.handle, C.byref(cam), T_G_C.ctypes.data_as(f64p), F,
-                          C.c_void_p(images.data_ptr()), frame, row, ch, int(colored), *margin))
+                          C.c_void_p(images.data_ptr()), frame, row, ch, int(colored), *extra))
             if sync:
                 map.synchronize()
             return
@@ -438,9 +459,9 @@ class OrthoBackwardGrid(object):
             ptrs[k] = im.ctypes.data
             steps[k] = im.strides[0]
         # layers are already device resident: pass NULL for all of them
-        entry = lib.amhip_ortho_backward_process_occl if occl else lib.amhip_ortho_backward_process
+        entry = getattr(lib, "amhip_ortho_backward_process%s" % mode)
         L.check(entry(map.handle, C.byref(cam), T_G_C.ctypes.data_as(f64p), F, ptrs, steps, ch,
-                      int(colored), None, None, None, None, None, None, *margin))
+                      int(colored), None, None, None, None, None, None, *extra))
 
 
 LAYER_INIT = {"ortho": 255.0, "elevation": float("nan"), "elevation_angle": 0.0,
@@ -552,16 +573,14 @@ class HostSession(object):
             ptrs[k] = im.ctypes.data
             steps[k] = im.strides[0]
         lay = self.layers
-        occl = bool(getattr(ortho_settings, "occlusion_test", False))
-        margin = (float(ortho_settings.occlusion_margin_m),) if occl else ()
-        entry = self._lib.amhip_session_ortho_backward_process_occl if occl else \
-            self._lib.amhip_session_ortho_backward_process
+        mode, extra = _ortho_mode(ortho_settings)
+        entry = getattr(self._lib, "amhip_session_ortho_backward_process%s" % mode)
         L.check(entry(
             self._h, C.byref(ncameras.camera), T_G_C.ctypes.data_as(C.POINTER(C.c_double)), F, ptrs,
             steps, 3 if colored else 1, int(colored), lay["elevation"].ctypes.data,
             lay["elevation_angle"].ctypes.data, lay["observation_index"].ctypes.data,
             lay["num_observations"].ctypes.data, lay["ortho"].ctypes.data,
-            lay["colored_ortho"].ctypes.data, *margin))
+            lay["colored_ortho"].ctypes.data, *extra))
 
 
 class OrthoFromPclSettings(object):

@@ -48,6 +48,14 @@ class OrthoBackwardGrid {
   // below the map's elevation layer ("true ortho": amhip_session_ortho_backward_process_occl).
   void setOcclusionTest(bool enabled, double margin_m = 0.0);
 
+  // An extension (the reference has no such method; off by default): the process() calls that
+  // follow give a cell the weighted mean of the nearest pixels of every view that is visible from
+  // it (and unoccluded, with setOcclusionTest), weighted by sin^2 of the view angle squared
+  // `sharpness` times (0 .. 4), instead of the most-nadir view's pixel.  The sums live with the
+  // map's session: frames may come in several calls, and a map whose layers were set back to their
+  // initial values starts over (amhip_session_ortho_backward_process_blend).
+  void setBlend(bool enabled, int sharpness = 2);
+
  private:
   void ensureSession(const grid_map::GridMap& map) const;
   void printParams() const;
@@ -59,6 +67,8 @@ class OrthoBackwardGrid {
   mutable amhip_session* session_;
   bool occlusion_test_ = false;
   double occlusion_margin_m_ = 0.0;
+  bool blend_ = false;
+  int blend_sharpness_ = 2;
 };
 
 }  // namespace ortho

@@ -372,6 +372,50 @@ int amhip_ortho_backward_process_occl(
     float* observation_index, float* num_observations, float* ortho,
     float* colored_ortho, double margin_m);
 
+/* The same two, blended (an extension: the reference has none).  The
+ * reference paints a cell with the nearest pixel of its single most-nadir view; here EVERY view
+ * that is visible from the cell (in_box && z > 1e-10 with a finite elevation; with occlusion_test
+ * also !occluded(cell, frame), the march above with occlusion_margin_m) contributes its nearest
+ * pixel, weighted by a power of the sine of its view angle, and the cell gets the weighted mean.
+ * Whether a view wins or loses the angle fold does not matter for contributing.  One pair, FP64,
+ * every operation rounded on its own, in this order -- (cx, cy, cz) the landmark in the camera
+ * frame, I the pixel at the plain mosaic's keypoint (min((int)round(v), height - 1), x likewise):
+ *   zz = cz * cz; n2 = (cx * cx + cy * cy) + zz; w = zz / n2; `sharpness` times: w = w * w;
+ *   acc = acc + w * (double)I (gray; colour: B, G and R each with a sum of its own);
+ *   wsum = wsum + w;
+ * frames ascending over all F frames of the call.  sharpness in [0, 4] (sin^2 .. sin^32 of the view
+ * angle; 2 is a good default).  At the end of the call a cell with at least one contributing pair
+ * in this call and wsum > 0 gets rint(acc / wsum) (round half to even; colour: per channel, packed
+ * R << 16 | G << 8 | B like the plain mosaic's); any other cell keeps what the layer held.
+ * elevation_angle, observation_index and num_observations are written exactly as by the plain
+ * (occlusion_test = 0) or the occlusion-tested mosaic on the same inputs.
+ *   The sums are per-cell FP64 device buffers of the context, allocated (zero) by the first blended
+ * call, gray and colour each their own: 16 bytes per cell for gray, 32 for colour.  A cell whose
+ * observation_index is NaN at the start of a call restarts from zero -- a reset map needs no
+ * other hook --, any other continues from what the buffers hold: frames 0..k in one call and
+ * k+1..F in the next give the bits of one call with all of them.  Blended and unblended calls may
+ * be mixed on one map: each call follows its own rule, and the sums know only the blended calls.
+ *   AMHIP_ERR_ARG before any device work: null opts, sharpness outside [0, 4], and with
+ * occlusion_test the refusals of amhip_ortho_backward_process_occl (margin, window contexts).
+ * Without the occlusion test a window context is served: no ray leaves it. */
+typedef struct amhip_ortho_blend_opts {
+  int32_t sharpness;
+  int32_t occlusion_test;      /* 0: the reference's visibility rule */
+  double occlusion_margin_m;   /* only read with occlusion_test */
+} amhip_ortho_blend_opts;
+int amhip_ortho_backward_process_blend_dev(amhip_ctx* ctx, const amhip_camera* cam,
+                                           const double* host_T_G_C, size_t F,
+                                           const uint8_t* dev_frames,
+                                           size_t frame_stride, size_t row_step,
+                                           int channels, int colored,
+                                           const amhip_ortho_blend_opts* opts);
+int amhip_ortho_backward_process_blend(
+    amhip_ctx* ctx, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+    const uint8_t* const* images, const size_t* steps, int channels,
+    int colored, const float* elevation, float* elevation_angle,
+    float* observation_index, float* num_observations, float* ortho,
+    float* colored_ortho, const amhip_ortho_blend_opts* opts);
+
 /* ---- ortho::OrthoForwardHomography
  *      (aerial_mapper_ortho/src/ortho-forward-homography.cc; SURVEY section 8b/8f,
  *      named in the API surface to keep) --
@@ -1141,6 +1185,16 @@ int amhip_session_ortho_backward_process_occl(
     const uint8_t* const* images, const size_t* steps, int channels, int colored,
     const float* elevation, float* elevation_angle, float* observation_index,
     float* num_observations, float* ortho, float* colored_ortho, double margin_m);
+/* ... blended (amhip_ortho_backward_process_blend): every window's context holds its own cells'
+ * sums, and a map whose matrices were set back to their initial constants restarts them (its
+ * observation_index is NaN).  Without the occlusion test a session of several windows runs it and
+ * gives the one-window layers; with it only a session of one window (AMHIP_ERR_ARG otherwise). */
+int amhip_session_ortho_backward_process_blend(
+    amhip_session* s, const amhip_camera* cam, const double* host_T_G_C, size_t F,
+    const uint8_t* const* images, const size_t* steps, int channels, int colored,
+    const float* elevation, float* elevation_angle, float* observation_index,
+    float* num_observations, float* ortho, float* colored_ortho,
+    const amhip_ortho_blend_opts* opts);
 
 /* With timing enabled every launch is bracketed by hipEvents on the
  * context's stream.  amhip_ctx_kernel_time() synchronises, then reports the
